@@ -5,6 +5,13 @@ analytic gradient (BASELINE.json metric), on synthetic events already resident i
     python bench.py --gpus N --steps K --warmup W          (N > 1 without a launcher: re-executes itself under
                                                             torch.distributed.run, one rank per GPU)
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N ... bench.py --gpus N ...
+    python bench.py ... --full                             (everything below besides the headline)
+    python bench.py ... --dump-outputs DIR                 (what the headline's last timed step returned: DIR/result.npy, grad.npy;
+                                                            on one GPU also iwe.npy, the handle's image of warped events read back
+                                                            after that step -- an internal buffer, not returned by the call)
+
+A plain run sets the headline workload up, warms it up, times it and prints the line; `also`, `roofline.kernels` / `dominant` /
+`launch_floor_us`, the counter traffic of this run, `graph_replay`, the CPU baselines and (N > 1) `comm_probe` come with --full.
 
 Workload (config.workload): BASELINE configs[1] = cfg2 = 1M synthetic events, 346x260 (H=260, W=346), 2-DoF
 translational flow, image-variance cost + analytic gradient.  `value` times the COMPLETE evaluation: cmax_objective = K1
@@ -21,8 +28,9 @@ evaluation's grids, measured in the same run.  For N > 1 every rank owns one 1M-
 slice of an N x 1M-event batch (weak scaling); both all-reduces of an evaluation (IWE, gradient) are enqueued by
 libcmax_hip.so itself (RCCL, cmax_objective_dist), and `also.cfg5_strong` is cfg5 split into N time slices.
 
-Timing: W warm-up steps, then `windows` (default 25) windows of EXACTLY K steps, each bracketed by barrier +
-torch.cuda.synchronize() on both sides, MAX over ranks per window; ms_per_step / value are the MEDIAN window.
+Timing: W warm-up steps, then `windows` (default 1) windows of EXACTLY K steps, each bracketed by barrier +
+torch.cuda.synchronize() on both sides, MAX over ranks per window; ms_per_step / value are the MEDIAN window (by default: the
+K timed steps).
 
 One JSON line on stdout (rank 0).  Extra objects:
   roofline      bound hbm; achieved = SURVEY 8(d) algorithmic bytes of ONE EVALUATION / median step time
@@ -351,9 +359,29 @@ def cpu_baseline_torch(workload, cfg, affinity, budget_s=4.0):
     return out
 
 
-def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=True, keep_inputs=False):
+DUMP_LIMIT_BYTES = 64 * 2**20  # --dump-outputs: all arrays together
+
+
+def dump_outputs(out_dir, arrays):
+    """Writes every host array of `arrays` ({name: array}) as out_dir/<name>.npy in float32 or float64 (at most DUMP_LIMIT_BYTES in
+    all).  Returns the file names written."""
+    host = {}
+    for name, a in arrays.items():
+        a = np.asarray(a)
+        host[name] = a.astype(np.float64 if a.dtype == np.float64 else np.float32, copy=False)
+    total = sum(a.nbytes for a in host.values())
+    if total > DUMP_LIMIT_BYTES:
+        raise ValueError("--dump-outputs: %d bytes of outputs, more than the %d allowed" % (total, DUMP_LIMIT_BYTES))
+    os.makedirs(out_dir, exist_ok=True)
+    for name, a in host.items():
+        np.save(os.path.join(out_dir, name + ".npy"), a)
+    return sorted(name + ".npy" for name in host)
+
+
+def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=True, keep_inputs=False, headline=False):
     """Sets the workload up on this rank, times `windows` windows of `steps` evaluations, optionally profiles the kernel
-    classes.  Returns a dict (rank 0 uses it; every rank must call this: the timing holds collectives)."""
+    classes.  Returns a dict (rank 0 uses it; every rank must call this: the timing holds collectives).  `headline`: the row the
+    line's `value` comes from (settle windows before the timed ones; the outputs of its last timed step under `_outputs`)."""
     import torch
     import torch.distributed as dist
 
@@ -396,6 +424,7 @@ def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=T
     # "host": cmax_objective_host, every step waits for its numbers on the host (sequential: what one optimiser iteration costs).
     form = cfg.get("form") or args.form
     finalize = None
+    res_b = None  # batch form: the results of every candidate
     per_call = 1  # evaluations per call (cfg2_batch8: 8)
     if form == "batch" and world == 1:
         per_call = int(cfg["batch"])
@@ -438,7 +467,7 @@ def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=T
     ev0, ev1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
     settle = []  # headline row only: untimed windows until the clocks have settled (two consecutive windows within 1 % of the best), <= 6 s
     t_settle = time.perf_counter()
-    while keep_inputs and args.ramp > 0 and world == 1 and time.perf_counter() - t_settle < 6.0:
+    while headline and args.ramp > 0 and world == 1 and time.perf_counter() - t_settle < 6.0:
         ev0.record()
         for _ in range(max(steps, 100)):
             step()
@@ -459,6 +488,19 @@ def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=T
             dist.barrier()
         host_times.append(time.perf_counter() - t0)
         times.append(ev0.elapsed_time(ev1) * 1e-3)
+    outputs = None
+    if headline and rank == 0 and args.dump_outputs:
+        # what a caller of the timed call holds after its last step: result[8] (loss first) and gradient -- the raw form's after the
+        # consumer's fold, every candidate's for a batch call -- plus, on one GPU, the image of warped events of that step (reference time 0):
+        # not part of what the call returns, but the handle's internal buffer, copied out (cmax_copy_iwe) after the step for comparisons
+        if finalize:
+            outputs = dict(zip(("result", "grad"), finalize()))
+        else:
+            outputs = {"result": res_b if res_b is not None else res, "grad": grad}
+        if form != "batch" and world == 1:  # (N > 1: the handle's image may be a buffer of the phase-split call)
+            outputs["iwe"] = handle.last_iwe(0)
+        # host copies now: every later call (the --full passes) overwrites the prepared buffers
+        outputs = {k: v.cpu().numpy() if isinstance(v, torch.Tensor) else np.array(v) for k, v in outputs.items() if v is not None}
     both = torch.tensor([times, host_times], dtype=torch.float64, device=dev)
     if world > 1:
         dist.all_reduce(both, op=dist.ReduceOp.MAX)  # a window lasts as long as its slowest rank
@@ -479,6 +521,8 @@ def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=T
                            "device": "loss + gradient on the device (cmax_objective)",
                            "batch": "loss + gradient of every candidate on the device (cmax_objective_batch)",
                            "host": "loss + gradient on the host after every evaluation (cmax_objective_host)"}[form]}
+    if outputs is not None:
+        out["_outputs"] = outputs
     if world > 1:
         out["rccl"] = dict(zip(("nranks", "rank", "version"), handle.comm_info()))
     # B / t_eval.  Per GPU: N/g events + the full images (every rank evaluates the image-space part)
@@ -538,7 +582,7 @@ def run_workload(name, args, rank, world, dev, steps, warmup, windows, profile=T
         out["physical_GBps"] = out["physical_bytes_per_evaluation"] / (out["ms_per_step"] * 1e-3) / 1e9
     if keep_inputs:
         out["_inputs"] = (cfg, ev, motion)
-        if world == 1:
+        if world == 1 and args.full:  # a run of its own: --full only
             try:
                 out["launch_floor_us"] = handle.launch_floor_us()
             except Exception as e:  # never fail the bench line over a side figure
@@ -737,17 +781,20 @@ def compact_line(out, verbose_path):
     line["config"] = {"workload": c["workload"], "events_per_gpu": c["events_per_gpu"], "image": c.get("image"), "motion_model": c["motion_model"],
                       "cost": c["cost"], "blur_sigma": c["blur_sigma"], "parallelism": c["parallelism"],
                       "result_form": c["result_form"].split(" (")[-1].rstrip(")"), "collectives": c["collectives"], "rccl": c["rccl"]}
-    dom = r["dominant"]
     line["roofline"] = {"bound": "hbm", "achieved": _r(r["achieved"]), "peak": r["peak"], "unit": "GB/s", "frac": _r(r["frac"]),
                         "traffic": r["traffic"], "algorithmic_bytes": r["algorithmic_bytes_per_evaluation"],
-                        "scope": "one evaluation: B = 24N + 16HW + B_model (SURVEY 8d) / median step time",
-                        "dominant": {"kernel": dom["kernel"].split(" ")[0], "launch_us": _r(dom["launch_us"]), "frac": _r(dom["frac"]),
-                                     "bytes": dom["algorithmic_bytes_per_launch"], "traffic": dom["traffic"]},
-                        "kernels_us": {k: _r(v.get("launch_us", v.get("single_launch_bracket_us"))) for k, v in r["kernels"].items()},
-                        "launch_floor_us": _r(r.get("launch_floor_us")), "frac_raw_form": _r(r.get("frac_raw_form")),
-                        "frac_host_result": _r(r.get("frac_host_result")), "frac_batch8": _r(r.get("frac_batch8")),
-                        "frac_batch32": _r(r.get("frac_batch32")), "frac_host_clock": _r(r.get("frac_host_clock")),
-                        "physical_GBps": _r(r.get("physical_GBps")), "traffic_source": (r.get("traffic_source") or "")[:60] or None}
+                        "scope": "one evaluation: B = 24N + 16HW + B_model (SURVEY 8d) / median step time"}
+    if "dominant" in r:  # --full: the per-kernel passes, the launch floor and the other forms' rows
+        dom = r["dominant"]
+        line["roofline"].update({
+            "dominant": {"kernel": dom["kernel"].split(" ")[0], "launch_us": _r(dom["launch_us"]), "frac": _r(dom["frac"]),
+                         "bytes": dom["algorithmic_bytes_per_launch"], "traffic": dom["traffic"]},
+            "kernels_us": {k: _r(v.get("launch_us", v.get("single_launch_bracket_us"))) for k, v in r["kernels"].items()},
+            "launch_floor_us": _r(r.get("launch_floor_us")), "frac_raw_form": _r(r.get("frac_raw_form")),
+            "frac_host_result": _r(r.get("frac_host_result")), "frac_batch8": _r(r.get("frac_batch8")),
+            "frac_batch32": _r(r.get("frac_batch32"))})
+    line["roofline"].update({"frac_host_clock": _r(r.get("frac_host_clock")), "physical_GBps": _r(r.get("physical_GBps")),
+                             "traffic_source": (r.get("traffic_source") or "")[:60] or None})
     line["timing_us"] = {k: _r(out["timing"][k] * 1e3) for k in ("min", "median", "max")}
     if "host_clock_median" in out["timing"]:  # (records of rounds 1-5 were timed with the host clock alone)
         line["timing_us"]["clock"] = "hip_events"
@@ -776,7 +823,8 @@ def compact_line(out, verbose_path):
                                       "threads_sweep": {k: _r(v) if not isinstance(v, str) else v[:40] for k, v in ct.get("threads_sweep", {}).items()}}
     if out.get("comm_probe"):
         line["comm_probe"] = out["comm_probe"]
-    line["verbose"] = os.path.relpath(verbose_path, ROOT) if os.path.isabs(verbose_path) else verbose_path
+    if verbose_path:  # (a plain run writes no full record unless --verbose-out names a file)
+        line["verbose"] = os.path.relpath(verbose_path, ROOT) if os.path.isabs(verbose_path) else verbose_path
     return line
 
 
@@ -828,21 +876,28 @@ def self_launch(args):
     raise SystemExit(subprocess.call(cmd, env=env))
 
 
-def main():
-    if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-torch-worker":
-        _cpu_torch_worker(sys.argv[2], int(sys.argv[3]), float(sys.argv[4]))
-        return
+ROW_WINDOWS = 12  # --full: timed windows of every other row (--windows sets the headline's alone)
+
+
+def parse_args(argv=None):
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=200)
+    ap.add_argument("--steps", type=int, default=200, help="timed evaluations of the headline (per window)")
     ap.add_argument("--warmup", type=int, default=20)
-    ap.add_argument("--windows", type=int, default=25, help="timed windows of --steps evaluations; the median window is reported")
+    ap.add_argument("--windows", type=int, default=1, help="timed windows of --steps evaluations for the headline; the median window is "
+                    "reported (default 1: exactly --steps timed evaluations)")
+    ap.add_argument("--full", action="store_true", help="besides the headline: the other configurations (`also`), per-kernel durations and "
+                    "the launch floor (instrumented passes), counter traffic of this run (rocprofv3 --pmc), the hipGraph replay rate, the CPU "
+                    "baselines and, for N > 1, the collectives probe; the full record goes to --verbose-out")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write what the headline's last timed step returned (result[8], "
+                    "gradient) as DIR/result.npy, DIR/grad.npy; on one GPU also DIR/iwe.npy, the handle's internal image of warped events "
+                    "read back after that step (not returned by the call)")
     ap.add_argument("--no-pin", action="store_true", help="do not pin the process to the CPUs of its GPU's NUMA node")
     ap.add_argument("--ramp", type=float, default=1.5, help="seconds of untimed evaluations after the warm-up steps, before the timed "
                     "windows (lets an idle GPU reach its clocks; 0 = none)")
     ap.add_argument("--workload", default="cfg2", choices=sorted(WORKLOADS))
-    ap.add_argument("--no-cpu-baseline", action="store_true")
-    ap.add_argument("--no-also", action="store_true", help="skip the other configurations (cfg3, cfg4, cfg5) reported under `also`")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baselines")
+    ap.add_argument("--no-also", action="store_true", help="--full: skip the other configurations (cfg3, cfg4, cfg5) reported under `also`")
     ap.add_argument("--events", default="uniform", choices=["uniform", "structured"])
     ap.add_argument("--backend", default="nccl", choices=["nccl", "gloo"],
                     help="torch.distributed backend for N > 1 (nccl = RCCL over xGMI; gloo only to exercise the N > 1 path on a 1-GPU box)")
@@ -854,12 +909,20 @@ def main():
                          "finished on the device; raw = cmax_objective_raw where the objective has that form (2-DoF), the consumer folds "
                          "the partial sums; host = cmax_objective_host (every step waits for its numbers)")
     ap.add_argument("--deterministic", action="store_true", help="cmax_set_deterministic(1): integer accumulation, bit-repeatable results (slower)")
-    ap.add_argument("--no-pmc", action="store_true", help="N = 1: do not re-execute the headline workload under rocprofv3 --pmc FETCH_SIZE / WRITE_SIZE "
-                    "for roofline.traffic (two short passes, ~40 s); the committed counter summary under profiles/ is replayed instead")
+    ap.add_argument("--no-pmc", action="store_true", help="--full, N = 1: do not re-execute the headline workload under rocprofv3 --pmc FETCH_SIZE / "
+                    "WRITE_SIZE for roofline.traffic (two short passes, ~40 s); the committed counter summary under profiles/ is replayed instead")
     ap.add_argument("--verbose", action="store_true", help="print the full record (per-kernel dictionaries, every row's windows: ~30 KB) instead "
-                    "of the compact line; the full record is written to --verbose-out either way")
-    ap.add_argument("--verbose-out", default=None, help="file for the full record (default gpurun_out/bench_verbose_<workload>_n<N>.json)")
-    args = ap.parse_args()
+                    "of the compact line")
+    ap.add_argument("--verbose-out", default=None, help="file for the full record (default with --full: bench_out/bench_verbose_<workload>_n<N>.json; "
+                    "without --full none is written unless this names one)")
+    return ap.parse_args(argv)
+
+
+def main():
+    if len(sys.argv) >= 5 and sys.argv[1] == "--cpu-torch-worker":
+        _cpu_torch_worker(sys.argv[2], int(sys.argv[3]), float(sys.argv[4]))
+        return
+    args = parse_args()
 
     if args.gpus > 1 and "WORLD_SIZE" not in os.environ:
         self_launch(args)
@@ -888,7 +951,7 @@ def main():
     host_affinity = None if args.no_pin else pin_to_gpu_numa_node(dev.index)
 
     also = {}
-    if not args.no_also:
+    if args.full and not args.no_also:
         # the other configurations, fewer steps (their evaluations are 2-10x longer); same timing protocol
         # N = 1: the other single-GPU configurations, cfg5 as BASELINE states it on ONE GPU (the N = 1 point of its strong-scaling
         # curve), a working set larger than the Infinity Cache, and the headline's second rows (blur; sharp image)
@@ -899,7 +962,7 @@ def main():
         for wname in names:
             # (the K-step contract binds the headline line only: these rows use windows of >= 50 evaluations, so that the barrier +
             # synchronize around a window -- ~20 us -- does not weigh on a 30 us evaluation; steps_per_window is reported per row)
-            r = run_workload(wname, args, rank, world, dev, max(50, args.steps // 2), max(3, args.warmup // 4), max(5, args.windows // 2))
+            r = run_workload(wname, args, rank, world, dev, max(50, args.steps // 2), max(3, args.warmup // 4), ROW_WINDOWS)
             dom = r.get("dominant")
             also[wname] = {"workload": r["workload"], "events_total": r["events_total"], "events_per_gpu": r["events_per_gpu"],
                            "ms_per_step": r["ms_per_step"], "value": r["value"], "unit": "events/s",
@@ -914,16 +977,17 @@ def main():
                            "physical_GBps": r.get("physical_GBps"), "host_clock_ms_per_step": r["window_ms_per_step"]["host_clock_median"],
                            "collectives": r["collectives"], "prepare_ms_once_per_batch": r["prepare_ms_once_per_batch"]}
 
-    # The headline row runs LAST, behind the other rows' ~40 s of GPU work (round 6): a process that starts on an idle box measures its
-    # first seconds in a lower power state -- the default command as the FIRST GPU process on a fresh box gave K1 / K3 7.3 / 7.1 us and
-    # 18.2 us per evaluation, the same command behind a test run 6.5 / 6.6 and 15.2 (gpurun_out/r06_bench_a / _b) -- and the 1.5 s ramp
-    # does not cover it.  Its own W warm-up steps and the ramp still precede its K timed steps.
-    main_res = run_workload(args.workload, args, rank, world, dev, args.steps, args.warmup, args.windows, keep_inputs=True)
+    # The headline row runs LAST: with --full, behind the other rows' ~40 s of GPU work (a process that starts on an idle box measures its
+    # first seconds in a lower power state; round 6 measured 18.2 us per evaluation as the first GPU process on a fresh box, 15.2 behind a
+    # test run).  Its own W warm-up steps, the ramp and the settle windows precede its K timed steps in either mode.
+    main_res = run_workload(args.workload, args, rank, world, dev, args.steps, args.warmup, args.windows, profile=args.full, keep_inputs=True,
+                            headline=True)
     cfg, ev, motion = main_res.pop("_inputs")
+    outputs = main_res.pop("_outputs", None)
 
     # roofline.traffic measured in THIS run (N = 1; the sub-runs pass --no-pmc): else the replayed summary of an earlier run
     pmc_traffic, pmc_note = None, None
-    if world == 1 and not args.no_pmc and not args.deterministic:
+    if args.full and world == 1 and not args.no_pmc and not args.deterministic:
         torch.cuda.synchronize()
         pmc_traffic, pmc_note = pmc_traffic_this_run(args.workload)
         if pmc_traffic:
@@ -935,7 +999,7 @@ def main():
             main_res["physical_GBps"] = ptotal / (main_res["ms_per_step"] * 1e-3) / 1e9
 
     comm_probe = None
-    if world > 1:
+    if args.full and world > 1:
         try:
             comm_probe = comm_probe_run(dev, world, rank, args)
         except Exception as e:  # never fail the bench line over a side figure (every rank takes the same path: the probe is collective)
@@ -943,8 +1007,6 @@ def main():
 
     if rank == 0:
         H, W, n = cfg["H"], cfg["W"], main_res["events_per_gpu"]
-        dom = main_res["dominant"]
-        kd = main_res["kernels"][dom]
         out = {
             "metric": "events/sec through warp+IWE+cost+grad (one objective evaluation)",
             "value": main_res["value"],
@@ -986,34 +1048,41 @@ def main():
                          "traffic": (sum(pmc_traffic.get(k, 0) for k in ("vote", "stats", "gimage", "grad", "finish")) if pmc_traffic else
                                      sum(v for v in (measured_traffic(args.workload, k) for k in ("vote", "stats", "gimage", "grad", "finish")) if v) or None),
                          "traffic_source": pmc_note if pmc_traffic else traffic_source(args.workload),
-                         "traffic_this_run_error": None if (pmc_traffic or args.no_pmc or world > 1) else pmc_note,
-                         "dominant": {"kernel": kd["kernel"], "achieved": kd["GBps"], "frac": kd["frac"], "launch_us": kd["launch_us"],
-                                      "algorithmic_bytes_per_launch": kd["algorithmic_bytes_per_launch"], "traffic": kd["traffic"]},
-                         "kernels": main_res["kernels"], "method": main_res["profile_method"]},
+                         "traffic_this_run_error": None if (pmc_traffic or args.no_pmc or world > 1) else pmc_note},
             "loss": main_res["loss"],
             "prepare_ms_once_per_batch": main_res["prepare_ms_once_per_batch"],
         }
+        if "dominant" in main_res:  # --full: the instrumented per-kernel passes
+            kd = main_res["kernels"][main_res["dominant"]]
+            out["roofline"].update({"dominant": {"kernel": kd["kernel"], "achieved": kd["GBps"], "frac": kd["frac"], "launch_us": kd["launch_us"],
+                                                 "algorithmic_bytes_per_launch": kd["algorithmic_bytes_per_launch"], "traffic": kd["traffic"]},
+                                    "kernels": main_res["kernels"], "method": main_res["profile_method"]})
         if also:
             out["also"] = also
-        if world == 1 and not args.deterministic and cfg["model"] == "2d-translation":
-            out["graph_replay"] = graph_replay_rate(cfg, ev, motion, dev, max(args.steps, 50), min(args.windows, 11))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.deterministic and cfg["model"] == "2d-translation":
+            out["graph_replay"] = graph_replay_rate(cfg, ev, motion, dev, max(args.steps, 50), 11)
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(cfg, ev, motion)
             tc = cpu_baseline_torch(args.workload, cfg, launch_affinity)
             if tc is not None:
                 out["cpu_baseline_torch"] = tc
         if comm_probe is not None:
             out["comm_probe"] = comm_probe
+        if outputs is not None:
+            dump_outputs(args.dump_outputs, outputs)
         # The full record goes to a file; stdout carries ONE compact line (the verbose line was ~30 KB and the driver
         # keeps the last 8 KB of stdout, so the rows for cfg3 / cfg4 / cfg5 / cfg5_strong / hbm never reached BENCH_r04.json).
-        vpath = args.verbose_out or os.path.join(ROOT, "gpurun_out", "bench_verbose_%s_n%d.json" % (args.workload, world))
-        try:
-            if os.path.dirname(vpath):  # (a bare file name has no directory part: makedirs('') raises)
-                os.makedirs(os.path.dirname(vpath), exist_ok=True)
-            with open(vpath, "w") as f:
-                json.dump(out, f)
-        except OSError as e:
-            vpath = "not written: %s" % e
+        vpath = args.verbose_out
+        if args.full and not vpath:
+            vpath = os.path.join(ROOT, "bench_out", "bench_verbose_%s_n%d.json" % (args.workload, world))
+        if vpath:
+            try:
+                if os.path.dirname(vpath):  # (a bare file name has no directory part: makedirs('') raises)
+                    os.makedirs(os.path.dirname(vpath), exist_ok=True)
+                with open(vpath, "w") as f:
+                    json.dump(out, f)
+            except OSError as e:
+                vpath = "not written: %s" % e
         print(json.dumps(out if args.verbose else compact_line(out, vpath)), flush=True)
     if world > 1:
         dist.barrier()

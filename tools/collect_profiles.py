@@ -72,8 +72,8 @@ for wl in ("cfg2", "cfg3", "cfg4", "cfg5", "cfg5_strong", "hbm"):
                            "per_wave:X = X / SQ_WAVES; lds_bank_conflict_rate = SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE" % wl,
                "kernels": json.load(open(f))}
         json.dump(doc, open(os.path.join(dst, "%s_sq_%s.json" % (tag, wl)), "w"), indent=1, sort_keys=True)
-for name, header in (("bench_deterministic.json", "# python bench.py --no-cpu-baseline --deterministic --steps 50 --windows 5 (cmax_set_deterministic: integer accumulation)\n"),
-                     ("bench_2ranks_shared_gpu.json", "# python bench.py --gpus 2 --share-gpu --backend gloo --steps 20 --warmup 5 --windows 5 --no-cpu-baseline: the N > 1 CODE PATH on a\n"
+for name, header in (("bench_deterministic.json", "# python bench.py --full --no-cpu-baseline --deterministic --steps 50 --windows 5 (cmax_set_deterministic: integer accumulation)\n"),
+                     ("bench_2ranks_shared_gpu.json", "# python bench.py --full --gpus 2 --share-gpu --backend gloo --steps 20 --warmup 5 --windows 5 --no-cpu-baseline: the N > 1 CODE PATH on a\n"
                                                      "# 1-GPU box (self-launched ranks, both on cuda:0, gloo + torch collectives because RCCL refuses two ranks per device).\n"
                                                      "# NOT a scaling number: two processes time-share one GPU and every all-reduce goes through the host.\n")):
     f = os.path.join(src, "refresh", name)

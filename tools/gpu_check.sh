@@ -1,13 +1,14 @@
 #!/bin/bash
-# Runs on the GPU box (via gpurun): smoke, GPU parity tests, bench.  Logs go to gpurun_out/.
-mkdir -p gpurun_out
-python __graft_entry__.py smoke > gpurun_out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 gpurun_out/smoke.log
-timeout 1200 python -m pytest tests -m gpu -q --maxfail=20 ${PYTEST_ARGS} > gpurun_out/pytest.log 2>&1; echo "pytest rc=$?"; tail -${PYTEST_TAIL:-15} gpurun_out/pytest.log
+# Runs on the GPU box: smoke, GPU parity tests, bench --full.  Logs go to $BENCH_LOGS (default bench_out/).
+out=${BENCH_LOGS:-bench_out}
+mkdir -p $out
+python __graft_entry__.py smoke > $out/smoke.log 2>&1; echo "smoke rc=$?"; tail -2 $out/smoke.log
+timeout 1200 python -m pytest tests -m gpu -q --maxfail=20 ${PYTEST_ARGS} > $out/pytest.log 2>&1; echo "pytest rc=$?"; tail -${PYTEST_TAIL:-15} $out/pytest.log
 for wl in ${WORKLOADS:-cfg2}; do
-  timeout 600 python bench.py --verbose --workload $wl --steps ${STEPS:-200} --warmup 20 ${BENCH_ARGS} > gpurun_out/bench_$wl.log 2>&1; echo "bench $wl rc=$?"
+  timeout 600 python bench.py --full --verbose --workload $wl --steps ${STEPS:-200} --warmup 20 ${BENCH_ARGS} > $out/bench_$wl.log 2>&1; echo "bench $wl rc=$?"
   python - <<PY
 import json
-for line in open("gpurun_out/bench_$wl.log"):
+for line in open("$out/bench_$wl.log"):
     if line.startswith("{"):
         d = json.loads(line)
         r = d["roofline"]
@@ -22,6 +23,6 @@ for line in open("gpurun_out/bench_$wl.log"):
                 a["dominant_kernel_frac"] or 0, {q: round(v, 1) for q, v in a["kernels_us"].items()}))
         break
 else:
-    print(open("gpurun_out/bench_$wl.log").read()[-2000:])
+    print(open("$out/bench_$wl.log").read()[-2000:])
 PY
 done
