@@ -1,33 +1,52 @@
-// Event kernels of the fused objective.  Included by cmax_fused.hip once per workgroup size (namespaces t256, t512,
-// t1024; CMAX_THREADS = 256 / 512 / 1024): a segment of up to 2040 events is processed by 256 threads x 8 events,
-// 512 x 4 or 1024 x 2.  The host picks 512 when there are more segments than the chip holds at once (measured:
-// cfg3/cfg5 -5..-15 % per evaluation, cfg2 +-0) and 1024 for the voxel K3 of such batches.  Everything here depends
-// on the workgroup size; shared helpers live in cmax_fused.hip.
-namespace CMAX_EVENT_NS {
+// Event kernels of the fused objective, templates over the segment layout L (EventLayout below: workgroup size, event slots,
+// LDS window).  A segment of up to 2040 events is processed by 256 threads x 8 events (t256), 512 x 4 (t512) or 1024 x 2 (t1024);
+// the mid (m512) and big (b512, b1024) layouts hold longer segments.  Which layout a launch takes is decided on the host, once per
+// kernel family (vote_layout, grad_layout, plain_layout in cmax_fused.hip).  Shared helpers live in cmax_fused.hip.
 
-constexpr int kThr = CMAX_THREADS;            // threads per workgroup of the event kernels
-constexpr int kNW = kThr / 64;                // waves per workgroup
-// CMAX_SLOTS: event slots per workgroup = the segment size of the host's work list + 8.  2048 (namespaces t256 / t512 / t1024), or
-// 4096 for BIG segments (b512 / b1024, round 3: batches of >= 8M events): twice the events behind one LDS window, one box reduction,
-// one window staging / flush and one segmented scan -- the per-thread fixed costs of K1 / K3 (~85 of ~300 VALU instructions per thread
-// at four events per thread) are spread over eight events.  4080 votes of 2^20 would overflow 31 bits: big segments vote in 13.19.
-constexpr int kSlots = CMAX_SLOTS;
-constexpr int kEPT = kSlots / kThr;           // events per thread (cached in registers between the two phases)
-constexpr int kSegMaxNS = kSlots - 8;         // events per segment
-constexpr bool kBig = kSlots > 2048;
-constexpr float kFixNS = kBig ? 524288.f : 1048576.f, kInvFixNS = 1.f / kFixNS;  // vote fixed point: 2^19 | 2^20
-constexpr int kAccExp = kBig ? 18 : 19;       // block-scaled flow-gradient accumulators: 2^(kAccExp - e), <= kSegMaxNS terms per cell
-static_assert(kEPT >= 2 && (kEPT % 2) == 0, "two events per 16-byte load");
-static_assert(kSlots == 2048 || kSlots == 3072 || kSlots == 4096, "segment sizes the host cuts");
-// The MID layout (namespace m512, round 4): 512 threads x 6 events = 3064 events per segment, FOUR source tiles (or five (tile, bin)
-// groups) wide, with a 6144-word window so that window + accumulators keep four workgroups per CU.  For batches whose standard cut
-// needs more workgroups than the chip holds at once (256 CUs x 4) while this one does not: the second round of a launch pays every
-// workgroup's ~2.5 us of start-up loads again (tools/timeline.py) -- cfg5's shard: 1693 workgroups in two rounds -> 900 in one.
-constexpr int kWinCap = CMAX_WINCAP;   // LDS window capacity in words (hides cmax::kWinCap inside this namespace)
-[[maybe_unused]] constexpr int kDummy = kWinCap;        // masked path: 64 per-lane scratch words behind the window
-constexpr int kAccDense = 256 * CMAX_ACC_TILES;         // flow-gradient accumulator cells per channel: owned dense segments span this many source tiles
-constexpr int kAccSmall = 256 * CMAX_ACC_SMALL_GROUPS;  // ... owned voxel segments of few, well-filled (tile, bin) groups (kGradOwnedSmall)
-static_assert((double)kSegMaxNS * kFixNS < 2147483648.0, "fixed-point vote accumulation would overflow");
+template <int THREADS, int SLOTS, int WINCAP, int ACC_TILES, int ACC_SMALL_GROUPS>
+struct EventLayout {
+    static constexpr int kThr = THREADS;  // threads per workgroup of the event kernels
+    static constexpr int kNW = kThr / 64;  // waves per workgroup
+    // SLOTS: event slots per workgroup = the segment size of the host's work list + 8.  2048 (t256 / t512 / t1024), or 4096 for BIG
+    // segments (b512 / b1024, round 3: batches of >= 8M events): twice the events behind one LDS window, one box reduction, one window
+    // staging / flush and one segmented scan -- the per-thread fixed costs of K1 / K3 (~85 of ~300 VALU instructions per thread at four
+    // events per thread) are spread over eight events.  4080 votes of 2^20 would overflow 31 bits: big segments vote in 13.19.
+    static constexpr int kSlots = SLOTS;
+    static constexpr int kEPT = kSlots / kThr;  // events per thread (cached in registers between the two phases)
+    static constexpr int kSegMaxNS = kSlots - 8;  // events per segment
+    static constexpr bool kBig = kSlots > 2048;
+    static constexpr float kFixNS = kBig ? 524288.f : 1048576.f, kInvFixNS = 1.f / kFixNS;  // vote fixed point: 2^19 | 2^20
+    static constexpr int kAccExp = kBig ? 18 : 19;  // block-scaled flow-gradient accumulators: 2^(kAccExp - e), <= kSegMaxNS terms per cell
+    static_assert(kEPT >= 2 && (kEPT % 2) == 0, "two events per 16-byte load");
+    static_assert(kSlots == 2048 || kSlots == 3072 || kSlots == 4096, "segment sizes the host cuts");
+    // The MID layout (m512, round 4): 512 threads x 6 events = 3064 events per segment, FOUR source tiles (or five (tile, bin) groups)
+    // wide, with a 6144-word window so that window + accumulators keep four workgroups per CU.  For batches whose standard cut needs more
+    // workgroups than the chip holds at once (256 CUs x 4) while this one does not: the second round of a launch pays every workgroup's
+    // ~2.5 us of start-up loads again (tools/timeline.py) -- cfg5's shard: 1693 workgroups in two rounds -> 900 in one.
+    static constexpr int kWinCap = WINCAP;  // LDS window capacity in words
+    static constexpr int kDummy = kWinCap;  // masked path: 64 per-lane scratch words behind the window
+    static constexpr int kAccDense = 256 * ACC_TILES;  // flow-gradient accumulator cells per channel: owned dense segments span this many source tiles
+    static constexpr int kAccSmall = 256 * ACC_SMALL_GROUPS;  // ... owned voxel segments of few, well-filled (tile, bin) groups (kGradOwnedSmall)
+    static_assert((double)kSegMaxNS * kFixNS < 2147483648.0, "fixed-point vote accumulation would overflow");
+    static constexpr int kBlkShift = kBig ? 6 : 5;  // Window::bmask: one bit per kSlots / 64 consecutive slots (see phase_warp)
+    static constexpr int kShiftWords = kSlots / 8;  // 32-bit words of cell offsets per (reference time, segment): 8 slots per word
+    // compact events (see EventLoads), bytes
+    static constexpr int kCompactPix = 4 * kSlots, kCompactHdr = 4 * kSlots + kSlots / 2, kCompactStride = kCompactHdr + 64;
+    // K1's second launch bound (see k_vote)
+    static constexpr int kVoteWaves = (kBig && kThr == 512) ? 8 : 1;
+    // k_vote_tan2: window pixels per plane (3 planes + scratch = the window + 200 words of k_vote), and the tangent planes' fixed
+    // point, 2^18 (big segments: 2^17)
+    static constexpr int kTanCap = kWinCap == 8192 ? 2720 : kWinCap / 3 - 8;
+    static constexpr float kTanFix = kBig ? 131072.f : 262144.f, kTanInvFix = 1.f / kTanFix;
+};
+// The layouts: distinct types, so that a kernel's name says which one it was compiled for (cmax::k_grad<cmax::t512, ...>).
+enum class Layout { t256, t512, t1024, m512, b512, b1024 };
+struct t256 : EventLayout<256, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t256; };
+struct t512 : EventLayout<512, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t512; };
+struct t1024 : EventLayout<1024, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t1024; };
+struct m512 : EventLayout<512, 3072, 6144, 4, 5> { static constexpr Layout kId = Layout::m512; };  // mid segments (3064 events, cmax_handle_s::mid)
+struct b512 : EventLayout<512, 4096, 8192, 6, 3> { static constexpr Layout kId = Layout::b512; };  // big segments (4088 events, cmax_handle_s::big)
+struct b1024 : EventLayout<1024, 4096, 8192, 6, 3> { static constexpr Layout kId = Layout::b1024; };
 
 // Phase A of both event kernels: warp this thread's <= kEPT events (kept in registers), reduce the
 // bounding box of their top-left vote corners over the workgroup and derive the LDS window.
@@ -47,8 +66,7 @@ static_assert((double)kSegMaxNS * kFixNS < 2147483648.0, "fixed-point vote accum
 // cells in fp64 and publishes what K3 needs to follow it WITHOUT any fp64 arithmetic of its own: the 64-bit Window::bmask (which
 // 1/64ths of the segment's slots hold an event whose cell moved) and, in the segment's `shifts` words, a nibble per slot = the cell's
 // offset from the fp32 one (row | col << 2, two-bit two's complement).  `nibbles` returns this thread's own (slot u in bits [4u, 4u + 4)).
-constexpr int kBlkShift = kBig ? 6 : 5;        // Window::bmask: one bit per kSlots / 64 consecutive slots
-constexpr int kShiftWords = kSlots / 8;        // 32-bit words of cell offsets per (reference time, segment): 8 slots per word
+//
 // The event loads of a workgroup, issued FIRST THING in a kernel: they need nothing but the segment and the event pointer, both of
 // which a workgroup holds without having seen the kernel's argument block (kernel parameters, k_vote) -- everything that reads the
 // argument block is then fetched while the events are on their way (a workgroup's first dependent loads are ~3 of the ~6 us it
@@ -74,29 +92,29 @@ constexpr int kShiftWords = kSlots / 8;        // 32-bit words of cell offsets p
 // K1), every thread's loads are 32- / 16-byte aligned whatever the segment's first event, and their addresses depend on the
 // workgroup's index alone -- they are issued before the segment descriptor has arrived (one dependent round trip less at the head
 // of K1 and K3).  The 8-byte array stays: the time residual byte (exact cells), re-binning, the tangent / search kernels read it.
-constexpr int kCompactPix = 4 * kSlots, kCompactHdr = 4 * kSlots + kSlots / 2, kCompactStride = kCompactHdr + 64;  // bytes
+template <class L>
 struct EventLoads {
-    uint4 raw[kEPT / 2];  // 8-byte format: kEPT / 2 event pairs; compact: tau in raw[0 .. kEPT / 4), pix behind it
+    uint4 raw[L::kEPT / 2];  // 8-byte format: kEPT / 2 event pairs; compact: tau in raw[0 .. kEPT / 4), pix behind it
     bool wave_live;  // this wave holds events (wave-uniform)
     bool compact;    // launch-uniform
     unsigned basexy; // compact: the region's header word
 };
-template <bool STRIDED>
-__device__ __forceinline__ void issue_event_loads(const uint2 *__restrict__ evp, const char *__restrict__ cev, int sidx, int4 sg, EventLoads &el) {
-    auto local_index = [](int u) { return STRIDED ? 2 * ((u >> 1) * kThr + (int)threadIdx.x) + (u & 1) : kEPT * (int)threadIdx.x + u; };
+template <class L, bool STRIDED>
+__device__ __forceinline__ void issue_event_loads(const uint2 *__restrict__ evp, const char *__restrict__ cev, int sidx, int4 sg, EventLoads<L> &el) {
+    auto local_index = [](int u) { return STRIDED ? 2 * ((u >> 1) * L::kThr + (int)threadIdx.x) + (u & 1) : L::kEPT * (int)threadIdx.x + u; };
     const int odd = sg.x & 1, cnt = sg.y;
     el.compact = false;
     el.basexy = 0u;
-    if constexpr (kBig && !STRIDED && (kEPT % 4) == 0) {
+    if constexpr (L::kBig && !STRIDED && (L::kEPT % 4) == 0) {
         if (cev != nullptr) {  // launch-uniform (a kernel parameter: known before the first load)
-            const char *reg = cev + (int64_t)sidx * kCompactStride;
-            const char *tp = reg + 4 * kEPT * (int)threadIdx.x;
+            const char *reg = cev + (int64_t)sidx * L::kCompactStride;
+            const char *tp = reg + 4 * L::kEPT * (int)threadIdx.x;
 #pragma unroll
-            for (int j = 0; j < kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
+            for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
 #pragma unroll
-            for (int j = 0; j < kEPT / 4; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(tp + 16 * j);
-            el.raw[kEPT / 4].x = *reinterpret_cast<const unsigned *>(reg + kCompactPix + 4 * ((kEPT * (int)threadIdx.x) >> 3));  // 8 nibbles per word
-            el.basexy = *reinterpret_cast<const unsigned *>(reg + kCompactHdr);
+            for (int j = 0; j < L::kEPT / 4; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(tp + 16 * j);
+            el.raw[L::kEPT / 4].x = *reinterpret_cast<const unsigned *>(reg + L::kCompactPix + 4 * ((L::kEPT * (int)threadIdx.x) >> 3));  // 8 nibbles per word
+            el.basexy = *reinterpret_cast<const unsigned *>(reg + L::kCompactHdr);
             el.compact = true;
             el.wave_live = __builtin_amdgcn_readfirstlane(local_index(0)) < cnt + odd;
             return;
@@ -115,21 +133,22 @@ __device__ __forceinline__ void issue_event_loads(const uint2 *__restrict__ evp,
     // memory at the head of K1 and K3.)
     const int l_last = (cnt + odd - 1) & ~1;  // local index of the segment's last pair
 #pragma unroll
-    for (int j = 0; j < kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
+    for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
     if (el.wave_live) {  // wave-uniform
 #pragma unroll
-        for (int j = 0; j < kEPT / 2; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(seg_ev + min(local_index(2 * j), l_last));
+        for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(seg_ev + min(local_index(2 * j), l_last));
     }
 }
 // word k (0 .. 3) of a 16-byte register quadruple, k a compile-time constant after unrolling
 __device__ __forceinline__ unsigned quad_word(const uint4 &q, int k) { return k == 0 ? q.x : (k == 1 ? q.y : (k == 2 ? q.z : q.w)); }
 // slot u of a thread's events, decoded for the warp (EvDec), whichever way they were loaded.  negd = minus the reference time, in a VGPR (tau - d is
 // rounded once either way: the compact time is an exact fp32 multiple of 2^-24, so the fma rounds what the subtraction would).
-__device__ __forceinline__ EvDec decode_slot(const EventLoads &el, int u, float negd, bool voxel) {
+template <class L>
+__device__ __forceinline__ EvDec decode_slot(const EventLoads<L> &el, int u, float negd, bool voxel) {
     EvDec e;
-    if (kBig && el.compact) {
+    if (L::kBig && el.compact) {
         const unsigned a = quad_word(el.raw[u >> 2], u & 3);
-        const unsigned tcol = __builtin_amdgcn_ubfe(el.raw[kEPT / 4].x, 4 * (((kEPT * (int)threadIdx.x) & 7) + u), 3);
+        const unsigned tcol = __builtin_amdgcn_ubfe(el.raw[L::kEPT / 4].x, 4 * (((L::kEPT * (int)threadIdx.x) & 7) + u), 3);
         e.ixr = __builtin_amdgcn_ubfe(a, 4, 4);
         e.iyr = (tcol << 4) | (a & 15u);
         e.top = 0u;
@@ -147,10 +166,9 @@ __device__ __forceinline__ EvDec decode_slot(const EventLoads &el, int u, float 
     return e;
 }
 
-// One workgroup per segment: writes the segment's compact region (see EventLoads).  A template so that only the namespaces that
-// launch it carry it.
-template <int DUMMY>
-__global__ void __launch_bounds__(kThr) k_pack_compact(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, int ntc, char *__restrict__ cev, int *__restrict__ bad) {
+// One workgroup per segment: writes the segment's compact region (see EventLoads).
+template <class L>
+__global__ void __launch_bounds__(L::kThr) k_pack_compact(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, int ntc, char *__restrict__ cev, int *__restrict__ bad) {
     const int sidx = blockIdx.x;
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
@@ -158,11 +176,11 @@ __global__ void __launch_bounds__(kThr) k_pack_compact(const int4 *__restrict__ 
     const int trow = sg.z / ntc, tcol = sg.z - trow * ntc;
     const unsigned base_r = 16u * (unsigned)trow, base_c = 16u * (unsigned)tcol;
     const uint2 *seg_ev = evp + ((int64_t)sg.x - odd);
-    char *reg = cev + (int64_t)sidx * kCompactStride;
-    unsigned *out = reinterpret_cast<unsigned *>(reg), *tiles = reinterpret_cast<unsigned *>(reg + kCompactPix);
-    if (threadIdx.x < 16) reinterpret_cast<unsigned *>(reg + kCompactHdr)[threadIdx.x] = threadIdx.x == 0 ? (base_r | (base_c << 12)) : 0u;
+    char *reg = cev + (int64_t)sidx * L::kCompactStride;
+    unsigned *out = reinterpret_cast<unsigned *>(reg), *tiles = reinterpret_cast<unsigned *>(reg + L::kCompactPix);
+    if (threadIdx.x < 16) reinterpret_cast<unsigned *>(reg + L::kCompactHdr)[threadIdx.x] = threadIdx.x == 0 ? (base_r | (base_c << 12)) : 0u;
     bool wrong = false;
-    for (int w = threadIdx.x; w < kSlots / 8; w += kThr) {  // eight slots = one word of tile nibbles per iteration
+    for (int w = threadIdx.x; w < L::kSlots / 8; w += L::kThr) {  // eight slots = one word of tile nibbles per iteration
         unsigned nib = 0u, v[8];
 #pragma unroll
         for (int q = 0; q < 8; ++q) {
@@ -185,15 +203,15 @@ __global__ void __launch_bounds__(kThr) k_pack_compact(const int4 *__restrict__ 
     if (wrong) atomicOr(bad, 1);  // (never: a segment lies in one tile row and spans <= 6 tiles; checked by the host in debug runs)
 }
 
-template <int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, typename Init>
-__device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams &wp, int4 sg, EventLoads &el, unsigned (&rc)[kEPT],
-                                              float (&fa)[kEPT], float (&fb)[kEPT], float (&fdt)[kEPT], int (&fsrc)[kEPT],
+template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, typename Init>
+__device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams &wp, int4 sg, EventLoads<L> &el, unsigned (&rc)[L::kEPT],
+                                              float (&fa)[L::kEPT], float (&fb)[L::kEPT], float (&fdt)[L::kEPT], int (&fsrc)[L::kEPT],
                                               uint4 *s_box, const int4 *known, const unsigned *__restrict__ shifts, Init init, bool &wave_live,
                                               unsigned &nibbles) {
     constexpr bool kExact = MODEL >= 0;  // cells of events on a cell border are decided in fp64 (warp_exact); the un-warped image has no motion
     constexpr bool kFlow = MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL;
     static_assert(!(KNOWN && !WANT_DT), "K3 re-uses K1's windows");
-    auto local_index = [](int u) { return STRIDED ? 2 * ((u >> 1) * kThr + (int)threadIdx.x) + (u & 1) : kEPT * (int)threadIdx.x + u; };
+    auto local_index = [](int u) { return STRIDED ? 2 * ((u >> 1) * L::kThr + (int)threadIdx.x) + (u & 1) : L::kEPT * (int)threadIdx.x + u; };
     const int odd = sg.x & 1, cnt = sg.y;
     const int64_t first = (int64_t)sg.x - odd;
     const uint2 *seg_ev = ev.ev + first;
@@ -203,8 +221,8 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     eb.col = el.basexy >> 12;
     eb.src = mul24_u(eb.row, (unsigned)wp.W & 0xFFFFFFu) + eb.col;
     float negd = -wp.d;
-    if (kBig) asm volatile("" : "+v"(negd));  // (one VGPR for the whole loop: as an SGPR it is copied in front of every event's fma, whose other operands are scalar too)
-    const uint4 (&raw)[kEPT / 2] = el.raw;
+    if (L::kBig) asm volatile("" : "+v"(negd));  // (one VGPR for the whole loop: as an SGPR it is copied in front of every event's fma, whose other operands are scalar too)
+    const uint4 (&raw)[L::kEPT / 2] = el.raw;
     const double period = wp.normalize ? 1.0 : wp.tmm[1] - wp.tmm[0];
     const float tscale = (float)period;  // (time_scale)
     const float mcoef = exact_margin_coef(wp.d, tscale);
@@ -249,10 +267,10 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     constexpr bool kMaskInside = KNOWN;
     unsigned mnp = 0xFFFFFFFFu;  // minima of (row, col) as packed u16 (v_pk_min_u16); complemented into mnq behind the loop
     const int wl0 = __builtin_amdgcn_readfirstlane(local_index(0));
-    const bool wave_full = !STRIDED && wl0 >= odd && wl0 + kWave * kEPT - odd <= cnt;  // (wave-uniform)
+    const bool wave_full = !STRIDED && wl0 >= odd && wl0 + kWave * L::kEPT - odd <= cnt;  // (wave-uniform)
     if (!wave_live) {  // wave-uniform
 #pragma unroll
-        for (int u = 0; u < kEPT; ++u) {
+        for (int u = 0; u < L::kEPT; ++u) {
             rc[u] = 0u;
             fa[u] = 0.f;
             fb[u] = 0.f;
@@ -268,10 +286,10 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
         // segment's first) -- they get a copy of their pair's other, valid event; whatever that adds to the box is a cell the segment
         // votes into anyway.  Here, where the loads are consumed (not behind their issue: that would put a wait in front of every load
         // that follows), and in the waves that hold such a slot only.
-        if (!kMaskInside && !wave_full && !(kBig && el.compact)) {  // wave-uniform
+        if (!kMaskInside && !wave_full && !(L::kBig && el.compact)) {  // wave-uniform
             const int end = cnt + odd, l_last = (end - 1) & ~1;
 #pragma unroll
-            for (int j = 0; j < kEPT / 2; ++j) {
+            for (int j = 0; j < L::kEPT / 2; ++j) {
                 if (min(local_index(2 * j), l_last) + 1 >= end) {
                     el.raw[j].z = el.raw[j].x;
                     el.raw[j].w = el.raw[j].y;
@@ -283,20 +301,18 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
             }
         }
 #pragma unroll
-        for (int u = 0; u < kEPT; ++u) {
+        for (int u = 0; u < L::kEPT; ++u) {
             const int l = local_index(u);
             // kMaskInside (K3) | fractional batches (guards the residual loads): the slot's validity, here; else every slot is warped
             const bool valid = (!kMaskInside && !FRAC) || (unsigned)(l - odd) < (unsigned)cnt;
-            const EvDec e = decode_slot(el, u, negd, MODEL == CMAX_MODEL_VOXEL);
+            const EvDec e = decode_slot<L>(el, u, negd, MODEL == CMAX_MODEL_VOXEL);
             // empty slots run the same arithmetic on a zero event (finite values, in-bounds flow reads)
             const Warped w = warp_one<MODEL, FRAC>(ev, e, eb, first + l, valid, wp, tscale, th0, th1);
-#ifndef CMAX_NO_EXACT_CELLS  // (A/B builds only: profiles/r03_ablation.txt, r04_ablation.txt)
             if (kExact && !KNOWN) {
                 amin = fminf(fminf(amin, w.a), w.b);
                 amax = fmaxf(fmaxf(amax, w.a), w.b);
                 if (kFlow) fmt = fmaxf(fmaxf(fmt, fabsf(w.f0)), fabsf(w.f1));
             }
-#endif
             const unsigned packed = ((unsigned)(w.row + 16384) << 16) | (unsigned)(w.col + 16384);
             rc[u] = (kMaskInside && !valid) ? 0u : packed;
             fa[u] = w.a;
@@ -313,7 +329,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
         }
         if (!kMaskInside && !wave_full) {  // wave-uniform: the one wave of a segment that holds its end (and wave 0 of an odd start)
 #pragma unroll
-            for (int u = 0; u < kEPT; ++u) {
+            for (int u = 0; u < L::kEPT; ++u) {
                 const bool valid = (unsigned)(local_index(u) - odd) < (unsigned)cnt;
                 rc[u] = valid ? rc[u] : 0u;
                 if (WANT_DT) fdt[u] = valid ? fdt[u] : 0.f;
@@ -323,7 +339,6 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     if (KNOWN) {
         // K3: the few threads whose 1/64th of the segment holds an event K1 moved to another cell fetch the offsets and apply them.
         // The fractions follow: x' is the same number, a = x' - cell.  (No fp64, no second look at the flow: K1 decided.)
-#ifndef CMAX_NO_EXACT_CELLS
         if (kExact && win.border && wave_live) {  // workgroup-uniform && wave-uniform
             auto apply = [&](int u, unsigned nib) {
                 const int sr = (int)(nib << 30) >> 30, sc = (int)(nib << 28) >> 30;
@@ -333,9 +348,9 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
             };
             if (STRIDED) {
 #pragma unroll
-                for (int j = 0; j < kEPT / 2; ++j) {
+                for (int j = 0; j < L::kEPT / 2; ++j) {
                     const int l = local_index(2 * j);
-                    if (((win.bmask >> (l >> kBlkShift)) & 1ull) == 0ull) continue;
+                    if (((win.bmask >> (l >> L::kBlkShift)) & 1ull) == 0ull) continue;
                     const unsigned nb = (shifts[l >> 3] >> ((l & 7) * 4)) & 0xFFu;
                     if (nb & 0xFu) apply(2 * j, nb & 0xFu);
                     if (nb >> 4) apply(2 * j + 1, nb >> 4);
@@ -343,16 +358,16 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
             } else {
                 // a thread's kEPT consecutive slots lie in one word of eight nibbles, or (six events per thread) straddle two; likewise
                 // they lie in one or two of the segment's 64ths
-                const int l0 = local_index(0), l1 = l0 + kEPT - 1;
+                const int l0 = local_index(0), l1 = l0 + L::kEPT - 1;
                 // (a word is valid only where ITS OWN 64th is flagged: K1 clears the words of flagged blocks only, ADVICE r4)
-                const bool blk0 = ((win.bmask >> (l0 >> kBlkShift)) & 1ull) != 0ull, blk1 = ((win.bmask >> (l1 >> kBlkShift)) & 1ull) != 0ull;
+                const bool blk0 = ((win.bmask >> (l0 >> L::kBlkShift)) & 1ull) != 0ull, blk1 = ((win.bmask >> (l1 >> L::kBlkShift)) & 1ull) != 0ull;
                 if (blk0 || blk1) {
                     unsigned long long nb = blk0 ? shifts[l0 >> 3] : 0u;
                     if ((l1 >> 3) != (l0 >> 3) && blk1) nb |= (unsigned long long)shifts[l1 >> 3] << 32;
                     nb >>= (l0 & 7) * 4;
-                    if (kEPT < 16 && (nb & ((1ull << (4 * kEPT)) - 1ull)) != 0ull) {
+                    if (L::kEPT < 16 && (nb & ((1ull << (4 * L::kEPT)) - 1ull)) != 0ull) {
 #pragma unroll
-                        for (int u = 0; u < kEPT; ++u) {
+                        for (int u = 0; u < L::kEPT; ++u) {
                             const unsigned nib = (unsigned)(nb >> (4 * u)) & 0xFu;
                             if (nib) apply(u, nib);
                         }
@@ -360,31 +375,19 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
                 }
             }
         }
-#endif
         return win;
     }
-    if (!WANT_DT) CMAX_STAMP_AFTER(0, 1, rc[kEPT - 1]);  // (K1: events and flows have arrived, the warp arithmetic is done)
+    if (!WANT_DT) CMAX_STAMP_AFTER(0, 1, rc[L::kEPT - 1]);  // (K1: events and flows have arrived, the warp arithmetic is done)
     bool thread_exact = false;  // this thread moved one of its events to another cell than the fp32 arithmetic found
-#ifndef CMAX_NO_EXACT_CELLS
     if (kExact) {
         const float mthr = kFlow ? exact_margin<FRAC>(mcoef, fmt) : mt;  // at least as wide as the margin of each of this thread's events
-        bool border = amin < mthr || amax > 1.f - 1e-6f - mthr;
-#ifdef CMAX_AB_NOTRACK_FLOW  // (A/B builds only)
-        if (kFlow) border = false;
-#endif
-#ifdef CMAX_AB_RUNTIME_OFF  // (A/B builds only: the re-warp compiled in, never taken)
-        border = border && wp.T == 12345;
-#endif
-#ifdef CMAX_AB_NOSLOW  // (A/B builds only: the tracking and the published mask without the re-warp)
-        thread_exact = border;
-        border = false;
-#endif
+        const bool border = amin < mthr || amax > 1.f - 1e-6f - mthr;
         if (border) {  // rare (about one wave in a hundred): see warp_exact
             // Which slots?  From registers alone: every load below is a round trip to memory in front of the workgroup's next barrier.
             const float mhi = 1.f - 1e-6f - mthr;
             unsigned cand = 0u;
 #pragma unroll
-            for (int u = 0; u < kEPT; ++u)
+            for (int u = 0; u < L::kEPT; ++u)
                 if (rc[u] != 0u && (fa[u] < mthr || fa[u] > mhi || fb[u] < mthr || fb[u] > mhi)) cand |= 1u << u;
             // ONE copy of the re-warp, a rolled loop over the candidate slots (typically one): unrolled per slot it was kEPT copies of
             // ~150 instructions between the warp loop and the box reduction, and K1 paid for their mere presence (20M events: 39 -> 44 us
@@ -396,7 +399,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
                 unsigned rcu = rc[0];
                 float fau = fa[0], fbu = fb[0];
 #pragma unroll
-                for (int k = 1; k < kEPT; ++k) {
+                for (int k = 1; k < L::kEPT; ++k) {
                     rcu = u == k ? rc[k] : rcu;
                     fau = u == k ? fa[k] : fau;
                     fbu = u == k ? fb[k] : fbu;
@@ -404,13 +407,13 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
                 // the packed event again (eight events per thread: loaded again -- keeping them in registers for this rare path would cost
                 // every thread 16 VGPRs and the kernel a wave per SIMD) and its time beyond fp32: the residual in the packed word's top byte,
                 // or (binned handles: that byte is the voxel bin) the fp64 array, both loads in flight together
-                const int l = STRIDED ? 2 * ((u >> 1) * kThr + (int)threadIdx.x) + (u & 1) : kEPT * (int)threadIdx.x + u;
+                const int l = STRIDED ? 2 * ((u >> 1) * L::kThr + (int)threadIdx.x) + (u & 1) : L::kEPT * (int)threadIdx.x + u;
                 uint2 e;
-                if (kEPT <= 4 && !(kBig && el.compact)) {  // four events per thread: the packed events stay in registers (8 VGPRs these kernels have to spare) --
+                if (L::kEPT <= 4 && !(L::kBig && el.compact)) {  // four events per thread: the packed events stay in registers (8 VGPRs these kernels have to spare) --
                     // one round trip less in front of the barrier, and at one round of workgroups per launch the slowest workgroup IS the kernel
                     e = make_uint2(raw[0].x, raw[0].y);
 #pragma unroll
-                    for (int k = 1; k < kEPT; ++k) {
+                    for (int k = 1; k < L::kEPT; ++k) {
                         const uint2 ek = (k & 1) ? make_uint2(raw[k >> 1].z, raw[k >> 1].w) : make_uint2(raw[k >> 1].x, raw[k >> 1].y);
                         e.x = u == k ? ek.x : e.x;
                         e.y = u == k ? ek.y : e.y;
@@ -438,7 +441,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
                 const int sr = (int)(packed >> 16) - (int)(rcu >> 16), sc = (int)(packed & 0xFFFFu) - (int)(rcu & 0xFFFFu);
                 nibbles |= ((unsigned)(sr & 3) | ((unsigned)(sc & 3) << 2)) << (4 * u);
 #pragma unroll
-                for (int k = 0; k < kEPT; ++k) {
+                for (int k = 0; k < L::kEPT; ++k) {
                     rc[k] = u == k ? packed : rc[k];
                     fa[k] = u == k ? w.a : fa[k];
                     fb[k] = u == k ? w.b : fb[k];
@@ -449,7 +452,6 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
             thread_exact = nibbles != 0u;
         }
     }
-#endif
     // wave reduction on the VALU: 4 row shifts, then lane 15 of each row to the next row, lane 31 to rows 2-3;
     // lane 63 ends up with the wave's box
     mnq = ~mnp;
@@ -471,8 +473,8 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
         while (bal != 0ull) {  // wave-uniform
             const int ln = __builtin_ctzll(bal);
             bal &= bal - 1ull;
-            wave_mask |= 1ull << ((kEPT * (wave_first + ln)) >> kBlkShift);
-            wave_mask |= 1ull << ((kEPT * (wave_first + ln) + kEPT - 1) >> kBlkShift);  // (six events per thread can straddle two 64ths)
+            wave_mask |= 1ull << ((L::kEPT * (wave_first + ln)) >> L::kBlkShift);
+            wave_mask |= 1ull << ((L::kEPT * (wave_first + ln) + L::kEPT - 1) >> L::kBlkShift);  // (six events per thread can straddle two 64ths)
         }
     }
     if ((threadIdx.x & (kWave - 1)) == kWave - 1) s_box[threadIdx.x / kWave] = make_uint4(mnq, mxp, (unsigned)wave_mask, (unsigned)(wave_mask >> 32));
@@ -481,7 +483,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     const uint2 *s_b2 = reinterpret_cast<const uint2 *>(s_box);
     uint2 bx = s_b2[0];
 #pragma unroll
-    for (int wv = 1; wv < kNW; ++wv) {
+    for (int wv = 1; wv < L::kNW; ++wv) {
         const uint2 o = s_b2[2 * wv];
         bx.x = pk_max_u16(bx.x, o.x);
         bx.y = pk_max_u16(bx.y, o.y);
@@ -495,7 +497,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     if (kExact && threadIdx.x < kWave) {  // wave-uniform
         unsigned mz = 0u, mw = 0u;
 #pragma unroll
-        for (int wv = 0; wv < kNW; ++wv) {
+        for (int wv = 0; wv < L::kNW; ++wv) {
             mz |= s_box[wv].z;
             mw |= s_box[wv].w;
         }
@@ -510,7 +512,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
         const bool any = bmx != 0u;
         const int h = any ? bmxr - bmnr + 2 : 0, w = any ? bmxc - bmnc + 2 : 0;
         const int stride = window_stride(w);
-        if (w <= kWinMaxW && h * stride <= kWinCap) {
+        if (w <= kWinMaxW && h * stride <= L::kWinCap) {
             win.r0 = any ? bmnr : 0;
             win.c0 = any ? bmnc : 0;
             win.h = h;
@@ -531,7 +533,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
         w = kWinMaxW;
     }
     const int stride = window_stride(w);
-    const int hmax = kWinCap / stride;
+    const int hmax = L::kWinCap / stride;
     if (h > hmax) {
         r0 += (h - hmax) / 2;
         h = hmax;
@@ -569,23 +571,18 @@ __device__ __forceinline__ int fast_index(unsigned rc, unsigned neg_origin, int 
 // (second launch bound = waves per SIMD the register allocation has to leave room for: the 512 x 8 kernel of the big segments sat at 68
 // VGPRs -- seven waves -- once the border tracking joined its warp loop; scheduled for 64 it keeps eight: K1 of 20M events 46.2 -> see
 // profiles/r04_ablation.txt)
-#ifdef CMAX_AB_NO_VOTE_BOUND  // (A/B builds only)
-constexpr int kVoteWaves = 1;
-#else
-constexpr int kVoteWaves = (kBig && kThr == 512) ? 8 : 1;
-#endif
-template <int MODEL, bool FRAC, bool MU = false>
-__global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra) {
-    __shared__ int s_win[kWinCap + kScratch];
-    __shared__ uint4 s_box[kNW];
+template <class L, int MODEL, bool FRAC, bool MU = false>
+__global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra) {
+    __shared__ int s_win[L::kWinCap + kScratch];
+    __shared__ uint4 s_box[L::kNW];
     CMAX_STAMP(0, 0);
     // first thing: this workgroup's segment (segs, nseg and evp arrive in SGPRs: the load does not wait for the argument block)
     const int sidx = segment_of_block(nseg);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
     ev.ev = evp;
-    EventLoads el;
-    issue_event_loads<false>(evp, cev, sidx, sg, el);
+    EventLoads<L> el;
+    issue_event_loads<L, false>(evp, cev, sidx, sg, el);
     wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = ra.d_lo[blockIdx.y];  // (read by warp_exact only: the compiler sinks this scalar load into that rare path)
     wp.motion += (int64_t)blockIdx.z * ra.z_motion;  // blockIdx.z = candidate motion (cmax_objective_batch; one candidate otherwise)
@@ -598,19 +595,19 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
     unsigned *const shifts_base = ra.shifts;
     const int windows_only = ra.windows_only;
     asm volatile("" ::"s"(win_base), "s"(shifts_base), "s"(windows_only));
-    unsigned rc[kEPT];
-    float fa[kEPT], fb[kEPT], fdt[kEPT];
-    int fsrc[kEPT];
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
     bool live;  // this wave holds events (wave-uniform)
     unsigned nibbles;  // cell offsets of the events this thread decided in fp64 (phase_warp)
-    const Window win = phase_warp<MODEL, FRAC, false>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, MODEL, FRAC, false>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
-        for (int i = threadIdx.x; i < wn; i += kThr) s_win[i] = 0;
+        for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
     }, live, nibbles);
     CMAX_STAMP(0, 3);
     if (ra.grad_zero && blockIdx.y == 0 && blockIdx.z == 0) {  // launch-uniform: this workgroup's slice of the gradient buffer K3 will add into (write-through)
         const int64_t chunk4 = (ra.n_grad_zero4 + nseg - 1) / nseg, q1 = min(ra.n_grad_zero4, (int64_t)(sidx + 1) * chunk4);
-        for (int64_t q = (int64_t)sidx * chunk4 + threadIdx.x; q < q1; q += kThr) store_zero4_sc1(reinterpret_cast<float *>(ra.grad_zero + q));
+        for (int64_t q = (int64_t)sidx * chunk4 + threadIdx.x; q < q1; q += L::kThr) store_zero4_sc1(reinterpret_cast<float *>(ra.grad_zero + q));
     }
     if (blockIdx.x == 0) {  // (behind the event loads: their pointers come out of the argument block, and a wait for it at the head of the
         // kernel stood in front of every workgroup's first load)
@@ -624,11 +621,11 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
     }
     // for K3 of the same evaluation: the window, and -- rare -- the cell offsets of the events that were decided in fp64.  The words of
     // the 1/64ths of the segment that Window::bmask names are cleared here and filled behind the barrier below (the others are never read)
-    unsigned *__restrict__ shifts = (MODEL >= 0 && shifts_base) ? shifts_base + ((int64_t)zy * nseg + sidx) * kShiftWords : nullptr;
+    unsigned *__restrict__ shifts = (MODEL >= 0 && shifts_base) ? shifts_base + ((int64_t)zy * nseg + sidx) * L::kShiftWords : nullptr;
     if (win_base && threadIdx.x == 0) win_base[(int64_t)zy * nseg + sidx] = pack_window(win);  // (wave 0: its Window::bmask is the valid one)
     if (MODEL >= 0 && shifts && win.border) {  // wave 0 only (wave-uniform), rare
-        for (int t = threadIdx.x; t < kShiftWords; t += kWave)
-            if ((win.bmask >> (t >> (kBlkShift - 3))) & 1ull) /* a word holds 8 slots */ __hip_atomic_store(&shifts[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+        for (int t = threadIdx.x; t < L::kShiftWords; t += kWave)
+            if ((win.bmask >> (t >> (L::kBlkShift - 3))) & 1ull) /* a word holds 8 slots */ __hip_atomic_store(&shifts[t], 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     }
     // Blurred variance (RefArgs::musum, see k_blur_stats_adj_var): sum_p I[p] b(row) b(col) over the votes.  b = 1 except within two
     // pixels of the border and an event's four weights add up to 1, so the sum is the NUMBER OF EVENTS (which the host knows)
@@ -644,7 +641,7 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
     };
     __syncthreads();
     if (MODEL >= 0 && shifts && nibbles != 0u) {  // this thread's kEPT slots share one word of 8 nibbles, or (six per thread) straddle two
-        const int l0 = kEPT * (int)threadIdx.x;
+        const int l0 = L::kEPT * (int)threadIdx.x;
         const unsigned long long nb = (unsigned long long)nibbles << ((l0 & 7) * 4);
         if ((unsigned)nb) atomicOr(&shifts[l0 >> 3], (unsigned)nb);
         if ((unsigned)(nb >> 32)) atomicOr(&shifts[(l0 >> 3) + 1], (unsigned)(nb >> 32));
@@ -659,7 +656,7 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
         unsigned neg_origin = 0u - ((unsigned)(win.r0 + 16384) * (unsigned)win.stride + (unsigned)(win.c0 + 16384));
         asm volatile("" : "+v"(neg_origin));  // (a VGPR: v_mad_u32_u16's one scalar operand is the stride)
         const int stride = win.stride;
-        const unsigned scratch = kWinCap + (threadIdx.x & (kWave - 1));
+        const unsigned scratch = L::kWinCap + (threadIdx.x & (kWave - 1));
         // Consecutive events of a thread that fall into the same cell are summed in registers first (fixed point: exact).
         // On a sharp image -- what the optimiser converges to -- hundreds of votes land on a few LDS words and the LDS
         // atomic unit serialises equal addresses; neighbouring sorted events mostly share their cell then.  Uniform events:
@@ -667,14 +664,14 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
         {  // (a second copy of this loop for full waves -- no min in the index -- measured: 14 VALU instructions per wave less, the same time)
             int cur = -1, w0 = 0, w1 = 0, w2 = 0, w3 = 0;
 #pragma unroll
-            for (int u = 0; u < kEPT; ++u) {
+            for (int u = 0; u < L::kEPT; ++u) {
                 const float a = fa[u], b = fb[u];
-                const float ak = a * kFixNS, nak = kFixNS - ak;
+                const float ak = a * L::kFixNS, nak = L::kFixNS - ak;
                 const int idx = fast_index(rc[u], neg_origin, win.stride, scratch);
                 // Round 6: the two weights of a ROW from the row's total -- r0 = rpi((1 - a) K), v1 = rpi((1 - a) b K), v0 = r0 - v1; the lower
                 // row from K - r0 -- three conversions and three integer subtractions where four products and four conversions were: the four
                 // weights of an event now add up to K EXACTLY (each within one unit, 2^-19 / 2^-20 of a vote, of its separately rounded value)
-                const int r0 = cvt_rpi(nak), r1 = (int)kFixNS - r0;
+                const int r0 = cvt_rpi(nak), r1 = (int)L::kFixNS - r0;
                 const int v1 = cvt_rpi(nak * b), v0 = r0 - v1, v3 = cvt_rpi(ak * b), v2 = r1 - v3;
                 if (idx != cur) {
                     if (cur >= 0) {
@@ -704,7 +701,7 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
         // (the flush skips those cells)
         if (band && (win.r0 < 0 || win.r0 + win.h > wp.Hp || win.c0 < 0 || win.c0 + win.w > wp.Wp)) {
 #pragma unroll
-            for (int u = 0; u < kEPT; ++u) {
+            for (int u = 0; u < L::kEPT; ++u) {
                 const int row = (int)(rc[u] >> 16) - 16384, col = (int)(rc[u] & 0xFFFFu) - 16384;
                 const float a = fa[u], b = fb[u];
                 const float wr = ((unsigned)row < (unsigned)wp.Hp ? 1.f - a : 0.f) + ((unsigned)(row + 1) < (unsigned)wp.Hp ? a : 0.f);
@@ -715,9 +712,9 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
     } else {
         // workgroup-uniform, rare: every corner tested; a vote outside the window adds 0 to a per-lane scratch
         // word, and goes to the image with a global atomic if it is inside the image
-        const int dummy = kDummy + (int)(threadIdx.x & (kWave - 1));
+        const int dummy = L::kDummy + (int)(threadIdx.x & (kWave - 1));
 #pragma unroll
-        for (int u = 0; u < kEPT; ++u) {
+        for (int u = 0; u < L::kEPT; ++u) {
             const int row = (int)(rc[u] >> 16) - 16384, col = (int)(rc[u] & 0xFFFFu) - 16384;  // empty slot: (-16384, -16384)
             const float a = fa[u], b = fb[u], na = 1.f - a, nb = 1.f - b;
             const int lr = row - win.r0, lc = col - win.c0;
@@ -725,10 +722,10 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
             const bool c_in0 = (unsigned)lc < (unsigned)win.w, c_in1 = (unsigned)(lc + 1) < (unsigned)win.w;
             const int base = lr * win.stride + lc;
             const int stride = win.stride;
-            atomicAdd(&s_win[(r_in0 && c_in0) ? base : dummy], (r_in0 && c_in0) ? __float2int_rn(na * nb * kFixNS) : 0);
-            atomicAdd(&s_win[(r_in1 && c_in0) ? base + stride : dummy], (r_in1 && c_in0) ? __float2int_rn(a * nb * kFixNS) : 0);
-            atomicAdd(&s_win[(r_in0 && c_in1) ? base + 1 : dummy], (r_in0 && c_in1) ? __float2int_rn(na * b * kFixNS) : 0);
-            atomicAdd(&s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy], (r_in1 && c_in1) ? __float2int_rn(a * b * kFixNS) : 0);
+            atomicAdd(&s_win[(r_in0 && c_in0) ? base : dummy], (r_in0 && c_in0) ? __float2int_rn(na * nb * L::kFixNS) : 0);
+            atomicAdd(&s_win[(r_in1 && c_in0) ? base + stride : dummy], (r_in1 && c_in0) ? __float2int_rn(a * nb * L::kFixNS) : 0);
+            atomicAdd(&s_win[(r_in0 && c_in1) ? base + 1 : dummy], (r_in0 && c_in1) ? __float2int_rn(na * b * L::kFixNS) : 0);
+            atomicAdd(&s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy], (r_in1 && c_in1) ? __float2int_rn(a * b * L::kFixNS) : 0);
             if (rc[u] == 0u) continue;
             const float wv[4] = {na * nb, a * nb, na * b, a * b};
 #pragma unroll
@@ -736,7 +733,7 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
                 const int r = row + (q & 1), c = col + (q >> 1);
                 const bool in_win = (unsigned)(r - win.r0) < (unsigned)win.h && (unsigned)(c - win.c0) < (unsigned)win.w;
                 if (!in_win && (unsigned)r < (unsigned)wp.Hp && (unsigned)c < (unsigned)wp.Wp) {
-                    if (iwe64) atomic_add_i64(&iwe64[(int64_t)r * wp.Wp + c], (long long)__float2int_rn(wv[q] * kFixNS));
+                    if (iwe64) atomic_add_i64(&iwe64[(int64_t)r * wp.Wp + c], (long long)__float2int_rn(wv[q] * L::kFixNS));
                     else atomic_add(&iwe[(int64_t)r * wp.Wp + c], wv[q]);
                     if (band) macc += wv[q] * (band_weight(r, c) - 1.f);  // (a clipped window is a band window, and lies inside the image)
                 } else if (band && !in_win) {
@@ -757,17 +754,17 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
         //                    + sum over the BAND cells of the image of val (b b - 1),
         // the cells of this window in columns 0, 1, Wp - 2, Wp - 1 (rows outside the band rows), then in rows 0, 1, Hp - 2, Hp - 1:
         // one cell per thread and part, no loop-carried LDS latency.
-        for (int t = threadIdx.x; t < 4 * win.h; t += kThr) {
+        for (int t = threadIdx.x; t < 4 * win.h; t += L::kThr) {
             const int r = t >> 2, q = t & 3, R = win.r0 + r;
             const int C = q < 2 ? q : wp.Wp - 4 + q, c = C - win.c0;
-            if ((unsigned)c < (unsigned)win.w && R >= 2 && R < wp.Hp - 2) macc += (float)s_win[r * win.stride + c] * kInvFixNS * (band_weight(R, C) - 1.f);
+            if ((unsigned)c < (unsigned)win.w && R >= 2 && R < wp.Hp - 2) macc += (float)s_win[r * win.stride + c] * L::kInvFixNS * (band_weight(R, C) - 1.f);
         }
         for (int q = 0; q < 4; ++q) {
             const int R = q < 2 ? q : wp.Hp - 4 + q, r = R - win.r0;
             if ((unsigned)r >= (unsigned)win.h) continue;  // workgroup-uniform
-            for (int c = threadIdx.x; c < win.w; c += kThr) {
+            for (int c = threadIdx.x; c < win.w; c += L::kThr) {
                 const int C = win.c0 + c;
-                if ((unsigned)C < (unsigned)wp.Wp) macc += (float)s_win[r * win.stride + c] * kInvFixNS * (band_weight(R, C) - 1.f);
+                if ((unsigned)C < (unsigned)wp.Wp) macc += (float)s_win[r * win.stride + c] * L::kInvFixNS * (band_weight(R, C) - 1.f);
             }
         }
         float m = macc;  // fp32 over the wave, fp64 across waves and workgroups
@@ -778,12 +775,12 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
         m += dpp_f<kDppRowBcast15>(m);
         m += dpp_f<kDppRowBcast31>(m);
         // no reduction across the waves: every wave that found anything sends its own sum, ahead of its share of the flush
-        if (lane == kWave - 1 && m != 0.f) atomic_add(&musum[((sidx * kNW + wave) % kMuLines) * kSubStride], (double)m);
+        if (lane == kWave - 1 && m != 0.f) atomic_add(&musum[((sidx * L::kNW + wave) % kMuLines) * kSubStride], (double)m);
     }
     if (iwe64) {
         // deterministic mode: the window's integers go to a 64-bit integer image as they are (exact, any order);
         // k_fixed_to_image rounds the finished sums to fp32 once
-        for (int r = wave; r < win.h; r += kNW) {
+        for (int r = wave; r < win.h; r += L::kNW) {
             if ((unsigned)(win.r0 + r) >= (unsigned)wp.Hp) continue;
             long long *dst = iwe64 + (pix_index(win.r0 + r, 0, wp.Wp) + win.c0);
             for (int c = lane; c < win.w; c += kWave) {
@@ -791,7 +788,7 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
                 if (v != 0 && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) atomic_add_i64(&dst[c], (long long)v);
             }
         }
-    } else if (kBig) {
+    } else if (L::kBig) {
         // Big segments: FLAT walk over the window's LDS words (see K3's window staging; the padding column holds 0).  Measured: K1 of
         // 20M events 38.3 -> 37.6 us, 64M 127.3 -> 126.7; with standard segments it is the row form that wins (cfg5 shard 12.95 vs 13.4).
         // row = i / stride = (i * ceil(2^21 / stride)) >> 21, exact for i < 2^13, stride < 2^8; both products are 24-bit multiplies
@@ -803,36 +800,36 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
             // multiply, one multiply-add, the conversion and the scale -- 6 VALU instructions per non-zero word where the tested form has 14
             float *__restrict__ base = iwe + pix_index(win.r0, win.c0, wp.Wp);
             const unsigned pitch_diff = (unsigned)wp.Wp - ustride;  // (>= 0: tested above; a window as wide as the image may have stride = Wp + 1)
-            for (int i = threadIdx.x; i < wn; i += kThr) {
+            for (int i = threadIdx.x; i < wn; i += L::kThr) {
                 const int v = s_win[i];
                 if (v == 0) continue;
                 const unsigned r = mul24_u((unsigned)i, magic) >> 21;
-                atomic_add(&base[mad24_u(r, pitch_diff, (unsigned)i)], (float)v * kInvFixNS);
+                atomic_add(&base[mad24_u(r, pitch_diff, (unsigned)i)], (float)v * L::kInvFixNS);
             }
         } else {
-            for (int i = threadIdx.x; i < wn; i += kThr) {
+            for (int i = threadIdx.x; i < wn; i += L::kThr) {
                 const int v = s_win[i];
                 if (v == 0) continue;
                 const unsigned r = mul24_u((unsigned)i, magic) >> 21, c = (unsigned)i - mul24_u(r, ustride);
                 const int R = win.r0 + (int)r, C = win.c0 + (int)c;
-                if ((unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) atomic_add(&iwe[pix_index(R, C, wp.Wp)], (float)v * kInvFixNS);
+                if ((unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) atomic_add(&iwe[pix_index(R, C, wp.Wp)], (float)v * L::kInvFixNS);
             }
         }
     } else if (win.w > 32) {
-        for (int r = wave; r < win.h; r += kNW) {
+        for (int r = wave; r < win.h; r += L::kNW) {
             if ((unsigned)(win.r0 + r) >= (unsigned)wp.Hp) continue;
             float *dst = iwe + (pix_index(win.r0 + r, 0, wp.Wp) + win.c0);
             for (int c = lane; c < win.w; c += kWave) {
                 const int v = s_win[r * win.stride + c];
-                if (v != 0 && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) atomic_add(&dst[c], (float)v * kInvFixNS);
+                if (v != 0 && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) atomic_add(&dst[c], (float)v * L::kInvFixNS);
             }
         }
     } else {  // narrow window: two rows per wave
         const int half = lane >> 5, c = lane & 31;
-        for (int r = 2 * wave + half; r < win.h; r += 2 * kNW) {
+        for (int r = 2 * wave + half; r < win.h; r += 2 * L::kNW) {
             if (c < win.w && (unsigned)(win.r0 + r) < (unsigned)wp.Hp && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) {
                 const int v = s_win[r * win.stride + c];
-                if (v != 0) atomic_add(&iwe[pix_index(win.r0 + r, win.c0 + c, wp.Wp)], (float)v * kInvFixNS);
+                if (v != 0) atomic_add(&iwe[pix_index(win.r0 + r, win.c0 + c, wp.Wp)], (float)v * L::kInvFixNS);
             }
         }
     }
@@ -853,13 +850,10 @@ __global__ void __launch_bounds__(kThr, kVoteWaves) k_vote(const int4 *__restric
 // (|dt| <= 2 for the "before" / "after" reference times: 2040 x 2 x 2^18 = 2^30).  dt is the NORMALISED one here; the
 // image-space kernel multiplies by the batch period when normalize_t is off.
 // ---------------------------------------------------------------------------------------------
-constexpr int kTanCap = kWinCap == 8192 ? 2720 : kWinCap / 3 - 8;  // window pixels per plane (3 planes + scratch = the window + 200 words of k_vote)
-constexpr float kTanFix = kBig ? 131072.f : 262144.f, kTanInvFix = 1.f / kTanFix;  // 2^18 (big segments: 2^17)
-
-template <bool FRAC>
-__global__ void __launch_bounds__(kThr) k_vote_tan2(const int4 *__restrict__ segs, int nseg, EvView ev, WarpParams wp, RefArgs ra) {
-    __shared__ int s_win[3 * kTanCap + kScratch];
-    __shared__ uint4 s_box[kNW];
+template <class L, bool FRAC>
+__global__ void __launch_bounds__(L::kThr) k_vote_tan2(const int4 *__restrict__ segs, int nseg, EvView ev, WarpParams wp, RefArgs ra) {
+    __shared__ int s_win[3 * L::kTanCap + kScratch];
+    __shared__ uint4 s_box[L::kNW];
     wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = ra.d_lo[blockIdx.y];
     float *__restrict__ iwe = ra.img[blockIdx.y];                      // [Hp, Wp]
@@ -869,24 +863,24 @@ __global__ void __launch_bounds__(kThr) k_vote_tan2(const int4 *__restrict__ seg
     const int sidx = segment_of_block(nseg);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
-    EventLoads el;
-    issue_event_loads<false>(ev.ev, nullptr, 0, sg, el);
-    unsigned rc[kEPT];
-    float fa[kEPT], fb[kEPT], fdt[kEPT];
-    int fsrc[kEPT];
+    EventLoads<L> el;
+    issue_event_loads<L, false>(ev.ev, nullptr, 0, sg, el);
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
     bool live;
     unsigned nib_unused;
-    const Window win = phase_warp<CMAX_MODEL_2DOF, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, CMAX_MODEL_2DOF, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
-        if (wn <= kTanCap)
-            for (int i = threadIdx.x; i < wn; i += kThr) {
+        if (wn <= L::kTanCap)
+            for (int i = threadIdx.x; i < wn; i += L::kThr) {
                 s_win[i] = 0;
-                s_win[kTanCap + i] = 0;
-                s_win[2 * kTanCap + i] = 0;
+                s_win[L::kTanCap + i] = 0;
+                s_win[2 * L::kTanCap + i] = 0;
             }
     }, live, nib_unused);
     const int wn = win.h * win.stride;
-    const bool fits = !win.clipped && wn <= kTanCap;  // workgroup-uniform
+    const bool fits = !win.clipped && wn <= L::kTanCap;  // workgroup-uniform
     __syncthreads();
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
     if (fits) {
@@ -894,41 +888,41 @@ __global__ void __launch_bounds__(kThr) k_vote_tan2(const int4 *__restrict__ seg
             const unsigned origin = (unsigned)(win.r0 + 16384) * (unsigned)win.stride + (unsigned)(win.c0 + 16384);
             const int stride = win.stride;
 #pragma unroll
-            for (int u = 0; u < kEPT; ++u) {
+            for (int u = 0; u < L::kEPT; ++u) {
                 if (rc[u] == 0u) continue;
                 const float a = fa[u], b = fb[u], dt = fdt[u] * inv_ts;
-                const float ak = a * kFixNS, nak = kFixNS - ak, nb = 1.f - b;
+                const float ak = a * L::kFixNS, nak = L::kFixNS - ak, nb = 1.f - b;
                 const int idx = (int)(__umul24(rc[u] >> 16, (unsigned)win.stride) + (rc[u] & 0xFFFFu) - origin);  // inside the window by construction
                 // the image plane gets the SAME integers as k_vote (weights from row totals): both paths then sum identical votes
-                const int r0 = cvt_rpi(nak), r1 = (int)kFixNS - r0, v1 = cvt_rpi(nak * b), v3 = cvt_rpi(ak * b);
+                const int r0 = cvt_rpi(nak), r1 = (int)L::kFixNS - r0, v1 = cvt_rpi(nak * b), v3 = cvt_rpi(ak * b);
                 atomicAdd(&s_win[idx], r0 - v1);
                 atomicAdd(&s_win[idx + 1], v1);
                 atomicAdd(&s_win[idx + stride], r1 - v3);
                 atomicAdd(&s_win[idx + stride + 1], v3);
-                const float dk = dt * kTanFix;
-                atomicAdd(&s_win[kTanCap + idx], cvt_rpi(dk * nb));
-                atomicAdd(&s_win[kTanCap + idx + 1], cvt_rpi(dk * b));
-                atomicAdd(&s_win[2 * kTanCap + idx], cvt_rpi(dk * (1.f - a)));
-                atomicAdd(&s_win[2 * kTanCap + idx + stride], cvt_rpi(dk * a));
+                const float dk = dt * L::kTanFix;
+                atomicAdd(&s_win[L::kTanCap + idx], cvt_rpi(dk * nb));
+                atomicAdd(&s_win[L::kTanCap + idx + 1], cvt_rpi(dk * b));
+                atomicAdd(&s_win[2 * L::kTanCap + idx], cvt_rpi(dk * (1.f - a)));
+                atomicAdd(&s_win[2 * L::kTanCap + idx + stride], cvt_rpi(dk * a));
             }
         }
         __syncthreads();
         // flush: a wave per window row and plane
-        for (int r = wave; r < win.h; r += kNW) {
+        for (int r = wave; r < win.h; r += L::kNW) {
             const int R = win.r0 + r;
             for (int c = lane; c < win.w; c += kWave) {
                 const int C = win.c0 + c, q = r * win.stride + c;
-                const int v = s_win[q], e = s_win[kTanCap + q], f = s_win[2 * kTanCap + q];
+                const int v = s_win[q], e = s_win[L::kTanCap + q], f = s_win[2 * L::kTanCap + q];
                 const bool rin = (unsigned)R < (unsigned)wp.Hp, cin = (unsigned)C < (unsigned)wp.Wp;
-                if (v != 0 && rin && cin) atomic_add(&iwe[(int64_t)R * wp.Wp + C], (float)v * kInvFixNS);
-                if (e != 0 && cin && (unsigned)(R + 1) <= (unsigned)wp.Hp) atomic_add(&e0g[(int64_t)(R + 1) * wp.Wp + C], (float)e * kTanInvFix);
-                if (f != 0 && rin && (unsigned)(C + 1) <= (unsigned)wp.Wp) atomic_add(&f1g[(int64_t)R * (wp.Wp + 1) + C + 1], (float)f * kTanInvFix);
+                if (v != 0 && rin && cin) atomic_add(&iwe[(int64_t)R * wp.Wp + C], (float)v * L::kInvFixNS);
+                if (e != 0 && cin && (unsigned)(R + 1) <= (unsigned)wp.Hp) atomic_add(&e0g[(int64_t)(R + 1) * wp.Wp + C], (float)e * L::kTanInvFix);
+                if (f != 0 && rin && (unsigned)(C + 1) <= (unsigned)wp.Wp) atomic_add(&f1g[(int64_t)R * (wp.Wp + 1) + C + 1], (float)f * L::kTanInvFix);
             }
         }
     } else if (live) {
         // window too large for three planes (very large displacements): straight to memory, every vote tested
 #pragma unroll
-        for (int u = 0; u < kEPT; ++u) {
+        for (int u = 0; u < L::kEPT; ++u) {
             if (rc[u] == 0u) continue;
             const int row = (int)(rc[u] >> 16) - 16384, col = (int)(rc[u] & 0xFFFFu) - 16384;
             const float a = fa[u], b = fb[u], dt = fdt[u] * inv_ts, na = 1.f - a, nb = 1.f - b;
@@ -953,16 +947,17 @@ __global__ void __launch_bounds__(kThr) k_vote_tan2(const int4 *__restrict__ seg
     }
 }
 
-// kFoldStatsInside: the K2 of a plain variance as the leading workgroups of the K3 launch (k_stats<VARIANCE> with this file's
+// kFoldStatsInside: the K2 of a plain variance as the leading workgroups of the K3 launch (k_stats<VARIANCE> with the layout's
 // workgroup size).  They finish long before the gathering workgroups do, so the ticket that finds the last of them -- four
 // dependent fabric round trips -- costs the evaluation nothing; that one writes the loss.
+template <class L>
 __device__ __forceinline__ void stats_inside_role(const float *__restrict__ img, float *__restrict__ zero_img, int H, int W, const ObjParams &op,
                                                   double *__restrict__ stat_slot, const RefArgs &ra, double *__restrict__ result, double *smem) {
     const int nblk = ra.stat_blocks;
-    const unsigned npix = (unsigned)H * (unsigned)W, stride = (unsigned)nblk * kThr;
+    const unsigned npix = (unsigned)H * (unsigned)W, stride = (unsigned)nblk * L::kThr;
     const int i0 = op.omit ? 1 : 0;
     double v[2] = {0.0, 0.0};
-    for (unsigned base = blockIdx.x * kThr + threadIdx.x; base < npix; base += 4u * stride) {
+    for (unsigned base = blockIdx.x * L::kThr + threadIdx.x; base < npix; base += 4u * stride) {
         float x[4];
         bool in[4];
 #pragma unroll
@@ -984,7 +979,7 @@ __device__ __forceinline__ void stats_inside_role(const float *__restrict__ img,
         }
     }
     // behind the loads (see k_stats): the vote image of the next evaluation, and the other buffer of the vote sums
-    zero_fill_sc1(zero_img, (int64_t)npix, (int64_t)blockIdx.x * kThr + threadIdx.x, (int64_t)nblk * kThr);
+    zero_fill_sc1(zero_img, (int64_t)npix, (int64_t)blockIdx.x * L::kThr + threadIdx.x, (int64_t)nblk * L::kThr);
     if (blockIdx.x == 0 && threadIdx.x < kMuLines)
         __hip_atomic_store(&ra.musum_next[threadIdx.x * kSubStride], 0.0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
     block_sum<2>(v, smem);
@@ -1020,8 +1015,8 @@ __device__ __forceinline__ void stats_inside_role(const float *__restrict__ img,
 //                     groups (zeros included), coalesced 64-byte rows -- no atomics, and nobody has to clear the gradient
 //                     buffer first
 // ---------------------------------------------------------------------------------------------
-template <int MODEL, bool FRAC, int FOLD, int VARIANT>
-__global__ void __launch_bounds__(kThr)
+template <class L, int MODEL, bool FRAC, int FOLD, int VARIANT>
+__global__ void __launch_bounds__(L::kThr)
 k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base, int stat_blocks, EvView ev,
        WarpParams wp, RefArgs ra, ObjParams op, const double *__restrict__ stat, double *__restrict__ gpart_base, float *__restrict__ gflow,
        double *__restrict__ result) {
@@ -1034,8 +1029,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     static_assert(!kInside || MODEL != CMAX_MODEL_2DOF, "statistics inside K3: flow-gradient models, one reference time");
     static_assert(!kOwned || MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL, "owned groups: flow-gradient models only");
     if (kInside && (int)blockIdx.x < stat_blocks) {  // workgroup-uniform: this workgroup is one of K2's (first thing: nothing else is live)
-        __shared__ double s_stat[2 * kNW];
-        stats_inside_role(ra.img[0], ra.zero[0], wp.Hp, wp.Wp, op, const_cast<double *>(stat), ra, result, s_stat);
+        __shared__ double s_stat[2 * L::kNW];
+        stats_inside_role<L>(ra.img[0], ra.zero[0], wp.Hp, wp.Wp, op, const_cast<double *>(stat), ra, result, s_stat);
         return;
     }
     CMAX_STAMP(1, 0);
@@ -1048,8 +1043,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     const int4 *known = win_base + (int64_t)zy * nseg + sidx;
     ev.ev = evp;
     wp.motion += (int64_t)blockIdx.z * ra.z_motion;
-    EventLoads el;
-    issue_event_loads<VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
+    EventLoads<L> el;
+    issue_event_loads<L, VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
     wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
     const int k = ra.k0 + (int)blockIdx.y;
     const float *__restrict__ img = ra.img[blockIdx.y] + blockIdx.z * ra.z_img;
@@ -1059,8 +1054,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     double *__restrict__ gpart = gpart_base ? gpart_base + blockIdx.z * ra.z_raw + (int64_t)k * kRawStride : nullptr;
     static_assert(FOLD != kFoldDeferred || MODEL == CMAX_MODEL_2DOF, "deferred statistics: 2-DoF only");
     static_assert(!STRIDED || MODEL == CMAX_MODEL_DENSE, "the strided slot layout exists for the dense scan only");
-    __shared__ float s_win[kWinCap + kScratch];
-    __shared__ double s_red[6 * kNW];
+    __shared__ float s_win[L::kWinCap + kScratch];
+    __shared__ double s_red[6 * L::kNW];
     // flow-gradient accumulators (x | y) in LDS: voxel only.  Measured on MI355X (cfg3 / cfg5): the dense model is
     // faster with a segmented scan + one global atomic per run (25 vs 34 us) -- its runs are long (16 events per
     // pixel) -- while voxel runs are ~2 events and the accumulators win (cfg4 K3 37 -> 26 us in fixed point)
@@ -1068,20 +1063,20 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     // dense (owned) segments span <= 3 source tiles; voxel ones kAccCells / 256 (tile, bin) groups.  The smaller array keeps
     // four 512-thread workgroups per CU for the dense model (33 KB window + 6 KB instead of + 24 KB)
     // (kGradOwnedSmall: a voxel work list cut into segments of <= 3 (tile, bin) groups, see build_segments)
-    static_assert(VARIANT != kGradOwnedSmall || (MODEL == CMAX_MODEL_VOXEL && kSlots <= 3072), "small accumulators: voxel, standard / mid segments");
-    constexpr int kAcc = (MODEL == CMAX_MODEL_DENSE ? kAccDense : (VARIANT == kGradOwnedSmall ? kAccSmall : kAccCells));
+    static_assert(VARIANT != kGradOwnedSmall || (MODEL == CMAX_MODEL_VOXEL && L::kSlots <= 3072), "small accumulators: voxel, standard / mid segments");
+    constexpr int kAcc = (MODEL == CMAX_MODEL_DENSE ? L::kAccDense : (VARIANT == kGradOwnedSmall ? L::kAccSmall : kAccCells));
     __shared__ int s_acc[kLdsAcc ? 2 * kAcc : 1];
-    __shared__ float s_max[kNW];
+    __shared__ float s_max[L::kNW];
     // The loss: all statistics are complete when this kernel starts (K2 ran).  Written by the last wave of the FIRST workgroup
     // -- at the tail of the kernel (the last segment's workgroup, one thread walking the accumulators' cache lines) it cost
     // K3 ~0.5 us with 8 lines per image and 3 us with 32.
-    if (!kInside && result && k == 0 && sidx == 0 && threadIdx.x >= kThr - kWave) write_result<true>(op, stat, result);
+    if (!kInside && result && k == 0 && sidx == 0 && threadIdx.x >= L::kThr - kWave) write_result<true>(op, stat, result);
     // Segments of a sparse batch (the solver's 30k events: ~100 events per segment, cut by the 12-group span) skip the
     // LDS accumulators: zeroing and flushing 2 x 3072 cells plus the block-wide scale reduction cost more than the two
     // global atomics per event they save (voxel K3 of the YAML objective, 3 reference times: 21.4 -> see profiles).
     const bool sparse_seg = kLdsAcc && !kOwned && sg.y < kSparseSegment;  // (an owned segment stores all its cells anyway)
     if (kLdsAcc && !sparse_seg) {
-        for (int i = threadIdx.x; i < 2 * kAcc; i += kThr) s_acc[i] = 0;  // made visible by the barriers of phase_warp
+        for (int i = threadIdx.x; i < 2 * kAcc; i += L::kThr) s_acc[i] = 0;  // made visible by the barriers of phase_warp
     }
     const int i0 = op.omit ? 1 : 0;
     // What the LDS window holds at an in-image pixel.  The chain factor (kFoldStats / kFoldScale) and the mean (kFoldStats) are
@@ -1136,12 +1131,12 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     // outside Omega): the LAST wave (segments rarely fill their 2048 slots, so it is the one with the fewest events, often
     // none) fetches the statistics ahead of its event loads.  Otherwise the factor is a constant of the objective.
     const bool chain_from_stats = FOLD == kFoldStats || (FOLD == kFoldScale && op.normalized);  // launch-uniform
-    if (chain_from_stats && (kDet || threadIdx.x >= kThr - kWave)) {
+    if (chain_from_stats && (kDet || threadIdx.x >= L::kThr - kWave)) {
         double mud = 0.0;
         const double coef = chain_coef<true>(op, stat, k, &mud);  // whole converged waves
         c2 = FOLD == kFoldStats ? (float)(coef * 2.0 / (region_pixels(op.H, op.W, op.omit) - 1.0)) : (float)coef;
         mu = (float)mud;
-        if (threadIdx.x == kThr - 1) {
+        if (threadIdx.x == L::kThr - 1) {
             s_chain[0] = c2;
             s_chain[1] = mu;
         }
@@ -1149,11 +1144,11 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         const double coef = (op.negate ? -1.0 : 1.0) * op.mult[k] * (op.minimize ? -1.0 : 1.0);  // chain_coef without the statistics
         c2 = kStatsFold ? (float)(coef * 2.0 / (region_pixels(op.H, op.W, op.omit) - 1.0)) : (float)coef;
     }
-    if (kInside && threadIdx.x >= kThr - kWave) {  // the mean from K1's vote sums: (events + corrections) / |Omega|
-        const int ln = (int)threadIdx.x - (kThr - kWave);
+    if (kInside && threadIdx.x >= L::kThr - kWave) {  // the mean from K1's vote sums: (events + corrections) / |Omega|
+        const int ln = (int)threadIdx.x - (L::kThr - kWave);
         double m = ln < kMuLines ? ra.musum[blockIdx.y][ln * kSubStride] : 0.0;
         m = wave_sum_lane63(m);
-        if (threadIdx.x == kThr - 1) s_chain[1] = (float)(((double)ra.n_events + m) / region_pixels(op.H, op.W, op.omit));
+        if (threadIdx.x == L::kThr - 1) s_chain[1] = (float)(((double)ra.n_events + m) / region_pixels(op.H, op.W, op.omit));
     }
     // deterministic mode: fixed-point scale of this reference time (2-DoF) / of the whole launch (flow gradient), from
     // bounds that every workgroup evaluates identically: |term| <= |dt|max * 2 max|G|, max|G| from max|image|
@@ -1175,9 +1170,9 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         det_s = det_scale(bound, ra.n_events);
         if (sidx == 0 && threadIdx.x == 0 && (MODEL == CMAX_MODEL_2DOF || k == 0)) ra.det_inv_scale[MODEL == CMAX_MODEL_2DOF ? k : 0] = 1.0 / det_s;
     }
-    unsigned rc[kEPT];
-    float fa[kEPT], fb[kEPT], fdt[kEPT];
-    int fsrc[kEPT];
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
     const int lane = threadIdx.x & (kWave - 1);
     // stage dL/dIWE of the window in LDS, zero outside the image (masked vote)
     auto load_window = [&](const Window &w) {
@@ -1207,35 +1202,35 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             // mask per word (workgroup-uniform; most windows): word i = r stride + c is pixel [r0 Wp + c0] + r (Wp - stride) + i, four VALU
             // instructions per word where the tested form has ~20 -- at nine words per thread a fifth of this kernel's VALU instructions.
             // (The padding column then holds the pixel right of the window instead of 0: no footprint reads it.)
-            if (kBig && w.r0 >= i0 && w.c0 >= i0 && w.r0 + w.h <= wp.Hp - i0 && w.c0 + w.stride <= wp.Wp - i0) {
+            if (L::kBig && w.r0 >= i0 && w.c0 >= i0 && w.r0 + w.h <= wp.Hp - i0 && w.c0 + w.stride <= wp.Wp - i0) {
                 const float *__restrict__ base = img + pix_index(w.r0, w.c0, wp.Wp);
                 const unsigned pitch_diff = (unsigned)wp.Wp - ustride;
-                for (int i = threadIdx.x; i < wn; i += kThr) {
+                for (int i = threadIdx.x; i < wn; i += L::kThr) {
                     const unsigned r = mul24_u((unsigned)i, magic) >> 21;
                     s_win[i] = base[mad24_u(r, pitch_diff, (unsigned)i)];
                 }
             } else {
-                for (int i = threadIdx.x; i < wn; i += kThr) {
+                for (int i = threadIdx.x; i < wn; i += L::kThr) {
                     const unsigned r = mul24_u((unsigned)i, magic) >> 21, c = (unsigned)i - mul24_u(r, ustride);
                     s_win[i] = (int)c < w.w ? g_win((int)r, (int)c) : 0.f;
                 }
             }
         } else if (w.w > 32) {  // a wave per window row: coalesced, no integer division
-            for (int r = threadIdx.x / kWave; r < w.h; r += kNW)
+            for (int r = threadIdx.x / kWave; r < w.h; r += L::kNW)
                 for (int c = lane; c < w.w; c += kWave) s_win[r * w.stride + c] = g_win(r, c);
         } else {  // narrow window: two rows per wave
             const int half = lane >> 5, c = lane & 31;
-            for (int r = 2 * (threadIdx.x / kWave) + half; r < w.h; r += 2 * kNW)
+            for (int r = 2 * (threadIdx.x / kWave) + half; r < w.h; r += 2 * L::kNW)
                 if (c < w.w) s_win[r * w.stride + c] = g_win(r, c);
         }
     };
     // the window K1 used for this segment, and the cell offsets of the events K1 decided in fp64 (the host runs K1 first, always)
-    const unsigned *__restrict__ shifts = ra.shifts + ((int64_t)zy * nseg + sidx) * kShiftWords;
+    const unsigned *__restrict__ shifts = ra.shifts + ((int64_t)zy * nseg + sidx) * L::kShiftWords;
     bool live;  // this wave holds events (wave-uniform)
     unsigned nib_unused;
-    const Window win = phase_warp<MODEL, FRAC, true, STRIDED, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused);
-    CMAX_STAMP_AFTER(1, 1, rc[kEPT - 1]);
-    if (threadIdx.x < kScratch) s_win[kWinCap + threadIdx.x] = 0.f;  // empty slots / masked corners read 0 from here
+    const Window win = phase_warp<L, MODEL, FRAC, true, STRIDED, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused);
+    CMAX_STAMP_AFTER(1, 1, rc[L::kEPT - 1]);
+    if (threadIdx.x < kScratch) s_win[L::kWinCap + threadIdx.x] = 0.f;  // empty slots / masked corners read 0 from here
     __syncthreads();
     CMAX_STAMP(1, 2);
     // per event: dt <- c2 dt (every sum below is linear in dt), and -- kFoldStats, windows that reach outside Omega only -- the mean's
@@ -1248,16 +1243,16 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         }
         if (kInside) mu = s_chain[1];
 #pragma unroll
-        for (int j = 0; j < kEPT; ++j) fdt[j] *= c2;
+        for (int j = 0; j < L::kEPT; ++j) fdt[j] *= c2;
     }
     if (kStatsFold)  // workgroup-uniform
         edge_mu = win.clipped || win.r0 < i0 || win.r0 + win.h > wp.Hp - i0 || win.c0 < i0 || win.c0 + win.w > wp.Wp - i0;
     const int hw = wp.H * wp.W;
-    const int dummy = kDummy + lane;
+    const int dummy = L::kDummy + lane;
     const int stride = win.stride;
     unsigned neg_origin = 0u - ((unsigned)(win.r0 + 16384) * (unsigned)win.stride + (unsigned)(win.c0 + 16384));
     asm volatile("" : "+v"(neg_origin));  // (a VGPR: see fast_index)
-    const unsigned scratch = kWinCap + lane;
+    const unsigned scratch = L::kWinCap + lane;
     // per event: dL/dx' = (1-b)(G10-G00) + b(G11-G01), dL/dy' = (1-a)(G01-G00) + a(G11-G10)
     auto gather = [&](int j, float &gx, float &gy) {
         // g[0] = G00 (row, col), g[1] = G10 (row+1, col), g[2] = G01 (row, col+1), g[3] = G11
@@ -1342,7 +1337,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             // one pair per event).
             unsigned kcur = 0xFFFFFFFFu;
 #pragma unroll
-            for (int j = 0; j < kEPT; ++j) {
+            for (int j = 0; j < L::kEPT; ++j) {
                 float gx, gy;
                 gather(j, gx, gy);
                 const float sgn = MODEL == CMAX_MODEL_2DOF ? 1.f : -1.f;
@@ -1386,7 +1381,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     if (MODEL == CMAX_MODEL_2DOF) {
         if (live) {
 #pragma unroll
-        for (int j = 0; j < kEPT; ++j) {
+        for (int j = 0; j < L::kEPT; ++j) {
             float gx, gy;
             gather(j, gx, gy);
             accx = fmaf(fdt[j], gx, accx);  // dt = 0 for an empty slot; <= kEPT terms in fp32, then fp64 across the workgroup
@@ -1400,7 +1395,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             const bool edge = win.clipped || win.r0 < i0 || win.r0 + win.h > wp.Hp - i0 || win.c0 < i0 || win.c0 + win.w > wp.Wp - i0;
             if (edge) {
 #pragma unroll
-                for (int j = 0; j < kEPT; ++j) {
+                for (int j = 0; j < L::kEPT; ++j) {
                     const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;
                     const float mr0 = (unsigned)(row - i0) < (unsigned)hi ? 1.f : 0.f, mr1 = (unsigned)(row + 1 - i0) < (unsigned)hi ? 1.f : 0.f;
                     const float mc0 = (unsigned)(col - i0) < (unsigned)wi ? 1.f : 0.f, mc1 = (unsigned)(col + 1 - i0) < (unsigned)wi ? 1.f : 0.f;
@@ -1471,18 +1466,18 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             // a wave without events has no run to reduce
         } else if (STRIDED) {
 #pragma unroll
-            for (int j = 0; j < kEPT; j += 2) reduce_chunk(j, std::integral_constant<int, 2>{});
+            for (int j = 0; j < L::kEPT; j += 2) reduce_chunk(j, std::integral_constant<int, 2>{});
         } else {
-            reduce_chunk(0, std::integral_constant<int, kEPT>{});
+            reduce_chunk(0, std::integral_constant<int, L::kEPT>{});
         }
     } else {
         // LDS accumulators in block-scaled fixed point.  ds_add_f32 runs at 1/12 of the ds_add_u32 rate on gfx950
         // (profiles/r01_microbench.txt) and voxel runs are ~2 events long, so every event adds its two terms as
         // integers: scale = 2^(19 - e) with 2^e > max |term| of the workgroup; <= kSegMax terms per cell stay
         // below 2^30.  Rounding: 2^-20 of the workgroup's largest term per addition.
-        float vx[kEPT], vy[kEPT], vmax = 0.f;
+        float vx[L::kEPT], vy[L::kEPT], vmax = 0.f;
 #pragma unroll
-        for (int j = 0; j < kEPT; ++j) {
+        for (int j = 0; j < L::kEPT; ++j) {
             float gx = 0.f, gy = 0.f;
             if (live) gather(j, gx, gy);
             vx[j] = -fdt[j] * gx;
@@ -1491,7 +1486,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         }
         if (sparse_seg) {  // workgroup-uniform
 #pragma unroll
-            for (int j = 0; j < kEPT; ++j) {
+            for (int j = 0; j < L::kEPT; ++j) {
                 if (rc[j] == 0u) continue;
                 const int64_t g = flow_index((unsigned)fsrc[j]);
                 atomic_add(&gflow[g], vx[j]);
@@ -1511,10 +1506,10 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         __syncthreads();
         vmax = s_max[0];
 #pragma unroll
-        for (int wv = 1; wv < kNW; ++wv) vmax = fmaxf(vmax, s_max[wv]);
+        for (int wv = 1; wv < L::kNW; ++wv) vmax = fmaxf(vmax, s_max[wv]);
         int e = 0;
         (void)frexpf(vmax, &e);  // vmax = f * 2^e, f in [0.5, 1)
-        const float scale = ldexpf(1.f, kAccExp - e), inv_scale = ldexpf(1.f, e - kAccExp);
+        const float scale = ldexpf(1.f, L::kAccExp - e), inv_scale = ldexpf(1.f, e - L::kAccExp);
         if (kOwned) {
             // events ordered by pixel (dense: inside the tile; voxel: inside the (tile, bin) group), consecutive ones per
             // thread: equal cells are summed in registers first (exact in fixed point) -- fewer LDS atomics and no
@@ -1522,7 +1517,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             if (live && vmax > 0.f && vmax < 3.0e38f) {
                 int cur = -1, sx = 0, sy = 0;
 #pragma unroll
-                for (int j = 0; j < kEPT; ++j) {
+                for (int j = 0; j < L::kEPT; ++j) {
                     const int cell = rc[j] != 0u ? acc_cell((unsigned)fsrc[j]) : -1;
                     const int qx = cvt_rpi(vx[j] * scale), qy = cvt_rpi(vy[j] * scale);  // 0 for an empty slot (dt = 0)
                     if (cell != cur) {
@@ -1545,7 +1540,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             }
         } else if (vmax > 0.f && vmax < 3.0e38f) {
 #pragma unroll
-            for (int j = 0; j < kEPT; ++j) {
+            for (int j = 0; j < L::kEPT; ++j) {
                 if (rc[j] == 0u) continue;
                 const unsigned key = (unsigned)fsrc[j];
                 const int cell = acc_cell(key);
@@ -1573,7 +1568,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         const int trow = strip_trow, tcol0 = strip_tcol0;
         const unsigned magic = ((1u << 20) + (unsigned)Tg - 1u) / (unsigned)Tg;  // (b * magic) >> 20 = b / T for b < 2^12, T < 2^8
         const unsigned strip_magic = ((1u << 20) + strip_w - 1u) / (strip_w > 0u ? strip_w : 1u);  // cell / strip_w for cell < 2^11, strip_w <= 96
-        for (int cell = threadIdx.x; cell < ncell; cell += kThr) {
+        for (int cell = threadIdx.x; cell < ncell; cell += L::kThr) {
             const int ax = s_acc[cell], ay = s_acc[kAcc + cell];
             if (!kOwned && ax == 0 && ay == 0) continue;
             int tcol = tcol0 + (cell >> 8), bin = 0;
@@ -1613,12 +1608,12 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             v += dpp_f<kDppRowShr8>(v);
             v += dpp_f<kDppRowBcast15>(v);
             v += dpp_f<kDppRowBcast31>(v);
-            if (lane == kWave - 1) s_f[q * kNW + threadIdx.x / kWave] = v;
+            if (lane == kWave - 1) s_f[q * L::kNW + threadIdx.x / kWave] = v;
         }
         __syncthreads();
         if (threadIdx.x < 2) {  // two fp64 atomics per workgroup into accumulator line (segment mod kRawLines), as in the deferred tail
             double a = 0.0;
-            for (int w = 0; w < kNW; ++w) a += (double)s_f[threadIdx.x * kNW + w];
+            for (int w = 0; w < L::kNW; ++w) a += (double)s_f[threadIdx.x * L::kNW + w];
             atomic_add(&gpart[(sidx & (kRawLines - 1)) * kSubStride + threadIdx.x], a);
         }
     }
@@ -1638,7 +1633,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             v += dpp_f<kDppRowShr8>(v);
             v += dpp_f<kDppRowBcast15>(v);
             v += dpp_f<kDppRowBcast31>(v);
-            if (lane == kWave - 1) s_f[q * kNW + threadIdx.x / kWave] = v;
+            if (lane == kWave - 1) s_f[q * L::kNW + threadIdx.x / kWave] = v;
         }
         if (threadIdx.x < kWave) {
             double sx = 0.0, sxx = 0.0;
@@ -1655,8 +1650,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             sx = wave_sum_lane63(sx);
             sxx = wave_sum_lane63(sxx);
             if (lane == kWave - 1) {
-                s_red[2 * kNW] = sx;
-                s_red[2 * kNW + 1] = sxx;
+                s_red[2 * L::kNW] = sx;
+                s_red[2 * L::kNW + 1] = sxx;
             }
         }
         if (FOLD == kFoldDeferred && zero_img) {
@@ -1669,10 +1664,10 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             if ((npix & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_img) & 15u) == 0) {
                 const int n4 = npix >> 2, chunk4 = (n4 + nseg - 1) / nseg;
                 const int q1 = min(n4, (sidx + 1) * chunk4);
-                for (int q = sidx * chunk4 + (int)threadIdx.x; q < q1; q += kThr) store_zero4_sc1(zero_img + 4 * (int64_t)q);
+                for (int q = sidx * chunk4 + (int)threadIdx.x; q < q1; q += L::kThr) store_zero4_sc1(zero_img + 4 * (int64_t)q);
             } else {
                 const int chunk = (npix + nseg - 1) / nseg, p1 = min(npix, (sidx + 1) * chunk);
-                for (int p = sidx * chunk + (int)threadIdx.x; p < p1; p += kThr)
+                for (int p = sidx * chunk + (int)threadIdx.x; p < p1; p += L::kThr)
                     __hip_atomic_store(&zero_img[p], 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }
         }
@@ -1684,9 +1679,9 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         if (threadIdx.x < 6) {
             double a = 0.0;
             if (threadIdx.x < 4) {
-                for (int w = 0; w < kNW; ++w) a += (double)s_f[threadIdx.x * kNW + w];
+                for (int w = 0; w < L::kNW; ++w) a += (double)s_f[threadIdx.x * L::kNW + w];
             } else {
-                a = s_red[2 * kNW + (threadIdx.x - 4)];
+                a = s_red[2 * L::kNW + (threadIdx.x - 4)];
             }
             atomic_add(&gpart[(sidx & (kRawLines - 1)) * kSubStride + threadIdx.x], a);
         }
@@ -1694,13 +1689,13 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     }
 }
 
-template <int MODEL, bool FRAC>
+template <class L, int MODEL, bool FRAC>
 // dimg64 (deterministic mode): the window's integers (and the overflow of a clipped window, rounded at the same scale) go to a
 // 64-bit integer image with integer atomics -- exact in any order; k_fixed_to_image rounds the finished sums once
-__global__ void __launch_bounds__(kThr) k_vote_tan(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg,
+__global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg,
                                                   float *__restrict__ dimg, double *__restrict__ stat_zero, long long *__restrict__ dimg64) {
-    __shared__ int s_win[kWinCap + kScratch];
-    __shared__ uint4 s_box[kNW];
+    __shared__ int s_win[L::kWinCap + kScratch];
+    __shared__ uint4 s_box[L::kNW];
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = 0.f;
     // (the by-value parameter block is only read: writing to it would move it to scratch memory for the indexing)
@@ -1712,16 +1707,16 @@ __global__ void __launch_bounds__(kThr) k_vote_tan(EvView ev, WarpParams wp, Tan
     const int sidx = segment_of_block(nseg);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
-    EventLoads el;
-    issue_event_loads<false>(ev.ev, nullptr, 0, sg, el);
-    unsigned rc[kEPT];
-    float fa[kEPT], fb[kEPT], fdt[kEPT];
-    int fsrc[kEPT];
+    EventLoads<L> el;
+    issue_event_loads<L, false>(ev.ev, nullptr, 0, sg, el);
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
     bool live;
     unsigned nib_unused;
-    const Window win = phase_warp<MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
-        for (int i = threadIdx.x; i < wn; i += kThr) s_win[i] = 0;
+        for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
     }, live, nib_unused);
     float u0 = 0.f, u1 = 0.f;
     if (MODEL == CMAX_MODEL_2DOF) {
@@ -1729,9 +1724,9 @@ __global__ void __launch_bounds__(kThr) k_vote_tan(EvView ev, WarpParams wp, Tan
         u1 = tp.u[1];
     }
     __syncthreads();
-    const int dummy = kDummy + (int)(threadIdx.x & (kWave - 1));
+    const int dummy = L::kDummy + (int)(threadIdx.x & (kWave - 1));
 #pragma unroll
-    for (int u = 0; u < kEPT; ++u) {
+    for (int u = 0; u < L::kEPT; ++u) {
         const bool valid = rc[u] != 0u;
         const int row = (int)(rc[u] >> 16) - 16384, col = (int)(rc[u] & 0xFFFFu) - 16384;
         const float a = fa[u], b = fb[u], na = 1.f - a, nb = 1.f - b;
@@ -1762,7 +1757,7 @@ __global__ void __launch_bounds__(kThr) k_vote_tan(EvView ev, WarpParams wp, Tan
     }
     __syncthreads();
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    for (int r = wave; r < win.h; r += kNW) {
+    for (int r = wave; r < win.h; r += L::kNW) {
         if ((unsigned)(win.r0 + r) >= (unsigned)wp.Hp) continue;  // the fast window is not clipped to the image
         float *dst = dimg + (int64_t)(win.r0 + r) * wp.Wp + win.c0;
         long long *dst64 = dimg64 ? dimg64 + (int64_t)(win.r0 + r) * wp.Wp + win.c0 : nullptr;
@@ -1777,8 +1772,8 @@ __global__ void __launch_bounds__(kThr) k_vote_tan(EvView ev, WarpParams wp, Tan
 }
 
 // T3: per-event second-order gather.  G = dL/dIWE (current), Gp = its tangent.
-template <int MODEL, bool FRAC>
-__global__ void __launch_bounds__(kThr) 
+template <class L, int MODEL, bool FRAC>
+__global__ void __launch_bounds__(L::kThr)
 k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg, const float *__restrict__ G,
            const float *__restrict__ Gp, double *__restrict__ gpart, float *__restrict__ hflow, HvpDet det) {
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
@@ -1786,23 +1781,23 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
     G += blockIdx.y * tp.bs;
     Gp += blockIdx.y * tp.bs;
     if (gpart) gpart += (int64_t)blockIdx.y * nseg * 2;
-    __shared__ float s_g[kWinCap + kWave];
-    __shared__ float s_p[kWinCap + kWave];
-    __shared__ uint4 s_box[kNW];
-    __shared__ double s_red[2 * kNW];
+    __shared__ float s_g[L::kWinCap + kWave];
+    __shared__ float s_p[L::kWinCap + kWave];
+    __shared__ uint4 s_box[L::kNW];
+    __shared__ double s_red[2 * L::kNW];
     const int sidx = segment_of_block(nseg);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
-    EventLoads el;
-    issue_event_loads<false>(ev.ev, nullptr, 0, sg, el);
-    unsigned rc[kEPT];
-    float fa[kEPT], fb[kEPT], fdt[kEPT];
-    int fsrc[kEPT];
+    EventLoads<L> el;
+    issue_event_loads<L, false>(ev.ev, nullptr, 0, sg, el);
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
     const int lane = threadIdx.x & (kWave - 1);
     bool live;
     unsigned nib_unused;
-    const Window win = phase_warp<MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
-        for (int r = threadIdx.x / kWave; r < w.h; r += kNW)
+    const Window win = phase_warp<L, MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+        for (int r = threadIdx.x / kWave; r < w.h; r += L::kNW)
             for (int c = lane; c < w.w; c += kWave) {
                 const int64_t q = (int64_t)(w.r0 + r) * wp.Wp + w.c0 + c;
                 const bool in = (unsigned)(w.r0 + r) < (unsigned)wp.Hp && (unsigned)(w.c0 + c) < (unsigned)wp.Wp;
@@ -1816,12 +1811,12 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
         u1 = tp.u[1];
     }
     if (threadIdx.x < kWave) {
-        s_g[kDummy + threadIdx.x] = 0.f;
-        s_p[kDummy + threadIdx.x] = 0.f;
+        s_g[L::kDummy + threadIdx.x] = 0.f;
+        s_p[L::kDummy + threadIdx.x] = 0.f;
     }
     __syncthreads();
     const int hw = wp.H * wp.W;
-    const int dummy = kDummy + lane, stride = win.stride;
+    const int dummy = L::kDummy + lane, stride = win.stride;
     float accx = 0.f, accy = 0.f;
     // deterministic mode (det.g64 != null): every term becomes a 64-bit integer at a scale all workgroups derive identically from
     // max |G| and max |G'| of this reference time (|hx| <= 4 max|G| dtmax + 2 max|G'|, |term| <= dtmax |hx|; x4 for the fp32 roundings)
@@ -1850,7 +1845,7 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
         }
     }
 #pragma unroll
-    for (int j = 0; j < kEPT; ++j) {
+    for (int j = 0; j < L::kEPT; ++j) {
         const bool valid = rc[j] != 0u;
         const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;
         const int lr = row - win.r0, lc = col - win.c0;
@@ -1935,4 +1930,3 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
     }
 }
 
-}  // namespace CMAX_EVENT_NS

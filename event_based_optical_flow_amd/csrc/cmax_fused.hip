@@ -29,8 +29,10 @@
 //                   accumulators in block-scaled fixed point)
 //   k_finish / k_finish_deferred   sum the per-segment partials (2-DoF), write loss + gradient
 // Every launch covers all reference times of the objective (blockIdx.y).  The event kernels live in
-// cmax_event_kernels.inc, compiled for 256-, 512- and 1024-thread workgroups (namespaces t256 / t512 /
-// t1024); the host picks 512 above 1024 segments (1024 for the voxel K3).
+// cmax_event_kernels.inc, templates over the segment layout (EventLayout: t256 / t512 / t1024 for segments of
+// up to 2040 events, m512 for mid and b512 / b1024 for big segments).  The layout of a launch is chosen in one
+// function per kernel family: vote_layout (K1: 512 threads above 512 segments), grad_layout (K3: the same, 1024
+// for the voxel K3 above 1024 segments) and plain_layout (deterministic K3 and the tangent kernels).
 //
 // fp32 per event with the integer source pixel split from the fp32 displacement (keeps the
 // bilinear fractions accurate to ulp(displacement) instead of ulp(coordinate)); fp64 reductions.
@@ -51,7 +53,6 @@
 // Environment knobs (tuning experiments and A/B tests only; none changes results beyond rounding):
 //   CMAX_NO_OWNED=1      never build the group-aligned "owned groups" work list (cmax_set_events)
 //   CMAX_NO_RUN_SORT=1   leave the events of a source pixel in the order the tile sort produced (no ordering by time)
-//   CMAX_VOTE_NS / CMAX_GRAD_NS = 256 | 512 | 1024   force the workgroup size of K1 / K3
 //   CMAX_SEG_CAP=n        free-cut work lists: events per segment (<= the layout's cap; profiles/r04_ablation.txt 18)
 //   CMAX_NO_STATS_INSIDE=1   plain variance on owned groups: k_stats as a launch of its own instead of inside K3's
 //   CMAX_STAT_SWEEPS=n       statistics inside K3's launch: 4-pixel sweeps per statistics workgroup (fewer, longer workgroups)
@@ -68,7 +69,6 @@ constexpr int kSparseSegment = 512;  // voxel K3: segments below this many event
 constexpr int kTile = 16;  // source-pixel tile edge of the counting sort
 constexpr int kSegMax = 2040;                 // events per segment (+1 for the even-aligned start still fits 2048);
                                               // |sum of votes| <= 2040 * 2^20 < 2^31
-constexpr int kWinCap = 8192;                 // LDS window capacity in 32-bit words (32 KiB)
 constexpr int kAccCells = 3072;               // flow-gradient accumulator cells per channel in LDS (voxel K3): 12 (tile, bin) groups
 constexpr int kAccCellsDense = 768;           // the same for the dense K3 with owned tiles: 3 source tiles
 constexpr int kWinMaxW = 128;                 // widest window when the bounding box has to be clipped
@@ -535,15 +535,8 @@ __device__ __forceinline__ Warped warp_one(const EvView &ev, const EvDec &e, con
         // per channel, instead of 64-bit per-lane pointer arithmetic (the field is < 4 GiB: checked by the host)
         const unsigned off = (unsigned)w.src * 4u;
         const char *m0 = reinterpret_cast<const char *>(wp.motion), *m1 = reinterpret_cast<const char *>(wp.motion + hw);
-#ifdef CMAX_AB_NOFLOW  // (A/B builds only, profiles/r05_ablation.txt 8: no flow reads at all -- what the dense kernels pay for them)
-        w.f0 = 0.25f + 1e-9f * (float)off;
-        w.f1 = -0.125f;
-        (void)m0;
-        (void)m1;
-#else
         w.f0 = *reinterpret_cast<const float *>(m0 + off);
         w.f1 = *reinterpret_cast<const float *>(m1 + off);
-#endif
         dx = fmaf(-w.dt, w.f0, dx);  // x' = x - dt*F[0,ix,iy], src/warp.py:305-306
         dy = fmaf(-w.dt, w.f1, dy);
     }
@@ -622,12 +615,8 @@ __device__ __forceinline__ float time_scale(const WarpParams &wp) {
 // contiguous range [x * per, (x+1) * per) keeps neighbouring tiles (shared halo rows of the IWE / G
 // windows, neighbouring flow pixels) in one XCD's L2.  Placement only affects speed.
 __device__ __forceinline__ int segment_of_block(int nseg, unsigned bx = blockIdx.x) {
-#ifdef CMAX_NO_XCD_MAP
-    return (int)bx;
-#else
     const int per = (nseg + 7) >> 3;
     return (int)(bx & 7u) * per + (int)(bx >> 3);
-#endif
 }
 
 // Row stride of an LDS window of width w.  With a power-of-two stride (the first version: a shift per index) the bank of a
@@ -677,7 +666,6 @@ constexpr int kFoldNone = 0, kFoldStats = 1, kFoldDeferred = 2, kFoldScale = 3; 
 // gradient waits for the statistics: the chain factor is a constant and the mean comes from K1's vote sums (RefArgs::musum)
 constexpr int kFoldStatsInside = 4;
 constexpr int kGradRuns = 0, kGradStrided = 1, kGradOwned = 2, kGradDet = 3, kGradOwnedSmall = 4;  // k_grad's VARIANT (see cmax_event_kernels.inc)
-[[maybe_unused]] constexpr int kDummy = kWinCap;     // masked path: 64 per-lane scratch words behind the window
 constexpr int kScratch = 200;       // scratch words behind the window; the fast path sends the 2x2 footprint of an
                                     // empty slot to kWinCap + lane + {0, 1, stride, stride + 1}, stride <= 128
 static_assert(kScratch >= 64 + kWinMaxW + 2, "scratch must hold a per-lane 2x2 footprint at the widest stride");
@@ -1740,64 +1728,9 @@ k_finish_lines(const double *__restrict__ raw, int n_ref, double *__restrict__ g
 
 }  // namespace cmax
 
-// the event kernels, once per workgroup size
+// the event kernels
 namespace cmax {
-#define CMAX_SLOTS 2048
-#define CMAX_WINCAP 8192
-#define CMAX_ACC_TILES 3
-#define CMAX_ACC_SMALL_GROUPS 3
-#define CMAX_THREADS 256
-#define CMAX_EVENT_NS t256
 #include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-#define CMAX_THREADS 512
-#define CMAX_EVENT_NS t512
-#include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-#define CMAX_THREADS 1024
-#define CMAX_EVENT_NS t1024
-#include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-// mid segments (3064 events, four source tiles wide: cmax_handle_s::mid): 512 threads x 6 events
-#undef CMAX_SLOTS
-#undef CMAX_WINCAP
-#undef CMAX_ACC_TILES
-#undef CMAX_ACC_SMALL_GROUPS
-#define CMAX_SLOTS 3072
-#define CMAX_WINCAP 6144
-#define CMAX_ACC_TILES 4
-#define CMAX_ACC_SMALL_GROUPS 5
-#define CMAX_THREADS 512
-#define CMAX_EVENT_NS m512
-#include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-// big segments (4088 events: cmax_handle_s::big): 512 threads x 8 events, 1024 x 4
-#undef CMAX_SLOTS
-#undef CMAX_WINCAP
-#undef CMAX_ACC_TILES
-#undef CMAX_ACC_SMALL_GROUPS
-#define CMAX_SLOTS 4096
-#define CMAX_WINCAP 8192
-#define CMAX_ACC_TILES 6
-#define CMAX_ACC_SMALL_GROUPS 3
-#define CMAX_THREADS 512
-#define CMAX_EVENT_NS b512
-#include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-#define CMAX_THREADS 1024
-#define CMAX_EVENT_NS b1024
-#include "cmax_event_kernels.inc"
-#undef CMAX_THREADS
-#undef CMAX_EVENT_NS
-#undef CMAX_SLOTS
-#undef CMAX_WINCAP
-#undef CMAX_ACC_TILES
-#undef CMAX_ACC_SMALL_GROUPS
 
 __global__ void k_empty(const int4 *) {}  // cmax_debug_launch_floor
 
@@ -1959,13 +1892,50 @@ static float ref_fraction_lo(int ref_mode, double frac) {
     return (float)(frac - (double)(float)frac);
 }
 
-// 512-thread workgroups (4 events per thread) once the work list exceeds what the chip holds at once
-// (the voxel K3 then even 1024 x 2)
-static bool wide_groups(const cmax_handle_s *h) { return h->nseg > 1024; }
-// tuning experiments only: CMAX_VOTE_NS / CMAX_GRAD_NS = 256 | 512 | 1024 force the workgroup size of K1 / K3
-static int forced_ns(const char *name) {
-    const char *e = getenv(name);
-    return e ? atoi(e) : 0;
+// The layout of the event kernels, chosen ONCE per kernel family (each family is instantiated for the layouts its function returns).
+// A work list of big / mid segments (up to 4088 / 3064 events) can only be run by the big / mid layouts.
+// K1: 512 threads (4 events per thread) once the work list exceeds what the chip holds at once -- as for K3: cfg2 (704 half-tile
+// segments) K1 6.35 -> 5.97 us, evaluation 18.06 -> 17.38
+static Layout vote_layout(const cmax_handle_s *h) {
+    if (h->big) return Layout::b512;
+    if (h->mid) return Layout::m512;
+    return h->nseg > 512 ? Layout::t512 : Layout::t256;
+}
+// K3 (not deterministic): as K1, with the voxel K3 at 1024 threads on big segments and above 1024 segments (cfg4: 22.1 us with 512
+// threads -> 19.3 us), and at 512 threads with the small accumulator array on owned groups of <= 3 groups per segment (build_segments)
+static Layout grad_layout(const cmax_handle_s *h, int model, bool owned) {
+    const bool voxel = model == CMAX_MODEL_VOXEL;
+    if (h->big) return voxel ? Layout::b1024 : Layout::b512;
+    if (h->mid) return Layout::m512;
+    if (voxel && owned && h->small_acc) return Layout::t512;
+    if (voxel && h->nseg > 1024) return Layout::t1024;
+    return h->nseg > 512 ? Layout::t512 : Layout::t256;  // K3 hides its latencies better with 8 waves per workgroup (cfg2: 7.5 -> 7.1 us)
+}
+// deterministic K3, the tangent votes (k_vote_tan, k_vote_tan2) and the second-order gather (k_grad_hvp)
+static Layout plain_layout(const cmax_handle_s *h) {
+    if (h->big) return Layout::b512;
+    if (h->mid) return Layout::m512;
+    return Layout::t256;
+}
+
+// f(L{}) for the layout L among Ls whose id is `id`
+template <class... Ls, class F>
+static void with_layout(Layout id, F &&f) {
+    const bool found = ((Ls::kId == id ? (f(Ls{}), true) : false) || ...);
+    if (!found) std::abort();  // (a choice function returned a layout its family is not instantiated for)
+}
+// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
+template <class F>
+static void with_bool(bool b, F &&f) {
+    if (b) f(std::true_type{});
+    else f(std::false_type{});
+}
+template <int V>
+using int_c = std::integral_constant<int, V>;  // (fold / variant of k_grad)
+static int layout_threads(Layout id) {
+    int thr = 0;
+    with_layout<t256, t512, t1024, m512, b512, b1024>(id, [&](auto l) { thr = decltype(l)::kThr; });
+    return thr;
 }
 
 template <int MODEL>
@@ -1973,38 +1943,15 @@ static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
     const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref, nz);  // z: candidate motions of cmax_objective_batch
     ProfScope prof(h, kProfVote, s);
     const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // 6-byte events, one region per segment
-#define CMAX_LAUNCH_VOTE(NS, FRAC)                                                                                           \
-    do {                                                                                                                    \
-        if (ra.musum[0]) hipLaunchKernelGGL((NS::k_vote<MODEL, FRAC, true>), grid, dim3(NS::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra); \
-        else hipLaunchKernelGGL((NS::k_vote<MODEL, FRAC>), grid, dim3(NS::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);     \
-    } while (0)
-    static const int force = forced_ns("CMAX_VOTE_NS");
-    for (int rep = 0; rep < h->prof_repeat; ++rep) {
-        if (h->big) {  // the work list holds segments of up to 4088 events: only the big-segment kernels can run it
-            if (h->has_frac) CMAX_LAUNCH_VOTE(b512, true);
-            else CMAX_LAUNCH_VOTE(b512, false);
-        } else if (h->mid) {  // ... of up to 3064 events
-            if (h->has_frac) CMAX_LAUNCH_VOTE(m512, true);
-            else CMAX_LAUNCH_VOTE(m512, false);
-        } else if (force ? force == 512 : h->nseg > 512) {  // as for K3: cfg2 (704 half-tile segments) K1 6.35 -> 5.97 us, evaluation 18.06 -> 17.38
-            if (h->has_frac) CMAX_LAUNCH_VOTE(t512, true);
-            else CMAX_LAUNCH_VOTE(t512, false);
-        } else {
-            if (h->has_frac) CMAX_LAUNCH_VOTE(t256, true);
-            else CMAX_LAUNCH_VOTE(t256, false);
-        }
-    }
-#undef CMAX_LAUNCH_VOTE
-}
-
-// workgroup size launch_grad picks (tuning knob CMAX_GRAD_NS aside)
-static int grad_threads(const cmax_handle_s *h, int model) {
-    static const int force = forced_ns("CMAX_GRAD_NS");
-    if (h->big) return model == CMAX_MODEL_VOXEL ? 1024 : 512;
-    if (h->mid) return 512;
-    if (model == CMAX_MODEL_VOXEL && h->small_acc && h->owned && !force) return 512;
-    if (force ? (force == 1024 && model == CMAX_MODEL_VOXEL) : (model == CMAX_MODEL_VOXEL && wide_groups(h))) return 1024;
-    return (force ? force >= 512 : h->nseg > 512) ? 512 : 256;
+    for (int rep = 0; rep < h->prof_repeat; ++rep)
+        with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+            using L = decltype(l);
+            with_bool(h->has_frac, [&](auto frac) {
+                with_bool(ra.musum[0] != nullptr, [&](auto mu) {
+                    hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);
+                });
+            });
+        });
 }
 
 // seg0 / seg_n: sub-range of the work list (a band of tile rows, see cmax_comm_set_c2_bands); seg_n < 0 = the whole list.  The
@@ -2018,104 +1965,63 @@ static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
     const dim3 grid(8 * ((nseg + 7) / 8) + (fold == kFoldStatsInside ? ra.stat_blocks : 0), n_ref, nz);
     ProfScope prof(h, kProfGrad, s);
     const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
+    auto launch = [&](auto l, auto frac, auto fold_c, auto variant) {
+        using L = decltype(l);
+        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev, cev,
+                           (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
+    };
     if (h->deterministic) {  // one workgroup size, two ways of obtaining dL/dIWE (objective_finish runs the unfused image path)
-#define CMAX_LAUNCH_DET(FRAC, FOLD)                                                                                                         \
-    do {                                                                                                                                    \
-        if (h->big) hipLaunchKernelGGL((b512::k_grad<MODEL, FRAC, FOLD, kGradDet>), grid, dim3(b512::kThr), 0, s, segs, nseg, ev.ev, cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result); \
-        else if (h->mid) hipLaunchKernelGGL((m512::k_grad<MODEL, FRAC, FOLD, kGradDet>), grid, dim3(m512::kThr), 0, s, segs, nseg, ev.ev, cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result); \
-        else hipLaunchKernelGGL((t256::k_grad<MODEL, FRAC, FOLD, kGradDet>), grid, dim3(t256::kThr), 0, s, segs, nseg, ev.ev, cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result); \
-    } while (0)
-        if (h->has_frac) {
-            if (fold == kFoldStats) CMAX_LAUNCH_DET(true, kFoldStats);
-            else CMAX_LAUNCH_DET(true, kFoldNone);
-        } else {
-            if (fold == kFoldStats) CMAX_LAUNCH_DET(false, kFoldStats);
-            else CMAX_LAUNCH_DET(false, kFoldNone);
-        }
-#undef CMAX_LAUNCH_DET
+        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+            with_bool(h->has_frac, [&](auto frac) {
+                if (fold == kFoldStats) launch(l, frac, int_c<kFoldStats>{}, int_c<kGradDet>{});
+                else launch(l, frac, int_c<kFoldNone>{}, int_c<kGradDet>{});
+            });
+        });
         return;
     }
     // dense model: runs of equal source pixel are reduced serially per thread when they are long (pixel-sorted
     // handle, >= 8 events per active pixel), else with a segmented scan per slot over lanes holding consecutive events;
     // owned groups (dense / voxel, one reference time, group-aligned work list): LDS accumulators + plain stores
     const bool strided = MODEL == CMAX_MODEL_DENSE && !(h->long_runs && h->n_time_bin == 0);
-#define CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, VARIANT) \
-    hipLaunchKernelGGL((NS::k_grad<MODEL, FRAC, FOLD, VARIANT>), grid, dim3(NS::kThr), 0, s, segs, nseg, ev.ev, cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result)
-#define CMAX_LAUNCH_GRAD(NS, FRAC, FOLD)                                      \
-    do {                                                                      \
-        if constexpr (MODEL == CMAX_MODEL_DENSE) {                            \
-            if (owned) {                                                      \
-                CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradOwned);               \
-            } else if (strided) {                                             \
-                CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradStrided);             \
-            } else {                                                          \
-                CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradRuns);                \
-            }                                                                 \
-        } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {                     \
-            if (owned && small) {                                             \
-                if constexpr (NS::kThr == 512 && NS::kSlots <= 3072) { CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradOwnedSmall); } \
-            } else if (owned) {                                               \
-                CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradOwned);               \
-            } else {                                                          \
-                CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradRuns);                \
-            }                                                                 \
-        } else {                                                              \
-            CMAX_LAUNCH_GRAD_L(NS, FRAC, FOLD, kGradRuns);                    \
-        }                                                                     \
-    } while (0)
-#define CMAX_LAUNCH_GRAD_FR(NS, FRAC)                                                        \
-    if (fold == kFoldDeferred) {                                                             \
-        if constexpr (MODEL == CMAX_MODEL_2DOF) { CMAX_LAUNCH_GRAD(NS, FRAC, kFoldDeferred); } \
-    } else if (fold == kFoldStatsInside) {                                                   \
-        if constexpr (MODEL == CMAX_MODEL_VOXEL && NS::kThr == 512 && NS::kSlots <= 3072) {   \
-            if (!owned) { CMAX_LAUNCH_GRAD(NS, FRAC, kFoldStatsInside); }                    \
-            else if (small) { CMAX_LAUNCH_GRAD_L(NS, FRAC, kFoldStatsInside, kGradOwnedSmall); } \
-            else { CMAX_LAUNCH_GRAD_L(NS, FRAC, kFoldStatsInside, kGradOwned); }            \
-        } else if constexpr (MODEL != CMAX_MODEL_2DOF) {                                     \
-            if (owned) { CMAX_LAUNCH_GRAD_L(NS, FRAC, kFoldStatsInside, kGradOwned); }       \
-            else { CMAX_LAUNCH_GRAD(NS, FRAC, kFoldStatsInside); }                           \
-        }                                                                                    \
-    } else if (fold == kFoldStats) {                                                         \
-        CMAX_LAUNCH_GRAD(NS, FRAC, kFoldStats);                                              \
-    } else if (fold == kFoldScale) {                                                         \
-        CMAX_LAUNCH_GRAD(NS, FRAC, kFoldScale);                                              \
-    } else {                                                                                 \
-        CMAX_LAUNCH_GRAD(NS, FRAC, kFoldNone);                                               \
-    }
-#define CMAX_LAUNCH_GRAD_NS(NS)          \
-    if (h->has_frac) {                   \
-        CMAX_LAUNCH_GRAD_FR(NS, true)    \
-    } else {                             \
-        CMAX_LAUNCH_GRAD_FR(NS, false)   \
-    }
-    static const int force = forced_ns("CMAX_GRAD_NS");
-    // voxel, owned groups of <= 3 groups per segment: 512 threads x 4 events with the small accumulator array (see build_segments)
-    const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big && !force;
-    for (int rep = 0; rep < h->prof_repeat; ++rep) {
-        if (h->big) {  // segments of up to 4088 events
-            if constexpr (MODEL == CMAX_MODEL_VOXEL) {
-                CMAX_LAUNCH_GRAD_NS(b1024)
+    // voxel, owned groups of <= 3 groups per segment: the small accumulator array (grad_layout: 512 threads x 4 events, or mid segments)
+    const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big;
+    auto body = [&](auto l) {
+        using L = decltype(l);
+        auto with_variant = [&](auto frac, auto fold_c) {
+            if constexpr (MODEL == CMAX_MODEL_DENSE) {
+                if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{});
+                else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{});
+                else launch(l, frac, fold_c, int_c<kGradRuns>{});
+            } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
+                if (owned && small) {
+                    if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{});
+                } else if (owned) {
+                    launch(l, frac, fold_c, int_c<kGradOwned>{});
+                } else {
+                    launch(l, frac, fold_c, int_c<kGradRuns>{});
+                }
             } else {
-                CMAX_LAUNCH_GRAD_NS(b512)
+                launch(l, frac, fold_c, int_c<kGradRuns>{});
             }
-        } else if (h->mid) {  // ... of up to 3064 events
-            CMAX_LAUNCH_GRAD_NS(m512)
-        } else if (small) {
-            CMAX_LAUNCH_GRAD_NS(t512)
-        } else if (force ? (force == 1024 && MODEL == CMAX_MODEL_VOXEL) : (MODEL == CMAX_MODEL_VOXEL && wide_groups(h))) {  // measured: voxel K3 of cfg4 22.1 us (512 threads) -> 19.3 us
-            if constexpr (MODEL == CMAX_MODEL_VOXEL) {
-                CMAX_LAUNCH_GRAD_NS(t1024)
+        };
+        with_bool(h->has_frac, [&](auto frac) {
+            if (fold == kFoldDeferred) {
+                if constexpr (MODEL == CMAX_MODEL_2DOF) with_variant(frac, int_c<kFoldDeferred>{});
+            } else if (fold == kFoldStatsInside) {
+                if constexpr (MODEL != CMAX_MODEL_2DOF) with_variant(frac, int_c<kFoldStatsInside>{});
+            } else if (fold == kFoldStats) {
+                with_variant(frac, int_c<kFoldStats>{});
+            } else if (fold == kFoldScale) {
+                with_variant(frac, int_c<kFoldScale>{});
+            } else {
+                with_variant(frac, int_c<kFoldNone>{});
             }
-        } else if (force ? force >= 512 : h->nseg > 512) {  // K3 hides its latencies better with 8 waves per workgroup (cfg2: 7.5 -> 7.1 us)
-            CMAX_LAUNCH_GRAD_NS(t512)
-        } else {
-            CMAX_LAUNCH_GRAD_NS(t256)
-        }
+        });
+    };
+    for (int rep = 0; rep < h->prof_repeat; ++rep) {
+        if constexpr (MODEL == CMAX_MODEL_VOXEL) with_layout<b1024, m512, t512, t1024, t256>(grad_layout(h, MODEL, owned), body);
+        else with_layout<b512, m512, t512, t256>(grad_layout(h, MODEL, owned), body);
     }
-#undef CMAX_LAUNCH_GRAD_NS
-#undef CMAX_LAUNCH_GRAD_FR
-#undef CMAX_LAUNCH_GRAD
-#undef CMAX_LAUNCH_GRAD_L
 }
 
 static EvView ev_view(const cmax_handle_s *h) {
@@ -2574,7 +2480,7 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
             if (rc) return rc;
             h->cev_cap = h->nseg;
         }
-        hipLaunchKernelGGL((b512::k_pack_compact<0>), dim3(h->nseg), dim3(b512::kThr), 0, s, (const int4 *)h->d_segs, h->nseg, (const uint2 *)h->evp, h->ntc,
+        hipLaunchKernelGGL((k_pack_compact<b512>), dim3(h->nseg), dim3(b512::kThr), 0, s, (const int4 *)h->d_segs, h->nseg, (const uint2 *)h->evp, h->ntc,
                            h->cev, h->d_flags + 3);
         CMAX_CHECK_HIP(hipGetLastError());
         static const bool debug_compact = getenv("CMAX_DEBUG_COMPACT") != nullptr;
@@ -3425,7 +3331,8 @@ static int objective_finish(cmax_handle_t h, const cmax_objective_t *d, const fl
         // with 232 statistics workgroups 1132 > 1024 resident, with 120 it fits -- K3 16.1 -> 14.8 us, the evaluation 28.8 -> 27.4 us;
         // 3 / 4 / 6 / 8 / 16 sweeps: 28.8 / 27.4 / 27.6 / 27.8 / 31.3 us, profiles/r04_ablation.txt 15).  CMAX_STAT_SWEEPS overrides.
         static const int sweeps_env = getenv("CMAX_STAT_SWEEPS") ? std::max(1, atoi(getenv("CMAX_STAT_SWEEPS"))) : 0;
-        const int gthreads = grad_threads(h, d->model);
+        // (h->owned, as before: the launch's grad_layout takes this call's `owned`, which can be false where h->owned is not)
+        const int gthreads = layout_threads(grad_layout(h, d->model, h->owned));
         auto blocks_for = [&](int sweeps) {
             const int64_t per_block = 4 * (int64_t)gthreads * sweeps;
             return (int)std::min<int64_t>(8 * div_up(div_up(npix, per_block), 8), 8 * (kStatBlocksMax / 8));
@@ -3570,14 +3477,12 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
         const dim3 grid(8 * ((h->nseg + 7) / 8), nr);
         ProfScope prof(h, kProfVote, s);
         for (int rep = 0; rep < h->prof_repeat; ++rep) {
-            if (h->big) {
-                if (h->has_frac) hipLaunchKernelGGL((b512::k_vote_tan2<true>), grid, dim3(b512::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-                else hipLaunchKernelGGL((b512::k_vote_tan2<false>), grid, dim3(b512::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-            } else if (h->mid) {
-                if (h->has_frac) hipLaunchKernelGGL((m512::k_vote_tan2<true>), grid, dim3(m512::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-                else hipLaunchKernelGGL((m512::k_vote_tan2<false>), grid, dim3(m512::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-            } else if (h->has_frac) hipLaunchKernelGGL((t256::k_vote_tan2<true>), grid, dim3(t256::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-            else hipLaunchKernelGGL((t256::k_vote_tan2<false>), grid, dim3(t256::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
+            with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+                using L = decltype(l);
+                with_bool(h->has_frac, [&](auto frac) {
+                    hipLaunchKernelGGL((k_vote_tan2<L, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
+                });
+            });
         }
         CMAX_CHECK_LAUNCH();
     }
@@ -4014,28 +3919,24 @@ template <int MODEL>
 static void launch_vote_tan(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, float *draw, hipStream_t s,
                             long long *draw64 = nullptr) {
     const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
-    if (h->big) {
-        if (h->has_frac) hipLaunchKernelGGL((b512::k_vote_tan<MODEL, true>), grid, dim3(b512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
-        else hipLaunchKernelGGL((b512::k_vote_tan<MODEL, false>), grid, dim3(b512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
-    } else if (h->mid) {
-        if (h->has_frac) hipLaunchKernelGGL((m512::k_vote_tan<MODEL, true>), grid, dim3(m512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
-        else hipLaunchKernelGGL((m512::k_vote_tan<MODEL, false>), grid, dim3(m512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
-    } else if (h->has_frac) hipLaunchKernelGGL((t256::k_vote_tan<MODEL, true>), grid, dim3(t256::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
-    else hipLaunchKernelGGL((t256::k_vote_tan<MODEL, false>), grid, dim3(t256::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
+    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
+        });
+    });
 }
 
 template <int MODEL>
 static void launch_grad_hvp(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, const float *G,
                             const float *Gp, double *gpart, float *hflow, hipStream_t s, const HvpDet &det) {
     const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
-    if (h->big) {
-        if (h->has_frac) hipLaunchKernelGGL((b512::k_grad_hvp<MODEL, true>), grid, dim3(b512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
-        else hipLaunchKernelGGL((b512::k_grad_hvp<MODEL, false>), grid, dim3(b512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
-    } else if (h->mid) {
-        if (h->has_frac) hipLaunchKernelGGL((m512::k_grad_hvp<MODEL, true>), grid, dim3(m512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
-        else hipLaunchKernelGGL((m512::k_grad_hvp<MODEL, false>), grid, dim3(m512::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
-    } else if (h->has_frac) hipLaunchKernelGGL((t256::k_grad_hvp<MODEL, true>), grid, dim3(t256::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
-    else hipLaunchKernelGGL((t256::k_grad_hvp<MODEL, false>), grid, dim3(t256::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
+    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
+        });
+    });
 }
 
 }  // namespace cmax
@@ -4476,7 +4377,7 @@ int cmax_debug_launch_floor(cmax_handle_t h, int pairs, cmax_stream_t stream) {
     CMAX_REQUIRE(h != nullptr && pairs > 0, "debug_launch_floor");
     CMAX_REQUIRE(h->n > 0 && h->nseg > 0, "debug_launch_floor: no events set");
     const dim3 grid(8 * ((h->nseg + 7) / 8));
-    const int k1 = (h->big || h->mid) ? 512 : (h->nseg > 512 ? 512 : 256), k3 = grad_threads(h, CMAX_MODEL_2DOF);
+    const int k1 = layout_threads(vote_layout(h)), k3 = layout_threads(grad_layout(h, CMAX_MODEL_2DOF, false));
     for (int i = 0; i < pairs; ++i) {
         hipLaunchKernelGGL(k_empty, grid, dim3(k1), 0, (hipStream_t)stream, h->d_segs);
         hipLaunchKernelGGL(k_empty, grid, dim3(k3), 0, (hipStream_t)stream, h->d_segs);

@@ -4,7 +4,7 @@
 instruction and SIMD, and / xor / add_u32 in ~3.2, everything else (conversions, floor, min / max / med3, bit-field and shift forms,
 24-bit multiplies, selects, packed-u16, DPP moves, packed fp32) in ~4.2.
 
-    python tools/isa_cost.py /tmp/fused.s 'b5126k_voteILi1ELb0ELb0' [--ops] [--blocks]
+    python tools/isa_cost.py /tmp/fused.s 'k_voteINS_4b512ELi1ELb0ELb0E' [--ops] [--blocks]
 
 --ops: histogram per opcode; --blocks: per basic block (label) totals, to find the straight-line event code."""
 import collections

@@ -1,6 +1,6 @@
 #!/usr/bin/env python
 """Static instruction mix per kernel from a gfx950 assembly listing (hipcc --cuda-device-only -S):
-   python tools/isa_mix.py /tmp/fused.s 'k_voteILi1ELb0' ['--dump' to print the body]"""
+   python tools/isa_mix.py /tmp/fused.s 'k_voteINS_4t512ELi1ELb0E' ['--dump' to print the body]"""
 import collections
 import re
 import sys

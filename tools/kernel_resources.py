@@ -3,7 +3,7 @@
    hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -fno-gpu-rdc --cuda-device-only -c csrc/cmax_fused.hip \
          -o /tmp/x.o -Rpass-analysis=kernel-resource-usage 2> /tmp/res.txt
    python tools/kernel_resources.py /tmp/res.txt [regex on the demangled name]
-(The rule of profiles/r02_ablation.txt: <= 80 SGPRs keeps 8 waves per SIMD; check the t512 / t1024 k_grad after every change.)"""
+(The rule of profiles/r02_ablation.txt: <= 80 SGPRs keeps 8 waves per SIMD; check k_grad<cmax::t512, ...> and k_grad<cmax::t1024, ...> after every change.)"""
 import re
 import subprocess
 import sys

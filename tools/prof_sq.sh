@@ -27,10 +27,10 @@ for p in (1, 2, 3):
     for row in csv.DictReader(open(files[0])):
         d[row["Kernel_Name"]][row["Counter_Name"]].append(float(row["Counter_Value"]))
     for k, ctrs in d.items():
-        m = re.search(r"cmax::(?:([tbm]\d+)::)?(k_\w+)", k)
+        m = re.search(r"cmax::(k_\w+)(?:<cmax::([tbm]\d+))?", k)  # the layout is an event kernel's first template argument
         if not m:
             continue
-        name = (m.group(1) + "::" if m.group(1) else "") + m.group(2)
+        name = (m.group(2) + "::" if m.group(2) else "") + m.group(1)
         for c, v in ctrs.items():
             if len(v) >= 10:
                 res[name][c] = sum(v) / len(v)
