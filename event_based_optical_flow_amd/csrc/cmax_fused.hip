@@ -259,11 +259,7 @@ struct cmax_handle_s {
     unsigned long long host_seq = 0;  // run counter of the finishing kernel that writes into hp_out (polled by cmax_objective_host)
     int *d_ticket = nullptr;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches
     double *d_musum = nullptr;  // [2 buffers][4 reference times][kMuStride] K1's sums for the blurred variance (RefArgs::musum)
-    float4 *vote_clear4 = nullptr;      // objective_eval -> vote_images: gradient buffer K1 is to clear (RefArgs::grad_zero), consumed by the launch
-    int64_t vote_nclear4 = 0;
-    const void *grad_cleared_by_vote = nullptr;  // ... and which buffer the K1 launch of the current evaluation did clear
-    int mu_buf = 0;             // buffer the next evaluation adds into (the other one is being cleared / is clear)
-    bool mu_valid = false;      // the K1 launch of the current cmax_objective call filled d_musum[mu_buf]
+    int mu_buf = 0;             // buffer the next evaluation adds into (the other one is being cleared / is clear); flipped by the launch that reads the sums
     // orig-IWE cache key
     bool orig_valid = false;
     double orig_sigma = -1;
@@ -1891,6 +1887,13 @@ static float ref_fraction_lo(int ref_mode, double frac) {
     if (ref_mode == CMAX_REF_FIRST || ref_mode == CMAX_REF_LAST) return 0.f;
     return (float)(frac - (double)(float)frac);
 }
+// the reference times of a launch (RefArgs::d / d_lo)
+static void fill_ref_times(RefArgs &ra, int n_ref, const int *ref_mode, const double *ref_frac) {
+    for (int k = 0; k < n_ref; ++k) {
+        ra.d[k] = ref_fraction(ref_mode[k], ref_frac[k]);
+        ra.d_lo[k] = ref_fraction_lo(ref_mode[k], ref_frac[k]);
+    }
+}
 
 // The layout of the event kernels, chosen ONCE per kernel family (each family is instantiated for the layouts its function returns).
 // A work list of big / mid segments (up to 4088 / 3064 events) can only be run by the big / mid layouts.
@@ -1932,6 +1935,13 @@ static void with_bool(bool b, F &&f) {
 }
 template <int V>
 using int_c = std::integral_constant<int, V>;  // (fold / variant of k_grad)
+// f(int_c<MODEL>{}) for the motion model of an objective (check_objective_args: one of the three)
+template <class F>
+static void with_model(int model, F &&f) {
+    if (model == CMAX_MODEL_2DOF) f(int_c<CMAX_MODEL_2DOF>{});
+    else if (model == CMAX_MODEL_DENSE) f(int_c<CMAX_MODEL_DENSE>{});
+    else f(int_c<CMAX_MODEL_VOXEL>{});
+}
 static int layout_threads(Layout id) {
     int thr = 0;
     with_layout<t256, t512, t1024, m512, b512, b1024>(id, [&](auto l) { thr = decltype(l)::kThr; });
@@ -2054,22 +2064,31 @@ static WarpParams warp_params(const cmax_handle_s *h, const float *motion, int T
     return wp;
 }
 
+// What a K1 launch does besides voting -- decided by eval_plan for the K1 of a whole evaluation; nothing for a plain vote (cmax_iwe, the
+// un-warped image, the second-order product)
+struct VoteJobs {
+    bool publish_windows = false;  // K3 of the same evaluation re-uses the LDS windows (see finish_grad_args)
+    bool sums = false;             // also accumulate sum_p I[p] B[p] (RefArgs::musum) into d_musum[mu_buf]; never deterministic, never without events
+    float band_b0 = 0.f, band_b1 = 0.f;  // ... b(0) and b(1) of B's border_weight
+    // 2-DoF objectives: K1 clears the raw sums its K3 adds into -- through its statistics slot when the objective keeps none
+    // (deferred: raw_reset), through RefArgs::raw_zero otherwise (raw_lines)
+    double *raw_reset = nullptr, *raw_lines = nullptr;
+    float4 *grad_zero = nullptr;   // flow-gradient buffer to clear (RefArgs::grad_zero), or null
+    int64_t n_grad_zero4 = 0;
+};
+
 // raw votes of n_ref reference times (one launch) into imgs[k] (cleared here unless bit k of zero_mask says it is
 // zero already); stat_slot0 >= 0: the statistics accumulators of slots stat_slot0 + k are reset by the launch
-// mu_taps: non-null = also accumulate sum_p I[p] B[p] for the blurred variance (taps k0, k1 of the blur, omit_boundary in [2])
 static int vote_images(cmax_handle_s *h, int model, const float *motion, int T, int n_ref, const int *ref_mode, const double *ref_frac,
-                       int normalize, float *const *imgs, unsigned zero_mask, int stat_slot0, hipStream_t s, bool publish_windows = false,
-                       const float *mu_taps = nullptr, int motion_f64 = 0, double *raw_reset = nullptr, double *raw_lines = nullptr) {
+                       int normalize, float *const *imgs, unsigned zero_mask, int stat_slot0, hipStream_t s, const VoteJobs &jobs = {},
+                       int motion_f64 = 0) {
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     RefArgs ra = {};
-    ra.k0 = 0;
-    ra.raw_zero = raw_lines;  // (the deferred objective resets its sums through ra.stat instead: raw_reset)
-    ra.grad_zero = h->vote_clear4;
-    ra.n_grad_zero4 = h->vote_nclear4;
-    h->grad_cleared_by_vote = h->vote_clear4;
-    h->vote_clear4 = nullptr;
-    h->vote_nclear4 = 0;
-    if (publish_windows && h->n > 0) {  // K3 of the same evaluation re-uses the LDS windows (see objective_finish)
+    ra.raw_zero = jobs.raw_lines;
+    ra.grad_zero = jobs.grad_zero;
+    ra.n_grad_zero4 = jobs.n_grad_zero4;
+    fill_ref_times(ra, n_ref, ref_mode, ref_frac);
+    if (jobs.publish_windows && h->n > 0) {
         ra.win = h->d_win;
         ra.shifts = h->d_shifts;
         h->win_motion = motion;
@@ -2077,7 +2096,7 @@ static int vote_images(cmax_handle_s *h, int model, const float *motion, int T, 
         h->win_nref = n_ref;
         h->win_T = T;
         h->win_normalize = normalize;
-        for (int k = 0; k < n_ref; ++k) h->win_d[k] = ref_fraction(ref_mode[k], ref_frac[k]);
+        for (int k = 0; k < n_ref; ++k) h->win_d[k] = ra.d[k];
         h->win_generation = h->generation;
     }
     const bool det = h->deterministic && h->n > 0;  // votes go to the integer images, imgs[k] are written by the conversion below
@@ -2086,29 +2105,20 @@ static int vote_images(cmax_handle_s *h, int model, const float *motion, int T, 
         if (det) ra.img64[k] = h->img64 + (int64_t)k * npix;
         // accumulators K1's first workgroup resets: the statistics of slot stat_slot0 + k, or (deferred 2-DoF objective: no
         // statistics kernel runs) the raw sums K3 of the same evaluation adds into
-        double *stat_zero = raw_reset ? raw_reset + (int64_t)k * kRawStride : (stat_slot0 >= 0 ? h->d_stat + (stat_slot0 + k) * kStatStride : nullptr);
+        double *stat_zero = jobs.raw_reset ? jobs.raw_reset + (int64_t)k * kRawStride : (stat_slot0 >= 0 ? h->d_stat + (stat_slot0 + k) * kStatStride : nullptr);
         if (h->n == 0 && stat_zero)  // no K1 launch on this rank: reset the accumulators explicitly
             CMAX_CHECK_HIP(hipMemsetAsync(stat_zero, 0, kStatStride * sizeof(double), s));
-        ra.d[k] = ref_fraction(ref_mode[k], ref_frac[k]);
-        ra.d_lo[k] = ref_fraction_lo(ref_mode[k], ref_frac[k]);
         ra.img[k] = imgs[k];
         ra.stat[k] = stat_zero;
-        if (mu_taps && !det && h->n > 0) ra.musum[k] = h->d_musum + ((int64_t)h->mu_buf * 4 + k) * kMuStride;
+        if (jobs.sums) ra.musum[k] = h->d_musum + ((int64_t)h->mu_buf * 4 + k) * kMuStride;
     }
-    if (mu_taps) h->mu_valid = ra.musum[0] != nullptr;
-    if (ra.musum[0]) {
-        ra.band_b0 = border_weight(0, h->Hp, (int)mu_taps[2], mu_taps[0], mu_taps[1]);
-        ra.band_b1 = border_weight(1, h->Hp, (int)mu_taps[2], mu_taps[0], mu_taps[1]);
-    }
+    ra.band_b0 = jobs.band_b0;
+    ra.band_b1 = jobs.band_b1;
     if (h->n == 0) return 0;
     const EvView ev = ev_view(h);
     const WarpParams wp = warp_params(h, motion, T, ref_mode[0], ref_frac[0], normalize, motion_f64);
-    switch (model) {
-        case CMAX_MODEL_2DOF: launch_vote<CMAX_MODEL_2DOF>(h, ev, wp, ra, n_ref, s); break;
-        case CMAX_MODEL_DENSE: launch_vote<CMAX_MODEL_DENSE>(h, ev, wp, ra, n_ref, s); break;
-        case CMAX_MODEL_VOXEL: launch_vote<CMAX_MODEL_VOXEL>(h, ev, wp, ra, n_ref, s); break;
-        default: launch_vote<-1>(h, ev, wp, ra, n_ref, s); break;
-    }
+    if (model < 0) launch_vote<-1>(h, ev, wp, ra, n_ref, s);  // the un-warped image
+    else with_model(model, [&](auto m) { launch_vote<m.value>(h, ev, wp, ra, n_ref, s); });
     CMAX_CHECK_LAUNCH();
     if (det) {  // exact integer sums -> fp32 images, one rounding each; the integer images are zero again afterwards
         FixedArgs fa = {};
@@ -2965,82 +2975,23 @@ static bool orig_cache_hit(const cmax_handle_s *h, const cmax_objective_t *d) {
     return h->orig_valid && h->orig_sigma == d->sigma && h->orig_cost == d->cost && h->orig_omit == d->omit_boundary;
 }
 
-// K3 stores every element of the flow gradient itself (one writer per pixel): needs the group-aligned work list, ONE reference
-// time (several would add into the same pixels) and the sort order that matches the model (dense: tiles; voxel: (tile, bin) of
-// the same T)
-static bool owned_groups_apply(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad) {
-    return !h->deterministic && grad && h->owned && h->n > 0 && d->n_ref == 1 &&
-           ((d->model == CMAX_MODEL_DENSE && h->n_time_bin == 0) || (d->model == CMAX_MODEL_VOXEL && h->n_time_bin == d->T));
-}
-
-// votes of every reference time (+ the un-warped image when needed) into images[0 .. n_images);
-// zero_mask bit k: images[k] is already zero (the handle's double-buffered images)
 // K1 without its votes: the LDS windows and the fp64 cell decisions (RefArgs::win / shifts) of this warp, for a K3 that follows
 static int publish_windows(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, hipStream_t s) {
     RefArgs ra = {};
     ra.win = h->d_win;
     ra.shifts = h->d_shifts;
     ra.windows_only = 1;
-    for (int k = 0; k < d->n_ref; ++k) {
-        ra.d[k] = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        ra.d_lo[k] = ref_fraction_lo(d->ref_mode[k], d->ref_frac[k]);
-    }
+    fill_ref_times(ra, d->n_ref, d->ref_mode, d->ref_frac);
     const EvView ev = ev_view(h);
     const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
-    switch (d->model) {
-        case CMAX_MODEL_2DOF: launch_vote<CMAX_MODEL_2DOF>(h, ev, wp, ra, d->n_ref, s); break;
-        case CMAX_MODEL_DENSE: launch_vote<CMAX_MODEL_DENSE>(h, ev, wp, ra, d->n_ref, s); break;
-        default: launch_vote<CMAX_MODEL_VOXEL>(h, ev, wp, ra, d->n_ref, s); break;
-    }
+    with_model(d->model, [&](auto m) { launch_vote<m.value>(h, ev, wp, ra, d->n_ref, s); });
     CMAX_CHECK_LAUNCH();
     h->win_motion = nullptr;  // (nobody may take these windows for those of a vote)
     return 0;
 }
 
-static int objective_vote(cmax_handle_t h, const cmax_objective_t *d, const float *motion, float *images, unsigned zero_mask,
-                          int *n_images_out, hipStream_t s, bool want_mu = false, double *raw_reset = nullptr, double *raw_lines = nullptr) {
-    const int64_t npix = (int64_t)h->Hp * h->Wp;
-    h->mu_valid = false;
-    {
-        float *imgs[4];
-        for (int k = 0; k < d->n_ref; ++k) imgs[k] = images + k * npix;
-        float mu_taps[3] = {0.f, 0.f, d->omit_boundary ? 1.f : 0.f};
-        if (want_mu) {
-            double k0 = 1, k1 = 0;  // no blur: B = 1_Omega
-            if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
-            mu_taps[0] = (float)k0;
-            mu_taps[1] = (float)k1;
-        }
-        int rc = vote_images(h, d->model, motion, d->T, d->n_ref, d->ref_mode, d->ref_frac, d->normalize_t, imgs, zero_mask, 0, s, true,
-                             want_mu ? mu_taps : nullptr, d->motion_dtype == CMAX_F64, raw_reset, raw_lines);
-        if (rc) return rc;
-    }
-    int n_images = d->n_ref;
-    if (d->normalized && !orig_cache_hit(h, d)) {  // un-warped image, once per batch (patch_contrast_base.py:295-301)
-        int rc = vote_image(h, -1, nullptr, 0, CMAX_REF_FIRST, 0.0, 1, images + (int64_t)d->n_ref * npix,
-                            (zero_mask >> d->n_ref) & 1u, 4, s);
-        if (rc) return rc;
-        ++n_images;
-    }
-    *n_images_out = n_images;
-    return 0;
-}
-
-int cmax_objective_vote(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, float *images, int *n_images_host,
-                        cmax_stream_t stream) {
-    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
-    int rc = check_objective_args(h, d, motion);
-    if (rc) return rc;
-    CMAX_REQUIRE(images && n_images_host, "objective_vote: images / n_images_host");
-    return objective_vote(h, d, motion, images, 0u, n_images_host, (hipStream_t)stream);
-}
-
-// zero_next: base of the image buffer of the NEXT evaluation (k_stats of image k zeroes zero_next[k]) or nullptr
-// reuse_windows: the caller guarantees that `motion` still holds the values of the vote that published h->d_win
-// (cmax_objective / cmax_objective_dist: same call).  The stand-alone cmax_objective_finish cannot know -- a caching
-// allocator hands the same address to a different motion -- and lets K3 derive its windows again.
-// raw: the accumulators of the deferred 2-DoF K3 (null: the handle's own); raw_is_reset: K1 of this evaluation cleared them;
-// raw_only: stop there -- the caller folds the sums itself (cmax_objective_raw / cmax_objective_host), no finishing launch
+// 2-DoF + plain variance with a gradient: K3 gathers the image statistics itself and k_finish_raw applies
+// the chain factors -- no K2 launch (unless a workgroup's slice of the image would get long)
 static bool deferred_applies(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad) {
     return !h->deterministic && grad && d->model == CMAX_MODEL_2DOF && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && h->n > 0 &&
            (int64_t)h->Hp * h->Wp <= (int64_t)h->nseg * 8192;
@@ -3051,14 +3002,23 @@ static bool two_dof_lines(const cmax_handle_s *h, const cmax_objective_t *d, con
     return !h->deterministic && grad && d->model == CMAX_MODEL_2DOF && h->n > 0;
 }
 
+// the motion gradient of an objective: elements, bytes, element type of its exchange
+struct GradExtent {
+    int64_t count;
+    size_t bytes;
+    CommType type;
+};
+static GradExtent grad_extent(const cmax_handle_s *h, const cmax_objective_t *d) {
+    if (d->model == CMAX_MODEL_2DOF) return {2, 2 * sizeof(double), kCommF64};
+    const int64_t count = (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
+    return {count, (size_t)count * sizeof(float), kCommF32};
+}
+
 // C2 in row bands (cmax_comm_set_c2_bands).  WHETHER the gradient is exchanged in bands, and in which, must not depend on anything a
 // rank knows about its own slice (a rank without events, or whose work list is not group-aligned, issued ONE all-reduce
 // while its peers issued `bands` grouped ones -- different collective sequences, i.e. a hang): the bands follow from the sensor's tile
 // rows and the setting alone, every rank issues the same `bands` grouped all-reduces on its second stream, and only HOW its K3 runs
-// in front of them is local -- band by band where the work list allows it (overlap), in one launch or not at all otherwise.
-static int c2_band_count(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, cmax::Comm *c2_comm) {
-    return (c2_comm && grad && d->model == CMAX_MODEL_DENSE && h->c2_bands > 1) ? std::min(h->c2_bands, h->ntr) : 1;
-}
+// in front of them is local -- band by band where the work list allows it (overlap), in one launch or not at all otherwise (eval_plan: bands).
 static int c2_prepare_bands(cmax_handle_s *h, int bands) {
     if (!h->comm_stream) CMAX_CHECK_HIP(hipStreamCreateWithFlags(&h->comm_stream, hipStreamNonBlocking));
     while ((int)h->band_ev.size() < bands + 1) {
@@ -3122,215 +3082,118 @@ static int c2_exchange_all_bands(cmax_handle_s *h, cmax::Comm *c2_comm, float *g
     return rc ? rc : c2_join_bands(h, bands, s);
 }
 
-static int objective_finish(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *images, int n_images,
-                            float *zero_next, double *result, void *grad, hipStream_t s, bool reuse_windows, double *raw = nullptr,
-                            bool raw_is_reset = false, bool raw_only = false, cmax::Comm *c2_comm = nullptr, bool *c2_done = nullptr,
-                            volatile unsigned long long *host_flag = nullptr, unsigned long long host_seq = 0) {
-    int rc = 0;
-    const int Hp = h->Hp, Wp = h->Wp;
-    const int64_t npix = (int64_t)Hp * Wp;
-    const int64_t gcount = d->model == CMAX_MODEL_2DOF ? 2 : (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
-    const size_t gbytes = d->model == CMAX_MODEL_2DOF ? 2 * sizeof(double) : (size_t)gcount * sizeof(float);
+// 2-DoF, plain variance: K1T (image + two tangent images) -> [ONE all-reduce] -> k_tan_stats_var -> k_finish_deferred.
+// No pass over the events for the gradient, and across GPUs no second exchange: after the all-reduce every rank holds
+// the whole batch's three images and finishes loss and gradient on its own.
+// force: CMAX_TAN2 (1 = also on one GPU, 0 = never, -1 = unset)
+static bool tan2_applicable(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool dist, int force) {
+    if (force == 0 || h->deterministic || !grad) return false;
+    if (d->model != CMAX_MODEL_2DOF || d->cost != CMAX_COST_VARIANCE || d->sigma > 0) return false;
+    // Rank-consistent scalars: behind the single exchange every rank finishes loss AND gradient on its own -- from the reduced planes in a
+    // fixed order (per-workgroup partials, one folding wave: bit-identical on every rank), but a NORMALISED variance also reads the
+    // un-warped image's cached statistics, which each rank summed with atomics in its own order.  Across real ranks that objective
+    // takes the two-exchange path, whose gradient is all-reduced and whose scalars ride along.
+    if (d->normalized && h->comm && comm_nranks(h->comm) > 1) return false;
+    if (d->normalized && !orig_cache_hit(h, d)) return false;  // the first evaluation of a batch builds the un-warped image's statistics on the standard path
+    return dist || force == 1;
+}
 
-    const ObjParams op = obj_params(h, d);
+// How one evaluation runs: every path decision, taken ONCE by eval_plan before anything is enqueued.  objective_eval, objective_vote /
+// vote_images and objective_finish read the plan; none of them derives a decision again.
+struct EvalPlan {
+    // ---- the form of the call
+    // whole: K1 of this very call voted the images (objective_eval), so `motion` still holds the values of the vote that published
+    // h->d_win and K3 re-uses the windows.  The stand-alone cmax_objective_finish cannot know -- a caching allocator hands the same
+    // address to a different motion -- and lets K3 derive its windows again; every decision that needs a job done by K1 is false for it.
+    bool whole;
+    bool tan2;                // the tangent-image path instead (objective_eval_tan2): nothing below applies
+    bool empty;               // empty batch and no communicator: loss 0, zero gradient, no launch
+    cmax::Comm *c2_comm;      // the gradient (result[8] riding along) is all-reduced: in `bands` row bands by objective_finish, in one call behind it when bands == 1
+    bool result_alone;        // value-only evaluation under a communicator: result[8] is exchanged on its own
+    double *raw;              // lines: the accumulators of the 2-DoF K3 -- the caller's (cmax_objective_raw) or the handle's own
+    bool raw_only;            // stop at those sums: the caller folds them itself (cmax_objective_raw), no finishing launch
+    volatile unsigned long long *host_flag;  // cmax_objective_host: `result` and `grad` are pinned host memory, the finishing kernel writes the
+    unsigned long long host_seq;             // run counter behind them
+    GradExtent g;
+    // ---- the path
+    bool deferred;  // deferred_applies: no K2, K3 gathers the statistics, k_finish_raw applies the chain factors
+    bool lines;     // two_dof_lines (includes the deferred case)
+    bool fused_gm;  // gradient magnitude with a gradient: K2 and K2b (and the blurs) are one kernel: statistics + G image without its chain factor
+    bool blur_var;  // blurred variance: blur + statistics in one kernel
+    bool fused_bv;  // ... with a gradient on one GPU: K1 also sums the votes against blur^T 1_Omega, so that ONE image kernel can blur, sum and
+                    // write the un-centred, unscaled A' = 2 / (n - 1) blur^T [Ib 1_Omega] (k_blur_stats_adj_var); K3 applies the chain factor
+                    // (kFoldScale) and, along the image border, the mean.  Across GPUs the sum would need its own exchange: two image kernels.
+    bool owned;     // owned groups: K3 stores every element of the flow gradient itself -- nothing to clear
+    bool stats_inside;  // plain variance, not normalised, K1 of this call summed its votes: the statistics run inside the K3 launch (kFoldStatsInside)
+    int stat_blocks;    // ... in this many leading workgroups (RefArgs::stat_blocks)
+    int fold;           // kFold* of K3
+    // who clears the flow gradient K3 adds into (no one on owned groups): K1 (vote.grad_zero), the statistics / fused image kernel, or a memset
+    float4 *stats_clear4;
+    int64_t n_stats_clear4;
+    bool memset_grad;
+    float tap0, tap1;   // blur taps (sigma > 0)
+    int bands;          // row bands the gradient is exchanged in: the same on every rank
+    bool k3_in_bands;   // ... and this rank's work list allows K3 band by band, each band's rows exchanged behind it
+    VoteJobs vote;      // what K1 does for the launches behind it
+};
 
-    // statistics of the un-warped image (slot 4) are cached per batch
-    if (d->normalized) {
-        if (n_images == d->n_ref + 1) {
-            const float *img = nullptr;
-            rc = blur_image(h, d->sigma, images + (int64_t)d->n_ref * npix, h->iweb[4], &img, s);
-            if (rc) return rc;
-            // orig_iwe is NOT boundary-cropped for the variance (normalized_image_variance.py:40-41)
-            const int omit_o = d->cost == CMAX_COST_VARIANCE ? 0 : d->omit_boundary;
-            rc = launch_stats(h, d->cost, img, omit_o, 4, zero_next ? zero_next + (int64_t)d->n_ref * npix : nullptr, s);
-            if (rc) return rc;
-            h->orig_valid = true;
-            h->orig_sigma = d->sigma;
-            h->orig_cost = d->cost;
-            h->orig_omit = d->omit_boundary;
-        } else if (!orig_cache_hit(h, d)) {
-            set_error("objective_finish: normalised cost needs the un-warped image (n_images == n_ref + 1)");
-            return CMAX_ESTATE;
-        }
-    }
-
-    // 2-DoF + plain variance with a gradient: K3 gathers the image statistics itself and k_finish_deferred applies
-    // the chain factors -- no K2 launch (unless a workgroup's slice of the image would get long)
-    const bool two_dof = d->model == CMAX_MODEL_2DOF;
+static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool whole, cmax::Comm *comm = nullptr, bool skip_c2 = false,
+                          double *raw_out = nullptr, volatile unsigned long long *host_flag = nullptr, unsigned long long host_seq = 0) {
+    static const int tan2_env = getenv("CMAX_TAN2") ? atoi(getenv("CMAX_TAN2")) : -1;
+    static const bool no_fused_bv = getenv("CMAX_NO_FUSED_BLURVAR") != nullptr;
+    static const bool no_stats_inside = getenv("CMAX_NO_STATS_INSIDE") != nullptr;
+    static const int sweeps_env = getenv("CMAX_STAT_SWEEPS") ? std::max(1, atoi(getenv("CMAX_STAT_SWEEPS"))) : 0;
+    EvalPlan p = {};
+    const bool dist = comm != nullptr;  // also a 1-rank communicator: the same enqueue sequence, RCCL included
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    p.whole = whole;
+    // (never with a host flag: the tangent-image path ends in kernels that know nothing of it -- ADVICE r3)
+    p.tan2 = whole && !raw_out && !host_flag && !skip_c2 && (h->n > 0 || dist) && tan2_applicable(h, d, grad, dist, tan2_env);
+    // empty batch: loss 0, zero gradient (patch_contrast_base.py:253-255).  A time slice may be empty while the batch is not.
+    p.empty = whole && h->n == 0 && !dist;
+    p.c2_comm = (dist && grad && !raw_out && !skip_c2) ? comm : nullptr;
+    p.result_alone = dist && !grad && !raw_out && !skip_c2;
+    p.raw_only = raw_out != nullptr;
+    p.host_flag = host_flag;
+    p.host_seq = host_seq;
+    p.g = grad_extent(h, d);
+    const bool det = h->deterministic, two_dof = d->model == CMAX_MODEL_2DOF;
     const bool fold_var = d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0);
-    // deterministic mode: the unfused image path (k_blur3, k_stats with one workgroup per accumulator, k_gimage, k_blur3_adj:
-    // every sum in a fixed order) and the integer-accumulating K3
-    const bool det = h->deterministic;
-    const bool deferred = deferred_applies(h, d, grad);
-    const bool lines = two_dof_lines(h, d, grad);  // (includes the deferred case)
-    if (raw_only && !lines) {
-        set_error("objective_raw: this objective has no raw form (2-DoF, a non-empty batch, not deterministic)");
-        return CMAX_EINVAL;
+    p.deferred = deferred_applies(h, d, grad);
+    p.lines = two_dof_lines(h, d, grad);
+    p.raw = p.lines ? (raw_out ? raw_out : h->d_raw) : nullptr;
+    p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
+    p.blur_var = !det && d->cost == CMAX_COST_VARIANCE && d->sigma > 0;
+    const bool k1_sums_ok = whole && !dist && h->Hp >= 4 && h->Wp >= 4;  // K1 can sum its votes for the kernels behind it
+    p.fused_bv = k1_sums_ok && p.blur_var && grad && h->n > 0 && !no_fused_bv;
+    // K3 stores every element of the flow gradient itself (one writer per pixel): needs the group-aligned work list, ONE reference
+    // time (several would add into the same pixels) and the sort order that matches the model (dense: tiles; voxel: (tile, bin) of
+    // the same T)
+    p.owned = !det && grad && h->owned && h->n > 0 && d->n_ref == 1 &&
+              ((d->model == CMAX_MODEL_DENSE && h->n_time_bin == 0) || (d->model == CMAX_MODEL_VOXEL && h->n_time_bin == d->T));
+    // plain variance (no blur, not normalised) on owned groups: nothing in the gradient needs the finished statistics once the
+    // mean comes from the votes, so K2 runs inside the K3 launch (kFoldStatsInside)
+    // ... and on work lists that are not group-aligned (K3 adds its gradient with atomics) once K1 clears the gradient buffer -- the
+    // other job of the separate statistics launch (round 4: 20M events 88.5 -> see profiles/r04_ablation.txt 16)
+    const bool inside_ok = k1_sums_ok && !no_stats_inside && fold_var && !d->normalized;
+    // a launch in front of K3 can clear the flow gradient with its 16-byte stores
+    const bool clearable = grad && !two_dof && !p.owned && !det && h->n > 0 && p.g.count % 4 == 0 && ((uintptr_t)grad & 15u) == 0;
+    const bool cleared_by_vote = inside_ok && clearable && d->n_ref == 1;
+    p.stats_inside = inside_ok && (p.owned || cleared_by_vote);
+    if (clearable && !cleared_by_vote) {
+        p.stats_clear4 = (float4 *)grad;
+        p.n_stats_clear4 = p.g.count / 4;
     }
-    if (lines && !raw) raw = h->d_raw;
-    if (lines && !raw_is_reset) CMAX_CHECK_HIP(hipMemsetAsync(raw, 0, (size_t)d->n_ref * kRawStride * sizeof(double), s));
-    // gradient magnitude with a gradient: K2 and K2b (and the blurs) are one kernel: statistics + G image without its chain factor
-    const bool fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
-    const bool blur_var = !det && d->cost == CMAX_COST_VARIANCE && d->sigma > 0;  // blur + statistics in one kernel
-    // ... with a gradient: + the un-centred, unscaled A' = 2 / (n - 1) blur^T [Ib 1_Omega] (k_blur_stats_adj_var); K3 applies the
-    // chain factor (kFoldScale) and, along the image border, the mean
-    const bool fused_bv = blur_var && grad && h->n > 0 && reuse_windows && h->mu_valid;  // (decided by objective_eval: blurvar_from_votes)
-    // owned groups: K3 stores every element of the flow gradient itself (one writer per pixel) -- nothing to clear.
-    // Needs the group-aligned work list, ONE reference time (several would add into the same pixels) and the sort
-    // order that matches the model (dense: tiles; voxel: (tile, bin) of the same T).
-    const bool owned = owned_groups_apply(h, d, grad);
-    // plain variance, not normalised, owned groups, K1 of this call summed its votes: the statistics run inside the K3 launch
-    const bool cleared_by_vote = grad && reuse_windows && h->grad_cleared_by_vote == grad && !owned;  // K1 of this call cleared the gradient buffer
-    h->grad_cleared_by_vote = nullptr;
-    const bool stats_inside = (owned || cleared_by_vote) && fold_var && !d->normalized && reuse_windows && h->mu_valid && !det;
-    const bool grad_cleared_by_stats = grad && !two_dof && !owned && !cleared_by_vote && !det && h->n > 0 && gcount % 4 == 0 && ((uintptr_t)grad & 15u) == 0;
-    float4 *clear4 = grad_cleared_by_stats ? (float4 *)grad : nullptr;
-    const int64_t nclear4 = grad_cleared_by_stats ? gcount / 4 : 0;
-    double k0 = 0, k1 = 0;
-    if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
-    const dim3 gm_grid(div_up(Hp, kGmTileH) * div_up(Wp, kGmTileW), d->n_ref);  // one 8 x 32 pixel tile per workgroup
-
-    // per-reference-time pointers of the image kernels (every kernel class covers all reference times in one launch)
-    ImgArgs ia = {};
-    for (int k = 0; k < d->n_ref; ++k) {
-        ia.in[k] = images + k * npix;
-        ia.blurred[k] = h->iweb[k];
-        ia.zero[k] = zero_next ? zero_next + k * npix : nullptr;
-        ia.G[k] = h->G + k * npix;
-        // not normalised: the chain factor of chain_coef is a constant -- the fused image kernels fold it into G and K3 reads a finished image
-        ia.chain[k] = op.normalized ? 1.f : (float)((op.negate ? -1.0 : 1.0) * op.mult[k] * (op.minimize ? -1.0 : 1.0));
-        h->last_iwe[k] = d->sigma > 0 ? h->iweb[k] : images + k * npix;  // the image the contrast is evaluated on
-    }
-
-    // ---- contrast statistics
-    if (fused_bv) {
-        ProfScope prof(h, kProfStats, s);
-        for (int rep = 0; rep < h->prof_repeat; ++rep)
-            hipLaunchKernelGGL(k_blur_stats_adj_var, gm_grid, dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, (float)k0, (float)k1, d->omit_boundary, op.nsub,
-                               h->d_stat, clear4, nclear4, h->d_musum + (int64_t)h->mu_buf * 4 * kMuStride,
-                               h->d_musum + (int64_t)(h->mu_buf ^ 1) * 4 * kMuStride, h->n);
-        CMAX_CHECK_LAUNCH();
-        h->mu_buf ^= 1;  // the next evaluation adds into the buffer this launch cleared
-        h->mu_valid = false;
-    } else if (blur_var) {
-        ProfScope prof(h, kProfStats, s);
-        for (int rep = 0; rep < h->prof_repeat; ++rep)
-            hipLaunchKernelGGL(k_blur_stats_var, dim3(stat_blocks(h), d->n_ref), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, (float)k0, (float)k1, d->omit_boundary,
-                               op.nsub, h->d_stat, clear4, nclear4);
-        CMAX_CHECK_LAUNCH();
-    } else if (!(deferred || fused_gm || stats_inside)) {  // those get their statistics from K3 / from the fused image kernel below
-        for (int k = 0; k < d->n_ref; ++k) {
-            const float *img = nullptr;
-            rc = blur_image(h, d->sigma, images + k * npix, h->iweb[k], &img, s);
-            if (rc) return rc;
-            rc = launch_stats(h, d->cost, img, d->omit_boundary, k, ia.zero[k], s, k == 0 ? (float *)clear4 : nullptr, k == 0 ? 4 * nclear4 : 0);
-            if (rc) return rc;
-        }
-    }
-    if (!grad || h->n == 0) {  // value only (or a rank without events): the loss needs its own tiny launch
-        ProfScope prof(h, kProfFinish, s);
-        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, op, h->d_stat, result);
-        CMAX_CHECK_LAUNCH();
-    }
-    if (!grad) return 0;
-    const int bands = c2_band_count(h, d, grad, c2_comm);  // the same on every rank
-    if (h->n == 0) {  // this rank holds no events of the batch
-        CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, gbytes, s));
-        if (bands > 1) {  // ... and still takes part in every band's exchange
-            rc = c2_exchange_all_bands(h, c2_comm, (float *)grad, bands, s, result);
-            if (rc) return rc;
-            if (c2_done) *c2_done = true;
-        }
-        return 0;
-    }
-
-    // ---- backward: dL/dIWE (folded into K3 for the plain variance; otherwise a G image per reference time)
-    if (!two_dof && !grad_cleared_by_stats && !cleared_by_vote && !owned && !det) CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, gbytes, s));
-    const int fold = deferred ? kFoldDeferred
-                              : (stats_inside ? kFoldStatsInside
-                                              : (fold_var ? kFoldStats : (((fused_gm || fused_bv) && d->normalized) ? kFoldScale : kFoldNone)));
-    if (det) {
-        // bound of the per-event terms: max |image the contrast is evaluated on| per reference time (integer max: order-free)
-        CMAX_CHECK_HIP(hipMemsetAsync(h->d_imax, 0, kStatSlots * sizeof(unsigned), s));
-        ImgArgs im = {};
-        for (int k = 0; k < d->n_ref; ++k) im.in[k] = h->last_iwe[k];
-        hipLaunchKernelGGL(k_image_absmax, dim3(std::min(stream_grid(npix, 1024), 256), d->n_ref), dim3(256), 0, s, im, npix, 0, h->d_imax);
-        CMAX_CHECK_LAUNCH();
-        if (fold == kFoldNone) {  // dL/dIWE with its chain factor: k_gimage on the (blurred) image, then the blur transpose
-            if (d->sigma > 0 && !h->Gt_det) {
-                rc = dev_alloc(h, &h->Gt_det, 4 * npix);
-                if (rc) return rc;
-            }
-            float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
-            const dim3 igrid(div_up(npix, 256), d->n_ref);
-            // the n_ref images are not contiguous (last_iwe[k] = blurred copies or the caller's buffer): one launch each
-            for (int k = 0; k < d->n_ref; ++k) {
-                if (d->cost == CMAX_COST_VARIANCE)
-                    hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-                else
-                    hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-            }
-            if (d->sigma > 0) hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt_det, Hp, Wp, (float)k0, (float)k1, h->G, npix);
-            CMAX_CHECK_LAUNCH();
-        }
-        if (!two_dof && gcount > h->g64_cap) {
-            CMAX_CHECK_HIP(hipStreamSynchronize(s));
-            dev_free(&h->g64);
-            h->g64_cap = 0;
-            rc = dev_alloc(h, &h->g64, gcount);
-            if (rc) return rc;
-            h->g64_cap = gcount;
-            CMAX_CHECK_HIP(hipMemsetAsync(h->g64, 0, (size_t)gcount * sizeof(long long), s));
-        }
-    }
-    if (fused_bv) {
-        // dL/dIWE was written (without mean and chain factor) by the statistics kernel
-    } else if (blur_var) {
-        ImgArgs ib = ia;
-        for (int k = 0; k < d->n_ref; ++k) ib.in[k] = h->iweb[k];
-        ProfScope prof(h, kProfGimage, s);
-        for (int rep = 0; rep < h->prof_repeat; ++rep)
-            hipLaunchKernelGGL(k_gimage_blur_adj_var, dim3(div_up(npix, 256), d->n_ref), dim3(256), 0, s, ib, op, h->d_stat, (float)k0, (float)k1);
-        CMAX_CHECK_LAUNCH();
-    } else if (fused_gm) {
-        ProfScope prof(h, kProfStats, s);
-        for (int rep = 0; rep < h->prof_repeat; ++rep) {
-            if (d->sigma > 0)  // raw votes -> blurred image, statistics and the finished G (blur transpose included)
-                hipLaunchKernelGGL(k_blur_stats_gimage_gm, gm_grid, dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, (float)k0, (float)k1, d->omit_boundary, op.nsub,
-                                   h->d_stat, clear4, nclear4);
-            else
-                hipLaunchKernelGGL(k_stats_gimage_gm, gm_grid, dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, d->omit_boundary, op.nsub, h->d_stat, clear4, nclear4);
-        }
-        CMAX_CHECK_LAUNCH();
-    }
-    // ---- per-event gather, all reference times in one launch
-    RefArgs ra = {};
-    ra.k0 = 0;
-    bool same_vote = reuse_windows && h->win_generation == h->generation && h->win_motion == motion && h->win_model == d->model &&
-                     h->win_nref == d->n_ref && h->win_T == d->T && h->win_normalize == d->normalize_t;
-    for (int k = 0; k < d->n_ref; ++k) {
-        ra.d[k] = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        ra.d_lo[k] = ref_fraction_lo(d->ref_mode[k], d->ref_frac[k]);
-        ra.img[k] = (fold == kFoldNone || fold == kFoldScale) ? h->G + k * npix : const_cast<float *>(h->last_iwe[k]);
-        ra.zero[k] = (deferred || stats_inside) ? ia.zero[k] : nullptr;
-        same_vote = same_vote && h->win_d[k] == ra.d[k];
-    }
-    // K3 follows the windows -- and the fp64 cell decisions -- of a K1 launch with exactly this warp: that of the same evaluation, or
-    // (the stand-alone cmax_objective_finish, whose vote the handle cannot vouch for) a K1 launch that only publishes them
-    if (!same_vote && grad && h->n > 0) {
-        rc = publish_windows(h, d, motion, s);
-        if (rc) return rc;
-    }
-    ra.win = h->d_win;
-    ra.shifts = h->d_shifts;
-    ra.n_events = h->n;
-    if (stats_inside) {
+    p.memset_grad = grad && !two_dof && !p.owned && !det && !clearable;
+    p.fold = p.deferred ? kFoldDeferred
+                        : (p.stats_inside ? kFoldStatsInside
+                                          : (fold_var ? kFoldStats : (((p.fused_gm || p.fused_bv) && d->normalized) ? kFoldScale : kFoldNone)));
+    if (p.stats_inside) {
         // Sweeps of 4 pixels per thread and statistics workgroup: two (round 3, standard segments: K3 of cfg5 with 1 / 2 / 4 / 8 sweeps 18.8 /
         // 17.9 / 18.3 / 18.3 us) -- unless the gathering workgroups fit the chip in ONE round and the statistics workgroups are what
         // spills into a second: then four, if that makes the launch fit (round 4, mid segments: cfg5's shard is 900 gathering workgroups;
         // with 232 statistics workgroups 1132 > 1024 resident, with 120 it fits -- K3 16.1 -> 14.8 us, the evaluation 28.8 -> 27.4 us;
         // 3 / 4 / 6 / 8 / 16 sweeps: 28.8 / 27.4 / 27.6 / 27.8 / 31.3 us, profiles/r04_ablation.txt 15).  CMAX_STAT_SWEEPS overrides.
-        static const int sweeps_env = getenv("CMAX_STAT_SWEEPS") ? std::max(1, atoi(getenv("CMAX_STAT_SWEEPS"))) : 0;
         // (h->owned, as before: the launch's grad_layout takes this call's `owned`, which can be false where h->owned is not)
         const int gthreads = layout_threads(grad_layout(h, d->model, h->owned));
         auto blocks_for = [&](int sweeps) {
@@ -3342,84 +3205,327 @@ static int objective_finish(cmax_handle_t h, const cmax_objective_t *d, const fl
             const int resident = 256 * (2048 / gthreads), gather = 8 * div_up(h->nseg, 8) * d->n_ref;  // workgroups the chip holds at once
             if (gather <= resident && gather + blocks_for(2) * d->n_ref > resident && gather + blocks_for(4) * d->n_ref <= resident) sweeps = 4;
         }
-        ra.stat_blocks = blocks_for(sweeps);
+        p.stat_blocks = blocks_for(sweeps);
+    }
+    double k0 = 0, k1 = 0;
+    if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
+    p.tap0 = (float)k0;
+    p.tap1 = (float)k1;
+    p.bands = (p.c2_comm && d->model == CMAX_MODEL_DENSE && h->c2_bands > 1) ? std::min(h->c2_bands, h->ntr) : 1;  // (the same on every rank, see c2_prepare_bands)
+    p.k3_in_bands = p.bands > 1 && p.owned && (int)h->row_seg_start.size() == h->ntr + 1;
+    if (!whole) return p;  // (no K1 in this call)
+    p.vote.publish_windows = true;
+    p.vote.sums = p.fused_bv || p.stats_inside;
+    if (p.vote.sums) {  // B = blur^T 1_Omega = b(r) b(c); no blur: B = 1_Omega
+        const float b0 = d->sigma > 0 ? p.tap0 : 1.f, b1 = d->sigma > 0 ? p.tap1 : 0.f;
+        p.vote.band_b0 = border_weight(0, h->Hp, d->omit_boundary ? 1 : 0, b0, b1);
+        p.vote.band_b1 = border_weight(1, h->Hp, d->omit_boundary ? 1 : 0, b0, b1);
+    }
+    if (p.deferred) p.vote.raw_reset = p.raw;
+    else p.vote.raw_lines = p.raw;
+    if (cleared_by_vote) {
+        p.vote.grad_zero = (float4 *)grad;
+        p.vote.n_grad_zero4 = p.g.count / 4;
+    }
+    return p;
+}
+
+// votes of every reference time (+ the un-warped image when needed) into images[0 .. n_images);
+// zero_mask bit k: images[k] is already zero (the handle's double-buffered images)
+static int objective_vote(cmax_handle_t h, const cmax_objective_t *d, const float *motion, float *images, unsigned zero_mask, int *n_images_out, hipStream_t s, const VoteJobs &jobs) {
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    float *imgs[4];
+    for (int k = 0; k < d->n_ref; ++k) imgs[k] = images + k * npix;
+    int rc = vote_images(h, d->model, motion, d->T, d->n_ref, d->ref_mode, d->ref_frac, d->normalize_t, imgs, zero_mask, 0, s, jobs, d->motion_dtype == CMAX_F64);
+    if (rc) return rc;
+    int n_images = d->n_ref;
+    if (d->normalized && !orig_cache_hit(h, d)) {  // un-warped image, once per batch (patch_contrast_base.py:295-301)
+        rc = vote_image(h, -1, nullptr, 0, CMAX_REF_FIRST, 0.0, 1, images + (int64_t)d->n_ref * npix, (zero_mask >> d->n_ref) & 1u, 4, s);
+        if (rc) return rc;
+        ++n_images;
+    }
+    *n_images_out = n_images;
+    return 0;
+}
+
+int cmax_objective_vote(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, float *images, int *n_images_host,
+                        cmax_stream_t stream) {
+    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    CMAX_REQUIRE(images && n_images_host, "objective_vote: images / n_images_host");
+    VoteJobs jobs;
+    jobs.publish_windows = true;
+    return objective_vote(h, d, motion, images, 0u, n_images_host, (hipStream_t)stream, jobs);
+}
+
+// ---- the stages of objective_finish, in the order they enqueue
+// blur (when the cost blurs) and statistics of the un-warped image `raw` into slot 4, cached per batch under the key orig_cache_hit compares
+static int orig_image_stats(cmax_handle_s *h, const cmax_objective_t *d, const float *raw, float *blur, float *zero_img, hipStream_t s) {
+    const float *img = nullptr;
+    int rc = blur_image(h, d->sigma, raw, blur, &img, s);
+    if (rc) return rc;
+    // orig_iwe is NOT boundary-cropped for the variance (normalized_image_variance.py:40-41)
+    const int omit_o = d->cost == CMAX_COST_VARIANCE ? 0 : d->omit_boundary;
+    rc = launch_stats(h, d->cost, img, omit_o, 4, zero_img, s);
+    if (rc) return rc;
+    h->orig_valid = true;
+    h->orig_sigma = d->sigma;
+    h->orig_cost = d->cost;
+    h->orig_omit = d->omit_boundary;
+    return 0;
+}
+
+static dim3 gm_grid(const cmax_handle_s *h, const cmax_objective_t *d) {  // one 8 x 32 pixel tile per workgroup
+    return dim3(div_up(h->Hp, kGmTileH) * div_up(h->Wp, kGmTileW), d->n_ref);
+}
+
+// contrast statistics: one fused blur + statistics kernel (blurred variance), or blur + k_stats per reference time -- or nothing
+// where K3 / the fused image kernel of finish_gimage produce them
+static int finish_contrast_stats(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, const ImgArgs &ia, hipStream_t s) {
+    const int Hp = h->Hp, Wp = h->Wp;
+    const int64_t npix = (int64_t)Hp * Wp;
+    if (p.fused_bv) {
+        ProfScope prof(h, kProfStats, s);
+        for (int rep = 0; rep < h->prof_repeat; ++rep)
+            hipLaunchKernelGGL(k_blur_stats_adj_var, gm_grid(h, d), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, p.tap0, p.tap1, d->omit_boundary, op.nsub,
+                               h->d_stat, p.stats_clear4, p.n_stats_clear4, h->d_musum + (int64_t)h->mu_buf * 4 * kMuStride,
+                               h->d_musum + (int64_t)(h->mu_buf ^ 1) * 4 * kMuStride, h->n);
+        CMAX_CHECK_LAUNCH();
+        h->mu_buf ^= 1;  // the next evaluation adds into the buffer this launch cleared
+    } else if (p.blur_var) {
+        ProfScope prof(h, kProfStats, s);
+        for (int rep = 0; rep < h->prof_repeat; ++rep)
+            hipLaunchKernelGGL(k_blur_stats_var, dim3(stat_blocks(h), d->n_ref), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, p.tap0, p.tap1, d->omit_boundary,
+                               op.nsub, h->d_stat, p.stats_clear4, p.n_stats_clear4);
+        CMAX_CHECK_LAUNCH();
+    } else if (!(p.deferred || p.fused_gm || p.stats_inside)) {  // those get their statistics from K3 / from the fused image kernel
+        for (int k = 0; k < d->n_ref; ++k) {
+            const float *img = nullptr;
+            int rc = blur_image(h, d->sigma, ia.in[k], h->iweb[k], &img, s);
+            if (rc) return rc;
+            rc = launch_stats(h, d->cost, img, d->omit_boundary, k, ia.zero[k], s, k == 0 ? (float *)p.stats_clear4 : nullptr, k == 0 ? 4 * p.n_stats_clear4 : 0);
+            if (rc) return rc;
+        }
+    }
+    return 0;
+}
+
+// value only, or a rank without events: the loss by its own tiny launch (k_finalize); a zero gradient that still takes part in every band's exchange
+static int finish_without_gather(cmax_handle_s *h, const EvalPlan &p, const ObjParams &op, double *result, void *grad, hipStream_t s) {
+    {
+        ProfScope prof(h, kProfFinish, s);
+        hipLaunchKernelGGL(k_finalize, dim3(1), dim3(64), 0, s, op, h->d_stat, result);
+        CMAX_CHECK_LAUNCH();
+    }
+    if (!grad) return 0;
+    CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, p.g.bytes, s));  // this rank holds no events of the batch
+    return p.bands > 1 ? c2_exchange_all_bands(h, p.c2_comm, (float *)grad, p.bands, s, result) : 0;
+}
+
+// room for `count` fixed-point gradient accumulators (deterministic flow gradients; zero between evaluations)
+static int reserve_g64(cmax_handle_s *h, int64_t count, hipStream_t s) {
+    if (count <= h->g64_cap) return 0;
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    dev_free(&h->g64);
+    h->g64_cap = 0;
+    int rc = dev_alloc(h, &h->g64, count);
+    if (rc) return rc;
+    h->g64_cap = count;
+    CMAX_CHECK_HIP(hipMemsetAsync(h->g64, 0, (size_t)count * sizeof(long long), s));
+    return 0;
+}
+
+// deterministic mode: the fixed-point sums of the gather -> the gradient (2-DoF: per-segment partials in d_gpart; flow: g64)
+static int launch_finish_det(cmax_handle_s *h, const cmax_objective_t *d, void *out, hipStream_t s) {
+    const int64_t gcount = grad_extent(h, d).count;
+    if (d->model == CMAX_MODEL_2DOF)
+        hipLaunchKernelGGL(k_finish_det, dim3(1), dim3(256), 0, s, reinterpret_cast<long long *>(h->d_gpart), h->nseg, d->n_ref, h->d_det_inv_scale, (double *)out);
+    else
+        hipLaunchKernelGGL(k_fixed_to_grad, dim3(stream_grid(gcount, 256)), dim3(256), 0, s, h->g64, (float *)out, gcount, h->d_det_inv_scale);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+// backward, image space: the clearing memset of the flow gradient where no launch does it, then dL/dIWE as a G image per reference time
+// (folded into K3 for the plain variance) -- deterministic: absmax pre-pass + the unfused k_gimage [+ blur transpose]
+static int finish_gimage(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, const ImgArgs &ia, void *grad, hipStream_t s) {
+    const int Hp = h->Hp, Wp = h->Wp;
+    const int64_t npix = (int64_t)Hp * Wp;
+    if (p.memset_grad) CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, p.g.bytes, s));
+    if (h->deterministic) {  // the unfused image path (k_blur3, k_stats with one workgroup per accumulator, k_gimage, k_blur3_adj: every sum in a fixed order)
+        // bound of the per-event terms: max |image the contrast is evaluated on| per reference time (integer max: order-free)
+        CMAX_CHECK_HIP(hipMemsetAsync(h->d_imax, 0, kStatSlots * sizeof(unsigned), s));
+        ImgArgs im = {};
+        for (int k = 0; k < d->n_ref; ++k) im.in[k] = h->last_iwe[k];
+        hipLaunchKernelGGL(k_image_absmax, dim3(std::min(stream_grid(npix, 1024), 256), d->n_ref), dim3(256), 0, s, im, npix, 0, h->d_imax);
+        CMAX_CHECK_LAUNCH();
+        if (p.fold == kFoldNone) {  // dL/dIWE with its chain factor: k_gimage on the (blurred) image, then the blur transpose
+            if (d->sigma > 0 && !h->Gt_det) {
+                int rc = dev_alloc(h, &h->Gt_det, 4 * npix);
+                if (rc) return rc;
+            }
+            float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
+            const dim3 igrid(div_up(npix, 256), d->n_ref);
+            // the n_ref images are not contiguous (last_iwe[k] = blurred copies or the caller's buffer): one launch each
+            for (int k = 0; k < d->n_ref; ++k) {
+                if (d->cost == CMAX_COST_VARIANCE)
+                    hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+                else
+                    hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+            }
+            if (d->sigma > 0) hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt_det, Hp, Wp, p.tap0, p.tap1, h->G, npix);
+            CMAX_CHECK_LAUNCH();
+        }
+        return d->model == CMAX_MODEL_2DOF ? 0 : reserve_g64(h, p.g.count, s);
+    }
+    if (p.fused_bv) {
+        // dL/dIWE was written (without mean and chain factor) by the statistics kernel
+    } else if (p.blur_var) {
+        ImgArgs ib = ia;
+        for (int k = 0; k < d->n_ref; ++k) ib.in[k] = h->iweb[k];
+        ProfScope prof(h, kProfGimage, s);
+        for (int rep = 0; rep < h->prof_repeat; ++rep)
+            hipLaunchKernelGGL(k_gimage_blur_adj_var, dim3(div_up(npix, 256), d->n_ref), dim3(256), 0, s, ib, op, h->d_stat, p.tap0, p.tap1);
+        CMAX_CHECK_LAUNCH();
+    } else if (p.fused_gm) {
+        ProfScope prof(h, kProfStats, s);
+        for (int rep = 0; rep < h->prof_repeat; ++rep) {
+            if (d->sigma > 0)  // raw votes -> blurred image, statistics and the finished G (blur transpose included)
+                hipLaunchKernelGGL(k_blur_stats_gimage_gm, gm_grid(h, d), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, p.tap0, p.tap1, d->omit_boundary, op.nsub,
+                                   h->d_stat, p.stats_clear4, p.n_stats_clear4);
+            else
+                hipLaunchKernelGGL(k_stats_gimage_gm, gm_grid(h, d), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, d->omit_boundary, op.nsub, h->d_stat, p.stats_clear4, p.n_stats_clear4);
+        }
+        CMAX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// the arguments of K3 (all reference times in one launch); enqueues the windows-only K1 where the handle's windows are not this warp's
+static int finish_grad_args(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const float *motion, const ImgArgs &ia, RefArgs &ra, hipStream_t s) {
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    fill_ref_times(ra, d->n_ref, d->ref_mode, d->ref_frac);
+    bool same_vote = p.whole && h->win_generation == h->generation && h->win_motion == motion && h->win_model == d->model &&
+                     h->win_nref == d->n_ref && h->win_T == d->T && h->win_normalize == d->normalize_t;
+    for (int k = 0; k < d->n_ref; ++k) {
+        ra.img[k] = (p.fold == kFoldNone || p.fold == kFoldScale) ? h->G + k * npix : const_cast<float *>(h->last_iwe[k]);
+        ra.zero[k] = (p.deferred || p.stats_inside) ? ia.zero[k] : nullptr;
+        same_vote = same_vote && h->win_d[k] == ra.d[k];
+    }
+    // K3 follows the windows -- and the fp64 cell decisions -- of a K1 launch with exactly this warp: that of the same evaluation, or
+    // (the stand-alone cmax_objective_finish, whose vote the handle cannot vouch for) a K1 launch that only publishes them
+    if (!same_vote) {
+        int rc = publish_windows(h, d, motion, s);
+        if (rc) return rc;
+    }
+    ra.win = h->d_win;
+    ra.shifts = h->d_shifts;
+    ra.n_events = h->n;
+    if (p.stats_inside) {
+        ra.stat_blocks = p.stat_blocks;
         ra.ticket = h->d_ticket;
         ra.musum[0] = h->d_musum + (int64_t)h->mu_buf * 4 * kMuStride;
         ra.musum_next = h->d_musum + (int64_t)(h->mu_buf ^ 1) * 4 * kMuStride;
         h->mu_buf ^= 1;  // the next evaluation adds into the buffer this launch clears
-        h->mu_valid = false;
     }
-    if (det) {
+    if (h->deterministic) {  // the integer-accumulating K3
         ra.imax = h->d_imax;
-        ra.g64 = two_dof ? reinterpret_cast<long long *>(h->d_gpart) : h->g64;  // (d_gpart: [4][nseg][6] doubles, 2 used per segment)
+        ra.g64 = d->model == CMAX_MODEL_2DOF ? reinterpret_cast<long long *>(h->d_gpart) : h->g64;  // (d_gpart: [4][nseg][6] doubles, 2 used per segment)
         ra.det_inv_scale = h->d_det_inv_scale;
-        ra.n_events = h->n;
     }
+    return 0;
+}
+
+// C2 in row bands (cmax_comm_set_c2_bands): dense objective on an owned work list under a communicator.  The owned K3 STORES
+// every gradient element of its segments' tiles, so after the launch that covers tile rows [a, b) the pixel rows [16 a, 16 b)
+// of both channels are final on this rank: they are all-reduced on the handle's second stream while the caller's stream
+// already runs the next band's K3.  One event per band hands the rows over, one event hands the reduced gradient back.
+static int finish_grad_in_bands(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const EvView &ev, const WarpParams &wp, const RefArgs &ra,
+                                const ObjParams &op, double *res, double *result, float *grad, hipStream_t s) {
+    int rc = c2_prepare_bands(h, p.bands);
+    if (rc) return rc;
+    for (int b = 0; b < p.bands; ++b) {
+        const int tr0 = (int)((int64_t)h->ntr * b / p.bands), tr1 = (int)((int64_t)h->ntr * (b + 1) / p.bands);
+        const int s0 = h->row_seg_start[tr0], s1 = h->row_seg_start[tr1];
+        RefArgs rb = ra;
+        rb.win += s0;  // (one reference time: the windows of segment i sit at win[i])
+        rb.shifts += (int64_t)s0 * (h->big ? 512 : (h->mid ? 384 : 256));
+        if (s1 > s0) launch_grad<CMAX_MODEL_DENSE>(h, ev, wp, rb, d->n_ref, p.fold, op, nullptr, grad, b == 0 ? res : nullptr, p.owned, s, s0, s1 - s0);
+        CMAX_CHECK_LAUNCH();
+        rc = c2_exchange_band(h, p.c2_comm, grad, b, p.bands, s, result);
+        if (rc) return rc;
+    }
+    return c2_join_bands(h, p.bands, s);
+}
+
+// 2-DoF, default mode: the one-wave kernel that folds the raw sums into (loss and) gradient -- unless the caller does that itself (raw_only)
+static int finish_two_dof(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, double *result, void *grad, hipStream_t s) {
+    if (!p.lines || p.raw_only) return 0;
+    ProfScope prof(h, kProfFinish, s);
+    if (p.deferred)
+        hipLaunchKernelGGL(k_finish_raw, dim3(1), dim3(64), 0, s, (const double *)p.raw, op.n_ref, op, h->d_stat, result, (double *)grad, p.host_flag, p.host_seq);
+    else  // (host_flag: K3's first workgroup wrote the loss into the pinned `result`)
+        hipLaunchKernelGGL(k_finish_lines, dim3(1), dim3(64), 0, s, p.raw, d->n_ref, (double *)grad, (const double *)nullptr, (double *)nullptr, p.host_flag, p.host_seq);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+static int objective_finish(cmax_handle_t h, const cmax_objective_t *d, const EvalPlan &p, const float *motion, const float *images, int n_images, float *zero_next, double *result,
+                            void *grad, hipStream_t s) {
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const ObjParams op = obj_params(h, d);
+    int rc = 0;
+    if (d->normalized) {  // statistics of the un-warped image (slot 4) are cached per batch
+        if (n_images == d->n_ref + 1) {
+            rc = orig_image_stats(h, d, images + (int64_t)d->n_ref * npix, h->iweb[4], zero_next ? zero_next + (int64_t)d->n_ref * npix : nullptr, s);
+            if (rc) return rc;
+        } else if (!orig_cache_hit(h, d)) {
+            set_error("objective_finish: normalised cost needs the un-warped image (n_images == n_ref + 1)");
+            return CMAX_ESTATE;
+        }
+    }
+    if (p.lines && !p.whole) CMAX_CHECK_HIP(hipMemsetAsync(p.raw, 0, (size_t)d->n_ref * kRawStride * sizeof(double), s));  // (whole: K1 cleared them)
+    // per-reference-time pointers of the image kernels (every kernel class covers all reference times in one launch)
+    // zero_next: base of the image buffer of the NEXT evaluation (the statistics of image k zero zero_next[k]) or nullptr
+    ImgArgs ia = {};
+    for (int k = 0; k < d->n_ref; ++k) {
+        ia.in[k] = images + k * npix;
+        ia.blurred[k] = h->iweb[k];
+        ia.zero[k] = zero_next ? zero_next + k * npix : nullptr;
+        ia.G[k] = h->G + k * npix;
+        // not normalised: the chain factor of chain_coef is a constant -- the fused image kernels fold it into G and K3 reads a finished image
+        ia.chain[k] = op.normalized ? 1.f : (float)((op.negate ? -1.0 : 1.0) * op.mult[k] * (op.minimize ? -1.0 : 1.0));
+        h->last_iwe[k] = d->sigma > 0 ? h->iweb[k] : images + k * npix;  // the image the contrast is evaluated on
+    }
+    rc = finish_contrast_stats(h, d, p, op, ia, s);
+    if (rc) return rc;
+    if (!grad || h->n == 0) return finish_without_gather(h, p, op, result, grad, s);
+    rc = finish_gimage(h, d, p, op, ia, grad, s);
+    if (rc) return rc;
+    RefArgs ra = {};
+    rc = finish_grad_args(h, d, p, motion, ia, ra, s);
+    if (rc) return rc;
     const EvView ev = ev_view(h);
     const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
     // the first workgroup writes the loss (deferred: the finishing step does).  Raw form of an objective with statistics: into doubles
     // 8..15 of the first line of the raw buffer (the sums use doubles 0, 1 of every line)
-    double *res = deferred ? nullptr : ((raw_only && lines) ? raw + 8 : result);
-    // C2 in row bands (cmax_comm_set_c2_bands): dense objective on an owned work list under a communicator.  The owned K3 STORES
-    // every gradient element of its segments' tiles, so after the launch that covers tile rows [a, b) the pixel rows [16 a, 16 b)
-    // of both channels are final on this rank: they are all-reduced on the handle's second stream while the caller's stream
-    // already runs the next band's K3.  One event per band hands the rows over, one event hands the reduced gradient back.
-    if (bands > 1 && owned && (int)h->row_seg_start.size() == h->ntr + 1) {  // K3 band by band, each band's rows exchanged behind it
-        rc = c2_prepare_bands(h, bands);
-        if (rc) return rc;
-        for (int b = 0; b < bands; ++b) {
-            const int tr0 = (int)((int64_t)h->ntr * b / bands), tr1 = (int)((int64_t)h->ntr * (b + 1) / bands);
-            const int s0 = h->row_seg_start[tr0], s1 = h->row_seg_start[tr1];
-            RefArgs rb = ra;
-            rb.win += s0;  // (one reference time: the windows of segment i sit at win[i])
-            rb.shifts += (int64_t)s0 * (h->big ? 512 : (h->mid ? 384 : 256));
-            if (s1 > s0) launch_grad<CMAX_MODEL_DENSE>(h, ev, wp, rb, d->n_ref, fold, op, nullptr, (float *)grad, b == 0 ? res : nullptr, owned, s, s0, s1 - s0);
-            CMAX_CHECK_LAUNCH();
-            rc = c2_exchange_band(h, c2_comm, (float *)grad, b, bands, s, result);
-            if (rc) return rc;
-        }
-        rc = c2_join_bands(h, bands, s);
-        if (rc) return rc;
-        if (c2_done) *c2_done = true;
-        return 0;
-    }
-    switch (d->model) {
-        case CMAX_MODEL_2DOF: launch_grad<CMAX_MODEL_2DOF>(h, ev, wp, ra, d->n_ref, fold, op, lines ? raw : h->d_gpart, nullptr, res, false, s); break;
-        case CMAX_MODEL_DENSE: launch_grad<CMAX_MODEL_DENSE>(h, ev, wp, ra, d->n_ref, fold, op, nullptr, (float *)grad, res, owned, s); break;
-        default: launch_grad<CMAX_MODEL_VOXEL>(h, ev, wp, ra, d->n_ref, fold, op, nullptr, (float *)grad, res, owned, s); break;
-    }
+    double *res = p.deferred ? nullptr : (p.raw_only ? p.raw + 8 : result);
+    if (p.k3_in_bands) return finish_grad_in_bands(h, d, p, ev, wp, ra, op, res, result, (float *)grad, s);
+    // K3 in one launch
+    const bool two_dof = d->model == CMAX_MODEL_2DOF;
+    double *gpart = two_dof ? (p.lines ? p.raw : h->d_gpart) : nullptr;
+    float *gflow = two_dof ? nullptr : (float *)grad;
+    with_model(d->model, [&](auto m) { launch_grad<m.value>(h, ev, wp, ra, d->n_ref, p.fold, op, gpart, gflow, res, p.owned, s); });
     CMAX_CHECK_LAUNCH();
-    if (det) {
+    if (h->deterministic) {
         ProfScope prof(h, kProfFinish, s);
-        if (two_dof)
-            hipLaunchKernelGGL(k_finish_det, dim3(1), dim3(256), 0, s, reinterpret_cast<long long *>(h->d_gpart), h->nseg, d->n_ref, h->d_det_inv_scale, (double *)grad);
-        else
-            hipLaunchKernelGGL(k_fixed_to_grad, dim3(stream_grid(gcount, 256)), dim3(256), 0, s, h->g64, (float *)grad, gcount, h->d_det_inv_scale);
-        CMAX_CHECK_LAUNCH();
-    }
-    if (bands > 1) {  // this rank's work list does not allow K3 in bands (or the mode is deterministic): the same exchanges behind one launch
-        rc = c2_exchange_all_bands(h, c2_comm, (float *)grad, bands, s, result);
+        rc = launch_finish_det(h, d, grad, s);
         if (rc) return rc;
-        if (c2_done) *c2_done = true;
-        return 0;
     }
-    if (det) {
-    } else if (deferred) {
-        if (!raw_only) {
-            ProfScope prof(h, kProfFinish, s);
-            hipLaunchKernelGGL(k_finish_raw, dim3(1), dim3(64), 0, s, (const double *)raw, op.n_ref, op, h->d_stat, result, (double *)grad, host_flag, host_seq);
-            CMAX_CHECK_LAUNCH();
-        }
-    } else if (two_dof) {
-        if (!raw_only) {
-            ProfScope prof(h, kProfFinish, s);
-            // (host_flag: cmax_objective_host -- `result` and `grad` are pinned host memory; K3's first workgroup wrote the loss there)
-            hipLaunchKernelGGL(k_finish_lines, dim3(1), dim3(64), 0, s, raw, d->n_ref, (double *)grad, (const double *)nullptr, (double *)nullptr,
-                               host_flag, host_seq);
-            CMAX_CHECK_LAUNCH();
-        }
-    }
-    return 0;
+    // this rank's work list does not allow K3 in bands (or the mode is deterministic): the same exchanges behind one launch
+    if (p.bands > 1) return c2_exchange_all_bands(h, p.c2_comm, (float *)grad, p.bands, s, result);
+    return finish_two_dof(h, d, p, op, result, grad, s);
 }
 
 int cmax_objective_finish(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, const float *images, int n_images,
@@ -3429,24 +3535,7 @@ int cmax_objective_finish(cmax_handle_t h, const cmax_objective_t *d, const void
     if (rc) return rc;
     CMAX_REQUIRE(images && result, "objective_finish: images / result");
     CMAX_REQUIRE(n_images == d->n_ref || n_images == d->n_ref + 1, "objective_finish: n_images");
-    return objective_finish(h, d, motion, images, n_images, nullptr, result, grad, (hipStream_t)stream, false);
-}
-
-// 2-DoF, plain variance: K1T (image + two tangent images) -> [ONE all-reduce] -> k_tan_stats_var -> k_finish_deferred.
-// No pass over the events for the gradient, and across GPUs no second exchange: after the all-reduce every rank holds
-// the whole batch's three images and finishes loss and gradient on its own.
-static bool tan2_applicable(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool dist) {
-    static const int force = getenv("CMAX_TAN2") ? atoi(getenv("CMAX_TAN2")) : -1;  // tuning: 1 = also on one GPU, 0 = never
-    if (force == 0 || h->deterministic || !grad) return false;
-    if (d->model != CMAX_MODEL_2DOF || d->cost != CMAX_COST_VARIANCE || d->sigma > 0) return false;
-    // Rank-consistent scalars: behind the single exchange every rank finishes loss AND gradient on its own -- from the reduced planes in a
-    // fixed order (per-workgroup partials, one folding wave: bit-identical on every rank), but a NORMALISED variance also reads the
-    // un-warped image's cached statistics, which each rank summed with atomics in its own order.  Across real ranks that objective
-    // takes the two-exchange path, whose gradient is all-reduced and whose scalars ride along.
-    if (d->normalized && h->comm && comm_nranks(h->comm) > 1) return false;
-    if (d->normalized && !(h->orig_valid && h->orig_sigma == d->sigma && h->orig_cost == d->cost && h->orig_omit == d->omit_boundary))
-        return false;  // the first evaluation of a batch builds the un-warped image's statistics on the standard path
-    return dist || force == 1;
+    return objective_finish(h, d, eval_plan(h, d, grad, false), motion, images, n_images, nullptr, result, grad, (hipStream_t)stream);
 }
 
 static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s,
@@ -3463,10 +3552,9 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
     }
     float *cur = h->tan + (int64_t)h->tan_cur * 4 * tstride, *nxt = h->tan + (int64_t)(h->tan_cur ^ 1) * 4 * tstride;
     RefArgs ra = {};
+    fill_ref_times(ra, nr, d->ref_mode, d->ref_frac);
     for (int k = 0; k < nr; ++k) {
         if (!((h->tan_zero_mask[h->tan_cur] >> k) & 1u)) CMAX_CHECK_HIP(hipMemsetAsync(cur + k * tstride, 0, (size_t)tstride * sizeof(float), s));
-        ra.d[k] = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        ra.d_lo[k] = ref_fraction_lo(d->ref_mode[k], d->ref_frac[k]);
         ra.img[k] = cur + k * tstride;
     }
     const unsigned used = (1u << nr) - 1u;
@@ -3511,77 +3599,49 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
 }
 
 // vote -> [all-reduce of the images] -> finish -> [all-reduce of the gradient], all on the handle's double-buffered images
-// raw_out: non-null = stop at the raw sums of the deferred 2-DoF K3 (cmax_objective_raw; `grad` is then only a non-null marker)
+// raw_out: non-null = stop at the raw sums of the 2-DoF K3 (cmax_objective_raw; `grad` is then only a non-null marker)
 static int objective_eval(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s,
                           cmax::Comm *comm, double *raw_out = nullptr, volatile unsigned long long *host_flag = nullptr,
                           unsigned long long host_seq = 0, bool skip_c2 = false) {
-    const bool dist = comm != nullptr;  // also a 1-rank communicator: the same enqueue sequence, RCCL included
-    // (never with a host flag: the tangent-image path ends in kernels that know nothing of it -- ADVICE r3)
-    if (!raw_out && !host_flag && !skip_c2 && (h->n > 0 || dist) && tan2_applicable(h, d, grad, dist)) return objective_eval_tan2(h, d, motion, result, grad, s, comm);
-    if (raw_out && !two_dof_lines(h, d, grad)) {
+    const EvalPlan p = eval_plan(h, d, grad, true, comm, skip_c2, raw_out, host_flag, host_seq);
+    if (p.tan2) return objective_eval_tan2(h, d, motion, result, grad, s, comm);
+    if (raw_out && !p.lines) {
         set_error("objective_raw: this objective has no raw form (2-DoF, a non-empty batch, not deterministic)");
         return CMAX_EINVAL;
     }
-    const int64_t gcount = d->model == CMAX_MODEL_2DOF ? 2 : (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
-    const size_t gbytes = d->model == CMAX_MODEL_2DOF ? 2 * sizeof(double) : (size_t)gcount * sizeof(float);
-    // empty batch: loss 0, zero gradient (patch_contrast_base.py:253-255).  A time slice may be empty while the batch is not.
-    if (h->n == 0 && !dist) {
+    if (p.empty) {
         CMAX_CHECK_HIP(hipMemsetAsync(result, 0, 8 * sizeof(double), s));
-        if (grad) CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, gbytes, s));
+        if (grad) CMAX_CHECK_HIP(hipMemsetAsync(grad, 0, p.g.bytes, s));
         return 0;
     }
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     float *cur = h->imgs + (int64_t)h->cur_buf * 5 * npix;
     float *nxt = h->imgs + (int64_t)(h->cur_buf ^ 1) * 5 * npix;
     int n_images = 0;
-    // blurred variance with a gradient on one GPU: K1 also sums the votes against blur^T 1_Omega, so that ONE image kernel can
-    // blur, sum and write dL/dIWE (k_blur_stats_adj_var).  Across GPUs the sum would need its own exchange: two image kernels.
-    static const bool no_fused_bv = getenv("CMAX_NO_FUSED_BLURVAR") != nullptr;  // tuning: k_blur_stats_var + k_gimage_blur_adj_var
-    const bool blurvar_from_votes = !dist && grad && !h->deterministic && h->n > 0 && d->cost == CMAX_COST_VARIANCE && d->sigma > 0 &&
-                                    h->Hp >= 4 && h->Wp >= 4 && !no_fused_bv;
-    // plain variance (no blur, not normalised) on owned groups: nothing in the gradient needs the finished statistics once the
-    // mean comes from the votes, so K2 runs inside the K3 launch (kFoldStatsInside)
-    static const bool no_stats_inside = getenv("CMAX_NO_STATS_INSIDE") != nullptr;  // tuning: k_stats as a launch of its own
-    // ... and on work lists that are not group-aligned (K3 adds its gradient with atomics) once K1 clears the gradient buffer -- the
-    // other job of the separate statistics launch (round 4: 20M events 88.5 -> see profiles/r04_ablation.txt 16)
-    const bool inside_ok = !dist && !no_stats_inside && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && !d->normalized && h->Hp >= 4 && h->Wp >= 4;
-    const bool clear_by_vote = inside_ok && grad && !owned_groups_apply(h, d, grad) && d->model != CMAX_MODEL_2DOF && d->n_ref == 1 && !h->deterministic &&
-                               h->n > 0 && gcount % 4 == 0 && ((uintptr_t)grad & 15u) == 0;
-    if (clear_by_vote) {
-        h->vote_clear4 = (float4 *)grad;
-        h->vote_nclear4 = gcount / 4;
-    }
-    const bool var_from_votes = inside_ok && (owned_groups_apply(h, d, grad) || clear_by_vote);
-    // 2-DoF objectives: K1 clears the raw sums its K3 adds into -- through its statistics slot when the objective keeps none
-    // (deferred), through RefArgs::raw_zero otherwise
-    double *raw = two_dof_lines(h, d, grad) ? (raw_out ? raw_out : h->d_raw) : nullptr;
-    const bool raw_deferred = raw && deferred_applies(h, d, grad);
-    int rc = objective_vote(h, d, motion, cur, h->zero_mask[h->cur_buf], &n_images, s, blurvar_from_votes || var_from_votes,
-                            raw_deferred ? raw : nullptr, raw_deferred ? nullptr : raw);
+    const int mu_buf = h->mu_buf;
+    int rc = objective_vote(h, d, motion, cur, h->zero_mask[h->cur_buf], &n_images, s, p.vote);
     if (rc) return rc;
     const unsigned used = (1u << n_images) - 1u;
     h->zero_mask[h->cur_buf] &= ~used;  // now holds votes
-    if (dist) {  // C1: every reference time (+ the un-warped image) in one call; the images are contiguous
+    if (comm) {  // C1: every reference time (+ the un-warped image) in one call; the images are contiguous
         ProfScope prof(h, kProfComm, s);
         rc = comm_allreduce(comm, cur, (size_t)n_images * npix, kCommF32, kCommSum, s);
         if (rc) return rc;
     }
-    bool c2_done = false;  // the gradient was all-reduced in row bands behind K3 already
-    rc = objective_finish(h, d, motion, cur, n_images, nxt, result, grad, s, true, raw, raw != nullptr, raw_out != nullptr,
-                          dist && grad && !raw_out && !skip_c2 ? comm : nullptr, &c2_done, host_flag, host_seq);
-    if (h->mu_valid) {  // K1 summed its votes and nothing consumed (and cleared) them -- an error on the way, or a path that does
-        // not use them after all: the next evaluation must find clean accumulators
-        (void)hipMemsetAsync(h->d_musum + (int64_t)h->mu_buf * 4 * kMuStride, 0, (size_t)4 * kMuStride * sizeof(double), s);
-        h->mu_valid = false;
+    rc = objective_finish(h, d, p, motion, cur, n_images, nxt, result, grad, s);
+    if (rc) {
+        // K1 summed its votes and the error came before the launch that reads them (it clears the other buffer and flips mu_buf): the
+        // next evaluation must find clean accumulators
+        if (p.vote.sums && h->mu_buf == mu_buf) (void)hipMemsetAsync(h->d_musum + (int64_t)mu_buf * 4 * kMuStride, 0, (size_t)4 * kMuStride * sizeof(double), s);
+        return rc;
     }
-    if (rc) return rc;
     h->zero_mask[h->cur_buf ^ 1] |= used;  // zeroed by this evaluation's k_stats launches
     h->cur_buf ^= 1;
-    if (dist && grad && !raw_out && !c2_done && !skip_c2) {  // C2, result[8] riding along (rank-consistent scalars)
+    if (p.c2_comm && p.bands == 1) {  // C2, result[8] riding along (rank-consistent scalars); bands > 1: exchanged behind K3 already
         ProfScope prof(h, kProfComm, s);
-        rc = grad_and_result_exchange(comm, grad, (size_t)gcount, d->model == CMAX_MODEL_2DOF ? kCommF64 : kCommF32, result, s);
+        rc = grad_and_result_exchange(comm, grad, (size_t)p.g.count, p.g.type, result, s);
         if (rc) return rc;
-    } else if (dist && !grad && !raw_out && !skip_c2) {  // value only: the 64 bytes on their own
+    } else if (p.result_alone) {  // value only: the 64 bytes on their own
         ProfScope prof(h, kProfComm, s);
         rc = result_exchange_alone(comm, result, s);
         if (rc) return rc;
@@ -3622,13 +3682,12 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
     CMAX_REQUIRE(results != nullptr && K >= 1 && K <= 64, "objective_batch: results / 1 <= K <= 64");
     hipStream_t s = (hipStream_t)stream;
     const bool two_dof = d->model == CMAX_MODEL_2DOF;
-    const int64_t gcount = two_dof ? 2 : (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
-    const int64_t mfloats = two_dof ? (d->motion_dtype == CMAX_F64 ? 4 : 2) : gcount;  // floats per candidate motion
-    const size_t gbytes = two_dof ? 2 * sizeof(double) : (size_t)gcount * sizeof(float);
+    const GradExtent g = grad_extent(h, d);
+    const int64_t mfloats = two_dof ? (d->motion_dtype == CMAX_F64 ? 4 : 2) : g.count;  // floats per candidate motion
     const bool fast = K > 1 && grads && deferred_applies(h, d, grads) && !d->normalized && !h->comm && !h->profiling;
     if (!fast) {
         for (int z = 0; z < K; ++z) {
-            rc = objective_eval(h, d, motions + z * mfloats, results + 8 * z, grads ? (char *)grads + (size_t)z * gbytes : nullptr, s, nullptr);
+            rc = objective_eval(h, d, motions + z * mfloats, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
             if (rc) return rc;
         }
         return 0;
@@ -3666,9 +3725,8 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
     ra.z_img = (int64_t)nr * npix;
     ra.z_raw = (int64_t)nr * kRawStride;
     ra.z_motion = (int)mfloats;
+    fill_ref_times(ra, nr, d->ref_mode, d->ref_frac);
     for (int k = 0; k < nr; ++k) {
-        ra.d[k] = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        ra.d_lo[k] = ref_fraction_lo(d->ref_mode[k], d->ref_frac[k]);
         ra.img[k] = cur + k * npix;
         ra.stat[k] = h->braw + (int64_t)k * kRawStride;  // K1's first workgroup of every (candidate, reference time) resets its lines
         ra.zero[k] = nxt + k * npix;                      // K3 clears the other buffer's image of the same (candidate, reference time)
@@ -3798,8 +3856,7 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
         std::memcpy(grad_host, h->hp_out + 8, 2 * sizeof(double));
         return 0;
     }
-    const int64_t gcount = d->model == CMAX_MODEL_2DOF ? 2 : (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
-    const int64_t gbytes = grad_host ? (d->model == CMAX_MODEL_2DOF ? 2 * (int64_t)sizeof(double) : gcount * (int64_t)sizeof(float)) : 0;
+    const int64_t gbytes = grad_host ? (int64_t)grad_extent(h, d).bytes : 0;
     if (gbytes > h->host_grad_bytes) {
         CMAX_CHECK_HIP(hipStreamSynchronize(s));
         if (h->d_host_grad) (void)hipFree(h->d_host_grad);
@@ -3953,9 +4010,8 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     const int Hp = h->Hp, Wp = h->Wp;
     const int64_t npix = (int64_t)Hp * Wp;
     const bool two_dof = d->model == CMAX_MODEL_2DOF;
-    const int64_t gcount = two_dof ? 2 : (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
-    const size_t gbytes = two_dof ? 2 * sizeof(double) : (size_t)gcount * sizeof(float);
-    CMAX_CHECK_HIP(hipMemsetAsync(hv, 0, gbytes, s));
+    const GradExtent g = grad_extent(h, d);
+    CMAX_CHECK_HIP(hipMemsetAsync(hv, 0, g.bytes, s));
     if (h->n == 0 && !dist) return 0;
     if (!h->hvp_img) {
         rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
@@ -3984,16 +4040,8 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
             rc = comm_allreduce(comm, I, (size_t)npix, kCommF32, kCommSum, s);
             if (rc) return rc;
         }
-        const float *img = nullptr;
-        rc = blur_image(h, d->sigma, I, Ib, &img, s);
+        rc = orig_image_stats(h, d, I, Ib, nullptr, s);
         if (rc) return rc;
-        const int omit_o = d->cost == CMAX_COST_VARIANCE ? 0 : d->omit_boundary;
-        rc = launch_stats(h, d->cost, img, omit_o, 4, nullptr, s);
-        if (rc) return rc;
-        h->orig_valid = true;
-        h->orig_sigma = d->sigma;
-        h->orig_cost = d->cost;
-        h->orig_omit = d->omit_boundary;
     }
 
     // derivative votes are bounded by 2 |dt|_max (the tangent has unit max-norm): fixed-point scale per reference time
@@ -4031,13 +4079,7 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     // loss and the gradient
     const bool det = h->deterministic;
     long long *dI64 = det ? h->img64 : nullptr;
-    if (h->n > 0) {
-        switch (d->model) {
-            case CMAX_MODEL_2DOF: launch_vote_tan<CMAX_MODEL_2DOF>(h, ev, wp, tp, nr, dI, s, dI64); break;
-            case CMAX_MODEL_DENSE: launch_vote_tan<CMAX_MODEL_DENSE>(h, ev, wp, tp, nr, dI, s, dI64); break;
-            default: launch_vote_tan<CMAX_MODEL_VOXEL>(h, ev, wp, tp, nr, dI, s, dI64); break;
-        }
-    }
+    if (h->n > 0) with_model(d->model, [&](auto m) { launch_vote_tan<m.value>(h, ev, wp, tp, nr, dI, s, dI64); });
     CMAX_CHECK_LAUNCH();
     if (det && h->n > 0) {
         FixedArgs fa = {};
@@ -4060,7 +4102,7 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     if (h->n == 0) {  // this rank holds no events of the batch: nothing to gather, but it takes part in every exchange
         if (dist && reduce_hv) {
             ProfScope prof(h, kProfComm, s);
-            rc = comm_allreduce(comm, hv, (size_t)gcount, two_dof ? kCommF64 : kCommF32, kCommSum, s);
+            rc = comm_allreduce(comm, hv, (size_t)g.count, g.type, kCommSum, s);
         }
         return rc;
     }
@@ -4109,14 +4151,9 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
         hipLaunchKernelGGL(k_image_absmax, mgrid, dim3(256), 0, s, ig, npix, 0, h->d_imax);
         hipLaunchKernelGGL(k_image_absmax, mgrid, dim3(256), 0, s, ip, npix, 4, h->d_imax);
         CMAX_CHECK_LAUNCH();
-        if (!two_dof && gcount > h->g64_cap) {
-            CMAX_CHECK_HIP(hipStreamSynchronize(s));
-            dev_free(&h->g64);
-            h->g64_cap = 0;
-            rc = dev_alloc(h, &h->g64, gcount);
+        if (!two_dof) {
+            rc = reserve_g64(h, g.count, s);
             if (rc) return rc;
-            h->g64_cap = gcount;
-            CMAX_CHECK_HIP(hipMemsetAsync(h->g64, 0, (size_t)gcount * sizeof(long long), s));
         }
         hd.g64 = two_dof ? reinterpret_cast<long long *>(h->d_gpart) : h->g64;  // (d_gpart: [4][nseg][2] doubles = as many 64-bit integers)
         hd.imax = h->d_imax;
@@ -4124,25 +4161,18 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
         hd.n_events = h->n;
         hd.n_ref = nr;
     }
-    switch (d->model) {
-        case CMAX_MODEL_2DOF: launch_grad_hvp<CMAX_MODEL_2DOF>(h, ev, wp, tp, nr, h->G, Gp, h->d_gpart, nullptr, s, hd); break;
-        case CMAX_MODEL_DENSE: launch_grad_hvp<CMAX_MODEL_DENSE>(h, ev, wp, tp, nr, h->G, Gp, nullptr, (float *)hv, s, hd); break;
-        default: launch_grad_hvp<CMAX_MODEL_VOXEL>(h, ev, wp, tp, nr, h->G, Gp, nullptr, (float *)hv, s, hd); break;
-    }
+    with_model(d->model, [&](auto m) { launch_grad_hvp<m.value>(h, ev, wp, tp, nr, h->G, Gp, two_dof ? h->d_gpart : nullptr, two_dof ? nullptr : (float *)hv, s, hd); });
     CMAX_CHECK_LAUNCH();
     if (det) {
-        if (two_dof)
-            hipLaunchKernelGGL(k_finish_det, dim3(1), dim3(256), 0, s, reinterpret_cast<long long *>(h->d_gpart), h->nseg, nr, h->d_det_inv_scale, (double *)hv);
-        else
-            hipLaunchKernelGGL(k_fixed_to_grad, dim3(stream_grid(gcount, 256)), dim3(256), 0, s, h->g64, (float *)hv, gcount, h->d_det_inv_scale);
-        CMAX_CHECK_LAUNCH();
+        rc = launch_finish_det(h, d, hv, s);
+        if (rc) return rc;
     } else if (two_dof) {
         hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, s, h->d_gpart, d->n_ref * h->nseg, (double *)hv);
         CMAX_CHECK_LAUNCH();
     }
     if (dist && reduce_hv) {
         ProfScope prof(h, kProfComm, s);
-        rc = comm_allreduce(comm, hv, (size_t)gcount, two_dof ? kCommF64 : kCommF32, kCommSum, s);
+        rc = comm_allreduce(comm, hv, (size_t)g.count, g.type, kCommSum, s);
         if (rc) return rc;
     }
     return 0;
