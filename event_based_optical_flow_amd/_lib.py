@@ -62,6 +62,7 @@ class CmaxPatchObjective(ctypes.Structure):
         ("pad_h", ctypes.c_int32),
         ("pad_w", ctypes.c_int32),
         ("tv_omit_boundary", ctypes.c_int32),
+        ("scale_later", ctypes.c_int32),
         ("t_scale", ctypes.c_double),
         ("weight", ctypes.c_double * 4),
         ("tv_weight", ctypes.c_double),
@@ -75,7 +76,7 @@ MODEL_2DOF, MODEL_DENSE, MODEL_VOXEL = 0, 1, 2
 REF_FIRST, REF_LAST, REF_FRAC = 0, 1, 2
 COST_VARIANCE, COST_GRADMAG = 0, 1
 SCHEME_BURGERS, SCHEME_UPWIND = 0, 1
-ABI_VERSION = 3
+ABI_VERSION = 4
 COMM_ID_BYTES = 128
 RAW_LINES = 32
 RAW_DOUBLES = RAW_LINES * 16
@@ -152,6 +153,8 @@ SIGNATURES = {
     "cmax_patch_plan_evaluate": (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_vp, c_vp]),
     "cmax_patch_plan_hvp": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_plan_set_t_scale": (c_int, [c_vp, c_dbl]),
+    "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
+    "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_search": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_vp]),
 }
 

@@ -23,13 +23,10 @@ __device__ __forceinline__ void bilin_tap(int dst, int scale, int n_in, int &i0,
 
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
-// TOut / scale: the plan writes the fp32 motion of the fused objective (flow * t_scale) straight from the fp64 patch grid
-template <typename T, typename TOut = T>
-__global__ void __launch_bounds__(256)
-k_patch_to_dense(const T *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
-                 TOut *__restrict__ flow, T scale = (T)1) {
-    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (p >= 2 * (int64_t)H * W) return;
+// value of the dense flow at flat index p of [2,H,W]
+template <typename T>
+__device__ __forceinline__ T patch_interp(const T *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
+                                          int64_t p) {
     const int c = (int)(p / ((int64_t)H * W));
     const int64_t q = p % ((int64_t)H * W);
     const int i = (int)(q / W), j = (int)(q % W);
@@ -41,7 +38,17 @@ k_patch_to_dense(const T *__restrict__ motion, int ph, int pw, int pad_h, int pa
     bilin_tap<T>(j + w1, sw_w, gw, c0, c1, lc);
     const T *m = motion + (int64_t)c * ph * pw;
     auto PM = [&](int R, int C) { return -m[(int64_t)clampi(R - pad_h, 0, ph - 1) * pw + clampi(C - pad_w, 0, pw - 1)]; };
-    const T v = ((T)1 - lr) * (((T)1 - lc) * PM(r0, c0) + lc * PM(r0, c1)) + lr * (((T)1 - lc) * PM(r1, c0) + lc * PM(r1, c1));
+    return ((T)1 - lr) * (((T)1 - lc) * PM(r0, c0) + lc * PM(r0, c1)) + lr * (((T)1 - lc) * PM(r1, c0) + lc * PM(r1, c1));
+}
+
+// TOut / scale: the plan writes the fp32 motion of the fused objective (flow * t_scale) straight from the fp64 patch grid
+template <typename T, typename TOut = T>
+__global__ void __launch_bounds__(256)
+k_patch_to_dense(const T *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
+                 TOut *__restrict__ flow, T scale = (T)1) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= 2 * (int64_t)H * W) return;
+    const T v = patch_interp<T>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
     flow[p] = (TOut)(v * scale);
 }
 
@@ -75,6 +82,45 @@ k_patch_to_dense_adj(const T *__restrict__ gflow, int ph, int pw, int pad_h, int
     }
     block_sum<1>(acc, smem);
     if (threadIdx.x == 0) gmotion[cell] = (T)acc[0];
+}
+
+
+// ---------------------------------------------------------------------------------------------
+// Signed maximum of a field (`scale = dense_flow.max()` of the scale_later map, patch_contrast_pyramid.py:489-490).
+// A double as an unsigned key whose order is the order of the values: negative numbers have all bits flipped, the
+// others the sign bit set (k_absmax of cmax_solver.hip compares raw bit patterns, which orders non-negative values only).
+// ---------------------------------------------------------------------------------------------
+__device__ __forceinline__ unsigned long long ordered_key(double v) {
+    const unsigned long long b = (unsigned long long)__double_as_longlong(v);
+    return (b >> 63) ? ~b : (b | 0x8000000000000000ull);
+}
+__device__ __forceinline__ double ordered_value(unsigned long long k) {
+    return __longlong_as_double((long long)((k >> 63) ? (k & 0x7FFFFFFFFFFFFFFFull) : ~k));
+}
+
+// Maximum over the calling workgroup (256 threads), valid in every thread
+__device__ __forceinline__ double block_max(double m) {
+    __shared__ double s_m[256 / kWave];
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) m = fmax(m, __shfl_xor(m, o, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0) s_m[threadIdx.x / kWave] = m;
+    __syncthreads();
+    return fmax(fmax(s_m[0], s_m[1]), fmax(s_m[2], s_m[3]));
+}
+
+// Maximum of a field whose workgroups hold `m` each, one atomic per workgroup (few workgroups: equal-address atomics
+// serialise); returns true in thread 0 of the LAST workgroup of the grid to arrive, which then holds the maximum of the whole
+// field in `field_max` and has reset *key and *arrived to 0 for the next launch (both start as 0: below the key of every value).
+__device__ __forceinline__ bool grid_max_last(double m, unsigned long long *key, unsigned int *arrived, double &field_max) {
+    m = block_max(m);
+    if (threadIdx.x != 0) return false;
+    atomicMax(key, ordered_key(m));
+    __threadfence();
+    if (atomicAdd(arrived, 1u) != gridDim.x - 1) return false;
+    __threadfence();
+    field_max = ordered_value(atomicExch(key, 0ull));
+    atomicExch(arrived, 0u);
+    return true;
 }
 
 }  // namespace cmax

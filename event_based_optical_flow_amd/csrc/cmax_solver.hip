@@ -68,6 +68,167 @@ __global__ void k_absmax_finish(const unsigned long long *__restrict__ bits, dou
     scal[1] = 1.0 / scal[0];
 }
 
+// ---------------------------------------------------------------------------------------------
+// solver.scale_later (src/solver/patch_contrast_pyramid.py:489-515, src/solver/base.py:219-224): with D = P x [2,H,W] the dense
+// flow, t = t_scale and C the Burgers / upwind voxel chain,
+//   s = max D (ONE signed scalar over both components),  u = t D / s,  V = C(u),  motion M = s V.
+// torch's full-reduction max back-propagates evenly over the n elements equal to the maximum: kappa = ds/dD = 1/n there.
+// With g_M = dL/dM and h = J(u)^T g_M (the adjoint sweep, unscaled seed):   g_D = t h + kappa (<g_M, V> - <h, u>).
+// Along a tangent Dd:  sd = <kappa, Dd>,  ud = (t Dd - u sd) / s,  W = J ud,  Md = sd V + s W,  gd_M = H_MM Md,
+//   hd = J^T gd_M + (dJ[ud])^T g_M (the dual sweep, seeds (g_M, gd_M)),  gd_D = t hd + kappa (<gd_M, V> + <g_M, W> - <hd, u> - <h, ud>).
+// s, the tie count and every inner product stay in device memory (the sequence is capturable).  Reductions: kSlBlocks
+// workgroups leave one partial sum each (plain stores), and every workgroup of the consuming kernel adds them up in the
+// same fixed order -- no floating-point atomics, bit-identical from run to run.
+// ---------------------------------------------------------------------------------------------
+constexpr int kSlBlocks = 256;  // = the consumers' workgroup size: one partial per thread
+// partial[slot][kSlBlocks]: 0..2 inner products taken before the adjoint sweep, 3..4 after it, 5 tie count, 6 sum of Dd over the ties,
+// 7 maxima of D
+constexpr int kSlSlots = 8, kSlPost = 3, kSlCount = 5, kSlTangent = 6, kSlMax = 7;
+// scalars: [0] s (1 when the maximum is 0 or not finite: the event kernels must see a finite motion), [1] 1 if s is usable, else 0
+// (the tail then writes NaN, the reference's 0/0), [2] sd
+constexpr int kSlScalars = 4;
+static inline int sl_grid(int64_t n) { const int g = div_up(n, 256); return g < kSlBlocks ? g : kSlBlocks; }
+
+// D = P x and, per workgroup, its signed maximum (no atomics: ~700 same-address atomics would cost more than the pass itself)
+__global__ void __launch_bounds__(256)
+k_patch_to_dense_max(const double *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
+                     double *__restrict__ D, double *__restrict__ partial) {
+    double m = -INFINITY;
+    const int64_t n = 2 * (int64_t)H * W;
+    for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
+        const double v = D[p] = patch_interp<double>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
+        m = fmax(m, v);
+    }
+    m = block_max(m);
+    if (threadIdx.x == 0) partial[kSlMax * kSlBlocks + blockIdx.x] = m;
+}
+
+// s = max D from the workgroups' maxima; u = t D / s; per workgroup: number of pixels with D == s and (Hessian-vector
+// products) the sum of the tangent Dd over them.  Workgroup 0 publishes s and whether it is usable.
+__global__ void __launch_bounds__(256)
+k_sl_scale(const double *__restrict__ D, const double *__restrict__ Dd, int64_t n, double t, int n_partial, double *__restrict__ sl,
+           double *__restrict__ u, double *__restrict__ partial) {
+    __shared__ double smem[2 * 256 / kWave];
+    const double fm = block_max((int)threadIdx.x < n_partial ? partial[kSlMax * kSlBlocks + threadIdx.x] : -INFINITY);
+    const bool ok = isfinite(fm) && fm != 0.0;
+    const double s = ok ? fm : 1.0;
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        sl[0] = s;
+        sl[1] = ok ? 1.0 : 0.0;
+    }
+    double v[2] = {0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+        const double d = D[i];
+        double q = d * t / s;  // the reference's order: dense_flow * t_scale / scale
+        if (!ok && !isfinite(q)) q = 0.0;
+        u[i] = q;
+        if (ok && d == s) {
+            v[0] += 1.0;
+            if (Dd) v[1] += Dd[i];
+        }
+    }
+    block_sum<2>(v, smem);
+    if (threadIdx.x == 0) {
+        partial[kSlCount * kSlBlocks + blockIdx.x] = v[0];
+        partial[kSlTangent * kSlBlocks + blockIdx.x] = v[1];
+    }
+}
+
+// ud = (t Dd - u sd) / s in place of Dd, with sd = <kappa, Dd>; Dd arrives un-normalised (times *dd_scale)
+__global__ void __launch_bounds__(256)
+k_sl_tangent(const double *__restrict__ u, double *__restrict__ Dd, int64_t n, double t, const double *__restrict__ dd_scale,
+             double *__restrict__ sl, const double *__restrict__ partial, int n_partial) {
+    __shared__ double smem[2 * 256 / kWave];
+    __shared__ double s_sd;
+    double v[2] = {0.0, 0.0};
+    if ((int)threadIdx.x < n_partial) {
+        v[0] = partial[kSlCount * kSlBlocks + threadIdx.x];
+        v[1] = partial[kSlTangent * kSlBlocks + threadIdx.x];
+    }
+    block_sum<2>(v, smem);
+    if (threadIdx.x == 0) s_sd = v[0] > 0.0 ? dd_scale[0] * v[1] / v[0] : 0.0;
+    __syncthreads();
+    const double sd = s_sd, s = sl[0];
+    if (blockIdx.x == 0 && threadIdx.x == 0) sl[2] = sd;
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) Dd[i] = (t * (Dd[i] * dd_scale[0]) - u[i] * sd) / s;
+}
+
+// Md = sd V + s W (fp64, its max-norm is taken next) and the fp32 motion s V in one pass
+__global__ void __launch_bounds__(256)
+k_sl_motion_tangent(const double *__restrict__ V, const double *__restrict__ Wt, int64_t n, const double *__restrict__ sl,
+                    double *__restrict__ Md, float *__restrict__ motion32) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double s = sl[0], sd = sl[2], v = V[i];
+    Md[i] = sd * v + s * Wt[i];
+    motion32[i] = (float)(s * v);
+}
+
+struct DotJobs {
+    const double *a[3], *b[3];
+    int n_dots;
+};
+// partial[slot0 + k][workgroup] = this workgroup's share of <a_k, b_k>, k < n_dots
+__global__ void __launch_bounds__(256) k_sl_dots(DotJobs jobs, int64_t n, int slot0, double *__restrict__ partial) {
+    __shared__ double smem[3 * 256 / kWave];
+    double v[3] = {0.0, 0.0, 0.0};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) {
+#pragma unroll
+        for (int k = 0; k < 3; ++k)
+            if (k < jobs.n_dots) v[k] += jobs.a[k][i] * jobs.b[k][i];
+    }
+    block_sum<3>(v, smem);
+    if (threadIdx.x == 0)
+        for (int k = 0; k < jobs.n_dots; ++k) partial[(slot0 + k) * kSlBlocks + blockIdx.x] = v[k];
+}
+
+struct SlCoef {
+    double c[kSlCount];  // weight of inner product `slot` in g_s (0: slot not used by this call)
+    int n_pre, n_post, n_count;  // partials per slot: before the sweep, after it, of the tie count
+};
+// g_D = t h + g_s kappa: the scatter of g_s over the ties rides on the pass that scales the sweep's result
+__global__ void __launch_bounds__(256)
+k_sl_grad_dense(const double *__restrict__ h, const double *__restrict__ D, int64_t n, double t, const double *__restrict__ sl,
+                const double *__restrict__ partial, SlCoef cf, double *__restrict__ gD) {
+    __shared__ double smem[2 * 256 / kWave];
+    __shared__ double s_gk;
+    double v[2] = {0.0, 0.0};
+    for (int k = 0; k < kSlCount; ++k)
+        if (cf.c[k] != 0.0 && (int)threadIdx.x < (k < kSlPost ? cf.n_pre : cf.n_post)) v[0] += cf.c[k] * partial[k * kSlBlocks + threadIdx.x];
+    if ((int)threadIdx.x < cf.n_count) v[1] = partial[kSlCount * kSlBlocks + threadIdx.x];
+    block_sum<2>(v, smem);
+    if (threadIdx.x == 0) s_gk = v[1] > 0.0 ? v[0] / v[1] : 0.0;
+    __syncthreads();
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) gD[i] = t * h[i] + (D[i] == sl[0] ? s_gk : 0.0);
+}
+
+// ---- the reduction as a leaf operator (the autograd-chained path): out[0] = max, out[1] = number of elements equal to it
+template <typename T>
+__global__ void __launch_bounds__(256) k_field_max(const T *__restrict__ x, int64_t n, double *__restrict__ out) {
+    double m = -INFINITY;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) m = fmax(m, (double)x[i]);
+    double fm;
+    if (grid_max_last(m, reinterpret_cast<unsigned long long *>(out + 2), reinterpret_cast<unsigned int *>(out + 3), fm)) out[0] = fm;
+}
+template <typename T>
+__global__ void __launch_bounds__(256) k_field_count(const T *__restrict__ x, int64_t n, double *__restrict__ out) {
+    __shared__ double smem[256 / kWave];
+    const double m = out[0];
+    double v[1] = {0.0};
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n; i += (int64_t)gridDim.x * blockDim.x) v[0] += (double)x[i] == m ? 1.0 : 0.0;
+    block_sum<1>(v, smem);
+    if (threadIdx.x == 0 && v[0] > 0.0) atomic_add(out + 1, v[0]);  // (whole numbers: exact in any order)
+}
+// adjoint: gx = gout / count on the elements equal to the maximum, 0 elsewhere
+template <typename T>
+__global__ void __launch_bounds__(256)
+k_field_max_adj(const T *__restrict__ x, int64_t n, const double *__restrict__ out, const double *__restrict__ gout, T *__restrict__ gx) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i < n) gx[i] = (double)x[i] == out[0] ? (T)(gout[0] / out[1]) : (T)0;
+}
+
 struct FinalParams {
     int n_terms, with_tv, nx;  // nx = 0: value only
     int flag_slot;             // index (in doubles) of the run counter in the output: 1 + the plan's nx, whatever this call's nx is
@@ -81,12 +242,12 @@ struct FinalParams {
 // sum of the contrast terms, and the chain through t_scale:
 //   out[0] = sum_i w_i result_i + w_tv TV(x),   out[1 + j] = gscale * gx[j] + w_tv dTV/dx[j]
 // gx comes as fp64 (gx64) or fp32 (gx32); gscale_dev multiplies gscale (Hessian-vector products).  `out` may be
-// pinned host memory.
+// pinned host memory.  ok_dev (scale_later plans): *ok_dev == 0 -> loss and gradient are NaN.
 constexpr int kTailLds = 4096;  // patch-grid values staged in LDS by k_patch_tail (2 x 45 x 45 patches)
 __global__ void __launch_bounds__(256)
 k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *__restrict__ x, const double *__restrict__ gx64,
              const float *__restrict__ gx32, const double *__restrict__ gscale_dev, double *__restrict__ out,
-             unsigned long long *__restrict__ seq_dev) {
+             unsigned long long *__restrict__ seq_dev, const double *__restrict__ ok_dev = nullptr) {
     __shared__ double smem[4];
     __shared__ double s_tv;
     __shared__ double s_x[kTailLds];
@@ -124,11 +285,12 @@ k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *_
     }
     double gscale = fp.gscale;
     if (gscale_dev) gscale *= gscale_dev[0];
+    const bool undefined = ok_dev && ok_dev[0] == 0.0;  // scale_later with max D = 0 (or not finite): the reference divides 0 by 0
     if (threadIdx.x == 0) {
         double loss = 0.0;
         for (int i = 0; i < fp.n_terms; ++i) loss += fp.weight[i] * results[8 * i];
         if (fp.with_tv) loss += fp.tv_weight * s_tv;
-        out[0] = loss;
+        out[0] = undefined ? (double)NAN : loss;
     }
     for (int p = threadIdx.x; p < fp.nx; p += blockDim.x) {
         double g = gscale * (gx64 ? gx64[p] : (double)gx32[p]);
@@ -154,7 +316,7 @@ k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *_
                 }
             g += fp.tv_weight * sgn / 8.0 / ntv;
         }
-        out[1 + p] = g;
+        out[1 + p] = undefined ? (double)NAN : g;
     }
     // completion flag for a host that polls the (pinned) output instead of sleeping in hipStreamSynchronize: a run
     // counter, written after every result of this launch is visible system-wide
@@ -180,6 +342,8 @@ struct cmax_patch_plan_s {
     // time-aware Hessian-vector product (allocated on first use): tangent flow / voxel, tangent of dL/dvoxel, scalars
     double *dflow64 = nullptr, *dvox64 = nullptr, *dgacc64 = nullptr, *dgflow64 = nullptr, *scal = nullptr;
     float *motion32 = nullptr, *grad32 = nullptr, *tan32 = nullptr, *gx32 = nullptr;
+    // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
+    double *dense64 = nullptr, *sl = nullptr, *sl_partial = nullptr;
     double *h_out_dev = nullptr;  // device view of the pinned output: the tail kernel writes the result there
     double *h_in = nullptr, *h_out = nullptr;  // pinned staging: x | v | 2 scalars, loss | grad | run counter
     unsigned long long *seq_dev = nullptr;     // device-side run counter of the tail kernel
@@ -255,6 +419,19 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
         CMAX_CHECK_LAUNCH();
         return 0;
     }
+    if (d.time_aware && d.scale_later && !scale_dev) {
+        // D = P x and s = max D; u = t D / s (tie count on the way); V = C(u); fp32 motion s V, s read from device memory
+        hipLaunchKernelGGL(k_patch_to_dense_max, dim3(sl_grid(p->nflow)), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W,
+                           p->dense64, p->sl_partial);
+        hipLaunchKernelGGL(k_sl_scale, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->dense64, (const double *)nullptr, p->nflow, scale, sl_grid(p->nflow),
+                           p->sl, p->flow64, p->sl_partial);
+        CMAX_CHECK_LAUNCH();
+        int rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, nullptr, nullptr, s);
+        if (rc) return rc;
+        hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)p->sl, dst32);
+        CMAX_CHECK_LAUNCH();
+        return 0;
+    }
     if (d.time_aware && !scale_dev) {
         // patch grid -> fp64 displacement field (x t_scale) in one kernel; the voxel is built on the displacement
         // field (patch_contrast_pyramid.py:452, 499-515) and leaves the chain kernel in fp64 and fp32 at once
@@ -302,7 +479,22 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
         return 0;
     }
     const double *gflow = p->gacc64;
-    if (d.time_aware) {  // the sweep leaves dL/dF in bin t0 of the gradient voxel: read it there
+    if (d.time_aware && d.scale_later) {
+        // g_D = t h + kappa (<g_M, V> - <h, u>), h = J^T g_M: the first product before the sweep clobbers g_M, the second after it
+        DotJobs pre = {{p->gacc64}, {p->vox64}, 1};
+        hipLaunchKernelGGL(k_sl_dots, dim3(sl_grid(p->nmotion)), dim3(256), 0, s, pre, p->nmotion, 0, p->sl_partial);
+        CMAX_CHECK_LAUNCH();
+        int rc = voxel_construct_adj_f64(p->vox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, s, handle_is_deterministic(p->handle));
+        if (rc) return rc;
+        const double *h = p->gacc64 + (int64_t)d.t0 * p->nflow;
+        DotJobs post = {{h}, {p->flow64}, 1};
+        hipLaunchKernelGGL(k_sl_dots, dim3(sl_grid(p->nflow)), dim3(256), 0, s, post, p->nflow, kSlPost, p->sl_partial);
+        SlCoef cf = {{1.0, 0.0, 0.0, -1.0, 0.0}, sl_grid(p->nmotion), sl_grid(p->nflow), sl_grid(p->nflow)};
+        hipLaunchKernelGGL(k_sl_grad_dense, dim3(div_up(p->nflow, 256)), dim3(256), 0, s, h, p->dense64, p->nflow, d.t_scale, p->sl, p->sl_partial, cf,
+                           p->gflow64);
+        CMAX_CHECK_LAUNCH();
+        gflow = p->gflow64;  // (t is applied above: the tail gets gscale 1)
+    } else if (d.time_aware) {  // the sweep leaves dL/dF in bin t0 of the gradient voxel: read it there
         int rc = voxel_construct_adj_f64(p->vox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, s, handle_is_deterministic(p->handle));
         if (rc) return rc;
         gflow = p->gacc64 + (int64_t)d.t0 * p->nflow;
@@ -346,7 +538,9 @@ int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t 
     for (int i = 0; i < 4; ++i) fp.weight[i] = d.weight[i];
     fp.tv_weight = d.tv_weight;
     fp.gscale = d.t_scale * wscale;  // d(flow * t_scale) / d flow
-    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, (const double *)nullptr, p->h_out_dev, p->seq_dev);
+    if (d.time_aware && d.scale_later) fp.gscale = 1.0;
+    const double *ok_dev = d.time_aware && d.scale_later ? p->sl + 1 : nullptr;
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, (const double *)nullptr, p->h_out_dev, p->seq_dev, ok_dev);
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -413,8 +607,77 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     return 0;
 }
 
+// ... with scale_later: the map x -> M = s C(t P x / s) and its second-order adjoint as derived above k_patch_to_dense_max.
+int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (2 * (size_t)p->nx + 2) * sizeof(double), hipMemcpyHostToDevice, s));
+    const double *inv_vmax = p->x64 + 2 * p->nx, *vmax = inv_vmax + 1;
+    const int fgrid = div_up(p->nflow, 256), mgrid = div_up(p->nmotion, 256);
+    // D = P x, s = max D;  Dd = P v;  u = t D / s (flow64);  ud = (t Dd / |v|_inf - u sd) / s (dflow64)
+    hipLaunchKernelGGL(k_patch_to_dense_max, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->x64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, p->dense64,
+                       p->sl_partial);
+    CMAX_CHECK_LAUNCH();
+    int rc = cmax_patch_to_dense(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->dflow64, s);
+    if (rc) return rc;
+    hipLaunchKernelGGL(k_sl_scale, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->dense64, (const double *)p->dflow64, p->nflow, d.t_scale, sl_grid(p->nflow),
+                       p->sl, p->flow64, p->sl_partial);
+    hipLaunchKernelGGL(k_sl_tangent, dim3(fgrid), dim3(256), 0, s, p->flow64, p->dflow64, p->nflow, d.t_scale, inv_vmax, p->sl, p->sl_partial, sl_grid(p->nflow));
+    CMAX_CHECK_LAUNCH();
+    // V = C(u), W = J ud
+    rc = cmax_voxel_construct_tan(p->flow64, p->dflow64, CMAX_F64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, p->dvox64, s);
+    if (rc) return rc;
+    // fp32 motion s V; tangent Md = sd V + s W (staged in dgacc64, free until the first product lands there), scaled to unit max-norm
+    hipLaunchKernelGGL(k_sl_motion_tangent, dim3(mgrid), dim3(256), 0, s, p->vox64, p->dvox64, p->nmotion, p->sl, p->dgacc64, p->motion32);
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(p->scal + 2);
+    CMAX_CHECK_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_absmax, dim3(mgrid < 256 ? mgrid : 256), dim3(256), 0, s, p->dgacc64, p->nmotion, bits);
+    hipLaunchKernelGGL(k_absmax_finish, dim3(1), dim3(1), 0, s, bits, p->scal);
+    hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, p->dgacc64, p->nmotion, 1.0, p->scal + 1, p->tan32);
+    CMAX_CHECK_LAUNCH();
+    for (int i = 0; i < d.n_terms; ++i) {
+        rc = plan_objective(p, &d.term[i], p->results + 8 * i, p->grad32, s);  // g_M
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_accumulate, dim3(mgrid), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->gacc64, (const double *)nullptr);
+        CMAX_CHECK_LAUNCH();
+        rc = plan_objective_hvp(p, &d.term[i], p->grad32, s);  // H_MM Md / max|Md|
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_accumulate, dim3(mgrid), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->dgacc64, (const double *)p->scal);
+        CMAX_CHECK_LAUNCH();
+    }
+    // <gd_M, V> and <g_M, W> before the dual sweep clobbers its seeds, <hd, u> and <h, ud> after it
+    DotJobs pre = {{p->dgacc64, p->gacc64}, {p->vox64, p->dvox64}, 2};
+    hipLaunchKernelGGL(k_sl_dots, dim3(sl_grid(p->nmotion)), dim3(256), 0, s, pre, p->nmotion, 0, p->sl_partial);
+    CMAX_CHECK_LAUNCH();
+    rc = voxel_construct_adj_tan_f64(p->vox64, p->dvox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, p->dgacc64, s, handle_is_deterministic(p->handle));
+    if (rc) return rc;
+    const double *h = p->gacc64 + (int64_t)d.t0 * p->nflow, *hd = p->dgacc64 + (int64_t)d.t0 * p->nflow;
+    DotJobs post = {{hd, h}, {p->flow64, p->dflow64}, 2};
+    hipLaunchKernelGGL(k_sl_dots, dim3(sl_grid(p->nflow)), dim3(256), 0, s, post, p->nflow, kSlPost, p->sl_partial);
+    SlCoef cf = {{1.0, 1.0, 0.0, -1.0, -1.0}, sl_grid(p->nmotion), sl_grid(p->nflow), sl_grid(p->nflow)};
+    hipLaunchKernelGGL(k_sl_grad_dense, dim3(fgrid), dim3(256), 0, s, hd, p->dense64, p->nflow, d.t_scale, p->sl, p->sl_partial, cf, p->dgflow64);
+    CMAX_CHECK_LAUNCH();
+    rc = cmax_patch_to_dense(p->dgflow64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 1, p->gx64, s);
+    if (rc) return rc;
+    FinalParams fp;
+    fp.n_terms = 0;
+    fp.flag_slot = 1 + (int)p->nx;
+    fp.with_tv = 0;
+    fp.nx = p->nx;
+    fp.ph = d.ph;
+    fp.pw = d.pw;
+    fp.tv_crop = 0;
+    for (int i = 0; i < 4; ++i) fp.weight[i] = 0.0;
+    fp.tv_weight = 0.0;
+    fp.gscale = 1.0;  // t is in gd_D; times |v|_inf from device memory
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, vmax, p->h_out_dev, p->seq_dev,
+                       (const double *)(p->sl + 1));
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 int enqueue_hvp(cmax_patch_plan_s *p, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
+    if (d.time_aware && d.scale_later) return enqueue_hvp_scale_later(p, s);
     if (d.time_aware) return enqueue_hvp_time_aware(p, s);
     // x64 | v64 | scal64 are one allocation: a single copy brings x, v and the two scalars
     CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (2 * (size_t)p->nx + 2) * sizeof(double), hipMemcpyHostToDevice, s));
@@ -569,6 +832,10 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
         CMAX_REQUIRE(d.term[i].model == (d.time_aware ? CMAX_MODEL_VOXEL : CMAX_MODEL_DENSE), "patch_plan_create: term model must match time_aware");
         CMAX_REQUIRE(!d.time_aware || d.term[i].T == d.T, "patch_plan_create: term T");
     }
+    if (d.time_aware && d.scale_later && handle_has_comm(h)) {
+        set_error("patch_plan_create: scale_later is not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EINVAL;
+    }
     cmax_patch_plan_s *p = new (std::nothrow) cmax_patch_plan_s();
     if (!p) {
         set_error("patch_plan_create: out of host memory");
@@ -587,6 +854,11 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     if (!rc && d.time_aware) rc = plan_alloc(&p->vox64, p->nmotion);
     if (!rc) rc = plan_alloc(&p->gacc64, p->nmotion);
     if (!rc && d.time_aware) rc = plan_alloc(&p->gflow64, p->nflow);
+    if (!rc && d.time_aware && d.scale_later) {
+        rc = plan_alloc(&p->dense64, p->nflow);
+        if (!rc) rc = plan_alloc(&p->sl, kSlScalars);
+        if (!rc) rc = plan_alloc(&p->sl_partial, kSlSlots * kSlBlocks);
+    }
     if (!rc) rc = plan_alloc(&p->gx64, p->nx);
     if (!rc) rc = plan_alloc(&p->results, 8 * 4);
     if (!rc) rc = plan_alloc(&p->motion32, p->nmotion);
@@ -635,7 +907,8 @@ int cmax_patch_plan_destroy(cmax_patch_plan_t p) {
     drop_graphs(p);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     if (p->ev_caller) (void)hipEventDestroy(p->ev_caller);
-    double *d64[] = {p->x64, p->flow64, p->vox64, p->gacc64, p->gflow64, p->gx64, p->results, p->dflow64, p->dvox64, p->dgacc64, p->dgflow64, p->scal};
+    double *d64[] = {p->x64, p->flow64, p->vox64, p->gacc64, p->gflow64, p->gx64, p->results, p->dflow64, p->dvox64, p->dgacc64, p->dgflow64, p->scal,
+                     p->dense64, p->sl, p->sl_partial};
     for (double *q : d64)
         if (q) (void)hipFree(q);
     float *d32[] = {p->motion32, p->grad32, p->tan32, p->gx32};
@@ -685,6 +958,33 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
     int rc = run_sequence(p, 4, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_hvp(p, s); });
     if (rc) return rc;
     std::memcpy(hv_host, p->h_out + 1, (size_t)p->nx * sizeof(double));
+    return 0;
+}
+
+int cmax_field_max(const void *x, int dtype, int64_t n, double *out, cmax_stream_t stream) {
+    CMAX_REQUIRE(x && out && n > 0, "field_max");
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "field_max: dtype");
+    hipStream_t s = (hipStream_t)stream;
+    CMAX_CHECK_HIP(hipMemsetAsync(out, 0, 4 * sizeof(double), s));
+    const int grid = sl_grid(n);
+    if (dtype == CMAX_F32) {
+        hipLaunchKernelGGL(k_field_max<float>, dim3(grid), dim3(256), 0, s, (const float *)x, n, out);
+        hipLaunchKernelGGL(k_field_count<float>, dim3(grid), dim3(256), 0, s, (const float *)x, n, out);
+    } else {
+        hipLaunchKernelGGL(k_field_max<double>, dim3(grid), dim3(256), 0, s, (const double *)x, n, out);
+        hipLaunchKernelGGL(k_field_count<double>, dim3(grid), dim3(256), 0, s, (const double *)x, n, out);
+    }
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+int cmax_field_max_adj(const void *x, int dtype, int64_t n, const double *out, const double *gout, void *gx, cmax_stream_t stream) {
+    CMAX_REQUIRE(x && out && gout && gx && n > 0, "field_max_adj");
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "field_max_adj: dtype");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == CMAX_F32) hipLaunchKernelGGL(k_field_max_adj<float>, dim3(div_up(n, 256)), dim3(256), 0, s, (const float *)x, n, out, gout, (float *)gx);
+    else hipLaunchKernelGGL(k_field_max_adj<double>, dim3(div_up(n, 256)), dim3(256), 0, s, (const double *)x, n, out, gout, (double *)gx);
+    CMAX_CHECK_LAUNCH();
     return 0;
 }
 

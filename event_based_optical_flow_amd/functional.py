@@ -377,6 +377,30 @@ def patch_to_dense(motion, image_size, sliding_window, pad):
                                  (int(sliding_window[0]), int(sliding_window[1])), (int(pad[0]), int(pad[1])))
 
 
+class _FieldMaxFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        out = torch.empty(4, dtype=torch.float64, device=x.device)  # max, tie count, scratch
+        check(_lib.load().cmax_field_max(_ptr(x), _code(x), x.numel(), _ptr(out), _stream()))
+        ctx.save_for_backward(x, out)
+        return out[0].to(x.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        x, out = ctx.saved_tensors
+        gs = gout.detach().to(torch.float64).reshape(1).contiguous()
+        gx = torch.empty_like(x)
+        check(_lib.load().cmax_field_max_adj(_ptr(x), _code(x), x.numel(), _ptr(out), _ptr(gs), _ptr(gx), _stream()))
+        return gx
+
+
+def field_max(x):
+    """torch.Tensor.max() of a whole tensor -- the signed maximum, as a 0-dim tensor -- whose backward spreads the incoming
+    gradient evenly over the elements equal to it (`scale = dense_flow.max()`, src/solver/patch_contrast_pyramid.py:489-490)."""
+    _lib.require_gpu()
+    return _FieldMaxFn.apply(_cuda(x, "x"))
+
+
 def gaussian_filter(img, sigma):
     """scipy.ndimage.gaussian_filter of one [H,W] image (numpy branch of the reference's create_iwe,
     src/event_image_converter.py:122-124).  Not differentiable (the numpy branch never is)."""

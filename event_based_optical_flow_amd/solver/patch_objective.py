@@ -5,6 +5,7 @@ Equivalent of `PyramidalPatchContrastMaximization.objective_scipy`
   patch motion -> dense flow (cmax_patch_to_dense, patch_contrast_base.py:462-506) -> x t_scale
   [-> Burgers / upwind voxel (cmax_voxel_construct)] -> fused contrast objective (cmax_objective)
   [+ weight * total_variation(patch motion)].
+With `scale_later` (time-aware only) the voxel is max(D) * construct(D * t_scale / max(D)), D the dense flow.
 Every stage is a HIP kernel with a hand-written adjoint; torch only chains them on the autograd tape.
 """
 import ctypes
@@ -50,12 +51,16 @@ class PatchFlowObjective:
     def __init__(self, handle: CMaxHandle, t_scale: float, patch_image_size, patch_size, sliding_window,
                  patch_shift=(0, 0), cost: str = "hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
                  blur_sigma: float = 1.0, time_aware: bool = False, time_bin: int = 10,
-                 flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None):
+                 flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None,
+                 scale_later: bool = False):
         """sliced: a distributed.TimeSlicedObjective around `handle` when the batch is time-sliced over ranks.  With the library's own
         communicator on the handle (RCCL) the native plan evaluates the whole batch (cmax_patch_plan_* exchange images + 2 n_patch
         numbers); otherwise -- torch.distributed collectives -- the autograd-chained path below does the same two exchanges.  That
         fall-back has no exact Hessian-vector product (TorchWrapper then takes a difference quotient of the gradient, which on this
-        piecewise-smooth objective is dominated by the kinks at cell borders): prefer a first-order method there, or the RCCL plan."""
+        piecewise-smooth objective is dominated by the kinks at cell borders): prefer a first-order method there, or the RCCL plan.
+        scale_later: the reference's `solver.scale_later` (src/solver/base.py:219-224, patch_contrast_pyramid.py:489-515): the flow is
+        divided by its signed maximum before the Burgers / upwind propagation and the voxel multiplied by it afterwards; the maximum is
+        differentiated like torch.Tensor.max().  Ignored unless `time_aware`.  Not built for time-sliced batches."""
         if filter_type != "bilinear":
             raise NotImplementedError("only the bilinear patch filter (the shipped configs) is built")
         self.handle = handle
@@ -67,6 +72,9 @@ class PatchFlowObjective:
         self.time_bin = int(time_bin)
         self.flow_interpolation = flow_interpolation
         self.t0_flow_location = t0_flow_location
+        self.scale_later = bool(scale_later) and self.time_aware
+        if self.scale_later and sliced is not None:
+            raise NotImplementedError("scale_later is not built for time-sliced batches")
         if self.time_aware and handle.time_bin != self.time_bin:
             handle.set_time_bins(self.time_bin)
         model = "dense-flow-voxel" if self.time_aware else "dense-flow"
@@ -99,6 +107,7 @@ class PatchFlowObjective:
         d.sw_h, d.sw_w = self.sliding_window
         d.pad_h, d.pad_w = self.pad
         d.tv_omit_boundary = int(self.contrast.omit_boundary)
+        d.scale_later = int(self.scale_later)
         d.t_scale = self.t_scale
         for i, (w, desc) in enumerate(fused):
             d.weight[i] = float(w)
@@ -162,7 +171,8 @@ class PatchFlowObjective:
     def hvp_numpy(self, x: np.ndarray, v: np.ndarray, disp_step: float = 0.05, exact: bool = True) -> np.ndarray:
         """Hessian-vector product on host arrays through cmax_patch_plan_hvp: exact, what the reference's
         torch.autograd.functional.vhp returns -- for time-aware objectives including the second-order adjoint of the
-        Burgers / upwind voxel chain (cmax_voxel_construct_tan / _adj_tan).  exact=False: central difference of the
+        Burgers / upwind voxel chain (cmax_voxel_construct_tan / _adj_tan), and with `scale_later` the derivatives of
+        the maximum and of the product max(D) * voxel(D t / max(D)).  exact=False: central difference of the
         analytic gradient of the smooth part, as in `hvp` (kept for cross-checks)."""
         x = np.ascontiguousarray(x, dtype=np.float64).reshape(-1)
         v = np.ascontiguousarray(v, dtype=np.float64).reshape(-1)
@@ -183,7 +193,12 @@ class PatchFlowObjective:
     def dense_flow(self, x: torch.Tensor) -> torch.Tensor:
         """[2*ph*pw] patch motion -> [2,H,W] (or [T,2,H,W]) flow in pixel per NORMALISED time."""
         motion = x.reshape((2,) + self.patch_image_size)
-        dense = F.patch_to_dense(motion, self.handle.image_size, self.sliding_window, self.pad) * self.t_scale
+        dense = F.patch_to_dense(motion, self.handle.image_size, self.sliding_window, self.pad)
+        if self.scale_later:
+            scale = F.field_max(dense)  # one signed scalar over both components (patch_contrast_pyramid.py:489-490)
+            voxel = F.construct_dense_flow_voxel(dense * self.t_scale / scale, self.time_bin, self.flow_interpolation, self.t0_flow_location)
+            return voxel * scale
+        dense = dense * self.t_scale
         if self.time_aware:
             # construct(dense_flow * t_scale / scale) * scale / t_scale with scale = 1, then * t_scale
             # (patch_contrast_pyramid.py:452, 499-515): the voxel is built on the displacement field
@@ -194,7 +209,7 @@ class PatchFlowObjective:
     def has_exact_hvp(self) -> bool:
         """TorchWrapper calls `hvp_numpy` / `hvp` when this is True.  Time-ignorant objectives: patch -> dense is linear,
         so H_x = t^2 P^T H_flow P.  Time-aware objectives add the second-order adjoint of the Burgers / upwind voxel
-        chain (cmax_voxel_construct_tan / _adj_tan).  The total-variation term is piecewise linear: zero Hessian
+        chain (cmax_voxel_construct_tan / _adj_tan), `scale_later` included (the native plan only).  The total-variation term is piecewise linear: zero Hessian
         almost everywhere (a difference quotient of the whole objective would push its kinks into the curvature); with an
         "inv" weight it still contributes its rank-one part phi'' <grad TV, v> grad TV."""
         return self.contrast.has_exact_hvp and self.sliced is None  # (fall-back across ranks: difference quotient of the gradient)

@@ -93,10 +93,10 @@ class PyramidalPatchContrastMaximization:
             self.time_bin = solver_config["time_bin"]
             self.flow_interpolation = solver_config["flow_interpolation"]
             self.t0_flow_location = solver_config["t0_flow_location"]
-            if _check_key_and_bool(solver_config, "scale_later"):
-                raise NotImplementedError("scale_later is not built")
+            self.scale_later = _check_key_and_bool(solver_config, "scale_later")  # "Scaling before upwind", base.py:219-224
         else:
             self.time_bin, self.flow_interpolation, self.t0_flow_location = 0, "burgers", "middle"
+            self.scale_later = False  # (the reference never reads the key without time_aware)
         # pyramid (patch_contrast_pyramid.py:50-61)
         patch = solver_config["patch"]
         self.filter_type = patch["filter_type"]
@@ -158,7 +158,7 @@ class PyramidalPatchContrastMaximization:
                     handle, t_scale, pis, self.scaled_patch_size[s], self.scaled_patch_size[s], self.patch_shift,
                     cost=self.cost_name, cost_with_weight=self.cost_weight, blur_sigma=self.iwe_config["blur_sigma"],
                     time_aware=self.is_time_aware, time_bin=self.time_bin, flow_interpolation=self.flow_interpolation,
-                    t0_flow_location=self.t0_flow_location, filter_type=self.filter_type)
+                    t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=self.scale_later)
             else:
                 objective.set_t_scale(t_scale)
             if self.previous_frame_best_estimation is not None and s == self.coarest_scale:
@@ -290,7 +290,8 @@ class PyramidalPatchContrastMaximization:
     def motion_to_dense_flow(self, motion_per_scale: dict, t_scale: float = 1.0) -> np.ndarray:
         """Finest-scale motion -> dense flow [2,H,W] in pixel per time unit (patch_contrast_pyramid.py:464-516); time-aware solvers:
         the flow voxel [time_bin,2,H,W] propagated from it at displacement scale (flow * t_scale through the Burgers / upwind chain,
-        divided by t_scale again)."""
+        divided by t_scale again); with `scale_later` the flow is also divided by its signed maximum before the chain and the voxel
+        multiplied by it afterwards (the numpy branch of lines 489-504)."""
         import torch
 
         from .. import functional as F
@@ -303,8 +304,9 @@ class PyramidalPatchContrastMaximization:
         dense = F.patch_to_dense(m, self.image_shape, ps, patch_pad(ps, ps, self.patch_shift))
         if not self.is_time_aware:
             return dense.cpu().numpy()
-        voxel = construct_dense_flow_voxel_torch(dense * t_scale, self.time_bin, self.flow_interpolation,
-                                                 t0_location=self.t0_flow_location) / t_scale
+        scale = F.field_max(dense) if self.scale_later else 1.0
+        voxel = construct_dense_flow_voxel_torch(dense * t_scale / scale, self.time_bin, self.flow_interpolation,
+                                                 t0_location=self.t0_flow_location) * scale / t_scale
         return voxel.cpu().numpy()
 
     # -- what main.py calls on a solver besides optimize(): metrics and (optional) pictures ---------------------------------------

@@ -29,7 +29,7 @@
 extern "C" {
 #endif
 
-#define CMAX_ABI_VERSION 3
+#define CMAX_ABI_VERSION 4
 
 /* dtypes */
 #define CMAX_F32 0
@@ -471,6 +471,13 @@ int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start
  *     -> loss = sum_i weight_i * cmax_objective(term_i)  + tv_weight * total_variation(x)
  *   and the gradient back through the adjoints, returned to host fp64.  One stream
  *   synchronisation per call; intermediates live in the plan.
+ * Time-aware plans with scale_later != 0 (solver.scale_later, src/solver/base.py:219-224,
+ * patch_contrast_pyramid.py:489-515) propagate the flow RESCALED BY ITS MAXIMUM: with D = dense flow of x,
+ *   s = max D  (one signed scalar over both components),  voxel = s * cmax_voxel_construct(t_scale * D / s);
+ *   the derivative of s goes evenly to the pixels equal to the maximum (torch.Tensor.max), and gradient and
+ *   Hessian-vector product follow the whole map.  s lives in device memory: no host read-back inside a call.
+ *   max D == 0 (x = 0) or not finite: loss, gradient and product are NaN, as the reference's 0/0 -- the event
+ *   kernels are given a finite motion all the same.
  * ============================================================================================= */
 typedef struct {
     int32_t n_terms;          /* 1..4 fused contrast terms of a hybrid cost (src/costs/hybrid.py:48-57) */
@@ -481,6 +488,7 @@ typedef struct {
     int32_t sw_h, sw_w;       /* sliding window = up-sampling factor */
     int32_t pad_h, pad_w;     /* replicate padding of the grid (patch_contrast_base.py:470-479) */
     int32_t tv_omit_boundary;
+    int32_t scale_later;      /* time_aware only (ignored otherwise): propagate t_scale * D / max(D), multiply the voxel by max(D) */
     double t_scale;           /* pixel per time unit -> pixel per normalised batch period */
     double weight[4];
     double tv_weight;         /* 0 = no total_variation term; sign of the cost direction included */
@@ -497,7 +505,9 @@ int cmax_patch_plan_set_t_scale(cmax_patch_plan_t plan, double t_scale);
  * CMAX_PLAN_GRAPHS=1 in the environment at plan creation, evaluations after the first few are replayed from
  * captured hipGraphs (one per distinct launch sequence; 0 again if a capture failed).                        */
 int cmax_patch_plan_info(cmax_patch_plan_t plan, int *n_graphs, int *graph_replay_enabled);
-/* On a handle that holds a communicator (cmax_comm_init: a time slice of the batch per rank) both calls below evaluate the WHOLE
+/* cmax_patch_plan_create on a handle that holds a communicator returns CMAX_EINVAL for a scale_later plan (not built for
+ * time-sliced batches).
+ * On a handle that holds a communicator (cmax_comm_init: a time slice of the batch per rank) both calls below evaluate the WHOLE
  * batch, the same numbers on every rank: the fused terms exchange their images like cmax_objective_dist (and the product its
  * tangent images), but the flow gradient is not exchanged -- each rank carries its share through the (linear) adjoints of the voxel
  * chain and of the patch interpolation, and the ranks all-reduce 2 ph pw numbers (4 KB for a 16 x 16 grid instead of 7.4 MB of flow
@@ -512,6 +522,14 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t plan, const double *x_host, int w
  * total_variation term has zero Hessian almost everywhere.                                      */
 int cmax_patch_plan_hvp(cmax_patch_plan_t plan, const double *x_host, const double *v_host, double *hv_host,
                         cmax_stream_t stream);
+
+/* The reduction of the scale_later map as a leaf operator (the autograd-chained path chains it with cmax_patch_to_dense and
+ * cmax_voxel_construct).  x: device fp32 / fp64 [n].  out: device double[4] -- out[0] = max x (signed), out[1] = number of
+ * elements EQUAL to it (exact comparison of the values the device holds), out[2..3] scratch.  Asynchronous.                 */
+int cmax_field_max(const void *x, int dtype, int64_t n, double *out, cmax_stream_t stream);
+/* Its adjoint, as torch.Tensor.max() back-propagates: gx[i] = gout[0] / out[1] where x[i] == out[0], 0 elsewhere.  `out` as
+ * cmax_field_max left it; gout: device double[1]; gx: like x.                                                                */
+int cmax_field_max_adj(const void *x, int dtype, int64_t n, const double *out, const double *gout, void *gx, cmax_stream_t stream);
 
 /* =============================================================================================
  * Per-patch translation search: the re-initialisation the pyramid solver runs at every scale above
