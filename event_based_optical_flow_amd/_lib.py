@@ -82,6 +82,7 @@ RAW_LINES = 32
 RAW_DOUBLES = RAW_LINES * 16
 PROF_CLASSES = 6
 ECOMM = -5
+EUNSUPPORTED = -6
 ENODEV = -4
 
 # every symbol include/cmax_hip.h declares: name -> (restype, argtypes)
@@ -112,6 +113,8 @@ SIGNATURES = {
     "cmax_set_events": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_dbl, c_int, c_vp]),
     "cmax_set_time_bins": (c_int, [c_vp, c_int, c_vp]),
     "cmax_set_time_slabs": (c_int, [c_vp, c_int, c_vp]),
+    "cmax_set_event_weights": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp]),
+    "cmax_batch_weighted": (c_int, [c_vp, ctypes.POINTER(c_int), ctypes.POINTER(c_dbl)]),
     "cmax_set_keep_outside": (c_int, [c_vp, c_int]),
     "cmax_batch_outside": (c_int, [c_vp, ctypes.POINTER(ctypes.c_int64)]),
     "cmax_iwe": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_dbl, c_int, c_dbl, c_vp, c_vp]),
@@ -205,6 +208,8 @@ def load():
 def check(rc: int):
     if rc != 0:
         msg = load().cmax_last_error()
+        if rc == EUNSUPPORTED:  # a call the library refuses in the handle's state (per-event weights): the library's own text
+            raise NotImplementedError(msg.decode("utf-8", "replace") if msg else "unsupported")
         raise CmaxError(rc, msg.decode("utf-8", "replace") if msg else "")
 
 

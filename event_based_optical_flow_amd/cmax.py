@@ -68,6 +68,24 @@ def make_descriptor(cost: str, motion_model: str, direction: str = "minimize", s
     return d
 
 
+def prepare_event_weights(weights, n: int) -> torch.Tensor:
+    """Per-event weights as the library takes them: [n] fp32 / fp64 on the device.  Shape and finiteness are checked where the data
+    lives (host arrays on the host, before anything is copied); moving host data to the device needs one (require_gpu)."""
+    if isinstance(weights, np.ndarray):
+        w = torch.from_numpy(np.ascontiguousarray(weights))
+    elif isinstance(weights, torch.Tensor):
+        w = weights
+    else:
+        raise TypeError(f"weights must be a numpy array or a torch tensor, got {type(weights)}")
+    if w.dim() != 1 or w.shape[0] != int(n):
+        raise ValueError(f"weights must be [n] = [{int(n)}] (one per event, in the events' order), got {tuple(w.shape)}")
+    if w.dtype not in (torch.float32, torch.float64):
+        w = w.to(torch.float64)
+    if w.numel() and not bool(torch.isfinite(w).all()):
+        raise ValueError("weights must be finite (any sign, zero allowed)")
+    return to_device_tensor(w, "weights").contiguous()
+
+
 class CMaxHandle:
     """One GPU workspace for one event batch (cmax_create / cmax_set_events / cmax_objective)."""
 
@@ -113,25 +131,30 @@ class CMaxHandle:
         return self
 
     def set_events(self, events, tmin: Optional[float] = None, tmax: Optional[float] = None, time_bin: int = 0,
-                   on_dropped: str = "warn"):
+                   on_dropped: str = "warn", weights=None):
         """Pack + sort one [n,4] batch (numpy or tensor, fp32/fp64).  (tmin, tmax): global batch
         extremes when this handle only holds a time slice of the batch (multi-GPU).
         on_dropped: what to do when events were NOT packed because their source pixel lies off the sensor (or is NaN) --
         the fused path indexes source tiles and the flow field with it; the reference's 2-DoF warp would still let such an
         event vote if it warps into a padded image, its dense warp indexes out of bounds there -- "warn" (log),
-        "raise" (a solver that must not diverge from the reference silently: ValueError) or "ignore"."""
+        "raise" (a solver that must not diverge from the reference silently: ValueError) or "ignore".
+        weights: optional [n] per-event weights (set_event_weights) -- the reference's `weight` of bilinear_vote_*."""
         if on_dropped not in ("warn", "raise", "ignore"):
             raise ValueError(f"on_dropped should be warn, raise or ignore. Got {on_dropped}.")
         ev = to_device_tensor(events, "events")
         if ev.dim() != 2 or ev.shape[1] != 4:
             raise ValueError(f"events must be [n, 4], got {tuple(ev.shape)}")
         ev = ev.contiguous()
+        w = prepare_event_weights(weights, ev.shape[0]) if weights is not None else None
         have = tmin is not None and tmax is not None
         check(self._lib.cmax_set_events(self._h, ev.data_ptr(), F._code(ev), ev.shape[0], int(have),
                                         float(tmin) if have else 0.0, float(tmax) if have else 0.0, int(time_bin),
                                         F._stream()))
         self.time_bin = int(time_bin)
         self.time_slabs = 0
+        self._n_in = int(ev.shape[0])
+        if w is not None:
+            check(self._lib.cmax_set_event_weights(self._h, w.data_ptr(), F._code(w), w.shape[0], F._stream()))
         info = self.batch_info() if on_dropped != "ignore" else {"dropped": 0, "outside": 0}
         dropped = info["dropped"]
         if info["outside"]:
@@ -151,6 +174,35 @@ class CMaxHandle:
             logger.warning(f"cmax_set_events dropped {dropped} of {ev.shape[0]} events: source pixel outside the "
                            f"{self.image_size[0]} x {self.image_size[1]} sensor (or NaN); the fused path cannot keep them")
         return self
+
+    def set_event_weights(self, weights):
+        """Per-event weights [n] of the CURRENT batch, in the order of the events handed to set_events (numpy or tensor, host or
+        device; cmax_set_event_weights) -- the `weight` argument of the reference's bilinear_vote_* / create_image_from_events_*
+        (src/event_image_converter.py:316-372).  None clears them.  evaluate / prepare / evaluate_host / evaluate_batch / iwe /
+        last_iwe and ContrastObjective then work on the weighted image; hvp, the raw and phase-split forms, evaluate_dist, comm_init,
+        patch plans, patch_search and deterministic mode raise NotImplementedError with the library's text.  The next set_events
+        starts unweighted; set_time_bins / set_time_slabs keep the weights."""
+        if weights is None:
+            check(self._lib.cmax_set_event_weights(self._h, None, 0, 0, F._stream()))
+            return self
+        w = prepare_event_weights(weights, getattr(self, "_n_in", 0))
+        check(self._lib.cmax_set_event_weights(self._h, w.data_ptr(), F._code(w), w.shape[0], F._stream()))
+        return self
+
+    def _batch_weighted(self):
+        flag, wmax = ctypes.c_int(0), ctypes.c_double(0.0)
+        check(self._lib.cmax_batch_weighted(self._h, ctypes.byref(flag), ctypes.byref(wmax)))
+        return bool(flag.value), wmax.value
+
+    @property
+    def weighted(self) -> bool:
+        """Whether the current batch carries per-event weights."""
+        return self._batch_weighted()[0]
+
+    @property
+    def weight_max(self) -> float:
+        """max |w| over the packed events of a weighted batch (the normalisation of the fixed-point votes); 0.0 when unweighted."""
+        return self._batch_weighted()[1]
 
     def batch_info(self) -> Dict[str, int]:
         """{"packed", "dropped", "fractional", "owned_groups", "outside"} of the last set_events (cmax_batch_info, cmax_batch_outside)."""
@@ -359,6 +411,9 @@ class CMaxHandle:
         hundred additions."""
         m, desc = self._motion_arg(desc, motion)
         if not self.has_raw(desc):
+            if self.weighted:  # what cmax_objective_raw itself answers on a weighted handle (CMAX_EUNSUPPORTED)
+                raise NotImplementedError("objective_raw: not built for a handle that holds per-event weights (cmax_set_event_weights); "
+                                          "set_event_weights(None) clears them")
             raise _lib.CmaxError(-1, "this objective has no raw form (2-DoF, default mode, non-empty batch; not a normalised plain variance)")
         raw = torch.empty((desc.n_ref, _lib.RAW_DOUBLES), dtype=torch.float64, device=self.device)
         host = torch.empty((desc.n_ref, _lib.RAW_DOUBLES), dtype=torch.float64).pin_memory()
@@ -547,6 +602,8 @@ class CMaxHandle:
         if "exc" in out:
             raise out["exc"]
         if out.get("rc", 0):
+            if out["rc"] == _lib.EUNSUPPORTED:  # refused in the handle's state (per-event weights), like `check` raises it
+                raise NotImplementedError((out.get("msg") or b"").decode("utf-8", "replace"))
             raise _lib.CmaxError(out["rc"], (out.get("msg") or b"").decode("utf-8", "replace"))
         self.rccl_path = path
         return self

@@ -70,6 +70,7 @@ __attribute__((visibility("hidden"))) int voxel_construct_adj_f64(const double *
 __attribute__((visibility("hidden"))) int voxel_construct_adj_tan_f64(const double *V, const double *dV, int Tn, int t0, int H, int W, int scheme,
                                                                    double *gV, double *dgV, hipStream_t s, bool det);
 __attribute__((visibility("hidden"))) bool handle_is_deterministic(cmax_handle_t h);
+__attribute__((visibility("hidden"))) bool handle_is_weighted(cmax_handle_t h);  // cmax_set_event_weights
 // time-sliced batches (cmax_fused.hip, for the patch plan): does the handle hold a communicator; cmax_objective_dist / the product
 // with the motion gradient left as this rank's share; in-place sum over the ranks on the handle's communicator (a no-op without one)
 __attribute__((visibility("hidden"))) bool handle_has_comm(cmax_handle_t h);

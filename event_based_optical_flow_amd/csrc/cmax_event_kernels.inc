@@ -166,6 +166,16 @@ __device__ __forceinline__ EvDec decode_slot(const EventLoads<L> &el, int u, flo
     return e;
 }
 
+// WEIGHTED instantiations of K1 / K3 (cmax_set_event_weights): the weights of a thread's slots.  The array is in packed order -- slot l of a
+// segment is sorted event first + l, for the plain and the compact event loads alike -- and padded with zeros behind the last event, so
+// the loads are unconditional; an empty slot's value is never used (rc == 0 / dt == 0 mask it).
+template <class L, bool STRIDED>
+__device__ __forceinline__ void load_slot_weights(const float *__restrict__ wgt, int4 sg, float (&fw)[L::kEPT]) {
+    const float *base = wgt + ((int64_t)sg.x - (sg.x & 1));
+#pragma unroll
+    for (int u = 0; u < L::kEPT; ++u) fw[u] = base[STRIDED ? 2 * ((u >> 1) * L::kThr + (int)threadIdx.x) + (u & 1) : L::kEPT * (int)threadIdx.x + u];
+}
+
 // One workgroup per segment: writes the segment's compact region (see EventLoads).
 template <class L>
 __global__ void __launch_bounds__(L::kThr) k_pack_compact(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, int ntc, char *__restrict__ cev, int *__restrict__ bad) {
@@ -571,7 +581,10 @@ __device__ __forceinline__ int fast_index(unsigned rc, unsigned neg_origin, int 
 // (second launch bound = waves per SIMD the register allocation has to leave room for: the 512 x 8 kernel of the big segments sat at 68
 // VGPRs -- seven waves -- once the border tracking joined its warp loop; scheduled for 64 it keeps eight: K1 of 20M events 46.2 -> see
 // profiles/r04_ablation.txt)
-template <class L, int MODEL, bool FRAC, bool MU = false>
+// WEIGHTED (cmax_set_event_weights): an event votes round(w / wmax * K) instead of K, split over its four cells from the row totals as
+// before (the four integers add up to it exactly); wmax is folded back in by the flush.  The window, the cells and the offsets
+// published for K3 do not depend on w.
+template <class L, int MODEL, bool FRAC, bool MU = false, bool WEIGHTED = false>
 __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra) {
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
@@ -583,6 +596,13 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
     ev.ev = evp;
     EventLoads<L> el;
     issue_event_loads<L, false>(evp, cev, sidx, sg, el);
+    static_assert(!(MU && WEIGHTED), "the vote sums of the blurred variance count events: weighted handles take the unfused image path");
+    float fw[L::kEPT];
+    float wscale = 0.f, inv_fix = L::kInvFixNS;  // K / wmax; 1 / K, weighted: wmax / K
+    if constexpr (WEIGHTED) {  // (the slot weights themselves are loaded behind the warp, below)
+        wscale = ra.wnorm[0] * L::kFixNS;
+        inv_fix = ra.wnorm[1] * L::kInvFixNS;
+    }
     wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = ra.d_lo[blockIdx.y];  // (read by warp_exact only: the compiler sinks this scalar load into that rare path)
     wp.motion += (int64_t)blockIdx.z * ra.z_motion;  // blockIdx.z = candidate motion (cmax_objective_batch; one candidate otherwise)
@@ -605,6 +625,10 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
         for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
     }, live, nibbles);
     CMAX_STAMP(0, 3);
+    // the weights of this thread's slots: loaded HERE, not with the events -- live through the warp they are kEPT more registers at the
+    // kernel's peak, and the b512 instantiations (eight events per thread under the 64-VGPR bound of kVoteWaves) spilled them to scratch;
+    // first used behind the barrier below, which hides the load
+    if constexpr (WEIGHTED) load_slot_weights<L, false>(ra.wgt, sg, fw);
     if (ra.grad_zero && blockIdx.y == 0 && blockIdx.z == 0) {  // launch-uniform: this workgroup's slice of the gradient buffer K3 will add into (write-through)
         const int64_t chunk4 = (ra.n_grad_zero4 + nseg - 1) / nseg, q1 = min(ra.n_grad_zero4, (int64_t)(sidx + 1) * chunk4);
         for (int64_t q = (int64_t)sidx * chunk4 + threadIdx.x; q < q1; q += L::kThr) store_zero4_sc1(reinterpret_cast<float *>(ra.grad_zero + q));
@@ -666,12 +690,18 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
 #pragma unroll
             for (int u = 0; u < L::kEPT; ++u) {
                 const float a = fa[u], b = fb[u];
-                const float ak = a * L::kFixNS, nak = L::kFixNS - ak;
+                float kf = L::kFixNS;
+                int ktot = (int)L::kFixNS;
+                if constexpr (WEIGHTED) {  // the event's whole vote, rounded once; its four shares below add up to it exactly
+                    ktot = cvt_rpi(fw[u] * wscale);
+                    kf = (float)ktot;
+                }
+                const float ak = a * kf, nak = kf - ak;
                 const int idx = fast_index(rc[u], neg_origin, win.stride, scratch);
                 // Round 6: the two weights of a ROW from the row's total -- r0 = rpi((1 - a) K), v1 = rpi((1 - a) b K), v0 = r0 - v1; the lower
                 // row from K - r0 -- three conversions and three integer subtractions where four products and four conversions were: the four
                 // weights of an event now add up to K EXACTLY (each within one unit, 2^-19 / 2^-20 of a vote, of its separately rounded value)
-                const int r0 = cvt_rpi(nak), r1 = (int)L::kFixNS - r0;
+                const int r0 = cvt_rpi(nak), r1 = ktot - r0;
                 const int v1 = cvt_rpi(nak * b), v0 = r0 - v1, v3 = cvt_rpi(ak * b), v2 = r1 - v3;
                 if (idx != cur) {
                     if (cur >= 0) {
@@ -722,12 +752,21 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
             const bool c_in0 = (unsigned)lc < (unsigned)win.w, c_in1 = (unsigned)(lc + 1) < (unsigned)win.w;
             const int base = lr * win.stride + lc;
             const int stride = win.stride;
-            atomicAdd(&s_win[(r_in0 && c_in0) ? base : dummy], (r_in0 && c_in0) ? __float2int_rn(na * nb * L::kFixNS) : 0);
-            atomicAdd(&s_win[(r_in1 && c_in0) ? base + stride : dummy], (r_in1 && c_in0) ? __float2int_rn(a * nb * L::kFixNS) : 0);
-            atomicAdd(&s_win[(r_in0 && c_in1) ? base + 1 : dummy], (r_in0 && c_in1) ? __float2int_rn(na * b * L::kFixNS) : 0);
-            atomicAdd(&s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy], (r_in1 && c_in1) ? __float2int_rn(a * b * L::kFixNS) : 0);
+            float kq = L::kFixNS, wq = 1.f;  // the event's vote in the window's fixed point / in the image's unit
+            if constexpr (WEIGHTED) {
+                kq = fw[u] * wscale;
+                wq = fw[u];
+            }
+            atomicAdd(&s_win[(r_in0 && c_in0) ? base : dummy], (r_in0 && c_in0) ? __float2int_rn(na * nb * kq) : 0);
+            atomicAdd(&s_win[(r_in1 && c_in0) ? base + stride : dummy], (r_in1 && c_in0) ? __float2int_rn(a * nb * kq) : 0);
+            atomicAdd(&s_win[(r_in0 && c_in1) ? base + 1 : dummy], (r_in0 && c_in1) ? __float2int_rn(na * b * kq) : 0);
+            atomicAdd(&s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy], (r_in1 && c_in1) ? __float2int_rn(a * b * kq) : 0);
             if (rc[u] == 0u) continue;
-            const float wv[4] = {na * nb, a * nb, na * b, a * b};
+            float wv[4] = {na * nb, a * nb, na * b, a * b};
+            if constexpr (WEIGHTED) {
+#pragma unroll
+                for (int q = 0; q < 4; ++q) wv[q] *= wq;
+            }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 const int r = row + (q & 1), c = col + (q >> 1);
@@ -804,7 +843,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
                 const int v = s_win[i];
                 if (v == 0) continue;
                 const unsigned r = mul24_u((unsigned)i, magic) >> 21;
-                atomic_add(&base[mad24_u(r, pitch_diff, (unsigned)i)], (float)v * L::kInvFixNS);
+                atomic_add(&base[mad24_u(r, pitch_diff, (unsigned)i)], (float)v * inv_fix);
             }
         } else {
             for (int i = threadIdx.x; i < wn; i += L::kThr) {
@@ -812,7 +851,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
                 if (v == 0) continue;
                 const unsigned r = mul24_u((unsigned)i, magic) >> 21, c = (unsigned)i - mul24_u(r, ustride);
                 const int R = win.r0 + (int)r, C = win.c0 + (int)c;
-                if ((unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) atomic_add(&iwe[pix_index(R, C, wp.Wp)], (float)v * L::kInvFixNS);
+                if ((unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) atomic_add(&iwe[pix_index(R, C, wp.Wp)], (float)v * inv_fix);
             }
         }
     } else if (win.w > 32) {
@@ -821,7 +860,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
             float *dst = iwe + (pix_index(win.r0 + r, 0, wp.Wp) + win.c0);
             for (int c = lane; c < win.w; c += kWave) {
                 const int v = s_win[r * win.stride + c];
-                if (v != 0 && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) atomic_add(&dst[c], (float)v * L::kInvFixNS);
+                if (v != 0 && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) atomic_add(&dst[c], (float)v * inv_fix);
             }
         }
     } else {  // narrow window: two rows per wave
@@ -829,7 +868,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
         for (int r = 2 * wave + half; r < win.h; r += 2 * L::kNW) {
             if (c < win.w && (unsigned)(win.r0 + r) < (unsigned)wp.Hp && (unsigned)(win.c0 + c) < (unsigned)wp.Wp) {
                 const int v = s_win[r * win.stride + c];
-                if (v != 0) atomic_add(&iwe[pix_index(win.r0 + r, win.c0 + c, wp.Wp)], (float)v * L::kInvFixNS);
+                if (v != 0) atomic_add(&iwe[pix_index(win.r0 + r, win.c0 + c, wp.Wp)], (float)v * inv_fix);
             }
         }
     }
@@ -1015,7 +1054,10 @@ __device__ __forceinline__ void stats_inside_role(const float *__restrict__ img,
 //                     groups (zeros included), coalesced 64-byte rows -- no atomics, and nobody has to clear the gradient
 //                     buffer first
 // ---------------------------------------------------------------------------------------------
-template <class L, int MODEL, bool FRAC, int FOLD, int VARIANT>
+//     WEIGHTED (cmax_set_event_weights): dt <- w dt per event -- every sum below is linear in dt, so the 2-DoF wave sums, the dense run
+//             reduction, the LDS accumulators and the block-scaled fixed point of the owned path (its scale is the workgroup's largest
+//             WEIGHTED term) all follow
+template <class L, int MODEL, bool FRAC, int FOLD, int VARIANT, bool WEIGHTED = false>
 __global__ void __launch_bounds__(L::kThr)
 k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base, int stat_blocks, EvView ev,
        WarpParams wp, RefArgs ra, ObjParams op, const double *__restrict__ stat, double *__restrict__ gpart_base, float *__restrict__ gflow,
@@ -1045,6 +1087,9 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     wp.motion += (int64_t)blockIdx.z * ra.z_motion;
     EventLoads<L> el;
     issue_event_loads<L, VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
+    static_assert(!WEIGHTED || (!kDet && !kInside && FOLD != kFoldDeferred), "weighted handles: the general K1 -> statistics -> K3 path");
+    float fw[L::kEPT];
+    if constexpr (WEIGHTED) load_slot_weights<L, VARIANT == kGradStrided>(ra.wgt, sg, fw);
     wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
     const int k = ra.k0 + (int)blockIdx.y;
     const float *__restrict__ img = ra.img[blockIdx.y] + blockIdx.z * ra.z_img;
@@ -1236,6 +1281,10 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     // per event: dt <- c2 dt (every sum below is linear in dt), and -- kFoldStats, windows that reach outside Omega only -- the mean's
     // share mu * bilinear-difference(1_Omega) of the gathered difference (zero wherever the four corners lie on one side of the mask)
     bool edge_mu = false;
+    if constexpr (WEIGHTED) {
+#pragma unroll
+        for (int j = 0; j < L::kEPT; ++j) fdt[j] *= fw[j];
+    }
     if (kStatsFold || FOLD == kFoldScale) {
         if (chain_from_stats && !kDet) {
             c2 = s_chain[0];

@@ -136,6 +136,10 @@ struct RefArgs {
     // launch of their own whose second job this was
     float4 *grad_zero;
     int64_t n_grad_zero4;
+    // weighted handles (cmax_set_event_weights; the WEIGHTED instantiations of K1 / K3 only): per-event weights in packed order and
+    // (1 / wmax, wmax) in device memory -- K1 votes round(w / wmax * K) and folds wmax back in when it flushes, K3 multiplies dt by w
+    const float *wgt;
+    const float *wnorm;
 };
 
 // the image-space kernels of an evaluation cover all reference times in one launch as well (blockIdx.y)
@@ -188,6 +192,15 @@ struct cmax_handle_s {
     float *rx = nullptr, *ry = nullptr;
     float2 *rl = nullptr;  // low parts of (rx, ry): written and read only for batches with fractional sources
     double *tau64 = nullptr;
+    int *src = nullptr, *src_alt = nullptr;  // index of every packed event in the caller's array, carried through every re-ordering
+    // per-event weights (cmax_set_event_weights): the caller's values in the caller's order, the same gathered into packed order (slot l of a
+    // segment reads w_packed[first + l]; padded with zeros so that the event kernels load unconditionally), and the normalisation
+    float *w_user = nullptr, *w_packed = nullptr;
+    int64_t w_user_cap = 0, w_packed_cap = 0;
+    float *d_wnorm = nullptr;  // [0] = 1 / wmax (0 when wmax == 0), [1] = wmax = max |w|, [2] = bits of wmax (reduction), [3] = non-finite flag
+    bool weighted = false;
+    double wmax_host = 0.0;
+    int64_t n_in = 0;          // events handed to the last cmax_set_events
     // staging SoA of the two-level sort (tile buckets before the per-tile ordering)
     uint2 *evp_alt = nullptr;
     float *rx_alt = nullptr, *ry_alt = nullptr;
@@ -1949,14 +1962,23 @@ static int layout_threads(Layout id) {
 }
 
 template <int MODEL>
-static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_ref, hipStream_t s, int nz = 1) {
+static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, hipStream_t s, int nz = 1) {
     const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref, nz);  // z: candidate motions of cmax_objective_batch
+    RefArgs ra = ra_in;
+    if (h->weighted) {  // every vote of a weighted handle is weighted: objective, cmax_iwe, the un-warped image
+        ra.wgt = h->w_packed;
+        ra.wnorm = h->d_wnorm;
+    }
     ProfScope prof(h, kProfVote, s);
     const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // 6-byte events, one region per segment
     for (int rep = 0; rep < h->prof_repeat; ++rep)
         with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
             using L = decltype(l);
             with_bool(h->has_frac, [&](auto frac) {
+                if (ra.wgt) {  // weighted handle (never with the vote sums: eval_plan)
+                    hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);
+                    return;
+                }
                 with_bool(ra.musum[0] != nullptr, [&](auto mu) {
                     hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);
                 });
@@ -1966,10 +1988,67 @@ static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
 
 // seg0 / seg_n: sub-range of the work list (a band of tile rows, see cmax_comm_set_c2_bands); seg_n < 0 = the whole list.  The
 // kernels only see a shifted list (RefArgs::win is shifted by the caller).
+// K3 of a weighted handle (cmax_set_event_weights): the same layouts and variants, the WEIGHTED instantiations, and only the folds of the
+// general path (eval_plan sends a weighted handle through K1 -> statistics -> K3; deterministic mode is refused)
+template <int MODEL>
+static void launch_grad_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, int fold,
+                                 const ObjParams &op, double *gpart, float *gflow, double *result, bool owned, hipStream_t s, int seg0,
+                                 int seg_n, int nz) {
+    const int4 *segs = h->d_segs + seg0;
+    const int nseg = seg_n < 0 ? h->nseg : seg_n;
+    const dim3 grid(8 * ((nseg + 7) / 8), n_ref, nz);
+    if (fold == kFoldDeferred || fold == kFoldStatsInside || h->deterministic) std::abort();  // (eval_plan never asks for these)
+    ProfScope prof(h, kProfGrad, s);
+    RefArgs ra = ra_in;
+    ra.wgt = h->w_packed;
+    ra.wnorm = h->d_wnorm;
+    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
+    auto launch = [&](auto l, auto frac, auto fold_c, auto variant) {
+        using L = decltype(l);
+        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, true>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev, cev,
+                           (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
+    };
+    const bool strided = MODEL == CMAX_MODEL_DENSE && !(h->long_runs && h->n_time_bin == 0);
+    const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big;
+    auto body = [&](auto l) {
+        using L = decltype(l);
+        auto with_variant = [&](auto frac, auto fold_c) {
+            if constexpr (MODEL == CMAX_MODEL_DENSE) {
+                if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{});
+                else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{});
+                else launch(l, frac, fold_c, int_c<kGradRuns>{});
+            } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
+                if (owned && small) {
+                    if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{});
+                } else if (owned) {
+                    launch(l, frac, fold_c, int_c<kGradOwned>{});
+                } else {
+                    launch(l, frac, fold_c, int_c<kGradRuns>{});
+                }
+            } else {
+                launch(l, frac, fold_c, int_c<kGradRuns>{});
+            }
+        };
+        with_bool(h->has_frac, [&](auto frac) {
+            if (fold == kFoldStats) with_variant(frac, int_c<kFoldStats>{});
+            else if (fold == kFoldScale) with_variant(frac, int_c<kFoldScale>{});
+            else with_variant(frac, int_c<kFoldNone>{});
+        });
+    };
+    for (int rep = 0; rep < h->prof_repeat; ++rep) {
+        if constexpr (MODEL == CMAX_MODEL_VOXEL) with_layout<b1024, m512, t512, t1024, t256>(grad_layout(h, MODEL, owned), body);
+        else with_layout<b512, m512, t512, t256>(grad_layout(h, MODEL, owned), body);
+    }
+}
+
 template <int MODEL>
 static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_ref, int fold,
                         const ObjParams &op, double *gpart, float *gflow, double *result, bool owned, hipStream_t s, int seg0 = 0,
                         int seg_n = -1, int nz = 1) {
+    if (h->weighted) {
+        launch_grad_weighted<MODEL>(h, ev, wp, ra, n_ref, fold, op, gpart, gflow, result, owned, s, seg0, seg_n, nz);
+        return;
+    }
     const int4 *segs = h->d_segs + seg0;
     const int nseg = seg_n < 0 ? h->nseg : seg_n;
     const dim3 grid(8 * ((nseg + 7) / 8) + (fold == kFoldStatsInside ? ra.stat_blocks : 0), n_ref, nz);
@@ -2520,17 +2599,19 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
         dev_free(&h->ry_alt);
         dev_free(&h->rl_alt);
         dev_free(&h->tau64_alt);
+        dev_free(&h->src_alt);
         int rc = dev_alloc(h, &h->evp_alt, h->cap + 2);
         if (!rc) rc = dev_alloc(h, &h->rx_alt, h->cap);
         if (!rc) rc = dev_alloc(h, &h->ry_alt, h->cap);
         if (!rc) rc = dev_alloc(h, &h->rl_alt, h->cap);
         if (!rc) rc = dev_alloc(h, &h->tau64_alt, h->cap);
+        if (!rc) rc = dev_alloc(h, &h->src_alt, h->cap);
         if (rc) return rc;
         h->cap_alt = h->cap;
     }
 
-    SortOut stage = {h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt};
-    SortOut fin = {h->evp, h->rx, h->ry, h->rl, h->tau64};
+    SortOut stage = {h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt, h->src_alt};
+    SortOut fin = {h->evp, h->rx, h->ry, h->rl, h->tau64, h->src};
     unsigned long long *keys = reduce_time ? reinterpret_cast<unsigned long long *>(h->d_tmm) : nullptr;
     // Large batches: the STABLE radix sort (cmax_radix_sort.h) -- every pass streams, the events of a pixel come out by time without
     // k_run_time_sort, and the packed order is a function of the batch alone.  Small ones (a few launches fewer) keep the counting sort.
@@ -2593,6 +2674,7 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
             std::swap(h->ry, h->ry_alt);
             std::swap(h->rl, h->rl_alt);
             std::swap(h->tau64, h->tau64_alt);
+            std::swap(h->src, h->src_alt);
             std::swap(stage, fin);
         }
         // the number of packed events (every pass's scan writes it again): where the other pipeline keeps its total, outside the histogram
@@ -2633,6 +2715,7 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
         std::swap(h->ry, h->ry_alt);
         std::swap(h->rl, h->rl_alt);
         std::swap(h->tau64, h->tau64_alt);
+        std::swap(h->src, h->src_alt);
     }
     static const bool run_sort = !getenv("CMAX_NO_RUN_SORT");
     BatchReadback rb;
@@ -2648,12 +2731,76 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
             std::swap(h->ry, h->ry_alt);
             std::swap(h->rl, h->rl_alt);
             std::swap(h->tau64, h->tau64_alt);
+            std::swap(h->src, h->src_alt);
         }
         return 0;
     });
 }
 
 bool handle_is_deterministic(cmax_handle_t h) { return h && h->deterministic; }
+bool handle_is_weighted(cmax_handle_t h) { return h && h->weighted; }
+
+// ---- per-event weights (cmax_set_event_weights) -------------------------------------------------------------------------------
+// W1: the caller's weights as fp32 in the caller's order (kept: a re-ordering of the batch gathers from them again); flags[3] != 0 if
+// one of them is not finite.
+template <typename T>
+__global__ void __launch_bounds__(256) k_weights_keep(const T *__restrict__ w, int64_t n, float *__restrict__ w_user, unsigned *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    const float v = (float)w[i];
+    w_user[i] = v;
+    if (!(fabsf(v) <= 3.4028234e38f)) atomicOr(&flags[3], 1u);
+}
+// W2: packed order (slot l of a segment reads w_packed[first + l]) through the source index the sort carried, zeros in the padding behind
+// the last event, and max |w| over the PACKED events (a dropped event drops its weight) as the bits of a non-negative float in flags[2].
+__global__ void __launch_bounds__(256) k_weights_gather(const float *__restrict__ w_user, const int *__restrict__ src, int64_t n, int64_t n_pad,
+                                                        float *__restrict__ w_packed, unsigned *__restrict__ flags) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    float v = 0.f;
+    if (i < n) v = w_user[src[i]];
+    if (i < n_pad) w_packed[i] = v;
+    float m = fabsf(v);
+    if (!(m <= 3.4028234e38f)) m = 0.f;  // (non-finite values are reported by k_weights_keep)
+#pragma unroll
+    for (int o = kWave / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, kWave));
+    if ((threadIdx.x & (kWave - 1)) == 0 && m > 0.f) atomicMax(&flags[2], __float_as_uint(m));
+}
+// W3: (1 / wmax, wmax) for the event kernels -- plain stores of one thread
+__global__ void k_weights_norm(float *__restrict__ wnorm) {
+    const float wmax = __uint_as_float(reinterpret_cast<const unsigned *>(wnorm)[2]);
+    wnorm[0] = wmax > 0.f ? 1.f / wmax : 0.f;
+    wnorm[1] = wmax;
+}
+constexpr int64_t kWeightPad = 4096 + 16;  // an event kernel's unconditional loads reach at most one segment's slots behind the last event
+
+// the packed-order copy of the kept weights for the CURRENT order of the batch (after cmax_set_event_weights and after every re-ordering)
+static int gather_weights(cmax_handle_s *h, hipStream_t s) {
+    const int64_t n_pad = h->n + kWeightPad;
+    if (n_pad > h->w_packed_cap) {
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(&h->w_packed);
+        h->w_packed_cap = 0;
+        int rc = dev_alloc(h, &h->w_packed, n_pad);
+        if (rc) return rc;
+        h->w_packed_cap = n_pad;
+    }
+    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm);
+    CMAX_CHECK_HIP(hipMemsetAsync(flags + 2, 0, sizeof(unsigned), s));
+    hipLaunchKernelGGL(k_weights_gather, dim3(div_up(n_pad, 256)), dim3(256), 0, s, (const float *)h->w_user, (const int *)h->src, h->n, n_pad, h->w_packed, flags);
+    hipLaunchKernelGGL(k_weights_norm, dim3(1), dim3(1), 0, s, h->d_wnorm);
+    CMAX_CHECK_LAUNCH();
+    h->orig_valid = false;  // the un-warped image is weighted too
+    h->win_generation = ~(uint64_t)0;
+    return 0;
+}
+
+#define CMAX_REFUSE_WEIGHTED(h, what)                                                                                                 \
+    do {                                                                                                                              \
+        if ((h) && (h)->weighted) {                                                                                                   \
+            ::cmax::set_error("%s: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them", what); \
+            return CMAX_EUNSUPPORTED;                                                                                                 \
+        }                                                                                                                             \
+    } while (0)
 
 void handle_get_eval_state(cmax_handle_t h, HandleEvalState *out) {
     out->cur_buf = h->cur_buf;
@@ -2816,6 +2963,11 @@ int cmax_destroy(cmax_handle_t h) {
     dev_free(&h->ry);
     dev_free(&h->rl);
     dev_free(&h->tau64);
+    dev_free(&h->src);
+    dev_free(&h->src_alt);
+    dev_free(&h->w_user);
+    dev_free(&h->w_packed);
+    dev_free(&h->d_wnorm);
     dev_free(&h->cev);
     dev_free(&h->evp_alt);
     dev_free(&h->rx_alt);
@@ -2839,6 +2991,9 @@ int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, i
     h->n = 0;
     h->n_dropped = 0;
     h->n_outside = 0;
+    h->weighted = false;  // weights belong to a batch (like time slabs)
+    h->wmax_host = 0.0;
+    h->n_in = n;
     ++h->generation;
     h->generation_counted = ~(uint64_t)0;
     if (n > h->cap) {
@@ -2849,11 +3004,13 @@ int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, i
         dev_free(&h->ry);
         dev_free(&h->rl);
         dev_free(&h->tau64);
+        dev_free(&h->src);
         int rc = dev_alloc(h, &h->evp, n + 2);  // +2: the vector loads may touch one event past the end
         if (!rc) rc = dev_alloc(h, &h->rx, n);
         if (!rc) rc = dev_alloc(h, &h->ry, n);
         if (!rc) rc = dev_alloc(h, &h->rl, n);
         if (!rc) rc = dev_alloc(h, &h->tau64, n);
+        if (!rc) rc = dev_alloc(h, &h->src, n);
         if (rc) return rc;
         h->cap = n;
         dev_free(&h->evp_alt);  // the staging SoA follows (sort_events)
@@ -2861,6 +3018,7 @@ int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, i
         dev_free(&h->ry_alt);
         dev_free(&h->rl_alt);
         dev_free(&h->tau64_alt);
+        dev_free(&h->src_alt);
         h->cap_alt = 0;
     }
     // global time extremes: given (a time slice of a larger batch), or reduced by the first sort kernel
@@ -2906,7 +3064,9 @@ int cmax_set_time_bins(cmax_handle_t h, int n_time_bin, cmax_stream_t stream) {
     if (h->n == 0) return 0;
     hipStream_t s = (hipStream_t)stream;
     // re-order the packed events in place (through the staging SoA); [0] "fractional sources" stays what it was
-    return sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0}, h->n, false, 1, s);
+    int rc = sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0, h->src}, h->n, false, 1, s);
+    if (!rc && h->weighted) rc = gather_weights(h, s);  // the weights follow the new order
+    return rc;
 }
 
 int cmax_set_time_slabs(cmax_handle_t h, int n_slab, cmax_stream_t stream) {
@@ -2919,7 +3079,81 @@ int cmax_set_time_slabs(cmax_handle_t h, int n_slab, cmax_stream_t stream) {
     h->slab_major = n_slab > 0;
     bump_generation_keep_counts(h);
     if (h->n == 0) return 0;
-    return sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0}, h->n, false, 1, (hipStream_t)stream);
+    int rc = sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0, h->src}, h->n, false, 1, (hipStream_t)stream);
+    if (!rc && h->weighted) rc = gather_weights(h, (hipStream_t)stream);
+    return rc;
+}
+
+int cmax_set_event_weights(cmax_handle_t h, const void *weights, int dtype, int64_t n, cmax_stream_t stream) {
+    CMAX_REQUIRE(h != nullptr, "set_event_weights: handle");
+    hipStream_t s = (hipStream_t)stream;
+    if (weights == nullptr) {  // back to the unweighted state: the kernels, instantiations and numbers of a handle that never had weights
+        if (h->weighted) {
+            h->weighted = false;
+            h->wmax_host = 0.0;
+            h->orig_valid = false;
+            h->win_generation = ~(uint64_t)0;
+            bump_generation_keep_counts(h);  // launch sequences captured in the other state (patch plans) are dropped
+        }
+        return 0;
+    }
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "set_event_weights: dtype");
+    CMAX_REQUIRE(n == h->n_in, "set_event_weights: n must equal the n of the last cmax_set_events (one weight per event, in the caller's order)");
+    if (h->deterministic) {
+        set_error("set_event_weights: not built for deterministic mode (cmax_set_deterministic)");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (h->comm) {
+        set_error("set_event_weights: not built for a handle with a communicator (cmax_comm_init)");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (n == 0) {
+        h->weighted = true;
+        h->wmax_host = 0.0;
+        return 0;
+    }
+    if (!h->d_wnorm) {
+        int rc = dev_alloc(h, &h->d_wnorm, 4);
+        if (rc) return rc;
+    }
+    if (n > h->w_user_cap) {
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(&h->w_user);
+        h->w_user_cap = 0;
+        int rc = dev_alloc(h, &h->w_user, n);
+        if (rc) return rc;
+        h->w_user_cap = n;
+    }
+    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm);
+    CMAX_CHECK_HIP(hipMemsetAsync(h->d_wnorm, 0, 4 * sizeof(float), s));
+    if (dtype == CMAX_F32) hipLaunchKernelGGL((k_weights_keep<float>), dim3(div_up(n, 256)), dim3(256), 0, s, (const float *)weights, n, h->w_user, flags);
+    else hipLaunchKernelGGL((k_weights_keep<double>), dim3(div_up(n, 256)), dim3(256), 0, s, (const double *)weights, n, h->w_user, flags);
+    CMAX_CHECK_LAUNCH();
+    int rc = gather_weights(h, s);
+    if (rc) return rc;
+    // blocks once, like cmax_set_events: the non-finite flag and wmax for cmax_batch_weighted
+    float host[4];
+    CMAX_CHECK_HIP(hipMemcpyAsync(host, h->d_wnorm, sizeof(host), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    unsigned bad;
+    std::memcpy(&bad, &host[3], sizeof(bad));
+    if (bad) {
+        h->weighted = false;
+        h->wmax_host = 0.0;
+        set_error("set_event_weights: weights must be finite in fp32, the format they are kept in (|w| <= 3.4e38; the handle is unweighted now)");
+        return CMAX_EINVAL;
+    }
+    h->weighted = true;
+    h->wmax_host = (double)host[1];
+    bump_generation_keep_counts(h);
+    return 0;
+}
+
+int cmax_batch_weighted(cmax_handle_t h, int *weighted, double *wmax_host) {
+    CMAX_REQUIRE(h != nullptr, "batch_weighted: handle");
+    if (weighted) *weighted = h->weighted ? 1 : 0;
+    if (wmax_host) *wmax_host = h->weighted ? h->wmax_host : 0.0;
+    return 0;
 }
 
 int cmax_iwe(cmax_handle_t h, int model, const float *motion, int T, int ref_mode, double ref_frac, int normalize_t,
@@ -2993,7 +3227,8 @@ static int publish_windows(cmax_handle_s *h, const cmax_objective_t *d, const fl
 // 2-DoF + plain variance with a gradient: K3 gathers the image statistics itself and k_finish_raw applies
 // the chain factors -- no K2 launch (unless a workgroup's slice of the image would get long)
 static bool deferred_applies(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad) {
-    return !h->deterministic && grad && d->model == CMAX_MODEL_2DOF && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && h->n > 0 &&
+    // (a weighted handle takes the general K1 -> statistics -> K3 path: the raw sums' indicator image and sum I are not carried)
+    return !h->deterministic && !h->weighted && grad && d->model == CMAX_MODEL_2DOF && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && h->n > 0 &&
            (int64_t)h->Hp * h->Wp <= (int64_t)h->nseg * 8192;
 }
 
@@ -3087,7 +3322,7 @@ static int c2_exchange_all_bands(cmax_handle_s *h, cmax::Comm *c2_comm, float *g
 // the whole batch's three images and finishes loss and gradient on its own.
 // force: CMAX_TAN2 (1 = also on one GPU, 0 = never, -1 = unset)
 static bool tan2_applicable(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool dist, int force) {
-    if (force == 0 || h->deterministic || !grad) return false;
+    if (force == 0 || h->deterministic || h->weighted || !grad) return false;
     if (d->model != CMAX_MODEL_2DOF || d->cost != CMAX_COST_VARIANCE || d->sigma > 0) return false;
     // Rank-consistent scalars: behind the single exchange every rank finishes loss AND gradient on its own -- from the reduced planes in a
     // fixed order (per-workgroup partials, one folding wave: bit-identical on every rank), but a NORMALISED variance also reads the
@@ -3164,7 +3399,8 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.raw = p.lines ? (raw_out ? raw_out : h->d_raw) : nullptr;
     p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
     p.blur_var = !det && d->cost == CMAX_COST_VARIANCE && d->sigma > 0;
-    const bool k1_sums_ok = whole && !dist && h->Hp >= 4 && h->Wp >= 4;  // K1 can sum its votes for the kernels behind it
+    // K1 can sum its votes for the kernels behind it (not on a weighted handle: the sum counts events)
+    const bool k1_sums_ok = whole && !dist && !h->weighted && h->Hp >= 4 && h->Wp >= 4;
     p.fused_bv = k1_sums_ok && p.blur_var && grad && h->n > 0 && !no_fused_bv;
     // K3 stores every element of the flow gradient itself (one writer per pixel): needs the group-aligned work list, ONE reference
     // time (several would add into the same pixels) and the sort order that matches the model (dense: tiles; voxel: (tile, bin) of
@@ -3250,6 +3486,7 @@ static int objective_vote(cmax_handle_t h, const cmax_objective_t *d, const floa
 
 int cmax_objective_vote(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, float *images, int *n_images_host,
                         cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_vote");
     const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -3530,6 +3767,7 @@ static int objective_finish(cmax_handle_t h, const cmax_objective_t *d, const Ev
 
 int cmax_objective_finish(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, const float *images, int n_images,
                           double *result, void *grad, cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_finish");
     const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -3660,6 +3898,7 @@ int cmax_objective(cmax_handle_t h, const cmax_objective_t *d, const void *motio
 
 int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad,
                         cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_dist");
     const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -3746,13 +3985,14 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
 }
 
 int cmax_objective_has_raw(cmax_handle_t h, const cmax_objective_t *d) {
-    if (!h || !d) return 0;
+    if (!h || !d || h->weighted) return 0;  // (the raw form is not carried for per-event weights)
     if (!two_dof_lines(h, d, (const void *)h)) return 0;
     // (a NORMALISED plain variance runs the deferred K3, whose fold needs the un-warped image's statistics from the device)
     return deferred_applies(h, d, (const void *)h) && d->normalized ? 0 : 1;
 }
 
 int cmax_objective_raw(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *raw, cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_raw");
     const float *motion = static_cast<const float *>(motion_v);
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -3881,6 +4121,7 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
 
 int cmax_set_deterministic(cmax_handle_t h, int enable) {
     CMAX_REQUIRE(h != nullptr, "set_deterministic: handle");
+    if (enable) CMAX_REFUSE_WEIGHTED(h, "set_deterministic");
     if (enable) {  // each buffer on its own: a failed allocation must not leave a later call believing everything is there
         const int64_t npix = (int64_t)h->Hp * h->Wp;
         if (!h->img64) {
@@ -3926,6 +4167,7 @@ int cmax_comm_unique_id(void *id_host) {
 }
 
 int cmax_comm_init(cmax_handle_t h, const void *id_host, int nranks, int rank) {
+    CMAX_REFUSE_WEIGHTED(h, "comm_init");
     CMAX_REQUIRE(h != nullptr, "comm_init: handle");
     CMAX_REQUIRE(nranks >= 1 && rank >= 0 && rank < nranks, "comm_init: need 0 <= rank < nranks");
     if (h->comm) {
@@ -4180,6 +4422,7 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
 
 int cmax_objective_hvp(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, const float *tangent, void *hv,
                        cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_hvp");
     const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -4189,6 +4432,7 @@ int cmax_objective_hvp(cmax_handle_t h, const cmax_objective_t *d, const void *m
 
 int cmax_objective_hvp_dist(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, const float *tangent, void *hv,
                             cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "objective_hvp_dist");
     const float *motion = static_cast<const float *>(motion_v);
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
@@ -4204,11 +4448,13 @@ int cmax_objective_hvp_dist(cmax_handle_t h, const cmax_objective_t *d, const vo
 namespace cmax {
 bool handle_has_comm(cmax_handle_t h) { return h && h->comm != nullptr; }
 int objective_dist_local_grad(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s) {
+    CMAX_REFUSE_WEIGHTED(h, "patch plan evaluation");
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     return objective_eval(h, d, motion, result, grad, s, h->comm, nullptr, nullptr, 0, true);
 }
 int objective_hvp_dist_local(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *tangent, void *hv, hipStream_t s) {
+    CMAX_REFUSE_WEIGHTED(h, "patch plan product");
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     return objective_hvp_impl(h, d, motion, tangent, hv, s, h->comm, false);
@@ -4296,6 +4542,7 @@ int cmax_copy_iwe(cmax_handle_t h, int k, float *iwe_out, cmax_stream_t stream) 
 
 int cmax_patch_search(cmax_handle_t h, int n_patch, const int *boxes, int img_h, int img_w, int n_cand, const float *cand,
                       double sigma, float *gm_out, int *count_out, cmax_stream_t stream) {
+    CMAX_REFUSE_WEIGHTED(h, "patch_search");
     CMAX_REQUIRE(h && boxes && gm_out && count_out, "patch_search: null argument");
     CMAX_REQUIRE(n_patch > 0 && n_cand >= 0 && (n_cand == 0 || cand), "patch_search: n_patch > 0, n_cand >= 0");
     CMAX_REQUIRE(img_h > 0 && img_w > 0 && sigma >= 0.0, "patch_search: patch image size / sigma");

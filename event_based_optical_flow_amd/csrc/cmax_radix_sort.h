@@ -61,6 +61,7 @@ struct RsItem {
     double tau;
     float rx, ry;
     float2 rl;
+    int src;
 };
 __device__ __forceinline__ RsItem rs_pack(const SortItem &it, int T) {
     RsItem r;
@@ -71,6 +72,7 @@ __device__ __forceinline__ RsItem rs_pack(const SortItem &it, int T) {
     r.rx = it.rx;
     r.ry = it.ry;
     r.rl = make_float2(it.rxl, it.ryl);
+    r.src = it.src;
     return r;
 }
 
@@ -244,6 +246,7 @@ __device__ __forceinline__ void rs_store(const SortOut &out, int64_t pos, const 
         out.rl[pos] = it.rl;
     }
     out.tau64[pos] = it.tau;
+    out.src[pos] = it.src;
 }
 
 // R3, pass 0: pack + scatter by the first digit.  base [D][nwg] = exclusive scan of R1's histogram.  Dynamic LDS: D ints + D 64-bit words.
@@ -318,6 +321,7 @@ k_rs_scatter(SortOut in, const int *__restrict__ total, int64_t range, RsKey key
             const int64_t j = i < r1 ? i : r1 - 1;  // (unconditional loads at a clamped index: all in flight at once)
             nxt[u].e = in.evp[j];
             nxt[u].tau = in.tau64[j];
+            nxt[u].src = in.src[j];
             if (frac) {
                 nxt[u].rx = in.rx[j];
                 nxt[u].ry = in.ry[j];

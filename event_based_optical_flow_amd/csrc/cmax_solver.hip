@@ -824,6 +824,10 @@ int cmax_sizeof_patch_objective(void) { return (int)sizeof(cmax_patch_objective_
 
 int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, cmax_patch_plan_t *out) {
     CMAX_REQUIRE(h && desc && out, "patch_plan_create: null pointer");
+    if (handle_is_weighted(h)) {
+        set_error("patch_plan_create: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
     const cmax_patch_objective_t &d = *desc;
     CMAX_REQUIRE(d.n_terms >= 1 && d.n_terms <= 4, "patch_plan_create: n_terms");
     CMAX_REQUIRE(d.H > 0 && d.W > 0 && d.ph > 0 && d.pw > 0 && d.sw_h > 0 && d.sw_w > 0 && d.pad_h >= 0 && d.pad_w >= 0, "patch_plan_create: sizes");
@@ -924,6 +928,10 @@ int cmax_patch_plan_destroy(cmax_patch_plan_t p) {
 int cmax_patch_plan_evaluate(cmax_patch_plan_t p, const double *x_host, int with_tv, double *loss_host, double *grad_host,
                              cmax_stream_t stream) {
     CMAX_REQUIRE(p && x_host && loss_host, "patch_plan_evaluate: null pointer");
+    if (handle_is_weighted(p->handle)) {  // (a plan made before the handle received weights: refused like cmax_patch_plan_create)
+        set_error("patch_plan_evaluate: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
     const bool tv = with_tv && p->d.tv_weight != 0.0;
     std::memcpy(p->h_in, x_host, (size_t)p->nx * sizeof(double));
     const int kind = (tv ? 1 : 0) | (grad_host ? 2 : 0);
@@ -936,6 +944,10 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t p, const double *x_host, int with
 
 int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double *v_host, double *hv_host, cmax_stream_t stream) {
     CMAX_REQUIRE(p && x_host && v_host && hv_host, "patch_plan_hvp: null pointer");
+    if (handle_is_weighted(p->handle)) {
+        set_error("patch_plan_hvp: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
     const cmax_patch_objective_t &d = p->d;
     if (d.time_aware && !p->dvox64) {  // second-order buffers of the voxel chain, on first use
         int rc = plan_alloc(&p->dflow64, p->nflow);

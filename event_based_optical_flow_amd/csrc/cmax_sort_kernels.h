@@ -79,6 +79,7 @@ struct SortItem {
     float rxl, ryl; // ... and what fp32 could not hold of them: residual = (double)rx + (double)rxl to 2^-48 (round 5: the cells of events
                     // on a cell border are decided from the source coordinate the reference's fp64 arithmetic sees, warp_exact)
     double tn;      // time normalised to the batch
+    int src;        // index of the event in the caller's array (carried through every re-ordering: cmax_set_event_weights gathers by it)
     bool frac;
     bool outside;   // kept although off the sensor (RawSource::keep_outside): (ix, iy) is the NEAREST sensor pixel, (rx, ry) the rest
 };
@@ -121,8 +122,9 @@ struct RawSource {
         T x, y, t;
     };
     __device__ __forceinline__ Fetched fetch(int64_t i) const { return Fetched{ev[4 * i + 0], ev[4 * i + 1], ev[4 * i + 2]}; }
-    __device__ __forceinline__ SortItem resolve(const Fetched &f, int64_t) const {
+    __device__ __forceinline__ SortItem resolve(const Fetched &f, int64_t i) const {
         SortItem it = classify(f.x, f.y);
+        it.src = (int)i;
         if (it.ix >= 0) {
             const double rxd = (double)f.x - (double)it.ix, ryd = (double)f.y - (double)it.iy;
             it.rx = (float)rxd;
@@ -143,6 +145,7 @@ struct RawSource {
     __device__ __forceinline__ SortItem full(int64_t i) const {
         const T x = ev[4 * i + 0], y = ev[4 * i + 1];
         SortItem it = classify(x, y);
+        it.src = (int)i;
         if (it.ix >= 0) {
             const double rxd = (double)x - (double)it.ix, ryd = (double)y - (double)it.iy;  // exact (on the sensor: ix = floor(x))
             it.rx = (float)rxd;
@@ -169,6 +172,7 @@ struct PackedSource {
     const float2 *rl;      // (rxl, ryl), likewise
     const double *tau64;
     int has_frac;
+    const int *src;        // source index of every packed event (SortItem::src)
     __device__ __forceinline__ bool reduces_time() const { return false; }
     __device__ __forceinline__ double time(int64_t) const { return 0.0; }
     __device__ __forceinline__ SortItem pixel(int64_t i) const {
@@ -185,6 +189,7 @@ struct PackedSource {
         float rx, ry;
         float2 lo;
         double tn;
+        int src;
     };
     __device__ __forceinline__ Fetched fetch(int64_t i) const {
         Fetched f;
@@ -193,6 +198,7 @@ struct PackedSource {
         f.ry = has_frac ? ry[i] : 0.f;
         f.lo = has_frac ? rl[i] : make_float2(0.f, 0.f);
         f.tn = tau64[i];
+        f.src = src[i];
         return f;
     }
     __device__ __forceinline__ SortItem resolve(const Fetched &f, int64_t) const {
@@ -206,6 +212,7 @@ struct PackedSource {
         it.rxl = f.lo.x;
         it.ryl = f.lo.y;
         it.tn = f.tn;
+        it.src = f.src;
         return it;
     }
     __device__ __forceinline__ SortItem full(int64_t i) const {
@@ -216,6 +223,7 @@ struct PackedSource {
         it.rxl = lo.x;
         it.ryl = lo.y;
         it.tn = tau64[i];
+        it.src = src[i];
         return it;
     }
 };
@@ -225,6 +233,7 @@ struct SortOut {
     float *rx, *ry;
     float2 *rl;  // (rxl, ryl): low parts of the fractional residuals (SortItem)
     double *tau64;
+    int *src;    // source index (SortItem::src)
 };
 
 // S0.  Everything the sort accumulates into, cleared by one launch (four hipMemsetAsync nodes cost ~3 us each):
@@ -366,6 +375,7 @@ k_bucket_scatter(SRC src, int64_t n, int ntc, int ntiles, int T, const int *__re
             out.rl[pos] = make_float2(it.rxl, it.ryl);
         }
         out.tau64[pos] = it.tn;
+        out.src[pos] = it.src;
     }
 }
 
@@ -461,6 +471,7 @@ k_tile_sort(int ntiles, int T, const int *__restrict__ tile_off, SortOut in, Sor
             }
         }
         const double ta = in.tau64[i0], tb = two ? in.tau64[i0 + 1] : 0.0;
+        const int sa = in.src[i0], sb = two ? in.src[i0 + 1] : 0;
         const int pa = b + atomicAdd(&s_cnt[sub_key(ea.x)], 1);
         out.evp[pa] = ea;
         if (frac) {
@@ -469,6 +480,7 @@ k_tile_sort(int ntiles, int T, const int *__restrict__ tile_off, SortOut in, Sor
             out.rl[pa] = rla;
         }
         out.tau64[pa] = ta;
+        out.src[pa] = sa;
         if (two) {
             const int pb = b + atomicAdd(&s_cnt[sub_key(eb.x)], 1);
             out.evp[pb] = eb;
@@ -478,6 +490,7 @@ k_tile_sort(int ntiles, int T, const int *__restrict__ tile_off, SortOut in, Sor
                 out.rl[pb] = rlb;
             }
             out.tau64[pb] = tb;
+            out.src[pb] = sb;
         }
     }
 }
@@ -525,6 +538,7 @@ __global__ void __launch_bounds__(256) k_slab_regroup(const int *__restrict__ ol
     for (int i = threadIdx.x; i < n; i += 256) {
         out.evp[d + i] = in.evp[b + i];
         out.tau64[d + i] = in.tau64[b + i];
+        out.src[d + i] = in.src[b + i];
         if (frac) {
             out.rx[d + i] = in.rx[b + i];
             out.ry[d + i] = in.ry[b + i];
@@ -655,6 +669,7 @@ __global__ void __launch_bounds__(256) k_run_time_sort(SortOut in, SortOut out, 
             out.rl[pos] = in.rl[i];
         }
         out.tau64[pos] = in.tau64[i];
+        out.src[pos] = in.src[i];
     }
 }
 

@@ -45,3 +45,16 @@ def generate_structured_events(n_events: int, height: int, width: int, velocity:
     ev[:, 2] = t
     ev[:, 3] = rng.integers(0, 2, n_events)
     return ev
+
+
+def polarity_weights(events):
+    """Per-event weights +1 / -1 from the polarity column of [n, 4] events (numpy or tensor): +1 where `events[:, 3] > 0`, -1 elsewhere --
+    the sign split the reference's "polarity" image makes (src/event_image_converter.py:110).  Same kind and dtype as `events`; pass it
+    as `weights=` to CMaxHandle.set_events for a polarity-signed contrast."""
+    pos = events[:, 3] > 0
+    if isinstance(events, np.ndarray):
+        return np.where(pos, 1.0, -1.0).astype(events.dtype if events.dtype.kind == "f" else np.float64)
+    import torch
+
+    one = torch.ones((), dtype=events.dtype if events.dtype.is_floating_point else torch.float64, device=events.device)
+    return torch.where(pos, one, -one)

@@ -59,6 +59,7 @@ extern "C" {
 #define CMAX_ESTATE -3   /* call order (e.g. objective before set_events) */
 #define CMAX_ENODEV -4   /* no usable gfx950 device / RCCL not loadable */
 #define CMAX_ECOMM -5    /* an RCCL call failed (message in cmax_last_error) */
+#define CMAX_EUNSUPPORTED -6 /* the call is not built for the state of the handle (e.g. per-event weights; message in cmax_last_error) */
 
 typedef void *cmax_stream_t; /* hipStream_t */
 typedef struct cmax_handle_s *cmax_handle_t;
@@ -191,8 +192,10 @@ int cmax_destroy(cmax_handle_t h);
  * the sensor (or NaN) are dropped.  If have_tminmax, (tmin, tmax) are the GLOBAL batch extremes
  * (multi-GPU time slices); otherwise they are reduced from this call's events (all of them) on the
  * device.  n_time_bin > 0 precomputes the voxel bin of every event with the reference's fp64 edge
- * arithmetic (src/warp.py:342-345).  Blocks once (work list sized on the host); 0.10 ms per 1M events.
- * Device memory per event: 64 B (packed events, fp64 times, the sort's staging copy) + 4.5 B for the compact copy the hot kernels read
+ * arithmetic (src/warp.py:342-345).  Blocks once (work list sized on the host); 0.10 ms per 1M events
+ * (measured before every sort pass also carried the 4-byte source index; not re-measured since -- bench.py's once-per-batch preparation
+ * of its 1M-event batch reads 0.21 ms with the index against 0.19 - 0.21 ms without, profiles/weights_cost.txt).
+ * Device memory per event: 72 B (packed events, fp64 times, the source index cmax_set_event_weights gathers by, the sort's staging copy) + 4.5 B for the compact copy the hot kernels read
  * when the work list is cut into big segments (un-binned batches of >= 8M events, or by the work-list rule from ~4M). */
 int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, int have_tminmax,
                     double tmin, double tmax, int n_time_bin, cmax_stream_t stream);
@@ -205,6 +208,32 @@ int cmax_set_time_bins(cmax_handle_t h, int n_time_bin, cmax_stream_t stream);
  * order since round 5); n_slab <= 1 returns to the un-binned order; the next cmax_set_events starts un-slabbed again.  Blocks once
  * like cmax_set_time_bins.                                                                                                        */
 int cmax_set_time_slabs(cmax_handle_t h, int n_slab, cmax_stream_t stream);
+
+/* Per-event weights of the current batch -- the `weight` argument of EventImageConverter.bilinear_vote_tensor / bilinear_vote_numpy and
+ * of create_image_from_events_* (src/event_image_converter.py:316-372, 257-314): event e adds w_e times its bilinear footprint.
+ *   weights : device pointer, fp32 or fp64 [n], in the CALLER's event order of the last cmax_set_events (n must equal that call's n);
+ *             NULL returns the handle to the unweighted state (the kernels and numbers of a handle that never held weights).
+ * Weights must be finite IN FP32, the format the library keeps them in (an fp64 weight above 3.4e38 counts as non-finite, one below
+ * 1.4e-45 becomes 0): CMAX_EINVAL otherwise, and the handle is left unweighted; any sign and zero are allowed.  Votes are quantised to
+ * wmax / 2^20, so results stay within the library's 1e-4 for min|w != 0| / wmax >= 0.01.  They apply to the
+ * current batch only: the next cmax_set_events starts unweighted, the same rule as time slabs; cmax_set_time_bins /
+ * cmax_set_time_slabs keep them (the library keeps the caller-order copy and every packed event's source index, and gathers again).
+ * An event the packing dropped (cmax_set_keep_outside(h, 0)) drops its weight with it.  Device memory: + 8 B per event while weighted
+ * (+ 8 B per event for the source index, always).
+ * Weighted: cmax_objective, cmax_objective_host, cmax_objective_batch (candidate by candidate), cmax_iwe, cmax_copy_iwe and the
+ * un-warped image of the normalised costs (the reference's orig_iwe built with the same weight) -- every model, cost, n_ref, sigma,
+ * un-binned / binned / slab order and segment size.  2-DoF objectives take the general vote -> statistics -> gather path; the raw form
+ * is not carried (cmax_objective_has_raw returns 0).
+ * Numerics: the votes are normalised by wmax = max |w| over the packed events (reduced on the device, kept in device memory): an event
+ * votes round(w / wmax * 2^20) (2^19 on big segments) split over its four cells so that the four integers add up to it exactly, and wmax
+ * is folded back in where the fixed-point window is flushed to the fp32 image.  The gradient pass multiplies every event's
+ * dL/d(x', y') by w.  All weights zero: the image is zero, loss and gradient are what the cost gives on a zero image.
+ * REFUSED on a weighted handle with CMAX_EUNSUPPORTED: cmax_objective_hvp[_dist], cmax_objective_raw, cmax_objective_vote / _finish,
+ * cmax_objective_dist, cmax_comm_init, cmax_patch_plan_create (and cmax_patch_plan_evaluate / _hvp of a plan made earlier), cmax_patch_search, cmax_set_deterministic(h, 1); and this call on a
+ * deterministic handle or one with a communicator.  Blocks once (non-finite check, wmax read-back).                                  */
+int cmax_set_event_weights(cmax_handle_t h, const void *weights, int dtype, int64_t n, cmax_stream_t stream);
+/* Whether the current batch is weighted, and wmax = max |w| over its packed events (0 when unweighted).  Any pointer may be NULL.   */
+int cmax_batch_weighted(cmax_handle_t h, int *weighted, double *wmax_host);
 
 /* Image of warped events for one reference time (fp32 [Hp,Wp], blurred if sigma > 0).
  * motion: fp32 theta[2] | flow[2,H,W] | voxel[T,2,H,W] in pixel per (normalised) time.
