@@ -1136,40 +1136,10 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         const bool in = (r >= i0) && (r < wp.Hp - i0) && (c >= i0) && (c < wp.Wp - i0);
         return in ? x : 0.f;  // masked raw image (kFoldStats, kFoldStatsInside, kFoldDeferred)
     };
-    // deferred statistics: this workgroup's slice [p_lo, p_hi) of the image (K2's work, see k_finish_deferred) and
-    // of the zeroing of the next evaluation's vote image.  The first load per thread is issued here, ahead of the
-    // event loads, and consumed after the gather.
-    constexpr int kStatPrefetch = 3;  // (cfg2: 129 pixels per workgroup = 64 + 64 + 1)
-    float x_first[kStatPrefetch];
-#pragma unroll
-    for (int u = 0; u < kStatPrefetch; ++u) x_first[u] = 0.f;
-    int p_lo = 0, p_hi = 0;
-    auto stat_pixel = [&](int p) -> float {
-        const int r = p / wp.Wp, c = p - r * wp.Wp;
-        const bool in = (r >= i0) && (r < wp.Hp - i0) && (c >= i0) && (c < wp.Wp - i0);
-        return in ? img[p] : 0.f;
-    };
-    if (FOLD == kFoldDeferred && threadIdx.x < kWave) {  // wave 0 walks the slice
-        const int npix = wp.Hp * wp.Wp;
-        const int chunk = (npix + nseg - 1) / nseg;
-        p_lo = sidx * chunk + (int)threadIdx.x;
-        p_hi = min(npix, (sidx + 1) * chunk);
-        // the first loads of the slice are issued here, all at once and unconditionally (clamped index, pin(), select: see pin()) -- the
-        // loop behind the gather waited for one load per iteration on the critical path of wave 0, i.e. of the workgroup's last barrier
-        // (cfg2 K3 6.84 -> 6.75 us, profiles/r03_ablation.txt 19)
-        bool ok[kStatPrefetch];
-#pragma unroll
-        for (int u = 0; u < kStatPrefetch; ++u) {
-            const int p = p_lo + u * kWave, q = min(p, npix - 1);
-            const int r = q / wp.Wp, c = q - r * wp.Wp;
-            ok[u] = p < p_hi && (r >= i0) && (r < wp.Hp - i0) && (c >= i0) && (c < wp.Wp - i0);
-            x_first[u] = img[q];
-        }
-#pragma unroll
-        for (int u = 0; u < kStatPrefetch; ++u) pin(x_first[u]);
-#pragma unroll
-        for (int u = 0; u < kStatPrefetch; ++u) x_first[u] = ok[u] ? x_first[u] : 0.f;
-    }
+    // deferred statistics (K2's work, see k_finish_deferred): no pass over the image.  The image is the sum of the events' bilinear
+    // votes, so over the region Omega
+    //     sum_p I[p]^2 = sum_e sum_{c in corners(e)} w_ec I[c] 1_Omega(c),     sum_p I[p] = sum_e sum_c w_ec 1_Omega(c),
+    // and the gather below already holds an event's four (masked) corner values and its fractions: one bilinear interpolation per event.
     __shared__ float s_chain[2];  // chain factor and mean of this reference time
     float c2 = 1.f, mu = 0.f;
     // A normalised cost's chain factor depends on the variances, and kFoldStats needs the mean (for the windows that reach
@@ -1303,6 +1273,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     asm volatile("" : "+v"(neg_origin));  // (a VGPR: see fast_index)
     const unsigned scratch = L::kWinCap + lane;
     // per event: dL/dx' = (1-b)(G10-G00) + b(G11-G01), dL/dy' = (1-a)(G01-G00) + a(G11-G10)
+    // (deferred statistics: also g_bil = the masked image interpolated at the event, sum_c w_ec I[c] 1_Omega(c), for sum I^2)
+    float g_bil = 0.f;
     auto gather = [&](int j, float &gx, float &gy) {
         // g[0] = G00 (row, col), g[1] = G10 (row+1, col), g[2] = G01 (row, col+1), g[3] = G11
         float g[4];
@@ -1341,6 +1313,10 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         const float a = fa[j], b = fb[j];
         gx = (1.f - b) * (g[1] - g[0]) + b * (g[3] - g[2]);
         gy = (1.f - a) * (g[2] - g[0]) + a * (g[3] - g[1]);
+        if (FOLD == kFoldDeferred) {  // (1-b)((1-a) G00 + a G10) + b((1-a) G01 + a G11) on the row differences gx already has
+            const float t0 = fmaf(a, g[1] - g[0], g[0]), t1 = fmaf(a, g[3] - g[2], g[2]);
+            g_bil = fmaf(b, t1 - t0, t0);
+        }
         if (kStatsFold && edge_mu) {  // workgroup-uniform: the mean's share mu * bilinear-difference(1_Omega) (nothing is kept per event:
             // two more registers per slot put the 512-thread owned kernel at 66 VGPRs, i.e. 7 waves per SIMD instead of 8)
             const int hi = wp.Hp - 2 * i0, wi = wp.Wp - 2 * i0;
@@ -1372,6 +1348,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         return ((group - sg.z) << 8) + ((ix & 15) << 4) + (iy & 15);
     };
     float accx = 0.f, accy = 0.f, s2x = 0.f, s2y = 0.f;
+    float sum_i = 0.f, sum_ii = 0.f;  // deferred statistics: this thread's share of sum I and sum I^2 over Omega (see above)
     if (kDet) {
         __shared__ long long s_acc64[2];
         if (MODEL == CMAX_MODEL_2DOF) {
@@ -1435,23 +1412,31 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             gather(j, gx, gy);
             accx = fmaf(fdt[j], gx, accx);  // dt = 0 for an empty slot; <= kEPT terms in fp32, then fp64 across the workgroup
             accy = fmaf(fdt[j], gy, accy);
+            if (FOLD == kFoldDeferred) sum_ii += g_bil;  // an empty slot gathers zeros; <= kEPT terms in fp32, as above
         }
         if (FOLD == kFoldDeferred) {
             // the mean enters only where a footprint straddles the edge of the region Omega the variance is taken
-            // over: with m = 1_Omega, S2 = sum dt * bilinear-difference(m).  Workgroup-uniform test: most windows
-            // lie inside Omega and skip this.
+            // over: with m = 1_Omega, S2 = sum dt * bilinear-difference(m), and an event's share of sum I is the
+            // bilinear interpolation of m (the mask is a rectangle: a product of a row and a column factor).
+            // Workgroup-uniform test: most windows lie inside Omega, where S2 is exactly 0 and every event counts 1
+            // (K1's four integer weights add up to K exactly), and skip this.
             const int hi = wp.Hp - 2 * i0, wi = wp.Wp - 2 * i0;
             const bool edge = win.clipped || win.r0 < i0 || win.r0 + win.h > wp.Hp - i0 || win.c0 < i0 || win.c0 + win.w > wp.Wp - i0;
             if (edge) {
 #pragma unroll
                 for (int j = 0; j < L::kEPT; ++j) {
-                    const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;
+                    const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;  // empty slot: far outside, all masks 0
                     const float mr0 = (unsigned)(row - i0) < (unsigned)hi ? 1.f : 0.f, mr1 = (unsigned)(row + 1 - i0) < (unsigned)hi ? 1.f : 0.f;
                     const float mc0 = (unsigned)(col - i0) < (unsigned)wi ? 1.f : 0.f, mc1 = (unsigned)(col + 1 - i0) < (unsigned)wi ? 1.f : 0.f;
                     const float a = fa[j], b = fb[j];
-                    s2x = fmaf(fdt[j], (mr1 - mr0) * ((1.f - b) * mc0 + b * mc1), s2x);
-                    s2y = fmaf(fdt[j], (mc1 - mc0) * ((1.f - a) * mr0 + a * mr1), s2y);
+                    const float wr = (1.f - a) * mr0 + a * mr1, wc = (1.f - b) * mc0 + b * mc1;
+                    s2x = fmaf(fdt[j], (mr1 - mr0) * wc, s2x);
+                    s2y = fmaf(fdt[j], (mc1 - mc0) * wr, s2y);
+                    sum_i = fmaf(wr, wc, sum_i);
                 }
+            } else {
+#pragma unroll
+                for (int j = 0; j < L::kEPT; ++j) sum_i += rc[j] != 0u ? 1.f : 0.f;
             }
         }
         }  // live
@@ -1668,14 +1653,14 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     }
     if (FOLD == kFoldDeferred) {
         // Workgroup sums.  A block_sum of six doubles (36 dependent v_add_f64 behind 72 DPP moves per wave, two
-        // barriers) cost 2 of this kernel's 8.7 us.  The four gradient sums are reduced over the wave in fp32 --
-        // each of their <= 512 terms already carries fp32 rounding, a 6-level tree adds less than the terms bring --
-        // and in fp64 across waves and workgroups; the image sums stay fp64 but only wave 0 holds any.
-        float *s_f = reinterpret_cast<float *>(s_red);  // [4][kNW] floats; s_red[2 kNW ..] doubles for the image sums
-        float w4[4] = {accx, accy, s2x, s2y};
+        // barriers) cost 2 of this kernel's 8.7 us.  All six sums are reduced over the wave in fp32 -- each of their
+        // <= 512 terms already carries fp32 rounding, a 6-level tree adds less than the terms bring (sum I inside
+        // Omega is a count below 2^24: exact) -- and in fp64 across waves and workgroups.
+        float *s_f = reinterpret_cast<float *>(s_red);  // [6][kNW] floats
+        float w6[6] = {accx, accy, s2x, s2y, sum_i, sum_ii};
 #pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            float v = w4[q];
+        for (int q = 0; q < 6; ++q) {
+            float v = w6[q];
             v += dpp_f<kDppRowShr1>(v);
             v += dpp_f<kDppRowShr2>(v);
             v += dpp_f<kDppRowShr4>(v);
@@ -1684,27 +1669,8 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             v += dpp_f<kDppRowBcast31>(v);
             if (lane == kWave - 1) s_f[q * L::kNW + threadIdx.x / kWave] = v;
         }
-        if (threadIdx.x < kWave) {
-            double sx = 0.0, sxx = 0.0;
-#pragma unroll
-            for (int u = 0; u < kStatPrefetch; ++u) {
-                sx += (double)x_first[u];
-                sxx += (double)x_first[u] * (double)x_first[u];
-            }
-            for (int p = p_lo + kStatPrefetch * kWave; p < p_hi; p += kWave) {
-                const double x = (double)stat_pixel(p);
-                sx += x;
-                sxx += x * x;
-            }
-            sx = wave_sum_lane63(sx);
-            sxx = wave_sum_lane63(sxx);
-            if (lane == kWave - 1) {
-                s_red[2 * L::kNW] = sx;
-                s_red[2 * L::kNW + 1] = sxx;
-            }
-        }
         if (FOLD == kFoldDeferred && zero_img) {
-            // Issued here, behind the event, window and statistics loads (vmcnt retires in issue order: stores issued first sit
+            // Issued here, behind the event and window loads (vmcnt retires in issue order: stores issued first sit
             // on the critical path of every load behind them).
             // This workgroup's slice of the next evaluation's vote image is cleared with WRITE-THROUGH stores (sc1): a
             // plain store leaves the line in this XCD's L2, and the device-scope atomics of the next K1 then pay for
@@ -1727,11 +1693,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         CMAX_STAMP(1, 6);
         if (threadIdx.x < 6) {
             double a = 0.0;
-            if (threadIdx.x < 4) {
-                for (int w = 0; w < L::kNW; ++w) a += (double)s_f[threadIdx.x * L::kNW + w];
-            } else {
-                a = s_red[2 * L::kNW + (threadIdx.x - 4)];
-            }
+            for (int w = 0; w < L::kNW; ++w) a += (double)s_f[threadIdx.x * L::kNW + w];
             atomic_add(&gpart[(sidx & (kRawLines - 1)) * kSubStride + threadIdx.x], a);
         }
         return;

@@ -1407,8 +1407,8 @@ k_tan_stats_var(const float *__restrict__ T, float *__restrict__ Tnext, int64_t 
     }
     if (Tnext) zero_fill_sc1(Tnext + k * tstride, tstride, (int64_t)blockIdx.x * 256 + threadIdx.x, (int64_t)gridDim.x * 256);
     // the four gradient sums go over the wave in fp32 (DPP adds; their terms carry fp32 rounding already) and in fp64 across
-    // waves and workgroups, the two image sums stay fp64 throughout -- as in the deferred K3 (a block_sum of six doubles is
-    // 36 dependent v_add_f64 behind 72 DPP moves)
+    // waves and workgroups -- as in the deferred K3 -- while the two image sums, summed pixel by pixel here, stay fp64 throughout (a
+    // block_sum of six doubles is 36 dependent v_add_f64 behind 72 DPP moves)
     float *s_f = reinterpret_cast<float *>(smem + 2 * 4);  // [4][4] floats behind the doubles of block_sum<2>
     const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
 #pragma unroll
@@ -3394,7 +3394,9 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.g = grad_extent(h, d);
     const bool det = h->deterministic, two_dof = d->model == CMAX_MODEL_2DOF;
     const bool fold_var = d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0);
-    p.deferred = deferred_applies(h, d, grad);
+    // (the deferred K3 takes sum I and sum I^2 from its own events' gather: the image must be what THIS handle's events voted in this
+    // call -- an image the caller hands to cmax_objective_finish, or one that was all-reduced, keeps its statistics launch)
+    p.deferred = deferred_applies(h, d, grad) && whole && !dist;
     p.lines = two_dof_lines(h, d, grad);
     p.raw = p.lines ? (raw_out ? raw_out : h->d_raw) : nullptr;
     p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
