@@ -337,6 +337,27 @@ class CMaxHandle:
                                        grad.data_ptr() if grad is not None else None, F._stream()))
         return result, grad
 
+    def evaluate_weight_grad(self, desc: CmaxObjective, motion, want_grad: bool = True):
+        """One cmax_objective_weight_grad call: (result, grad or None, grad_w).  result and grad as `evaluate` returns them;
+        grad_w is dL/dw, float32 [n] on the device in the order of the events handed to set_events -- the reference's `weight.grad`
+        after `backward()` through create_image_from_events_*(weight=w) (src/event_image_converter.py:316-372).  It is not multiplied
+        by w (an event of weight 0 has a derivative), an unweighted handle means w = 1, and events that were not packed get 0.
+        Deterministic handles and handles with a communicator raise NotImplementedError with the library's text."""
+        m, desc = self._motion_arg(desc, motion)
+        result = torch.empty(8, dtype=torch.float64, device=self.device)
+        grad = None
+        if want_grad:
+            if desc.model == _lib.MODEL_2DOF:
+                grad = torch.empty(2, dtype=torch.float64, device=self.device)
+            else:
+                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+        n = int(getattr(self, "_n_in", 0))
+        buf = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)  # (an empty batch still hands over a valid pointer: a
+        grad_w = buf[:n]                                                        # tensor without elements has none)
+        check(self._lib.cmax_objective_weight_grad(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
+                                                   grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, F._stream()))
+        return result, grad, grad_w
+
     def prepare(self, desc: CmaxObjective, motion, want_grad: bool = True, dist: bool = False):
         """A prepared cmax_objective (dist: cmax_objective_dist) call for an inner loop that evaluates the SAME motion
         buffer again and again (an optimiser updating it in place, a benchmark): outputs allocated once, pointers
@@ -718,6 +739,29 @@ class _FusedFn(torch.autograd.Function):
         return g.to(ctx.mdevice), None, None
 
 
+class _FusedWeightedFn(torch.autograd.Function):
+    """The fused loss on the tape in BOTH the motion and the per-event weights (cmax_objective_weight_grad); the handle already holds
+    `weights` (ContrastObjective.__call__ set them)."""
+
+    @staticmethod
+    def forward(ctx, motion, weights, handle, desc):
+        result, grad, grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=motion.requires_grad)
+        ctx.grad = grad
+        ctx.grad_w = grad_w if weights.requires_grad else None
+        ctx.mdtype, ctx.mdevice = motion.dtype, motion.device
+        ctx.wdtype, ctx.wdevice = weights.dtype, weights.device
+        return result[0].to(motion.dtype if motion.dtype.is_floating_point else torch.float64)
+
+    @staticmethod
+    def backward(ctx, gout):
+        gm = gw = None
+        if ctx.grad is not None:
+            gm = (ctx.grad.to(ctx.mdtype) * gout.to(ctx.grad.device).to(ctx.mdtype)).to(ctx.mdevice)
+        if ctx.grad_w is not None:
+            gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
+        return gm, gw, None, None
+
+
 class ContrastObjective:
     """loss = objective(motion[, coarse_flow]) with the reference's cost names.
 
@@ -796,7 +840,15 @@ class ContrastObjective:
             loss = loss + combine(weight, value)
         return loss
 
-    def __call__(self, motion: torch.Tensor, coarse_flow: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, motion: torch.Tensor, coarse_flow: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+        """weights: None -- the loss of the handle as it stands, differentiable in `motion`.  A tensor [n] -- per-event weights of the
+        handle's batch (the reference's `weight` on the autograd tape): the loss is differentiable in `motion` AND `weights`
+        (either may not require grad); hybrid members, "inv" included, follow through `combine`, total_variation does not depend on
+        the weights.  Each such call pays set_event_weights: one gather plus its one synchronisation; the weights stay on the handle."""
+        if weights is not None:
+            if not isinstance(weights, torch.Tensor):
+                raise TypeError(f"weights must be a torch tensor, got {type(weights)}")
+            self.handle.set_event_weights(weights.detach())
         loss = 0.0
         for name, weight, desc in self.terms:
             if desc is None:
@@ -806,7 +858,8 @@ class ContrastObjective:
                 if self.direction != "minimize":
                     value = -value
             else:
-                value = _FusedFn.apply(motion, self.handle, desc)
+                value = (_FusedFn.apply(motion, self.handle, desc) if weights is None
+                         else _FusedWeightedFn.apply(motion, weights, self.handle, desc))
             value = value.to(motion.device) if isinstance(motion, torch.Tensor) else value
             loss = loss + combine(weight, value)
         return loss

@@ -1700,6 +1700,98 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K3w: dL/dw per event (cmax_objective_weight_grad), one workgroup per segment -- K3's segment, window and published-offset
+//     machinery (the window K1 used, the cells K1 decided), consecutive slots, a FINISHED G = dL/dIWE image per reference time:
+//        dL/dw_e = (1-a)(1-b) G00 + a(1-b) G10 + (1-a) b G01 + a b G11
+//     NOT multiplied by w (an event of weight 0 has a derivative).  Slot l of the segment stores gw[plane y][first + l] -- the index
+//     load_slot_weights reads a weight from -- coalesced, no atomics; empty slots store nothing (their index belongs to a neighbouring
+//     segment; the host clears the planes).  MODEL = -1: the un-warped events against dL/dI_orig (normalised costs).
+//     A kernel of its own rather than one more flag of k_grad: no existing instantiation changes (profiles/weight_grad_resources.txt).
+// ---------------------------------------------------------------------------------------------
+template <class L, int MODEL, bool FRAC>
+__global__ void __launch_bounds__(L::kThr)
+k_weight_gather(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base, EvView ev,
+                WarpParams wp, RefArgs ra, float *__restrict__ gw, int64_t plane) {
+    const int sidx = segment_of_block(nseg);
+    if (sidx >= nseg) return;
+    const int4 sg = segs[sidx];
+    const int4 *known = win_base + (int64_t)blockIdx.y * nseg + sidx;
+    ev.ev = evp;
+    EventLoads<L> el;
+    issue_event_loads<L, false>(evp, cev, sidx, sg, el);
+    wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
+    const float *__restrict__ img = ra.img[blockIdx.y];
+    __shared__ float s_win[L::kWinCap + kScratch];
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
+    const int lane = threadIdx.x & (kWave - 1);
+    auto g_at = [&](int r, int c) -> float { return img[pix_index(r, c, wp.Wp)]; };
+    auto load_window = [&](const Window &w) {  // G of the window, zero outside the image (flat walk, see k_grad)
+        const unsigned ustride = (unsigned)w.stride, magic = ((1u << 21) + ustride - 1u) / ustride;
+        const int wn = w.h * w.stride;
+        for (int i = threadIdx.x; i < wn; i += L::kThr) {
+            const unsigned r = mul24_u((unsigned)i, magic) >> 21, c = (unsigned)i - mul24_u(r, ustride);
+            const int R = w.r0 + (int)r, C = w.c0 + (int)c;
+            s_win[i] = ((int)c < w.w && (unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) ? g_at(R, C) : 0.f;
+        }
+    };
+    const unsigned *__restrict__ shifts = ra.shifts + ((int64_t)blockIdx.y * nseg + sidx) * L::kShiftWords;
+    bool live;
+    unsigned nib_unused;
+    const Window win = phase_warp<L, MODEL, FRAC, true, false, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused);
+    if (threadIdx.x < kScratch) s_win[L::kWinCap + threadIdx.x] = 0.f;  // empty slots / masked corners read 0 from here
+    __syncthreads();
+    if (!live) return;  // (wave-uniform, behind the last barrier)
+    const int dummy = L::kDummy + lane;
+    const int stride = win.stride;
+    unsigned neg_origin = 0u - ((unsigned)(win.r0 + 16384) * (unsigned)win.stride + (unsigned)(win.c0 + 16384));
+    asm volatile("" : "+v"(neg_origin));  // (a VGPR: see fast_index)
+    const unsigned scratch = L::kWinCap + lane;
+    const int odd = sg.x & 1;
+    float *__restrict__ out = gw + (int64_t)blockIdx.y * plane + ((int64_t)sg.x - odd);
+#pragma unroll
+    for (int j = 0; j < L::kEPT; ++j) {
+        float g[4];  // g[0] = G00 (row, col), g[1] = G10 (row+1, col), g[2] = G01 (row, col+1), g[3] = G11
+        if (!win.clipped) {  // fast window: the footprint is inside by construction
+            const int idx = fast_index(rc[j], neg_origin, win.stride, scratch);
+            g[0] = s_win[idx];
+            g[2] = s_win[idx + 1];
+            g[1] = s_win[idx + stride];
+            g[3] = s_win[idx + stride + 1];
+        } else {  // workgroup-uniform, rare: a corner outside the window reads global memory if it is inside the image (see k_grad)
+            const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;  // empty slot: far outside
+            const int lr = row - win.r0, lc = col - win.c0;
+            const bool r_in0 = (unsigned)lr < (unsigned)win.h, r_in1 = (unsigned)(lr + 1) < (unsigned)win.h;
+            const bool c_in0 = (unsigned)lc < (unsigned)win.w, c_in1 = (unsigned)(lc + 1) < (unsigned)win.w;
+            const int base = lr * win.stride + lc;
+            g[0] = s_win[(r_in0 && c_in0) ? base : dummy];
+            g[1] = s_win[(r_in1 && c_in0) ? base + stride : dummy];
+            g[2] = s_win[(r_in0 && c_in1) ? base + 1 : dummy];
+            g[3] = s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy];
+            if (rc[j] != 0u) {
+#pragma unroll 1
+                for (int q = 0; q < 4; ++q) {
+                    const int r = row + (q & 1), c = col + (q >> 1);
+                    const bool in_win = (unsigned)(r - win.r0) < (unsigned)win.h && (unsigned)(c - win.c0) < (unsigned)win.w;
+                    if (!in_win && (unsigned)r < (unsigned)wp.Hp && (unsigned)c < (unsigned)wp.Wp) {
+                        const float v = g_at(r, c);
+                        g[0] = q == 0 ? v : g[0];
+                        g[1] = q == 1 ? v : g[1];
+                        g[2] = q == 2 ? v : g[2];
+                        g[3] = q == 3 ? v : g[3];
+                    }
+                }
+            }
+        }
+        const float a = fa[j], b = fb[j];
+        const float t0 = fmaf(a, g[1] - g[0], g[0]), t1 = fmaf(a, g[3] - g[2], g[2]);
+        const int l = L::kEPT * (int)threadIdx.x + j;
+        if ((unsigned)(l - odd) < (unsigned)sg.y) out[l] = fmaf(b, t1 - t0, t0);
+    }
+}
+
 template <class L, int MODEL, bool FRAC>
 // dimg64 (deterministic mode): the window's integers (and the overflow of a clipped window, rounded at the same scale) go to a
 // 64-bit integer image with integer atomics -- exact in any order; k_fixed_to_image rounds the finished sums once

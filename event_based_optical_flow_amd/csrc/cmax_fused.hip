@@ -201,6 +201,12 @@ struct cmax_handle_s {
     bool weighted = false;
     double wmax_host = 0.0;
     int64_t n_in = 0;          // events handed to the last cmax_set_events
+    // cmax_objective_weight_grad: finished dL/dIWE images ([5][npix]: reference times 0..3, slot 4 = the un-warped image) and their
+    // blur-transpose input, the per-event interpolations in packed order (one plane of gw_plane floats per image), all allocated on first use;
+    // general_only: the evaluation inside that call takes the general K1 -> statistics / image kernel -> K3 path on any handle
+    float *gw_G = nullptr, *gw_Gt = nullptr, *gw_packed = nullptr;
+    int64_t gw_plane = 0;
+    bool general_only = false;
     // staging SoA of the two-level sort (tile buckets before the per-tile ordering)
     uint2 *evp_alt = nullptr;
     float *rx_alt = nullptr, *ry_alt = nullptr;
@@ -2968,6 +2974,9 @@ int cmax_destroy(cmax_handle_t h) {
     dev_free(&h->w_user);
     dev_free(&h->w_packed);
     dev_free(&h->d_wnorm);
+    dev_free(&h->gw_G);
+    dev_free(&h->gw_Gt);
+    dev_free(&h->gw_packed);
     dev_free(&h->cev);
     dev_free(&h->evp_alt);
     dev_free(&h->rx_alt);
@@ -3228,7 +3237,7 @@ static int publish_windows(cmax_handle_s *h, const cmax_objective_t *d, const fl
 // the chain factors -- no K2 launch (unless a workgroup's slice of the image would get long)
 static bool deferred_applies(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad) {
     // (a weighted handle takes the general K1 -> statistics -> K3 path: the raw sums' indicator image and sum I are not carried)
-    return !h->deterministic && !h->weighted && grad && d->model == CMAX_MODEL_2DOF && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && h->n > 0 &&
+    return !h->deterministic && !h->weighted && !h->general_only && grad && d->model == CMAX_MODEL_2DOF && d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0) && h->n > 0 &&
            (int64_t)h->Hp * h->Wp <= (int64_t)h->nseg * 8192;
 }
 
@@ -3322,7 +3331,7 @@ static int c2_exchange_all_bands(cmax_handle_s *h, cmax::Comm *c2_comm, float *g
 // the whole batch's three images and finishes loss and gradient on its own.
 // force: CMAX_TAN2 (1 = also on one GPU, 0 = never, -1 = unset)
 static bool tan2_applicable(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool dist, int force) {
-    if (force == 0 || h->deterministic || h->weighted || !grad) return false;
+    if (force == 0 || h->deterministic || h->weighted || h->general_only || !grad) return false;
     if (d->model != CMAX_MODEL_2DOF || d->cost != CMAX_COST_VARIANCE || d->sigma > 0) return false;
     // Rank-consistent scalars: behind the single exchange every rank finishes loss AND gradient on its own -- from the reduced planes in a
     // fixed order (per-workgroup partials, one folding wave: bit-identical on every rank), but a NORMALISED variance also reads the
@@ -3402,7 +3411,7 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
     p.blur_var = !det && d->cost == CMAX_COST_VARIANCE && d->sigma > 0;
     // K1 can sum its votes for the kernels behind it (not on a weighted handle: the sum counts events)
-    const bool k1_sums_ok = whole && !dist && !h->weighted && h->Hp >= 4 && h->Wp >= 4;
+    const bool k1_sums_ok = whole && !dist && !h->weighted && !h->general_only && h->Hp >= 4 && h->Wp >= 4;
     p.fused_bv = k1_sums_ok && p.blur_var && grad && h->n > 0 && !no_fused_bv;
     // K3 stores every element of the flow gradient itself (one writer per pixel): needs the group-aligned work list, ONE reference
     // time (several would add into the same pixels) and the sort order that matches the model (dense: tiles; voxel: (tile, bin) of
@@ -3896,6 +3905,175 @@ int cmax_objective(cmax_handle_t h, const cmax_objective_t *d, const void *motio
     if (rc) return rc;
     CMAX_REQUIRE(result, "objective: result");
     return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, nullptr);
+}
+
+}  // extern "C"
+
+// ---- dL/dw of the fused objective (cmax_objective_weight_grad) ---------------------------------------------------------------
+namespace cmax {
+// dL/dI_orig of a normalised cost: the un-warped image is a (weighted) vote too, so v_orig depends on the weights.
+//   L = +- sum_k m_k v_orig / v_k (minimize) | +- sum_k m_k v_k / v_orig   ->   dL/dv_orig = +- sum_k m_k / v_k | -+ sum_k m_k v_k / v_orig^2
+// from the fp64 statistics on the device (slots 0 .. n_ref - 1 and 4); dv_orig/dI as k_gimage, with the region orig_value uses.
+template <int COST>
+__global__ void __launch_bounds__(256) k_gimage_orig(const float *__restrict__ img, ObjParams op, const double *__restrict__ stat, float *__restrict__ G) {
+    const int H = op.H, W = op.W;
+    const int omit_o = COST == CMAX_COST_VARIANCE ? 0 : op.omit;  // orig_iwe is NOT boundary-cropped for the variance
+    const int i0 = omit_o ? 1 : 0;
+    const double npix = region_pixels(H, W, omit_o), npix_k = region_pixels(H, W, op.omit);
+    double acc[2], mu = 0.0;
+    stat_sum<true>(stat, 4, op.nsub, acc);  // every wave is converged here
+    const double v_orig = contrast_value(COST, acc, npix, &mu);
+    double coef = 0.0;
+    for (int k = 0; k < op.n_ref; ++k) {
+        double ak[2];
+        stat_sum<true>(stat, k, op.nsub, ak);
+        const double v = contrast_value(COST, ak, npix_k, nullptr);
+        coef += op.mult[k] * (op.minimize ? 1.0 / v : -v / (v_orig * v_orig));
+    }
+    if (op.negate) coef = -coef;
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= (int64_t)H * W) return;
+    const int i = (int)(p / W), j = (int)(p % W);
+    if (COST == CMAX_COST_VARIANCE) {
+        const bool in = (i >= i0) && (i < H - i0) && (j >= i0) && (j < W - i0);
+        G[p] = in ? (float)(coef * 2.0 * ((double)img[p] - mu) / (npix - 1.0)) : 0.f;
+    } else {
+        G[p] = (float)(coef * (2.0 / npix) / 8.0) * sobel8_adj_f32(img, H, W, i0, i, j);
+    }
+}
+
+// grad_w[src[i]] = sum over the planes, in index order, of gw_packed[plane][i] (behind a zero fill of grad_w: events that were not packed keep 0)
+__global__ void __launch_bounds__(256) k_weight_grad_scatter(const float *__restrict__ gw, int64_t plane, int n_planes, const int *__restrict__ src, int64_t n,
+                                                            float *__restrict__ grad_w) {
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n) return;
+    float a = gw[i];
+    for (int q = 1; q < n_planes; ++q) a += gw[(int64_t)q * plane + i];
+    grad_w[src[i]] = a;
+}
+
+// K3w of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
+template <int MODEL>
+static void launch_weight_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_img, int plane0, hipStream_t s) {
+    const dim3 grid(8 * ((h->nseg + 7) / 8), n_img);
+    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // as K1 (launch_vote)
+    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            hipLaunchKernelGGL((k_weight_gather<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev, wp, ra,
+                               h->gw_packed + (int64_t)plane0 * h->gw_plane, h->gw_plane);
+        });
+    });
+}
+
+// behind objective_eval of the same call: its images, statistics, windows and cell offsets are the handle's current ones
+static int weight_grad_finish(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *orig_raw, float *grad_w, hipStream_t s) {
+    const int Hp = h->Hp, Wp = h->Wp, nr = d->n_ref;
+    const int64_t npix = (int64_t)Hp * Wp;
+    const int n_planes = nr + (d->normalized ? 1 : 0);
+    int rc = 0;
+    if (!h->gw_G) {
+        rc = dev_alloc(h, &h->gw_G, 5 * npix);
+        if (!rc) rc = dev_alloc(h, &h->gw_Gt, 5 * npix);
+        if (rc) return rc;
+    }
+    if (h->n > h->gw_plane) {  // sized like w_packed
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(&h->gw_packed);
+        h->gw_plane = 0;
+        const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
+        rc = dev_alloc(h, &h->gw_packed, 5 * plane);
+        if (rc) return rc;
+        h->gw_plane = plane;
+    }
+    CMAX_CHECK_HIP(hipMemsetAsync(h->gw_packed, 0, (size_t)n_planes * h->gw_plane * sizeof(float), s));
+    const ObjParams op = obj_params(h, d);
+    double k0 = 0, k1 = 0;
+    if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
+    // G_k = dL/dIWE_k with its chain factor (multi-focal multipliers included), the blur transpose applied
+    float *gdst = d->sigma > 0 ? h->gw_Gt : h->gw_G;
+    const dim3 igrid(div_up(npix, 256));
+    for (int k = 0; k < nr; ++k) {
+        if (d->cost == CMAX_COST_VARIANCE)
+            hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+        else
+            hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+    }
+    if (d->normalized) {  // slot 4: G_orig on the (blurred) un-warped image
+        const float *img = d->sigma > 0 ? h->iweb[4] : orig_raw;
+        if (d->cost == CMAX_COST_VARIANCE) hipLaunchKernelGGL(k_gimage_orig<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, img, op, h->d_stat, gdst + 4 * npix);
+        else hipLaunchKernelGGL(k_gimage_orig<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, img, op, h->d_stat, gdst + 4 * npix);
+    }
+    if (d->sigma > 0) {
+        hipLaunchKernelGGL(k_blur3_adj<float>, dim3(igrid.x, nr), dim3(256), 0, s, h->gw_Gt, Hp, Wp, (float)k0, (float)k1, h->gw_G, npix);
+        if (d->normalized)
+            hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->gw_Gt + 4 * npix, Hp, Wp, (float)k0, (float)k1, h->gw_G + 4 * npix, (int64_t)0);
+    }
+    CMAX_CHECK_LAUNCH();
+    const EvView ev = ev_view(h);
+    {  // one plane per reference time: the windows and cells K1 of this evaluation published
+        RefArgs ra = {};
+        fill_ref_times(ra, nr, d->ref_mode, d->ref_frac);
+        for (int k = 0; k < nr; ++k) ra.img[k] = h->gw_G + k * npix;
+        ra.win = h->d_win;
+        ra.shifts = h->d_shifts;
+        const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
+        with_model(d->model, [&](auto m) { launch_weight_gather<m.value>(h, ev, wp, ra, nr, 0, s); });
+        CMAX_CHECK_LAUNCH();
+    }
+    if (d->normalized) {  // one more plane: the un-warped events against G_orig, behind a K1 launch that only publishes their windows
+        RefArgs ra = {};
+        const int ref_mode = CMAX_REF_FIRST;
+        const double frac = 0.0;
+        fill_ref_times(ra, 1, &ref_mode, &frac);
+        ra.win = h->d_win;
+        ra.shifts = h->d_shifts;
+        ra.windows_only = 1;
+        const WarpParams wp = warp_params(h, nullptr, 0, CMAX_REF_FIRST, 0.0, 1);
+        launch_vote<-1>(h, ev, wp, ra, 1, s);
+        CMAX_CHECK_LAUNCH();
+        h->win_motion = nullptr;  // (the handle's windows are no evaluation's any more)
+        h->win_generation = ~(uint64_t)0;
+        ra.windows_only = 0;
+        ra.img[0] = h->gw_G + 4 * npix;
+        launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
+        CMAX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_weight_grad_scatter, dim3(div_up(h->n, 256)), dim3(256), 0, s, (const float *)h->gw_packed, h->gw_plane, n_planes, (const int *)h->src, h->n, grad_w);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+}  // namespace cmax
+
+extern "C" {
+
+int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad, float *grad_w,
+                               int64_t n, cmax_stream_t stream) {
+    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    CMAX_REQUIRE(result && (grad_w || n == 0), "objective_weight_grad: result / grad_w (grad_w may be NULL only for n == 0)");
+    CMAX_REQUIRE(n == h->n_in, "objective_weight_grad: n must equal the n of the last cmax_set_events (one derivative per event, in the caller's order)");
+    if (h->deterministic) {
+        set_error("objective_weight_grad: not built for deterministic mode (cmax_set_deterministic)");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (h->comm) {
+        set_error("objective_weight_grad: not built for a handle with a communicator (cmax_comm_init)");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
+    // the general path (K1 -> statistics / image kernel -> K3) on any handle, and the un-warped image voted again: G_orig needs the image
+    // itself, the per-batch cache keeps its statistics only
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const float *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
+    h->general_only = true;
+    if (d->normalized) h->orig_valid = false;
+    rc = objective_eval(h, d, motion, result, grad, s, nullptr);
+    h->general_only = false;
+    if (rc || h->n == 0) return rc;
+    return weight_grad_finish(h, d, motion, orig_raw, grad_w, s);
 }
 
 int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad,

@@ -275,6 +275,23 @@ typedef struct {
 int cmax_objective(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion,
                    double *result, void *grad, cmax_stream_t stream);
 
+/* The same evaluation plus dL/dw, the derivative of the loss with respect to the per-event weights -- what the reference leaves in
+ * `weight.grad` when the image is built with a weight tensor on the autograd tape (src/event_image_converter.py:316-372) and the
+ * loss is back-propagated; per event it is what cmax_vote_bwd returns as gw, summed over the images of the objective:
+ *     dL/dw_e = sum_k bilin(G_k; x'_e,k)  (+ bilin(G_orig; x_e) for the normalised and multi-focal costs),
+ *     bilin(G; x') = (1-a)(1-b) G00 + a(1-b) G10 + (1-a) b G01 + a b G11,   G_k = dL/dIWE_k,  G_orig = dL/dI_orig
+ * (cell and fractions as the vote decided them; a corner outside the padded image, or outside the region the cost sums over, reads
+ * 0).  The value is NOT multiplied by w: an event of weight 0 has a derivative.  An unweighted handle means w = 1.
+ * result[8] and grad: exactly as cmax_objective (grad may be NULL).  grad_w: fp32 [n] in the CALLER'S event order, n = the n given to
+ * cmax_set_events (CMAX_EINVAL otherwise); events that were not packed get 0; an empty handle returns zeros.  Asynchronous on `stream`.
+ * Works on weighted and unweighted handles, after cmax_set_time_bins / cmax_set_time_slabs, on every segment layout, on the
+ * clipped-window path and for 2-DoF batches with kept off-sensor events.  The evaluation takes the general vote -> statistics ->
+ * gather path; a gather kernel of its own then interpolates a finished G image per reference time (and G_orig at the un-warped
+ * positions) into one plane per image in packed order, and a scatter sums the planes in index order into grad_w.  Device memory
+ * on first use: 20 B per event + 10 images.  CMAX_EUNSUPPORTED on a deterministic handle and on one that holds a communicator.   */
+int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion, double *result,
+                               void *grad /* may be NULL */, float *grad_w, int64_t n, cmax_stream_t stream);
+
 /* The same evaluation with its results delivered TO THE HOST -- what an optimiser written in C calls once per iteration
  * (the reference's TorchWrapper.get_value_and_grad ends in .cpu().numpy(), src/solver/scipy_autograd/torch_wrapper.py:46-49):
  * enqueues the evaluation and the copies on `stream` and returns when result_host[8] and grad_host (double[2] for 2DOF, else
