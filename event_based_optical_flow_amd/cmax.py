@@ -134,7 +134,8 @@ class CMaxHandle:
                    on_dropped: str = "warn", weights=None):
         """Pack + sort one [n,4] batch (numpy or tensor, fp32/fp64).  (tmin, tmax): global batch
         extremes when this handle only holds a time slice of the batch (multi-GPU).
-        on_dropped: what to do when events were NOT packed because their source pixel lies off the sensor (or is NaN) --
+        on_dropped: what to do when events were NOT packed because their source pixel lies off the sensor (or is NaN) or their time
+        is not finite --
         the fused path indexes source tiles and the flow field with it; the reference's 2-DoF warp would still let such an
         event vote if it warps into a padded image, its dense warp indexes out of bounds there -- "warn" (log),
         "raise" (a solver that must not diverge from the reference silently: ValueError) or "ignore".
@@ -168,11 +169,11 @@ class CMaxHandle:
             logger.warning(msg)
         if dropped and on_dropped == "raise":
             raise ValueError(f"cmax_set_events dropped {dropped} of {ev.shape[0]} events whose source pixel is outside the "
-                             f"{self.image_size[0]} x {self.image_size[1]} sensor (or NaN); use the leaf operators (Warp + "
+                             f"{self.image_size[0]} x {self.image_size[1]} sensor (or NaN) or whose time is not finite; use the leaf operators (Warp + "
                              "EventImageConverter) for such batches, set_keep_outside() for a 2-DoF objective, or crop / pad the sensor")
         if dropped:
             logger.warning(f"cmax_set_events dropped {dropped} of {ev.shape[0]} events: source pixel outside the "
-                           f"{self.image_size[0]} x {self.image_size[1]} sensor (or NaN); the fused path cannot keep them")
+                           f"{self.image_size[0]} x {self.image_size[1]} sensor (or NaN) or time not finite; the fused path cannot keep them")
         return self
 
     def set_event_weights(self, weights):

@@ -2632,10 +2632,13 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
         // (64M events: 1.41 ms per pass at 1024 digits, 0.53 at 32 -- cmax_radix_sort.h), so more, narrower passes win.
         // Un-binned handles: the whole key (8 pixel bits + tile bits) in equal digits -- every digit of it follows from the source pixel
         // alone.  Binned handles: the pixel byte first (the time bin, which needs the batch's extremes, sits above it), then the group bits.
-        int nb[8], sh[8], P = 0, shift = 0;
+        // (worst case: 2-bit digits -- un-binned 8 + 16 bits = 12 passes; fine binned, pixel byte + 21 bits = 12; coarse 24 bits = 12)
+        constexpr int kRsMaxPasses = 16;
+        int nb[kRsMaxPasses], sh[kRsMaxPasses], P = 0, shift = 0;
         static const int digit_bits = getenv("CMAX_RS_BITS") ? std::min(kRsMaxDigitBits, std::max(2, atoi(getenv("CMAX_RS_BITS")))) : kRsMaxDigitBits;  // tuning only
         auto split = [&](int total_bits) {
             const int parts = div_up(total_bits, digit_bits);
+            if (P + parts > kRsMaxPasses) return false;
             for (int q = 0, done = 0; q < parts; ++q) {
                 const int bits = div_up(total_bits - done, parts - q);
                 nb[P] = bits;
@@ -2643,17 +2646,20 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
                 shift += bits;
                 done += bits;
             }
+            return true;
         };
+        bool planned;
         if (T == 0) {
-            split(8 + gb);
+            planned = split(8 + gb);
         } else {
             if (key.fine) {
                 nb[P] = 8;
                 sh[P++] = 0;
                 shift = 8;
             }
-            split(gb);
+            planned = split(gb);
         }
+        CMAX_REQUIRE(planned, "sort_events: the radix sort's pass plan exceeds kRsMaxPasses");
         int maxbits = 0;
         for (int q = 0; q < P; ++q) maxbits = std::max(maxbits, nb[q]);
         const int nwg = (int)std::min<int64_t>(kRsMaxGroups, std::max<int64_t>(1, div_up(n_in, (int64_t)kRsChunk)));

@@ -92,8 +92,10 @@ __global__ void __launch_bounds__(kRsThreads) k_rs_time_extremes(SRC src, int64_
     double lo = INFINITY, hi = -INFINITY;
     for (int64_t i = (int64_t)blockIdx.x * kRsThreads + threadIdx.x; i < n; i += (int64_t)gridDim.x * kRsThreads) {
         const double t = src.time(i);
-        lo = fmin(lo, t);
-        hi = fmax(hi, t);
+        if (src.time_counts(t)) {
+            lo = fmin(lo, t);
+            hi = fmax(hi, t);
+        }
     }
 #pragma unroll
     for (int o = kWave / 2; o > 0; o >>= 1) {
@@ -137,8 +139,10 @@ k_rs_hist_src(SRC src, int64_t n, int64_t range, RsKey key, int bits, int *__res
         const SortItem it = key.fine ? src.pixel(i) : src.full(i);
         if (src.reduces_time()) {
             const double t = src.time(i);
-            lo = fmin(lo, t);
-            hi = fmax(hi, t);
+            if (src.time_counts(t)) {
+                lo = fmin(lo, t);
+                hi = fmax(hi, t);
+            }
         }
         if (it.ix < 0) {
             ++dropped;

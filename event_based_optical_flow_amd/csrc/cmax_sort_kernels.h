@@ -94,16 +94,21 @@ struct RawSource {
     int keep_outside;   // cmax_set_keep_outside: finite events off the sensor are packed at the nearest sensor pixel + a residual
     __device__ __forceinline__ bool reduces_time() const { return keyed != 0; }
     __device__ __forceinline__ double time(int64_t i) const { return (double)ev[4 * i + 2]; }
+    __device__ __forceinline__ static bool time_counts(double t) { return t - t == 0.0; }  // finite: takes part in the extremes
     __device__ __forceinline__ SortItem pixel(int64_t i) const {  // S1: the pixel only
-        return classify(ev[4 * i + 0], ev[4 * i + 1]);
+        return classify(ev[4 * i + 0], ev[4 * i + 1], ev[4 * i + 2]);
     }
-    __device__ __forceinline__ SortItem classify(T x, T y) const {
+    __device__ __forceinline__ SortItem classify(T x, T y, T t) const {
         SortItem it;
         const T fx = floor_t<T>(x), fy = floor_t<T>(y);
         it.ix = -1;
         it.iy = 0;
         it.frac = false;
         it.outside = false;
+        // An event whose time is not finite (NaN, +-inf) has no place in the batch: dropped like one without a pixel, in both pipelines
+        // (its normalised time would be NaN in word 1 and in tau64, and the un-warped image would still count it), and left out of
+        // the reduction of the batch's time extremes (time_counts)
+        if (!(t - t == (T)0)) return it;
         if (fx >= (T)0 && fx < (T)H && fy >= (T)0 && fy < (T)W) {  // NaN fails every comparison -> dropped
             it.ix = (int)fx;
             it.iy = (int)fy;
@@ -123,7 +128,7 @@ struct RawSource {
     };
     __device__ __forceinline__ Fetched fetch(int64_t i) const { return Fetched{ev[4 * i + 0], ev[4 * i + 1], ev[4 * i + 2]}; }
     __device__ __forceinline__ SortItem resolve(const Fetched &f, int64_t i) const {
-        SortItem it = classify(f.x, f.y);
+        SortItem it = classify(f.x, f.y, f.t);
         it.src = (int)i;
         if (it.ix >= 0) {
             const double rxd = (double)f.x - (double)it.ix, ryd = (double)f.y - (double)it.iy;
@@ -144,7 +149,7 @@ struct RawSource {
     }
     __device__ __forceinline__ SortItem full(int64_t i) const {
         const T x = ev[4 * i + 0], y = ev[4 * i + 1];
-        SortItem it = classify(x, y);
+        SortItem it = classify(x, y, ev[4 * i + 2]);
         it.src = (int)i;
         if (it.ix >= 0) {
             const double rxd = (double)x - (double)it.ix, ryd = (double)y - (double)it.iy;  // exact (on the sensor: ix = floor(x))
@@ -175,6 +180,7 @@ struct PackedSource {
     const int *src;        // source index of every packed event (SortItem::src)
     __device__ __forceinline__ bool reduces_time() const { return false; }
     __device__ __forceinline__ double time(int64_t) const { return 0.0; }
+    __device__ __forceinline__ static bool time_counts(double) { return true; }
     __device__ __forceinline__ SortItem pixel(int64_t i) const {
         SortItem it;
         const uint32_t pk = evp[i].x;
@@ -272,8 +278,10 @@ k_bucket_hist(SRC src, int64_t n, int ntc, int ntiles, int *__restrict__ tile_co
         const SortItem it = src.pixel(i);
         if (src.reduces_time()) {
             const double t = src.time(i);
-            lo = fmin(lo, t);
-            hi = fmax(hi, t);
+            if (src.time_counts(t)) {
+                lo = fmin(lo, t);
+                hi = fmax(hi, t);
+            }
         }
         if (it.ix < 0) {
             ++dropped;

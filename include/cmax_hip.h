@@ -189,7 +189,8 @@ int cmax_destroy(cmax_handle_t h);
 /* Pack (12-bit row | 12-bit col | 8-bit time bin ; fp32 normalised time ; optional fractional
  * residuals) and sort the batch: source tile (16 x 16 pixels) major, inside a tile by pixel
  * (n_time_bin == 0) or by time bin.  events: [n,4] dtype; events whose source pixel is outside
- * the sensor (or NaN) are dropped.  If have_tminmax, (tmin, tmax) are the GLOBAL batch extremes
+ * the sensor (or NaN), and events whose time is not finite, are dropped (the latter take no part in the
+ * time extremes either).  If have_tminmax, (tmin, tmax) are the GLOBAL batch extremes
  * (multi-GPU time slices); otherwise they are reduced from this call's events (all of them) on the
  * device.  n_time_bin > 0 precomputes the voxel bin of every event with the reference's fp64 edge
  * arithmetic (src/warp.py:342-345).  Blocks once (work list sized on the host); 0.10 ms per 1M events
@@ -466,7 +467,7 @@ int cmax_sizeof_objective(void);
 int cmax_copy_iwe(cmax_handle_t h, int k, float *iwe_out, cmax_stream_t stream);
 
 /* What cmax_set_events made of the last batch: events packed; events DROPPED because their source pixel lies
- * outside the sensor or is NaN (the fused path indexes the flow field and the source tiles with it; for 2-DoF
+ * outside the sensor or is NaN, or because their time is not finite (the fused path indexes the flow field and the source tiles with it; for 2-DoF
  * objectives cmax_set_keep_outside below keeps them, as the reference does -- the leaf operators cmax_warp_events +
  * cmax_vote have no such filter either way); whether
  * any source coordinate is fractional; whether the work list gives every group to one segment (owned groups:

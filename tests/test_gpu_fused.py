@@ -778,7 +778,8 @@ def test_packed_order(size, n, bins):
     TIME inside a pixel (k_run_time_sort: runs of up to 192 events -- the (48, 64) case holds ~195 per pixel, so both branches run);
     binned handles by (tile, bin).  Every input event appears exactly once with its pixel and its normalised time.  The two cases of
     8.5M / 9M events take the STABLE RADIX SORT (cmax_radix_sort.h, batches >= 8M events): every run by time whatever its length.
-    (CMAX_SORT=radix python -m pytest tests -m gpu runs the whole suite on that pipeline.)"""
+    (tests/test_gpu_radix_sort.py holds that pipeline to the exact stable order at small sizes, on every branch, in child processes that
+    set CMAX_SORT=radix.)"""
     ev = E.utils.generate_events(n, size[0], size[1], 0.0, 0.05, seed=3)
     h = E.CMaxHandle(size).set_events(ev, time_bin=bins)
     packed, gs = h.packed_events()
