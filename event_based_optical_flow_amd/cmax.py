@@ -86,6 +86,54 @@ def prepare_event_weights(weights, n: int) -> torch.Tensor:
     return to_device_tensor(w, "weights").contiguous()
 
 
+def ref_fractions(desc: CmaxObjective):
+    """The reference times of an objective as fractions d_k of the batch period (first 0, last 1)."""
+    return [0.0 if desc.ref_mode[k] == _lib.REF_FIRST else 1.0 if desc.ref_mode[k] == _lib.REF_LAST else float(desc.ref_frac[k])
+            for k in range(desc.n_ref)]
+
+
+def compose_events_grad(grad_events: torch.Tensor, csum: torch.Tensor, t: torch.Tensor, fractions: Sequence[float], normalize_t: bool,
+                        t_range: Optional[Tuple[float, float]] = None) -> torch.Tensor:
+    """The reference's `events.grad` [n, 4] in fp64 from what cmax_objective_event_grad returns (plain torch, any device):
+    grad_events [n, 3] = (dL/dx, dL/dy, C_e = sum_k dL/d dt_{e,k}), csum[k] = sum_e dL/d dt_{e,k}, t = the batch's times, fractions =
+    the objective's reference times d_k.  The x and y columns pass through and the polarity column is 0.  The time column is
+    C_e * d dt/d t_e plus what autograd routes through t.min() and t.max() (src/warp.py:201-259, t_ref = t_min + d (t_max - t_min)):
+        normalize_t:  dt = (t - t_ref) / P, P = t_max - t_min:  d dt/d t_e = 1 / P,  d dt/d t_min = (tau_e - 1) / P,  d dt/d t_max = -tau_e / P
+                      with tau = (t - t_min) / P -- the same for every reference time, so C_e is enough;
+        otherwise:    dt = t - t_ref:  d dt/d t_e = 1,  d dt/d t_min = -(1 - d_k),  d dt/d t_max = -d_k -- csum supplies the sums.
+    Ties at the minimum / maximum share the routed term evenly (torch.Tensor.min / max).  t_range: the (t_min, t_max) handed to
+    set_events for a time slice -- constants, nothing is routed.  Events with a non-finite time were not packed and take no part."""
+    ge = grad_events.detach().to(torch.float64)
+    t = t.detach().to(device=ge.device, dtype=torch.float64)
+    n = ge.shape[0]
+    out = torch.zeros((n, 4), dtype=torch.float64, device=ge.device)
+    if n == 0:
+        return out
+    out[:, 0:2] = ge[:, 0:2]
+    C = ge[:, 2]
+    finite = torch.isfinite(t)
+    if not bool(finite.any()):
+        return out
+    if t_range is None:
+        lo, hi = t[finite].min(), t[finite].max()
+    else:
+        lo, hi = (torch.as_tensor(v, dtype=torch.float64, device=ge.device) for v in t_range)
+    period = hi - lo
+    if normalize_t:
+        out[:, 2] = C / period
+        tau = torch.where(finite, (t - lo) / period, torch.zeros_like(t))
+        g_lo, g_hi = (C * (tau - 1.0)).sum() / period, -(C * tau).sum() / period
+    else:
+        out[:, 2] = C
+        d = torch.as_tensor(list(fractions), dtype=torch.float64, device=ge.device)
+        ck = csum.detach().to(device=ge.device, dtype=torch.float64)[: d.shape[0]]
+        g_lo, g_hi = -((1.0 - d) * ck).sum(), -(d * ck).sum()
+    if t_range is None:
+        at_lo, at_hi = finite & (t == lo), finite & (t == hi)
+        out[:, 2] += at_lo.to(torch.float64) * (g_lo / at_lo.sum()) + at_hi.to(torch.float64) * (g_hi / at_hi.sum())
+    return out
+
+
 class CMaxHandle:
     """One GPU workspace for one event batch (cmax_create / cmax_set_events / cmax_objective)."""
 
@@ -154,6 +202,8 @@ class CMaxHandle:
         self.time_bin = int(time_bin)
         self.time_slabs = 0
         self._n_in = int(ev.shape[0])
+        self._batch_t = ev[:, 2]  # a view, no copy: events_grad routes dL/dt through t.min() / t.max() with the batch's own times
+        self._batch_t_range = (float(tmin), float(tmax)) if have else None
         if w is not None:
             check(self._lib.cmax_set_event_weights(self._h, w.data_ptr(), F._code(w), w.shape[0], F._stream()))
         info = self.batch_info() if on_dropped != "ignore" else {"dropped": 0, "outside": 0}
@@ -358,6 +408,36 @@ class CMaxHandle:
         check(self._lib.cmax_objective_weight_grad(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
                                                    grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, F._stream()))
         return result, grad, grad_w
+
+    def evaluate_event_grad(self, desc: CmaxObjective, motion, want_grad: bool = True):
+        """One cmax_objective_event_grad call: (result, grad or None, grad_events, csum).  result and grad as `evaluate` returns them;
+        grad_events is float32 [n, 3] on the device in the order of the events handed to set_events: (dL/dx, dL/dy, C = sum_k dL/d dt_k),
+        dt_k the event's time offset as the warp uses it -- the first two are the reference's `events.grad[:, :2]`
+        (`self.events = ...requires_grad_()`, src/solver/patch_contrast_mixed.py:166), the third is what `events_grad` turns into its
+        time column; csum is float64 [4]: sum_e dL/d dt_{e,k} per reference time.  An unweighted handle means w = 1, events that were not
+        packed keep a row of zeros.  Deterministic handles and handles with a communicator raise NotImplementedError with the
+        library's text."""
+        m, desc = self._motion_arg(desc, motion)
+        result = torch.empty(8, dtype=torch.float64, device=self.device)
+        grad = None
+        if want_grad:
+            if desc.model == _lib.MODEL_2DOF:
+                grad = torch.empty(2, dtype=torch.float64, device=self.device)
+            else:
+                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+        n = int(getattr(self, "_n_in", 0))
+        buf = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)  # (an empty batch still hands over a valid pointer)
+        csum = torch.empty(4, dtype=torch.float64, device=self.device)
+        check(self._lib.cmax_objective_event_grad(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
+                                                  grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, csum.data_ptr(), F._stream()))
+        return result, grad, buf[:n], csum
+
+    def events_grad(self, desc: CmaxObjective, motion) -> torch.Tensor:
+        """The reference's `events.grad`, float64 [n, 4] on the device: evaluate_event_grad composed with the batch's times
+        (compose_events_grad; not a hot path).  The handle keeps a VIEW of the time column handed to set_events: the batch must not
+        have been modified in place since."""
+        _, _, ge, csum = self.evaluate_event_grad(desc, motion, want_grad=False)
+        return compose_events_grad(ge, csum, self._batch_t, ref_fractions(desc), bool(desc.normalize_t), self._batch_t_range)
 
     def prepare(self, desc: CmaxObjective, motion, want_grad: bool = True, dist: bool = False):
         """A prepared cmax_objective (dist: cmax_objective_dist) call for an inner loop that evaluates the SAME motion
@@ -763,6 +843,37 @@ class _FusedWeightedFn(torch.autograd.Function):
         return gm, gw, None, None
 
 
+class _FusedEventsFn(torch.autograd.Function):
+    """The fused loss on the tape in the motion, the events themselves (cmax_objective_event_grad + compose_events_grad) and, when
+    given, the per-event weights (one cmax_objective_weight_grad call more); the handle already holds the batch and the weights."""
+
+    @staticmethod
+    def forward(ctx, motion, events, weights, handle, desc):
+        result, grad, ge, csum = handle.evaluate_event_grad(desc, motion, want_grad=motion.requires_grad)
+        ctx.grad = grad
+        ctx.grad_ev = None
+        if events.requires_grad:
+            ctx.grad_ev = compose_events_grad(ge, csum, handle._batch_t, ref_fractions(desc), bool(desc.normalize_t), handle._batch_t_range)
+        ctx.grad_w = None
+        if weights is not None and weights.requires_grad:
+            ctx.grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=False)[2]
+            ctx.wdtype, ctx.wdevice = weights.dtype, weights.device
+        ctx.mdtype, ctx.mdevice = motion.dtype, motion.device
+        ctx.edtype, ctx.edevice = events.dtype, events.device
+        return result[0].to(motion.dtype if motion.dtype.is_floating_point else torch.float64)
+
+    @staticmethod
+    def backward(ctx, gout):
+        gm = ge = gw = None
+        if ctx.grad is not None:
+            gm = (ctx.grad.to(ctx.mdtype) * gout.to(ctx.grad.device).to(ctx.mdtype)).to(ctx.mdevice)
+        if ctx.grad_ev is not None:
+            ge = (ctx.grad_ev * gout.to(ctx.grad_ev.device).to(torch.float64)).to(ctx.edtype).to(ctx.edevice)
+        if ctx.grad_w is not None:
+            gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
+        return gm, ge, gw, None, None
+
+
 class ContrastObjective:
     """loss = objective(motion[, coarse_flow]) with the reference's cost names.
 
@@ -841,15 +952,25 @@ class ContrastObjective:
             loss = loss + combine(weight, value)
         return loss
 
-    def __call__(self, motion: torch.Tensor, coarse_flow: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None) -> torch.Tensor:
+    def __call__(self, motion: torch.Tensor, coarse_flow: Optional[torch.Tensor] = None, weights: Optional[torch.Tensor] = None,
+                 events: Optional[torch.Tensor] = None) -> torch.Tensor:
         """weights: None -- the loss of the handle as it stands, differentiable in `motion`.  A tensor [n] -- per-event weights of the
         handle's batch (the reference's `weight` on the autograd tape): the loss is differentiable in `motion` AND `weights`
         (either may not require grad); hybrid members, "inv" included, follow through `combine`, total_variation does not depend on
-        the weights.  Each such call pays set_event_weights: one gather plus its one synchronisation; the weights stay on the handle."""
+        the weights.  Each such call pays set_event_weights: one gather plus its one synchronisation; the weights stay on the handle.
+        events: an [n, 4] tensor that holds the batch the handle was given (checked by shape only) and requires grad -- the reference's
+        `events` leaf (src/solver/patch_contrast_mixed.py:166): backward fills `events.grad` [n, 4] (x, y, t, polarity = 0).  May be
+        combined with `weights`."""
         if weights is not None:
             if not isinstance(weights, torch.Tensor):
                 raise TypeError(f"weights must be a torch tensor, got {type(weights)}")
             self.handle.set_event_weights(weights.detach())
+        if events is not None:
+            if not isinstance(events, torch.Tensor):
+                raise TypeError(f"events must be a torch tensor, got {type(events)}")
+            n = int(getattr(self.handle, "_n_in", 0))
+            if tuple(events.shape) != (n, 4):
+                raise ValueError(f"events must be the handle's batch, [n, 4] = [{n}, 4], got {tuple(events.shape)}")
         loss = 0.0
         for name, weight, desc in self.terms:
             if desc is None:
@@ -859,8 +980,12 @@ class ContrastObjective:
                 if self.direction != "minimize":
                     value = -value
             else:
-                value = (_FusedFn.apply(motion, self.handle, desc) if weights is None
-                         else _FusedWeightedFn.apply(motion, weights, self.handle, desc))
+                if events is not None:
+                    value = _FusedEventsFn.apply(motion, events, weights, self.handle, desc)
+                elif weights is None:
+                    value = _FusedFn.apply(motion, self.handle, desc)
+                else:
+                    value = _FusedWeightedFn.apply(motion, weights, self.handle, desc)
             value = value.to(motion.device) if isinstance(motion, torch.Tensor) else value
             loss = loss + combine(weight, value)
         return loss

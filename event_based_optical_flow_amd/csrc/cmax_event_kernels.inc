@@ -1792,6 +1792,133 @@ k_weight_gather(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict
     }
 }
 
+// ---------------------------------------------------------------------------------------------
+// K3e: dL/d(event) per event (cmax_objective_event_grad), one workgroup per segment -- K3w's twin with the bilinear DIFFERENCES
+//     where K3w has the interpolation (the same window, the same published cells, consecutive slots, a FINISHED G image per
+//     reference time):
+//        gx = w [(1-b)(G10-G00) + b(G11-G01)],  gy = w [(1-a)(G01-G00) + a(G11-G10)]      (what cmax_vote_bwd returns per image)
+//        c  = dL/d(dt) = gx th0 + gy th1 (2-DoF: x' = x + dt theta)  |  -(gx f0 + gy f1) (dense / voxel: x' = x - dt f[src]),
+//     dt the time offset as the warp uses it; source pixel and bin are piecewise constant.  Slot l of the segment stores
+//     ge[plane 3 y + {0, 1, 2}][first + l] = (gx, gy, c), coalesced, no atomics; empty slots store nothing (the host clears the
+//     planes).  MODEL = -1: the un-warped events against dL/dI_orig -- the x and y planes only.  WEIGHTED: w = the slot's weight
+//     (load_slot_weights), else 1.  A kernel of its own: no existing instantiation changes (profiles/event_grad_resources.txt).
+// ---------------------------------------------------------------------------------------------
+template <class L, int MODEL, bool FRAC, bool WEIGHTED>
+__global__ void __launch_bounds__(L::kThr)
+k_event_grad_gather(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base, EvView ev,
+                    WarpParams wp, RefArgs ra, float *__restrict__ ge, int64_t plane) {
+    constexpr bool kFlow = MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL;
+    const int sidx = segment_of_block(nseg);
+    if (sidx >= nseg) return;
+    const int4 sg = segs[sidx];
+    const int4 *known = win_base + (int64_t)blockIdx.y * nseg + sidx;
+    ev.ev = evp;
+    EventLoads<L> el;
+    issue_event_loads<L, false>(evp, cev, sidx, sg, el);
+    wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
+    const float *__restrict__ img = ra.img[blockIdx.y];
+    __shared__ float s_win[L::kWinCap + kScratch];
+    unsigned rc[L::kEPT];
+    float fa[L::kEPT], fb[L::kEPT], fdt[L::kEPT];
+    int fsrc[L::kEPT];
+    const int lane = threadIdx.x & (kWave - 1);
+    auto g_at = [&](int r, int c) -> float { return img[pix_index(r, c, wp.Wp)]; };
+    auto load_window = [&](const Window &w) {  // G of the window, zero outside the image (flat walk, see k_grad)
+        const unsigned ustride = (unsigned)w.stride, magic = ((1u << 21) + ustride - 1u) / ustride;
+        const int wn = w.h * w.stride;
+        for (int i = threadIdx.x; i < wn; i += L::kThr) {
+            const unsigned r = mul24_u((unsigned)i, magic) >> 21, c = (unsigned)i - mul24_u(r, ustride);
+            const int R = w.r0 + (int)r, C = w.c0 + (int)c;
+            s_win[i] = ((int)c < w.w && (unsigned)R < (unsigned)wp.Hp && (unsigned)C < (unsigned)wp.Wp) ? g_at(R, C) : 0.f;
+        }
+    };
+    const unsigned *__restrict__ shifts = ra.shifts + ((int64_t)blockIdx.y * nseg + sidx) * L::kShiftWords;
+    bool live;
+    unsigned nib_unused;
+    const Window win = phase_warp<L, MODEL, FRAC, true, false, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused);
+    float fw[L::kEPT];  // (behind the warp, as in K1: not live through it)
+    if constexpr (WEIGHTED) load_slot_weights<L, false>(ra.wgt, sg, fw);
+    float th0 = 0.f, th1 = 0.f;
+    if (MODEL == CMAX_MODEL_2DOF) {  // theta as phase_warp reads it
+        if (wp.motion_f64) {
+            const int *mw = reinterpret_cast<const int *>(wp.motion);
+            th0 = (float)__hiloint2double(mw[1], mw[0]);
+            th1 = (float)__hiloint2double(mw[3], mw[2]);
+        } else {
+            th0 = wp.motion[0];
+            th1 = wp.motion[1];
+        }
+    }
+    if (threadIdx.x < kScratch) s_win[L::kWinCap + threadIdx.x] = 0.f;  // empty slots / masked corners read 0 from here
+    __syncthreads();
+    if (!live) return;  // (wave-uniform, behind the last barrier)
+    const int dummy = L::kDummy + lane;
+    const int stride = win.stride;
+    unsigned neg_origin = 0u - ((unsigned)(win.r0 + 16384) * (unsigned)win.stride + (unsigned)(win.c0 + 16384));
+    asm volatile("" : "+v"(neg_origin));  // (a VGPR: see fast_index)
+    const unsigned scratch = L::kWinCap + lane;
+    const int odd = sg.x & 1;
+    const int hw = wp.H * wp.W;
+    float *__restrict__ outx = ge + (int64_t)blockIdx.y * 3 * plane + ((int64_t)sg.x - odd);
+    float *__restrict__ outy = outx + plane;
+    float *__restrict__ outc = outy + plane;
+#pragma unroll
+    for (int j = 0; j < L::kEPT; ++j) {
+        float g[4];  // g[0] = G00 (row, col), g[1] = G10 (row+1, col), g[2] = G01 (row, col+1), g[3] = G11
+        if (!win.clipped) {  // fast window: the footprint is inside by construction
+            const int idx = fast_index(rc[j], neg_origin, win.stride, scratch);
+            g[0] = s_win[idx];
+            g[2] = s_win[idx + 1];
+            g[1] = s_win[idx + stride];
+            g[3] = s_win[idx + stride + 1];
+        } else {  // workgroup-uniform, rare: a corner outside the window reads global memory if it is inside the image (see k_grad)
+            const int row = (int)(rc[j] >> 16) - 16384, col = (int)(rc[j] & 0xFFFFu) - 16384;  // empty slot: far outside
+            const int lr = row - win.r0, lc = col - win.c0;
+            const bool r_in0 = (unsigned)lr < (unsigned)win.h, r_in1 = (unsigned)(lr + 1) < (unsigned)win.h;
+            const bool c_in0 = (unsigned)lc < (unsigned)win.w, c_in1 = (unsigned)(lc + 1) < (unsigned)win.w;
+            const int base = lr * win.stride + lc;
+            g[0] = s_win[(r_in0 && c_in0) ? base : dummy];
+            g[1] = s_win[(r_in1 && c_in0) ? base + stride : dummy];
+            g[2] = s_win[(r_in0 && c_in1) ? base + 1 : dummy];
+            g[3] = s_win[(r_in1 && c_in1) ? base + stride + 1 : dummy];
+            if (rc[j] != 0u) {
+#pragma unroll 1
+                for (int q = 0; q < 4; ++q) {
+                    const int r = row + (q & 1), c = col + (q >> 1);
+                    const bool in_win = (unsigned)(r - win.r0) < (unsigned)win.h && (unsigned)(c - win.c0) < (unsigned)win.w;
+                    if (!in_win && (unsigned)r < (unsigned)wp.Hp && (unsigned)c < (unsigned)wp.Wp) {
+                        const float v = g_at(r, c);
+                        g[0] = q == 0 ? v : g[0];
+                        g[1] = q == 1 ? v : g[1];
+                        g[2] = q == 2 ? v : g[2];
+                        g[3] = q == 3 ? v : g[3];
+                    }
+                }
+            }
+        }
+        const float a = fa[j], b = fb[j];
+        float gx = (1.f - b) * (g[1] - g[0]) + b * (g[3] - g[2]);
+        float gy = (1.f - a) * (g[2] - g[0]) + a * (g[3] - g[1]);
+        if constexpr (WEIGHTED) {
+            gx *= fw[j];
+            gy *= fw[j];
+        }
+        const int l = L::kEPT * (int)threadIdx.x + j;
+        if ((unsigned)(l - odd) < (unsigned)sg.y) {
+            outx[l] = gx;
+            outy[l] = gy;
+            if (MODEL == CMAX_MODEL_2DOF) {
+                outc[l] = fmaf(gx, th0, gy * th1);
+            } else if (kFlow) {  // the flow at the event's source pixel (and bin), as the warp read it
+                const unsigned key = (unsigned)fsrc[j];
+                const int ix = (int)(key & 0xFFFu), iy = (int)((key >> 12) & 0xFFFu), bin = (int)(key >> 24);
+                const int64_t fi = (MODEL == CMAX_MODEL_VOXEL ? (int64_t)bin * 2 * hw : (int64_t)0) + pix_index(ix, iy, wp.W);
+                outc[l] = -fmaf(gx, wp.motion[fi], gy * wp.motion[fi + hw]);
+            }
+        }
+    }
+}
+
 template <class L, int MODEL, bool FRAC>
 // dimg64 (deterministic mode): the window's integers (and the overflow of a clipped window, rounded at the same scale) go to a
 // 64-bit integer image with integer atomics -- exact in any order; k_fixed_to_image rounds the finished sums once

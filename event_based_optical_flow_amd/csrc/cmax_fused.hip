@@ -207,6 +207,12 @@ struct cmax_handle_s {
     float *gw_G = nullptr, *gw_Gt = nullptr, *gw_packed = nullptr;
     int64_t gw_plane = 0;
     bool general_only = false;
+    // cmax_objective_event_grad: (gx, gy, c) per packed event, three planes of ge_plane floats per reference time + two for the un-warped image,
+    // and the scatter's per-workgroup partial sums of c ([4][ge_part_cap]); allocated on first use, grown on demand
+    float *ge_packed = nullptr;
+    int64_t ge_plane = 0;
+    double *ge_part = nullptr;
+    int64_t ge_part_cap = 0;
     // staging SoA of the two-level sort (tile buckets before the per-tile ordering)
     uint2 *evp_alt = nullptr;
     float *rx_alt = nullptr, *ry_alt = nullptr;
@@ -2983,6 +2989,8 @@ int cmax_destroy(cmax_handle_t h) {
     dev_free(&h->gw_G);
     dev_free(&h->gw_Gt);
     dev_free(&h->gw_packed);
+    dev_free(&h->ge_packed);
+    dev_free(&h->ge_part);
     dev_free(&h->cev);
     dev_free(&h->evp_alt);
     dev_free(&h->rx_alt);
@@ -3972,27 +3980,115 @@ static void launch_weight_gather(cmax_handle_s *h, const EvView &ev, const WarpP
     });
 }
 
-// behind objective_eval of the same call: its images, statistics, windows and cell offsets are the handle's current ones
-static int weight_grad_finish(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *orig_raw, float *grad_w, hipStream_t s) {
+// cmax_objective_event_grad: grad_events[src[i]] = (sum_k gx, sum_k gy, sum_k c) over the planes of ge_packed in index order (+ the un-warped image's
+// x and y planes), behind a zero fill of grad_events.  csum[k] = sum_i c_{i,k} in fp64 without atomics: a fixed tree per workgroup into
+// part[k][block], folded by k_event_csum_finish in a fixed order -- the same bits on every run.
+constexpr int kEventGradPlanes = 14;  // three per reference time (at most four) + two for the un-warped image
+__device__ __forceinline__ double block_sum_256(double v, double *s_red) {  // every thread of a 256-thread workgroup; the sum in thread 0
+    __syncthreads();
+    s_red[threadIdx.x] = v;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) s_red[threadIdx.x] += s_red[threadIdx.x + w];
+        __syncthreads();
+    }
+    return s_red[0];
+}
+__global__ void __launch_bounds__(256) k_event_grad_scatter(const float *__restrict__ ge, int64_t plane, int n_ref, int has_orig, const int *__restrict__ src, int64_t n,
+                                                           float *__restrict__ grad_events, double *__restrict__ part, int64_t n_blocks) {
+    __shared__ double s_red[256];
+    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool valid = i < n;
+    float gx = 0.f, gy = 0.f, c = 0.f;
+    for (int k = 0; k < n_ref; ++k) {
+        const float *p = ge + (int64_t)(3 * k) * plane;
+        const float ck = valid ? p[2 * plane + i] : 0.f;
+        if (valid) {
+            gx += p[i];
+            gy += p[plane + i];
+            c += ck;
+        }
+        const double tot = block_sum_256((double)ck, s_red);
+        if (threadIdx.x == 0) part[(int64_t)k * n_blocks + blockIdx.x] = tot;
+    }
+    if (!valid) return;
+    if (has_orig) {
+        const float *p = ge + (int64_t)(3 * n_ref) * plane;
+        gx += p[i];
+        gy += p[plane + i];
+    }
+    float *out = grad_events + 3 * (int64_t)src[i];
+    out[0] = gx;
+    out[1] = gy;
+    out[2] = c;
+}
+// csum[k] (blockIdx.x = k < 4): thread t adds part[k][t], part[k][t + 256], ... in that order, then the tree; entries k >= n_ref are zero
+__global__ void __launch_bounds__(256) k_event_csum_finish(const double *__restrict__ part, int64_t n_blocks, int n_ref, double *__restrict__ csum) {
+    __shared__ double s_red[256];
+    const int k = blockIdx.x;
+    double a = 0.0;
+    if (k < n_ref)
+        for (int64_t b = threadIdx.x; b < n_blocks; b += 256) a += part[(int64_t)k * n_blocks + b];
+    const double tot = block_sum_256(a, s_red);
+    if (threadIdx.x == 0) csum[k] = tot;
+}
+
+// K3e of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
+template <int MODEL>
+static void launch_event_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_img, int plane0, hipStream_t s) {
+    const dim3 grid(8 * ((h->nseg + 7) / 8), n_img);
+    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // as K1 (launch_vote)
+    RefArgs ra = ra_in;
+    if (h->weighted) ra.wgt = h->w_packed;
+    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            with_bool(h->weighted, [&](auto wgt) {
+                hipLaunchKernelGGL((k_event_grad_gather<L, MODEL, frac.value, wgt.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev,
+                                   wp, ra, h->ge_packed + (int64_t)plane0 * h->ge_plane, h->ge_plane);
+            });
+        });
+    });
+}
+
+// behind objective_eval of the same call: its images, statistics, windows and cell offsets are the handle's current ones.
+// grad_events == nullptr: dL/dw into grad_w (one plane per image); else dL/d(event) into grad_events [n][3] and csum[4] (three planes
+// per reference time, two for the un-warped image)
+static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *orig_raw, float *grad_w, float *grad_events, double *csum,
+                            hipStream_t s) {
     const int Hp = h->Hp, Wp = h->Wp, nr = d->n_ref;
     const int64_t npix = (int64_t)Hp * Wp;
-    const int n_planes = nr + (d->normalized ? 1 : 0);
+    const bool events = grad_events != nullptr;
+    const int n_planes = events ? 3 * nr + (d->normalized ? 2 : 0) : nr + (d->normalized ? 1 : 0);
     int rc = 0;
     if (!h->gw_G) {
         rc = dev_alloc(h, &h->gw_G, 5 * npix);
         if (!rc) rc = dev_alloc(h, &h->gw_Gt, 5 * npix);
         if (rc) return rc;
     }
-    if (h->n > h->gw_plane) {  // sized like w_packed
+    float **packed = events ? &h->ge_packed : &h->gw_packed;
+    int64_t *plane_len = events ? &h->ge_plane : &h->gw_plane;
+    if (h->n > *plane_len) {  // sized like w_packed
         CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->gw_packed);
-        h->gw_plane = 0;
+        dev_free(packed);
+        *plane_len = 0;
         const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
-        rc = dev_alloc(h, &h->gw_packed, 5 * plane);
+        rc = dev_alloc(h, packed, (events ? kEventGradPlanes : 5) * plane);
         if (rc) return rc;
-        h->gw_plane = plane;
+        *plane_len = plane;
     }
-    CMAX_CHECK_HIP(hipMemsetAsync(h->gw_packed, 0, (size_t)n_planes * h->gw_plane * sizeof(float), s));
+    if (events) {  // per-workgroup partial sums of the scatter (csum), [4][blocks]
+        const int64_t blocks = div_up(h->n, 256);
+        if (blocks > h->ge_part_cap) {
+            CMAX_CHECK_HIP(hipStreamSynchronize(s));
+            dev_free(&h->ge_part);
+            h->ge_part_cap = 0;
+            rc = dev_alloc(h, &h->ge_part, 4 * blocks);
+            if (rc) return rc;
+            h->ge_part_cap = blocks;
+        }
+    }
+    CMAX_CHECK_HIP(hipMemsetAsync(*packed, 0, (size_t)n_planes * *plane_len * sizeof(float), s));
     const ObjParams op = obj_params(h, d);
     double k0 = 0, k1 = 0;
     if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
@@ -4024,7 +4120,10 @@ static int weight_grad_finish(cmax_handle_s *h, const cmax_objective_t *d, const
         ra.win = h->d_win;
         ra.shifts = h->d_shifts;
         const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
-        with_model(d->model, [&](auto m) { launch_weight_gather<m.value>(h, ev, wp, ra, nr, 0, s); });
+        with_model(d->model, [&](auto m) {
+            if (events) launch_event_gather<m.value>(h, ev, wp, ra, nr, 0, s);
+            else launch_weight_gather<m.value>(h, ev, wp, ra, nr, 0, s);
+        });
         CMAX_CHECK_LAUNCH();
     }
     if (d->normalized) {  // one more plane: the un-warped events against G_orig, behind a K1 launch that only publishes their windows
@@ -4042,10 +4141,18 @@ static int weight_grad_finish(cmax_handle_s *h, const cmax_objective_t *d, const
         h->win_generation = ~(uint64_t)0;
         ra.windows_only = 0;
         ra.img[0] = h->gw_G + 4 * npix;
-        launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
+        if (events) launch_event_gather<-1>(h, ev, wp, ra, 1, 3 * nr, s);
+        else launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
         CMAX_CHECK_LAUNCH();
     }
-    hipLaunchKernelGGL(k_weight_grad_scatter, dim3(div_up(h->n, 256)), dim3(256), 0, s, (const float *)h->gw_packed, h->gw_plane, n_planes, (const int *)h->src, h->n, grad_w);
+    if (events) {
+        const int64_t blocks = div_up(h->n, 256);
+        hipLaunchKernelGGL(k_event_grad_scatter, dim3(blocks), dim3(256), 0, s, (const float *)h->ge_packed, h->ge_plane, nr, d->normalized ? 1 : 0, (const int *)h->src, h->n,
+                           grad_events, h->ge_part, blocks);
+        hipLaunchKernelGGL(k_event_csum_finish, dim3(4), dim3(256), 0, s, (const double *)h->ge_part, blocks, nr, csum);
+    } else {
+        hipLaunchKernelGGL(k_weight_grad_scatter, dim3(div_up(h->n, 256)), dim3(256), 0, s, (const float *)h->gw_packed, h->gw_plane, n_planes, (const int *)h->src, h->n, grad_w);
+    }
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -4079,7 +4186,36 @@ int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const
     rc = objective_eval(h, d, motion, result, grad, s, nullptr);
     h->general_only = false;
     if (rc || h->n == 0) return rc;
-    return weight_grad_finish(h, d, motion, orig_raw, grad_w, s);
+    return per_event_finish(h, d, motion, orig_raw, grad_w, nullptr, nullptr, s);
+}
+
+int cmax_objective_event_grad(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad, float *grad_events,
+                              int64_t n, double *csum, cmax_stream_t stream) {
+    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    CMAX_REQUIRE(result && csum && (grad_events || n == 0), "objective_event_grad: result / csum / grad_events (grad_events may be NULL only for n == 0)");
+    CMAX_REQUIRE(n == h->n_in, "objective_event_grad: n must equal the n of the last cmax_set_events (one row per event, in the caller's order)");
+    if (h->deterministic) {
+        set_error("objective_event_grad: not built for deterministic mode (cmax_set_deterministic)");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (h->comm) {
+        set_error("objective_event_grad: not built for a handle with a communicator (cmax_comm_init)");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_events, 0, (size_t)n * 3 * sizeof(float), s));
+    CMAX_CHECK_HIP(hipMemsetAsync(csum, 0, 4 * sizeof(double), s));
+    // the general path and the un-warped image voted again, as cmax_objective_weight_grad
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const float *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
+    h->general_only = true;
+    if (d->normalized) h->orig_valid = false;
+    rc = objective_eval(h, d, motion, result, grad, s, nullptr);
+    h->general_only = false;
+    if (rc || h->n == 0) return rc;
+    return per_event_finish(h, d, motion, orig_raw, nullptr, grad_events, csum, s);
 }
 
 int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad,

@@ -293,6 +293,29 @@ int cmax_objective(cmax_handle_t h, const cmax_objective_t *desc_host, const voi
 int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion, double *result,
                                void *grad /* may be NULL */, float *grad_w, int64_t n, cmax_stream_t stream);
 
+/* The same evaluation plus dL/d(event), the third leaf of the reference's autograd graph: its solvers mark the events themselves as a
+ * leaf (`self.events = torch.from_numpy(events).double().requires_grad_()`, src/solver/patch_contrast_mixed.py:166, and the pyramid
+ * solver likewise), so `events.grad` exists after `backward()` through the warp (src/warp.py:254-259, 303-307, 506-515) and the
+ * bilinear vote (src/event_image_converter.py:316-372).  Row e of grad_events, fp32 [n][3] in the CALLER'S event order:
+ *     [0], [1]  dL/dx_e, dL/dy_e (x = row) = sum_k w_e (dL/dx'_e,k, dL/dy'_e,k)  (+ the same pair from G_orig at the un-warped position for
+ *               the normalised and multi-focal costs),  dL/dx' = (1-b)(G10-G00) + b(G11-G01),  dL/dy' = (1-a)(G01-G00) + a(G11-G10)
+ *               -- what cmax_vote_bwd returns as (gx, gy) per image; cell and fractions as the vote decided them, a corner outside the
+ *               padded image or outside the region the cost sums over reads 0; w_e = 1 on an unweighted handle;
+ *     [2]       C_e = sum_k c_e,k,  c_e,k = dL/d(dt_e,k): the derivative with respect to the event's time offset AS THE WARP USES IT
+ *               (normalised or raw, as normalize_t says): w_e (gx theta_x + gy theta_y) for 2-DoF, -w_e (gx f_x[src] + gy f_y[src]) for a
+ *               dense flow, the same with the flow of the event's bin for a voxel flow; source pixel and bin are piecewise constant,
+ *               as in the reference's autograd.
+ * csum: device double[4], csum[k] = sum_e c_e,k per reference time in fp64 (entries k >= n_ref are zero) -- with C_e and the events'
+ * times this is all the chain rule through t.min() / t.max() needs (CMaxHandle.events_grad composes the reference's [n,4]).
+ * result[8] and grad: exactly as cmax_objective (grad may be NULL).  n = the n given to cmax_set_events (CMAX_EINVAL otherwise); events
+ * that were not packed keep a row of zeros; an empty handle returns zeros.  Asynchronous on `stream`; the output is the same bits on
+ * every run for the same images (no atomics behind the evaluation).  Works wherever cmax_objective_weight_grad works; the evaluation
+ * takes the general path, `k_event_grad_gather` stores three packed-order planes per reference time (two for the un-warped image),
+ * `k_event_grad_scatter` sums them into the caller's order.  Device memory on first use: 56 B per event + 10 images.
+ * CMAX_EUNSUPPORTED on a deterministic handle and on one that holds a communicator.                                                  */
+int cmax_objective_event_grad(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion, double *result,
+                              void *grad /* may be NULL */, float *grad_events, int64_t n, double *csum, cmax_stream_t stream);
+
 /* The same evaluation with its results delivered TO THE HOST -- what an optimiser written in C calls once per iteration
  * (the reference's TorchWrapper.get_value_and_grad ends in .cpu().numpy(), src/solver/scipy_autograd/torch_wrapper.py:46-49):
  * enqueues the evaluation and the copies on `stream` and returns when result_host[8] and grad_host (double[2] for 2DOF, else
