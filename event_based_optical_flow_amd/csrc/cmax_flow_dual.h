@@ -47,6 +47,12 @@ template <typename T>
 __device__ __forceinline__ Dual<T> d_max0(Dual<T> a) { return Dual<T>(a.v > (T)0 ? a.v : (T)0, d_dmax0(a) * a.d); }
 template <typename T>
 __device__ __forceinline__ Dual<T> d_min0(Dual<T> a) { return Dual<T>(a.v < (T)0 ? a.v : (T)0, d_dmin0(a) * a.d); }
+// [a > 0] a and [a < 0] a as the Burgers term has them: max / min(sign(a), 0) * a.  The selector comes out of sign(), which is 0 at
+// a == 0 and carries no derivative, so unlike d_max0 / d_min0 there is no 1/2 at the tie: value and tangent are both switched off.
+template <typename T>
+__device__ __forceinline__ Dual<T> d_pos_part(Dual<T> a) { return a.v > (T)0 ? a : Dual<T>(); }
+template <typename T>
+__device__ __forceinline__ Dual<T> d_neg_part(Dual<T> a) { return a.v < (T)0 ? a : Dual<T>(); }
 template <typename T>
 __device__ __forceinline__ Dual<T> d_abs(Dual<T> a) { return Dual<T>(a.v < (T)0 ? -a.v : a.v, d_sgn(a) * a.d); }
 
@@ -126,8 +132,8 @@ __device__ __forceinline__ void flow_step_adj_dual_core(AU U, AV V, SU GU, SV GV
         const N one((T)1, (T)0);
         // channel u
         N self_u = gnu * (one - d_abs(u) * tau);  // d(u|u|/2)/du = |u|
-        GU(im, j, gnu * (-d_max0(ub)) * mt);
-        GU(ip, j, gnu * d_min0(uf) * mt);
+        GU(im, j, gnu * (-d_pos_part(ub)) * mt);
+        GU(ip, j, gnu * d_neg_part(uf) * mt);
         N self_v = gnu * (u_dy_back * d_dmax0(v) + u_dy_forw * d_dmin0(v)) * mt;
         const N mvp = d_max0(v), mvn = d_min0(v);
         if (j > 0) {
@@ -140,8 +146,8 @@ __device__ __forceinline__ void flow_step_adj_dual_core(AU U, AV V, SU GU, SV GV
         }
         // channel v
         self_v = self_v + gnv * (one - d_abs(v) * tau);
-        GV(i, jm, gnv * (-d_max0(vb)) * mt);
-        GV(i, jp, gnv * d_min0(vf) * mt);
+        GV(i, jm, gnv * (-d_pos_part(vb)) * mt);
+        GV(i, jp, gnv * d_neg_part(vf) * mt);
         self_u = self_u + gnv * (v_dx_back * d_dmax0(u) + v_dx_forw * d_dmin0(u)) * mt;
         const N mup = d_max0(u), mun = d_min0(u);
         if (i > 0) {
