@@ -605,7 +605,9 @@ class CMaxHandle:
         return images[: n_images.value]
 
     def objective_finish(self, desc: CmaxObjective, motion, images: torch.Tensor, want_grad: bool = True):
-        """Loss from the (globally reduced) images, gradient contribution of this handle's events."""
+        """Loss from the (globally reduced) images, gradient contribution of this handle's events.
+        Without a blur (sigma == 0) the handle keeps pointers into `images` instead of a copy: a later last_iwe() reads that
+        tensor's memory, so keep the tensor alive (and unchanged) until then -- a freed one gives stale values with no error."""
         m, desc = self._motion_arg(desc, motion)
         images = images.contiguous()
         result = torch.empty(8, dtype=torch.float64, device=self.device)
@@ -795,7 +797,8 @@ class CMaxHandle:
         return {n: (ms[i], cnt[i]) for i, n in enumerate(names)}
 
     def last_iwe(self, k: int = 0) -> torch.Tensor:
-        """Copy of the IWE of reference time k of the last evaluation (fp32 [Hp, Wp])."""
+        """Copy of the IWE of reference time k of the last evaluation (fp32 [Hp, Wp]).  After objective_finish with sigma == 0 this
+        reads the `images` tensor the caller handed over, which must still be alive (see there)."""
         out = torch.empty(self.padded_size, dtype=torch.float32, device=self.device)
         check(self._lib.cmax_copy_iwe(self._h, int(k), out.data_ptr(), F._stream()))
         return out

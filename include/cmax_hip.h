@@ -378,6 +378,7 @@ int cmax_objective_hvp(cmax_handle_t h, const cmax_objective_t *desc_host, const
  *                          gradient contribution of THIS slice's events
  *   -- caller all-reduces (sum) grad --
  * images: fp32 [5, Hp, Wp] caller-owned.  cmax_objective == vote + finish on internal images.
+ * Without a blur the handle keeps POINTERS into `images` for cmax_copy_iwe (see there): keep the buffer until the image was read.
  * `motion` of the finish call must be the buffer AND the values of the preceding vote call: the gather re-uses
  * the LDS windows the vote derived for every segment.                                          */
 int cmax_objective_vote(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion,
@@ -486,7 +487,9 @@ int cmax_read_profile_all(cmax_handle_t h, double *total_ms_host, int64_t *count
 int cmax_sizeof_objective(void);
 
 /* Copy the fp32 IWE [Hp,Wp] of reference time k of the last cmax_objective call (the image the
- * contrast was evaluated on, i.e. blurred when sigma > 0) into iwe_out, on `stream`.          */
+ * contrast was evaluated on, i.e. blurred when sigma > 0) into iwe_out, on `stream`.
+ * After cmax_objective_finish WITHOUT a blur (sigma == 0) that image is the caller's own `images` buffer, which the library
+ * does not copy: it has to stay allocated and unchanged until this call has run, or stale memory is copied with no error.      */
 int cmax_copy_iwe(cmax_handle_t h, int k, float *iwe_out, cmax_stream_t stream);
 
 /* What cmax_set_events made of the last batch: events packed; events DROPPED because their source pixel lies
