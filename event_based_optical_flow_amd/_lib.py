@@ -44,6 +44,22 @@ class CmaxObjective(ctypes.Structure):
     ]
 
 
+class CmaxIwes(ctypes.Structure):
+    """Mirror of cmax_iwes_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("model", ctypes.c_int32),
+        ("normalize_t", ctypes.c_int32),
+        ("n_ref", ctypes.c_int32),
+        ("ref_mode", ctypes.c_int32 * 4),
+        ("ref_frac", ctypes.c_double * 4),
+        ("sigma", ctypes.c_double),
+        ("T", ctypes.c_int32),
+        ("motion_dtype", ctypes.c_int32),
+        ("with_orig", ctypes.c_int32),
+    ]
+
+
 class CmaxPatchObjective(ctypes.Structure):
     """Mirror of cmax_patch_objective_t (include/cmax_hip.h)."""
 
@@ -121,6 +137,11 @@ SIGNATURES = {
     "cmax_objective": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_weight_grad": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "cmax_objective_event_grad": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp]),
+    "cmax_sizeof_iwes": (c_int, []),
+    "cmax_iwes": (c_int, [c_vp, ctypes.POINTER(CmaxIwes), c_vp, c_vp, c_vp]),
+    "cmax_iwes_vjp": (c_int, [c_vp, ctypes.POINTER(CmaxIwes), c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "cmax_iwes_jvp": (c_int, [c_vp, ctypes.POINTER(CmaxIwes), c_vp, c_vp, c_vp, c_vp]),
+    "cmax_iwes_vjp_tan": (c_int, [c_vp, ctypes.POINTER(CmaxIwes), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_host": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_has_raw": (c_int, [c_vp, ctypes.POINTER(CmaxObjective)]),
     "cmax_objective_raw": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_vp, c_vp]),
@@ -199,6 +220,8 @@ def load():
             fn.argtypes = args
         if lib.cmax_sizeof_objective() != ctypes.sizeof(CmaxObjective):
             raise RuntimeError("cmax_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_iwes() != ctypes.sizeof(CmaxIwes):
+            raise RuntimeError("cmax_iwes_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_patch_objective() != ctypes.sizeof(CmaxPatchObjective):
             raise RuntimeError("cmax_patch_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_abi_version() != ABI_VERSION:

@@ -16,7 +16,7 @@ import torch
 
 from . import _lib
 from . import functional as F
-from ._lib import CmaxObjective, check
+from ._lib import CmaxIwes, CmaxObjective, check
 from .array_types import to_device_tensor
 from .costs.hybrid import combine
 
@@ -33,6 +33,12 @@ _COST_TABLE = {
     "multi_focal_normalized_gradient_magnitude": (_lib.COST_GRADMAG, 1, (("last", 1.0), ("first", 1.0), ("middle", 2.0))),
 }
 FUSED_COSTS = tuple(_COST_TABLE)
+
+
+def _cost_registry():
+    from . import costs  # (lazy: the costs package is imported after this module)
+
+    return costs.functions
 
 
 def make_descriptor(cost: str, motion_model: str, direction: str = "minimize", sigma: float = 0.0,
@@ -201,6 +207,7 @@ class CMaxHandle:
                                         F._stream()))
         self.time_bin = int(time_bin)
         self.time_slabs = 0
+        self._batch_id = getattr(self, "_batch_id", 0) + 1  # fused_iwes: a backward pass refuses a handle that holds another batch
         self._n_in = int(ev.shape[0])
         self._batch_t = ev[:, 2]  # a view, no copy: events_grad routes dL/dt through t.min() / t.max() with the batch's own times
         self._batch_t_range = (float(tmin), float(tmax)) if have else None
@@ -593,6 +600,96 @@ class CMaxHandle:
         check(self._lib.cmax_objective_hvp(self._h, ctypes.byref(desc), m.data_ptr(), un.data_ptr(), hv.data_ptr(), F._stream()))
         return hv * umax.to(hv.dtype)
 
+    # -- the image of warped events as a differentiable layer (cmax_iwes*, see fused_iwes) ---------------------------
+    def _iwes_args(self, motion, motion_model: str, directions, sigma: float, normalize_t: bool, with_orig: bool):
+        if motion_model not in F.MODEL_CODES:
+            raise KeyError(motion_model)
+        directions = (directions,) if isinstance(directions, (str, int, float)) else tuple(directions)
+        if not 1 <= len(directions) <= 4:
+            raise ValueError(f"1 to 4 reference times, got {len(directions)}")
+        m = self._motion32(motion)
+        d = CmaxIwes()
+        d.model = F.MODEL_CODES[motion_model]
+        d.normalize_t = int(bool(normalize_t))
+        d.n_ref = len(directions)
+        for k, ref_dir in enumerate(directions):
+            d.ref_mode[k], d.ref_frac[k] = F.direction_to_ref(ref_dir)
+        d.sigma = float(sigma)
+        d.T = int(m.shape[0]) if d.model == _lib.MODEL_VOXEL else 0
+        d.motion_dtype = _lib.F32
+        d.with_orig = int(bool(with_orig))
+        return m, d
+
+    def _iwes_planes(self, t, n_planes: int, what: str) -> torch.Tensor:
+        t = to_device_tensor(t, what).detach().to(torch.float32).contiguous()
+        if tuple(t.shape) != (n_planes,) + self.padded_size:
+            raise ValueError(f"{what} must be [{n_planes}, {self.padded_size[0]}, {self.padded_size[1]}], got {tuple(t.shape)}")
+        return t
+
+    def _iwes_grad_like(self, d: CmaxIwes, m: torch.Tensor) -> torch.Tensor:
+        if d.model == _lib.MODEL_2DOF:
+            return torch.empty(2, dtype=torch.float64, device=self.device)
+        return torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+
+    def iwes(self, motion, motion_model: str, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
+             with_orig: bool = False) -> torch.Tensor:
+        """The images of warped events at every reference time in `directions` in one call (cmax_iwes): fp32 [K, Hp, Wp], K =
+        len(directions) (+ 1 with_orig: the un-warped image last) -- image k is what `iwe(motion, motion_model, directions[k], ...)`
+        returns, the weighted image on a weighted handle."""
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        out = torch.empty((d.n_ref + d.with_orig,) + self.padded_size, dtype=torch.float32, device=self.device)
+        check(self._lib.cmax_iwes(self._h, ctypes.byref(d), m.data_ptr(), out.data_ptr(), F._stream()))
+        return out
+
+    def iwes_vjp(self, motion, motion_model: str, gimages, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
+                 with_orig: bool = False, want_grad_w: bool = False):
+        """(sum_k J_k^T gimages[k], grad_w or None) -- cmax_iwes_vjp: the motion gradient of <gimages, iwes(motion)> with the cells
+        held fixed (fp64 [2] for 2-DoF, else fp32 with the motion's shape) and, on request, its derivative with respect to the
+        per-event weights (fp32 [n] in the order of the events handed to set_events, not multiplied by w).  gimages: the shape of
+        `iwes`' result, the caller's dL/dI.  The result is that of the handle's state (order, weights) at the time of THIS call."""
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        g = self._iwes_planes(gimages, d.n_ref + d.with_orig, "gimages")
+        grad = self._iwes_grad_like(d, m)
+        n = int(getattr(self, "_n_in", 0))
+        buf = torch.empty(max(n, 1), dtype=torch.float32, device=self.device) if want_grad_w else None
+        check(self._lib.cmax_iwes_vjp(self._h, ctypes.byref(d), m.data_ptr(), g.data_ptr(), grad.data_ptr(),
+                                      buf.data_ptr() if want_grad_w else None, n, F._stream()))
+        return grad, (buf[:n] if want_grad_w else None)
+
+    def iwes_jvp(self, motion, motion_model: str, tangent, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
+                 with_orig: bool = False) -> torch.Tensor:
+        """J_k tangent per reference time, fp32 [len(directions), Hp, Wp] (cmax_iwes_jvp).  The tangent is brought to unit max-norm
+        for the fixed-point derivative votes and the result scaled back, as `hvp` does."""
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, False)
+        out = torch.zeros((d.n_ref,) + self.padded_size, dtype=torch.float32, device=self.device)
+        u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
+        umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
+        if float(umax) == 0.0:
+            return out
+        un = (u / umax).to(torch.float32).contiguous()
+        check(self._lib.cmax_iwes_jvp(self._h, ctypes.byref(d), m.data_ptr(), un.data_ptr(), out.data_ptr(), F._stream()))
+        return out * umax.to(torch.float32)
+
+    def iwes_vjp_tan(self, motion, motion_model: str, tangent, gimages, gimages_tan=None, directions=("first",), sigma: float = 0.0,
+                     normalize_t: bool = True, with_orig: bool = False) -> torch.Tensor:
+        """d/d(eps) [ J(motion + eps tangent)^T (gimages + eps gimages_tan) ] at eps = 0, summed over the reference times
+        (cmax_iwes_vjp_tan); gimages_tan None = 0: the mixed term alone.  With gimages_tan = (d2 l / dI2) J tangent this is the exact
+        Hessian-vector product of a loss l(iwes(motion)).  Shape and dtype of `iwes_vjp`'s gradient."""
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        n_planes = d.n_ref + d.with_orig
+        g = self._iwes_planes(gimages, n_planes, "gimages")
+        gt = torch.zeros_like(g) if gimages_tan is None else self._iwes_planes(gimages_tan, n_planes, "gimages_tan")
+        u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
+        umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
+        if float(umax) == 0.0:  # what is left is J^T gimages_tan
+            return self.iwes_vjp(motion, motion_model, gt, directions, sigma, normalize_t, with_orig)[0]
+        un = (u / umax).to(torch.float32).contiguous()
+        gt = (gt / umax.to(torch.float32)).contiguous()  # linear in (tangent, gimages_tan) jointly
+        out = self._iwes_grad_like(d, m)
+        check(self._lib.cmax_iwes_vjp_tan(self._h, ctypes.byref(d), m.data_ptr(), un.data_ptr(), g.data_ptr(), gt.data_ptr(),
+                                          out.data_ptr(), F._stream()))
+        return out * umax.to(out.dtype)
+
     # -- phase-split form (time-sliced multi-GPU, see distributed.py) --------------------------------
     def objective_vote(self, desc: CmaxObjective, motion) -> torch.Tensor:
         """Raw votes of this handle's events: fp32 [n_images, Hp, Wp] (n_ref images, plus the un-warped
@@ -877,12 +974,141 @@ class _FusedEventsFn(torch.autograd.Function):
         return gm, ge, gw, None, None
 
 
+class _IwesVjpFn(torch.autograd.Function):
+    """Backward of fused_iwes as a function of (dL/dimages, motion) -- itself differentiable: its backward is cmax_iwes_jvp (it is
+    linear in dL/dimages) and cmax_iwes_vjp_tan with G' = 0 (the mixed term)."""
+
+    @staticmethod
+    def forward(ctx, gout, motion, handle, cfg, batch_id, want_w):
+        _check_batch(handle, batch_id)
+        grad, grad_w = handle.iwes_vjp(motion, gimages=gout, want_grad_w=want_w, **cfg)
+        ctx.handle, ctx.cfg, ctx.batch_id = handle, cfg, batch_id
+        ctx.save_for_backward(gout, motion)
+        ctx.set_materialize_grads(False)
+        gm = grad.to(motion.dtype if motion.dtype.is_floating_point else torch.float64).reshape(motion.shape).to(motion.device)
+        if grad_w is None:
+            return gm, None
+        return gm, grad_w
+
+    @staticmethod
+    def backward(ctx, ggm, ggw):
+        if ggw is not None:
+            raise NotImplementedError("fused_iwes: a second derivative through the per-event weights is not built (first order only)")
+        if ggm is None:
+            return None, None, None, None, None, None
+        gout, motion = ctx.saved_tensors
+        handle, cfg = ctx.handle, ctx.cfg
+        _check_batch(handle, ctx.batch_id)
+        d_gout = d_motion = None
+        if ctx.needs_input_grad[0]:
+            d_gout = torch.zeros_like(gout)
+            d_gout[: len(cfg["directions"])] = handle.iwes_jvp(motion, tangent=ggm, **cfg).to(gout.dtype)
+        if ctx.needs_input_grad[1]:
+            d_motion = handle.iwes_vjp_tan(motion, tangent=ggm, gimages=gout, gimages_tan=None, **cfg)
+            d_motion = d_motion.to(motion.dtype).reshape(motion.shape).to(motion.device)
+        return d_gout, d_motion, None, None, None, None
+
+
+def _check_batch(handle, batch_id):
+    if getattr(handle, "_batch_id", 0) != batch_id:
+        raise RuntimeError("fused_iwes: the handle holds another batch than the one this graph was recorded on (set_events since the "
+                           "forward pass)")
+
+
+class _IwesFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, motion, weights, handle, cfg):
+        ctx.handle, ctx.cfg, ctx.batch_id = handle, cfg, getattr(handle, "_batch_id", 0)
+        ctx.save_for_backward(motion)
+        ctx.wmeta = (weights.dtype, weights.device) if weights is not None else None
+        ctx.set_materialize_grads(False)
+        return handle.iwes(motion, **cfg)
+
+    @staticmethod
+    def backward(ctx, gout):
+        if gout is None:
+            return None, None, None, None
+        (motion,) = ctx.saved_tensors
+        want_w = ctx.wmeta is not None and ctx.needs_input_grad[1]
+        gm, gw = _IwesVjpFn.apply(gout.contiguous(), motion, ctx.handle, ctx.cfg, ctx.batch_id, want_w)
+        if gw is not None:
+            gw = gw.to(ctx.wmeta[0]).to(ctx.wmeta[1])
+        return (gm if ctx.needs_input_grad[0] else None), gw, None, None
+
+
+def fused_iwes(handle: "CMaxHandle", motion: torch.Tensor, motion_model: str, directions=("first",), sigma: float = 0.0,
+               normalize_t: bool = True, with_orig: bool = False, weights: Optional[torch.Tensor] = None,
+               _weights_on_handle: bool = False) -> torch.Tensor:
+    """The images of warped events of the handle's batch ON THE AUTOGRAD TAPE: fp32 [K, Hp, Wp] (one image per reference time in
+    `directions`, then the un-warped image when with_orig) -- what the reference's `arg["iwe"]` is to its costs, so that any torch
+    expression on it (a CostBase subclass, a robust or learned loss, a loss against a frame) runs on the fused path.
+    Differentiable TWICE in `motion` (backward: cmax_iwes_vjp; its backward: cmax_iwes_jvp and cmax_iwes_vjp_tan), so
+    torch.autograd.grad(..., create_graph=True) and torch.autograd.functional.vhp give exact Hessian-vector products (cells held fixed,
+    as everywhere); differentiable ONCE in `weights` ([n] per-event weights, put on the handle by this call as ContrastObjective
+    does) -- a second derivative through the weights raises NotImplementedError, and the mixed derivative d2/(dmotion dweights) is
+    not on the tape.
+    The graph remembers the batch it was recorded on: backward raises RuntimeError after another set_events.  Anything else that
+    happened to the handle in between (time slabs, other weights, other evaluations) is allowed, and a backward pass then computes
+    with the handle's state AT BACKWARD TIME (the library re-derives windows and cells from the motion in every call)."""
+    if weights is not None:
+        if not isinstance(weights, torch.Tensor):
+            raise TypeError(f"weights must be a torch tensor, got {type(weights)}")
+        if not _weights_on_handle:  # (ContrastObjective has set them for all its terms: one gather and synchronisation per call)
+            handle.set_event_weights(weights.detach())
+    directions = (directions,) if isinstance(directions, (str, int, float)) else tuple(directions)
+    cfg = dict(motion_model=motion_model, directions=directions, sigma=float(sigma), normalize_t=bool(normalize_t), with_orig=bool(with_orig))
+    motion = to_device_tensor(motion, "motion")
+    return _IwesFn.apply(motion, weights, handle, cfg)
+
+
+_IWE_KEYS = ("iwe", "backward_iwe", "forward_iwe", "middle_iwe", "orig_iwe")
+
+
+class _CustomTerm:
+    """A cost without a fused kernel: a CostBase instance or a callable arg_dict -> 0-dim tensor, evaluated in torch on fused_iwes."""
+
+    def __init__(self, cost, warp_direction, sigma: float, normalize_t: bool):
+        self.cost = cost
+        self.calculate = cost.calculate if hasattr(cost, "calculate") else cost
+        keys = list(getattr(cost, "required_keys", None) or ["iwe", "omit_boundary"])
+        self.keys = [k for k in keys if k in _IWE_KEYS]
+        if not any(k != "orig_iwe" for k in self.keys):
+            self.keys.insert(0, "iwe")
+        self.wants_flow = "flow" in keys
+        # the mapping of _COST_TABLE: iwe / backward_iwe -> warp_direction, forward_iwe -> "last", middle_iwe -> "middle"
+        ref = {"iwe": warp_direction, "backward_iwe": warp_direction, "forward_iwe": "last", "middle_iwe": "middle"}
+        self.directions, self.index = [], {}
+        for k in self.keys:
+            if k == "orig_iwe":
+                continue
+            if ref[k] not in self.directions:
+                self.directions.append(ref[k])
+            self.index[k] = self.directions.index(ref[k])
+        self.with_orig = "orig_iwe" in self.keys
+        self.sigma, self.normalize_t = float(sigma), bool(normalize_t)
+
+    def value(self, handle, motion, motion_model, omit_boundary, coarse_flow=None, weights=None):
+        imgs = fused_iwes(handle, motion, motion_model, tuple(self.directions), self.sigma, self.normalize_t, self.with_orig, weights,
+                          _weights_on_handle=weights is not None)
+        arg = {k: imgs[i] for k, i in self.index.items()}
+        if self.with_orig:
+            arg["orig_iwe"] = imgs[len(self.directions)]
+        arg["omit_boundary"] = omit_boundary
+        if self.wants_flow and coarse_flow is not None:
+            arg["flow"] = coarse_flow
+        return self.calculate(arg)
+
+
 class ContrastObjective:
     """loss = objective(motion[, coarse_flow]) with the reference's cost names.
 
     cost: any key of costs.functions, or "hybrid" with cost_with_weight={name: weight | "inv"}
     (src/costs/hybrid.py).  Event-based costs run as fused kernels on `handle`; total_variation runs
-    on the patch flow handed in as `coarse_flow` (patch_contrast_base.py:349-350)."""
+    on the patch flow handed in as `coarse_flow` (patch_contrast_base.py:349-350).
+    A cost WITHOUT a fused kernel -- a CostBase instance, a callable arg_dict -> 0-dim tensor, or a name registered in
+    costs.functions that is not among FUSED_COSTS -- is evaluated in torch on `fused_iwes` (the images its `required_keys` name, in the
+    reference's `arg` dict with `omit_boundary`; padded images, cropped only by the cost itself); its gradient and `hvp` are torch's
+    backward and double backward through that layer.  Names unknown to costs.functions raise KeyError."""
 
     def __init__(self, handle: CMaxHandle, motion_model: str, cost: str = "image_variance",
                  cost_with_weight: Optional[Dict[str, Union[float, str]]] = None, direction: str = "minimize",
@@ -899,13 +1125,29 @@ class ContrastObjective:
         for name, weight in terms.items():
             if name == "total_variation":
                 self.terms.append((name, weight, None))
+            elif not isinstance(name, str) or (name not in _COST_TABLE and name in _cost_registry()):
+                cost_obj = _cost_registry()[name](direction=direction) if isinstance(name, str) else name
+                if not (callable(cost_obj) or hasattr(cost_obj, "calculate")):
+                    raise TypeError(f"cost must be a name, a CostBase instance or a callable, got {type(cost_obj)}")
+                self.terms.append((name, weight, _CustomTerm(cost_obj, warp_direction, sigma, normalize_t)))
             else:
                 desc = make_descriptor(name, motion_model, direction, sigma, omit_boundary, normalize_t,
                                        handle.time_bin if F.MODEL_CODES[motion_model] == _lib.MODEL_VOXEL else 0,
                                        warp_direction)
                 self.terms.append((name, weight, desc))
 
-    has_exact_hvp = True  # every fused term, numeric and "inv" weights (total_variation does not depend on `motion`)
+    has_exact_hvp = True  # every fused term, numeric and "inv" weights (total_variation does not depend on `motion`); custom terms by double backward
+
+    def _custom_hvp(self, term, weight, motion, v64):
+        """H v of combine(weight, cost(fused_iwes(motion))): torch's double backward through the layer."""
+        m = to_device_tensor(motion, "motion").detach().clone().requires_grad_()
+        with torch.enable_grad():
+            value = combine(weight, term.value(self.handle, m, self.motion_model, self.omit_boundary))
+            (g,) = torch.autograd.grad(value, m, create_graph=True)
+            if not g.requires_grad:
+                return torch.zeros_like(v64)
+            (hv,) = torch.autograd.grad((g * v64.reshape(g.shape).to(g.dtype)).sum(), m, allow_unused=True)
+        return torch.zeros_like(v64) if hv is None else hv.detach().to(torch.float64).reshape(v64.shape)
 
     def hvp(self, motion: torch.Tensor, vector: torch.Tensor) -> torch.Tensor:
         """Exact Hessian-vector product w.r.t. `motion` (same shape/dtype as motion).  A term of weight w contributes
@@ -918,6 +1160,10 @@ class ContrastObjective:
         for name, weight, desc in self.terms:
             if desc is None:
                 continue  # total_variation acts on the coarse flow, not on `motion`
+            if isinstance(desc, _CustomTerm):
+                hv = self._custom_hvp(desc, weight, motion, v64)
+                out = hv if out is None else out + hv.reshape(out.shape)
+                continue
             hv = self.handle.hvp(desc, motion, vector).to(torch.float64)
             if weight == "inv":
                 res, grad = self.handle.evaluate(desc, motion, want_grad=True)
@@ -949,6 +1195,10 @@ class ContrastObjective:
                 value = torch.stack([F.total_variation(cf[k], self.omit_boundary) for k in range(K)]).to(torch.float64)
                 if self.direction != "minimize":
                     value = -value
+            elif isinstance(desc, _CustomTerm):
+                with torch.no_grad():
+                    value = torch.stack([torch.as_tensor(desc.value(self.handle, mt[k], self.motion_model, self.omit_boundary)).to(torch.float64)
+                                         for k in range(K)]).to(self.handle.device)
             else:
                 results, _ = self.handle.evaluate_batch(desc, mt)
                 value = results[:, 0]
@@ -982,6 +1232,10 @@ class ContrastObjective:
                 value = F.total_variation(to_device_tensor(coarse_flow, "flow"), self.omit_boundary)
                 if self.direction != "minimize":
                     value = -value
+            elif isinstance(desc, _CustomTerm):
+                if events is not None:
+                    raise NotImplementedError("dL/d(event) of a cost without a fused kernel is not built")
+                value = desc.value(self.handle, motion, self.motion_model, self.omit_boundary, coarse_flow, weights)
             else:
                 if events is not None:
                     value = _FusedEventsFn.apply(motion, events, weights, self.handle, desc)

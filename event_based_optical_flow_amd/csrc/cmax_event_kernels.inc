@@ -1919,17 +1919,29 @@ k_event_grad_gather(const int4 *__restrict__ segs, int nseg, const uint2 *__rest
     }
 }
 
-template <class L, int MODEL, bool FRAC>
+// trailing kernel arguments of the WEIGHTED instantiations (a parameter pack: the unweighted kernels keep their argument block)
+__device__ __forceinline__ const float *pack_ptr(int) { return nullptr; }
+template <class... R>
+__device__ __forceinline__ const float *pack_ptr(int i, const float *a, R... r) { return i == 0 ? a : pack_ptr(i - 1, r...); }
+
 // dimg64 (deterministic mode): the window's integers (and the overflow of a clipped window, rounded at the same scale) go to a
 // 64-bit integer image with integer atomics -- exact in any order; k_fixed_to_image rounds the finished sums once
+// WEIGHTED = called with (w_packed, d_wnorm) behind dimg64 (cmax_iwes_jvp on a weighted handle; default mode only): the event's four
+// derivative votes are multiplied by w / wmax before they are rounded, the flush carries wmax -- (1 / wmax, wmax) from d_wnorm as in K1,
+// the slot weights loaded behind the warp as in K1 (profiles/weights_resources.txt).  The overflow of a clipped window is not rounded: w d.
+template <class L, int MODEL, bool FRAC, class... WGT>
 __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg,
-                                                  float *__restrict__ dimg, double *__restrict__ stat_zero, long long *__restrict__ dimg64) {
+                                                  float *__restrict__ dimg, double *__restrict__ stat_zero, long long *__restrict__ dimg64, WGT... wargs) {
+    constexpr bool WEIGHTED = sizeof...(WGT) > 0;
+    static_assert(sizeof...(WGT) == 0 || sizeof...(WGT) == 2, "k_vote_tan: (w_packed, d_wnorm) or nothing");
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = 0.f;
     // (the by-value parameter block is only read: writing to it would move it to scratch memory for the indexing)
-    const float fix = tp.fixk[blockIdx.y], inv_fix = 1.f / fix;
+    const float wn0 = WEIGHTED ? pack_ptr(1, wargs...)[0] : 1.f, wn1 = WEIGHTED ? pack_ptr(1, wargs...)[1] : 1.f;
+    // weighted: an event's votes are round(w d fix / wmax), the flush multiplies by wmax / fix
+    const float fix = WEIGHTED ? tp.fixk[blockIdx.y] * wn0 : tp.fixk[blockIdx.y], inv_fix = WEIGHTED ? wn1 / tp.fixk[blockIdx.y] : 1.f / fix;
     dimg += blockIdx.y * tp.bs;
     if (dimg64) dimg64 += blockIdx.y * tp.bs;
     stat_zero += blockIdx.y * kStatStride;
@@ -1953,6 +1965,8 @@ __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, 
         u0 = tp.u[0];
         u1 = tp.u[1];
     }
+    float fw[L::kEPT];  // (behind the warp, as in K1: not live through it)
+    if constexpr (WEIGHTED) load_slot_weights<L, false>(pack_ptr(0, wargs...), sg, fw);
     __syncthreads();
     const int dummy = L::kDummy + (int)(threadIdx.x & (kWave - 1));
 #pragma unroll
@@ -1962,6 +1976,11 @@ __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, 
         const float a = fa[u], b = fb[u], na = 1.f - a, nb = 1.f - b;
         float da = 0.f, db = 0.f;
         if (valid) tangent_delta<MODEL>(wp, tp, fdt[u], (unsigned)fsrc[u], u0, u1, da, db);
+        if constexpr (WEIGHTED) {  // the four votes are linear in (da, db): w scales the VOTES, here through their common factors
+            const float w = valid ? fw[u] : 0.f;  // (an empty slot's weight is padding)
+            da *= w;
+            db *= w;
+        }
         // derivatives of w00 = na nb, w10 = a nb, w01 = na b, w11 = a b along (da, db)
         const float d00 = -nb * da - na * db, d10 = nb * da - a * db, d01 = -b * da + na * db, d11 = b * da + a * db;
         const int lr = row - win.r0, lc = col - win.c0;
@@ -2002,10 +2021,14 @@ __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, 
 }
 
 // T3: per-event second-order gather.  G = dL/dIWE (current), Gp = its tangent.
-template <class L, int MODEL, bool FRAC>
+// WEIGHTED = called with w_packed behind det (cmax_iwes_vjp / cmax_iwes_vjp_tan on a weighted handle; default mode only): the factor w goes
+// on the final dt (hx, hy) product only -- tangent_delta is the displacement dt u of the warped POINT, which the weight does not move.
+template <class L, int MODEL, bool FRAC, class... WGT>
 __global__ void __launch_bounds__(L::kThr)
 k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg, const float *__restrict__ G,
-           const float *__restrict__ Gp, double *__restrict__ gpart, float *__restrict__ hflow, HvpDet det) {
+           const float *__restrict__ Gp, double *__restrict__ gpart, float *__restrict__ hflow, HvpDet det, WGT... wargs) {
+    constexpr bool WEIGHTED = sizeof...(WGT) > 0;
+    static_assert(sizeof...(WGT) <= 1, "k_grad_hvp: w_packed or nothing");
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = 0.f;
     G += blockIdx.y * tp.bs;
@@ -2044,6 +2067,8 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
         s_g[L::kDummy + threadIdx.x] = 0.f;
         s_p[L::kDummy + threadIdx.x] = 0.f;
     }
+    float fw[L::kEPT];  // (behind the warp, as in K1: not live through it)
+    if constexpr (WEIGHTED) load_slot_weights<L, false>(pack_ptr(0, wargs...), sg, fw);
     __syncthreads();
     const int hw = wp.H * wp.W;
     const int dummy = L::kDummy + lane, stride = win.stride;
@@ -2097,12 +2122,14 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
                 }
             }
         }
-        const float a = fa[j], b = fb[j], dt = fdt[j];
+        const float a = fa[j], b = fb[j];
+        float dt = fdt[j];
         float da = 0.f, db = 0.f;
         if (valid) tangent_delta<MODEL>(wp, tp, dt, (unsigned)fsrc[j], u0, u1, da, db);
         const float mixed = (g[3] - g[2]) - (g[1] - g[0]);  // d gx / d b = d gy / d a
         const float hx = mixed * db + (1.f - b) * (q[1] - q[0]) + b * (q[3] - q[2]);
         const float hy = mixed * da + (1.f - a) * (q[2] - q[0]) + a * (q[3] - q[1]);
+        if constexpr (WEIGHTED) dt = valid ? dt * fw[j] : 0.f;  // from here on dt only multiplies (hx, hy); an empty slot's weight is padding
         if (kdet) {
             const float sgn = MODEL == CMAX_MODEL_2DOF ? 1.f : -1.f;
             const long long qx = det_fixed((double)(sgn * dt * hx), det_s), qy = det_fixed((double)(sgn * dt * hy), det_s);

@@ -291,6 +291,8 @@ struct cmax_handle_s {
     int orig_cost = -1, orig_omit = -1;
     double tmin_host = 0.0, tmax_host = 0.0;  // batch extremes (copied once per batch)
     float *hvp_img = nullptr;                 // [6 kinds][4 reference times][Hp, Wp] scratch of cmax_objective_hvp (allocated on first use)
+    float *iw_zero = nullptr;                 // cmax_iwes_vjp: a zero tangent of the motion's size (the gather of J^T G is T3 with u = 0, G' = G)
+    int64_t iw_zero_cap = 0;
     double *d_stat_tan = nullptr;             // [4][kStatStride] tangent statistics
     // pinned host staging of the per-batch read-back (group starts, active pixels per tile, flags, time extremes) and
     // of the work list: copies to / from pageable memory are staged by the runtime and cost a synchronisation each
@@ -2989,6 +2991,7 @@ int cmax_destroy(cmax_handle_t h) {
     dev_free(&h->gw_G);
     dev_free(&h->gw_Gt);
     dev_free(&h->gw_packed);
+    dev_free(&h->iw_zero);
     dev_free(&h->ge_packed);
     dev_free(&h->ge_part);
     dev_free(&h->cev);
@@ -4760,6 +4763,320 @@ int cmax_objective_hvp_dist(cmax_handle_t h, const cmax_objective_t *d, const vo
     if (rc) return rc;
     CMAX_REQUIRE(tangent && hv, "objective_hvp_dist: tangent / hv");
     return objective_hvp_impl(h, d, motion, tangent, hv, (hipStream_t)stream, h->comm, true);
+}
+
+}  // extern "C"
+
+// ---- the image of warped events as a differentiable layer (cmax_iwes, _vjp, _jvp, _vjp_tan) --------------------------------------------
+namespace cmax {
+
+template <int MODEL>
+static void launch_vote_tan_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, float *draw, hipStream_t s) {
+    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
+    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw,
+                               h->d_stat_tan, (long long *)nullptr, (const float *)h->w_packed, (const float *)h->d_wnorm);
+        });
+    });
+}
+
+template <int MODEL>
+static void launch_grad_hvp_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, const float *G, const float *Gp,
+                                     double *gpart, float *hflow, hipStream_t s) {
+    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
+    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+        using L = decltype(l);
+        with_bool(h->has_frac, [&](auto frac) {
+            hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow,
+                               HvpDet{}, (const float *)h->w_packed);
+        });
+    });
+}
+
+// the part of an objective descriptor the event side reads (argument checks, warp parameters, windows)
+static cmax_objective_t iwes_as_objective(const cmax_iwes_t *d) {
+    cmax_objective_t o = {};
+    o.model = d->model;
+    o.cost = CMAX_COST_VARIANCE;
+    o.normalize_t = d->normalize_t;
+    o.n_ref = d->n_ref;
+    for (int k = 0; k < 4; ++k) {
+        o.ref_mode[k] = d->ref_mode[k];
+        o.ref_frac[k] = d->ref_frac[k];
+        o.mult[k] = 1.0;
+    }
+    o.sigma = d->sigma;
+    o.T = d->T;
+    o.motion_dtype = d->motion_dtype;
+    return o;
+}
+
+static int iwes_check(cmax_handle_t h, const cmax_iwes_t *d, const void *motion, const char *what, cmax_objective_t *o) {
+    CMAX_REQUIRE(h && d && motion, "iwes: null pointer");
+    CMAX_REQUIRE(d->n_ref >= 1 && d->n_ref <= 4, "iwes: n_ref");
+    *o = iwes_as_objective(d);
+    int rc = check_objective_args(h, o, static_cast<const float *>(motion));
+    if (rc) return rc;
+    if (h->deterministic) {
+        set_error("%s: not built for deterministic mode (cmax_set_deterministic)", what);
+        return CMAX_EUNSUPPORTED;
+    }
+    if (h->comm) {
+        set_error("%s: not built for a handle with a communicator (cmax_comm_init)", what);
+        return CMAX_EUNSUPPORTED;
+    }
+    return 0;
+}
+
+// scratch shared with cmax_objective_hvp: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
+static int iwes_scratch(cmax_handle_s *h) {
+    if (h->hvp_img) return 0;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    int rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
+    if (!rc) rc = dev_alloc(h, &h->d_stat_tan, 4 * kStatStride);
+    if (!rc) {
+        dev_free(&h->Gt);
+        rc = dev_alloc(h, &h->Gt, 4 * npix);
+    }
+    return rc;
+}
+
+// fixed-point scale of the derivative votes per reference time, as objective_hvp_impl
+static TanParams iwes_tan_params(const cmax_handle_s *h, const cmax_objective_t *d, const float *tangent) {
+    const double period = d->normalize_t ? 1.0 : (h->tmax_host - h->tmin_host);
+    TanParams tp = {};
+    tp.u = tangent;
+    tp.bs = (int64_t)h->Hp * h->Wp;
+    for (int k = 0; k < d->n_ref; ++k) {
+        const double dref = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
+        double dtmax = fabs(dref) > fabs(1.0 - dref) ? fabs(dref) : fabs(1.0 - dref);
+        dtmax *= period > 0 ? period : 1.0;
+        if (dtmax < 1e-30) dtmax = 1e-30;
+        tp.d[k] = (float)dref;
+        tp.fixk[k] = (float)(1073741824.0 / ((double)h->seg_max * 2.0 * dtmax));  // 2^30 / (events * max |derivative vote|)
+    }
+    tp.fix = tp.fixk[0];
+    tp.inv_fix = 1.f / tp.fix;
+    return tp;
+}
+
+// the caller's n planes as the event kernels read them: the planes themselves, or their blur transpose in `stage`
+static int iwes_stage(cmax_handle_s *h, double sigma, const float *planes, int n, float *stage, const float **out, hipStream_t s) {
+    *out = planes;
+    if (!(sigma > 0)) return 0;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    double k0 = 0, k1 = 0;
+    blur_taps(sigma, k0, k1);
+    hipLaunchKernelGGL(k_blur3_adj<float>, dim3(div_up(npix, 256), n), dim3(256), 0, s, planes, h->Hp, h->Wp, (float)k0, (float)k1, stage, npix);
+    CMAX_CHECK_LAUNCH();
+    *out = stage;
+    return 0;
+}
+
+// T3 with the caller's images (out zeroed by the caller): 2-DoF partials folded by k_finish, flow models added per event
+static int iwes_gather(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *tangent, const float *G, const float *Gp, void *out,
+                       hipStream_t s) {
+    const bool two_dof = d->model == CMAX_MODEL_2DOF;
+    const EvView ev = ev_view(h);
+    const TanParams tp = iwes_tan_params(h, d, tangent);
+    const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
+    double *gpart = two_dof ? h->d_gpart : nullptr;
+    float *hflow = two_dof ? nullptr : (float *)out;
+    with_model(d->model, [&](auto m) {
+        if (h->weighted) launch_grad_hvp_weighted<m.value>(h, ev, wp, tp, d->n_ref, G, Gp, gpart, hflow, s);
+        else launch_grad_hvp<m.value>(h, ev, wp, tp, d->n_ref, G, Gp, gpart, hflow, s, HvpDet{});
+    });
+    CMAX_CHECK_LAUNCH();
+    if (two_dof) {
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, s, h->d_gpart, d->n_ref * h->nseg, (double *)out);
+        CMAX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+// grad_w (zeroed by the caller) from finished planes G[0 .. n_ref) (+ G[n_ref] at the un-warped positions): per_event_finish's gather and
+// scatter, behind windows published for THIS motion
+static int iwes_weight_grad(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *G, bool with_orig, float *grad_w, hipStream_t s) {
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const int nr = d->n_ref, n_planes = nr + (with_orig ? 1 : 0);
+    int rc = 0;
+    if (h->n > h->gw_plane) {  // sized like w_packed
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(&h->gw_packed);
+        h->gw_plane = 0;
+        const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
+        rc = dev_alloc(h, &h->gw_packed, 5 * plane);
+        if (rc) return rc;
+        h->gw_plane = plane;
+    }
+    CMAX_CHECK_HIP(hipMemsetAsync(h->gw_packed, 0, (size_t)n_planes * h->gw_plane * sizeof(float), s));
+    const EvView ev = ev_view(h);
+    rc = publish_windows(h, d, motion, s);
+    if (rc) return rc;
+    h->win_generation = ~(uint64_t)0;
+    {
+        RefArgs ra = {};
+        fill_ref_times(ra, nr, d->ref_mode, d->ref_frac);
+        for (int k = 0; k < nr; ++k) ra.img[k] = const_cast<float *>(G) + k * npix;  // (read only by the gather)
+        ra.win = h->d_win;
+        ra.shifts = h->d_shifts;
+        const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
+        with_model(d->model, [&](auto m) { launch_weight_gather<m.value>(h, ev, wp, ra, nr, 0, s); });
+        CMAX_CHECK_LAUNCH();
+    }
+    if (with_orig) {  // the un-warped events, behind a K1 launch that only publishes their windows (as per_event_finish)
+        RefArgs ra = {};
+        const int ref_mode = CMAX_REF_FIRST;
+        const double frac = 0.0;
+        fill_ref_times(ra, 1, &ref_mode, &frac);
+        ra.win = h->d_win;
+        ra.shifts = h->d_shifts;
+        ra.windows_only = 1;
+        const WarpParams wp = warp_params(h, nullptr, 0, CMAX_REF_FIRST, 0.0, 1);
+        launch_vote<-1>(h, ev, wp, ra, 1, s);
+        CMAX_CHECK_LAUNCH();
+        ra.windows_only = 0;
+        ra.img[0] = const_cast<float *>(G) + nr * npix;
+        launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
+        CMAX_CHECK_LAUNCH();
+    }
+    hipLaunchKernelGGL(k_weight_grad_scatter, dim3(div_up(h->n, 256)), dim3(256), 0, s, (const float *)h->gw_packed, h->gw_plane, n_planes, (const int *)h->src, h->n, grad_w);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+}  // namespace cmax
+
+extern "C" {
+
+int cmax_sizeof_iwes(void) { return (int)sizeof(cmax_iwes_t); }
+
+int cmax_iwes(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, float *images, cmax_stream_t stream) {
+    cmax_objective_t o;
+    int rc = iwes_check(h, d, motion_v, "iwes", &o);
+    if (rc) return rc;
+    CMAX_REQUIRE(images != nullptr, "iwes: images");
+    const float *motion = static_cast<const float *>(motion_v);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const int nr = o.n_ref, n_img = nr + (d->with_orig ? 1 : 0);
+    if (h->n == 0) {
+        CMAX_CHECK_HIP(hipMemsetAsync(images, 0, (size_t)n_img * npix * sizeof(float), s));
+        return 0;
+    }
+    float *raw = images;
+    if (o.sigma > 0) {  // votes into the scratch (five consecutive images), the blur writes the caller's buffer
+        rc = iwes_scratch(h);
+        if (rc) return rc;
+        raw = h->hvp_img;
+    }
+    float *imgs[4];
+    for (int k = 0; k < nr; ++k) imgs[k] = raw + k * npix;
+    rc = vote_images(h, o.model, motion, o.T, nr, o.ref_mode, o.ref_frac, o.normalize_t, imgs, 0u, -1, s, {}, o.motion_dtype == CMAX_F64);
+    if (rc) return rc;
+    if (d->with_orig) {
+        rc = vote_image(h, -1, nullptr, 0, CMAX_REF_FIRST, 0.0, 1, raw + nr * npix, false, -1, s);
+        if (rc) return rc;
+    }
+    if (o.sigma > 0) {
+        double k0 = 0, k1 = 0;
+        blur_taps(o.sigma, k0, k1);
+        hipLaunchKernelGGL(k_blur3<float>, dim3(div_up(npix, 256), n_img), dim3(256), 0, s, (const float *)raw, h->Hp, h->Wp, (float)k0, (float)k1, images, npix);
+        CMAX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int cmax_iwes_vjp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, const float *gimages, void *grad_motion, float *grad_w, int64_t n,
+                  cmax_stream_t stream) {
+    cmax_objective_t o;
+    int rc = iwes_check(h, d, motion_v, "iwes_vjp", &o);
+    if (rc) return rc;
+    CMAX_REQUIRE(gimages && grad_motion, "iwes_vjp: gimages / grad_motion");
+    CMAX_REQUIRE(!grad_w || n == h->n_in, "iwes_vjp: n must equal the n of the last cmax_set_events (one derivative per event, in the caller's order)");
+    const float *motion = static_cast<const float *>(motion_v);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const GradExtent g = grad_extent(h, &o);
+    CMAX_CHECK_HIP(hipMemsetAsync(grad_motion, 0, g.bytes, s));
+    if (grad_w && n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
+    if (h->n == 0) return 0;
+    rc = iwes_scratch(h);
+    if (rc) return rc;
+    if (g.count > h->iw_zero_cap) {  // the zero tangent (once per motion size)
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(&h->iw_zero);
+        h->iw_zero_cap = 0;
+        rc = dev_alloc(h, &h->iw_zero, g.count);
+        if (rc) return rc;
+        CMAX_CHECK_HIP(hipMemset(h->iw_zero, 0, (size_t)g.count * sizeof(float)));
+        h->iw_zero_cap = g.count;
+    }
+    const int n_planes = o.n_ref + ((d->with_orig && grad_w) ? 1 : 0);
+    const float *G = nullptr;
+    rc = iwes_stage(h, o.sigma, gimages, n_planes, h->hvp_img + 16 * npix, &G, s);
+    if (rc) return rc;
+    // J^T G = T3 with u = 0 (no mixed term) and G' = G
+    rc = iwes_gather(h, &o, motion, h->iw_zero, G, G, grad_motion, s);
+    if (rc || !grad_w) return rc;
+    return iwes_weight_grad(h, &o, motion, G, d->with_orig != 0, grad_w, s);
+}
+
+int cmax_iwes_jvp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, const float *tangent, float *dimages, cmax_stream_t stream) {
+    cmax_objective_t o;
+    int rc = iwes_check(h, d, motion_v, "iwes_jvp", &o);
+    if (rc) return rc;
+    CMAX_REQUIRE(tangent && dimages, "iwes_jvp: tangent / dimages");
+    const float *motion = static_cast<const float *>(motion_v);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const int nr = o.n_ref;
+    if (h->n == 0) {
+        CMAX_CHECK_HIP(hipMemsetAsync(dimages, 0, (size_t)nr * npix * sizeof(float), s));
+        return 0;
+    }
+    rc = iwes_scratch(h);
+    if (rc) return rc;
+    float *draw = o.sigma > 0 ? h->hvp_img + 8 * npix : dimages;
+    CMAX_CHECK_HIP(hipMemsetAsync(draw, 0, (size_t)nr * npix * sizeof(float), s));
+    const EvView ev = ev_view(h);
+    const TanParams tp = iwes_tan_params(h, &o, tangent);
+    const WarpParams wp = warp_params(h, motion, o.T, o.ref_mode[0], o.ref_frac[0], o.normalize_t, o.motion_dtype == CMAX_F64);
+    with_model(o.model, [&](auto m) {
+        if (h->weighted) launch_vote_tan_weighted<m.value>(h, ev, wp, tp, nr, draw, s);
+        else launch_vote_tan<m.value>(h, ev, wp, tp, nr, draw, s);
+    });
+    CMAX_CHECK_LAUNCH();
+    if (o.sigma > 0) {
+        double k0 = 0, k1 = 0;
+        blur_taps(o.sigma, k0, k1);
+        hipLaunchKernelGGL(k_blur3<float>, dim3(div_up(npix, 256), nr), dim3(256), 0, s, (const float *)draw, h->Hp, h->Wp, (float)k0, (float)k1, dimages, npix);
+        CMAX_CHECK_LAUNCH();
+    }
+    return 0;
+}
+
+int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, const float *tangent, const float *gimages, const float *gimages_tan,
+                      void *out, cmax_stream_t stream) {
+    cmax_objective_t o;
+    int rc = iwes_check(h, d, motion_v, "iwes_vjp_tan", &o);
+    if (rc) return rc;
+    CMAX_REQUIRE(tangent && gimages && gimages_tan && out, "iwes_vjp_tan: tangent / gimages / gimages_tan / out");
+    const float *motion = static_cast<const float *>(motion_v);
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    const GradExtent g = grad_extent(h, &o);
+    CMAX_CHECK_HIP(hipMemsetAsync(out, 0, g.bytes, s));
+    if (h->n == 0) return 0;
+    rc = iwes_scratch(h);
+    if (rc) return rc;
+    const float *G = nullptr, *Gp = nullptr;
+    rc = iwes_stage(h, o.sigma, gimages, o.n_ref, h->hvp_img, &G, s);
+    if (!rc) rc = iwes_stage(h, o.sigma, gimages_tan, o.n_ref, h->hvp_img + 4 * npix, &Gp, s);
+    if (rc) return rc;
+    return iwes_gather(h, &o, motion, tangent, G, Gp, out, s);
 }
 
 }  // extern "C"

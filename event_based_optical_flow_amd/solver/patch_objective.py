@@ -49,7 +49,7 @@ def patch_pad(patch_size, sliding_window, patch_shift=(0, 0)) -> Tuple[int, int]
 
 class PatchFlowObjective:
     def __init__(self, handle: CMaxHandle, t_scale: float, patch_image_size, patch_size, sliding_window,
-                 patch_shift=(0, 0), cost: str = "hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
+                 patch_shift=(0, 0), cost="hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
                  blur_sigma: float = 1.0, time_aware: bool = False, time_bin: int = 10,
                  flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None,
                  scale_later: bool = False):
@@ -90,6 +90,10 @@ class PatchFlowObjective:
     def _build_native_plan(self):
         """The same chain as `__call__` + autograd, as ONE library call per evaluation.  Available for numeric
         hybrid weights ("inv" weights keep the autograd path)."""
+        from ..cmax import _CustomTerm
+
+        if any(isinstance(desc, _CustomTerm) for _, _, desc in self.contrast.terms):
+            return  # a cost without a fused kernel runs in torch on fused_iwes: the autograd-chained path
         fused = [(w, desc) for _, w, desc in self.contrast.terms if desc is not None]
         tv = [w for name, w, desc in self.contrast.terms if desc is None]
         if not fused or len(fused) > 4 or any(w == "inv" for w, _ in fused) or any(w == "inv" for w in tv):
@@ -216,7 +220,7 @@ class PatchFlowObjective:
 
     def _smooth_grad(self, x: torch.Tensor) -> torch.Tensor:
         """Gradient of the contrast terms (everything except total_variation) w.r.t. x."""
-        from ..cmax import _FusedFn
+        from ..cmax import _CustomTerm, _FusedFn
         from ..costs.hybrid import combine
 
         xt = x.detach().clone().requires_grad_()
@@ -224,7 +228,11 @@ class PatchFlowObjective:
         for name, weight, desc in self.contrast.terms:
             if desc is None:
                 continue
-            loss = loss + combine(weight, _FusedFn.apply(self.dense_flow(xt), self.handle, desc))
+            if isinstance(desc, _CustomTerm):
+                value = desc.value(self.handle, self.dense_flow(xt), self.contrast.motion_model, self.contrast.omit_boundary)
+            else:
+                value = _FusedFn.apply(self.dense_flow(xt), self.handle, desc)
+            loss = loss + combine(weight, value)
         (g,) = torch.autograd.grad(loss, xt)
         return g
 

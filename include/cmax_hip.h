@@ -316,6 +316,59 @@ int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *desc_hos
 int cmax_objective_event_grad(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion, double *result,
                               void *grad /* may be NULL */, float *grad_events, int64_t n, double *csum, cmax_stream_t stream);
 
+/* =============================================================================================
+ * The image of warped events as a differentiable layer: the caller stands in for the image-side kernels (statistics, dL/dIWE) and
+ * brings its own cost.  In the reference the IWE is an ordinary torch tensor, so any CostBase subclass -- or any torch expression on
+ * arg["iwe"] -- is differentiable once and twice (src/costs/base.py, torch.autograd.functional.vhp in
+ * src/solver/scipy_autograd/torch_wrapper.py:51-73); these four calls give the event side of that: the images, J^T G, J u and the
+ * derivative of J^T G along a tangent, with the segment / window / exact-cell machinery of the fused objective.
+ * I_k(m) below is the padded [Hp,Wp] image at reference time k, blurred when sigma > 0, weighted on a weighted handle: exactly what
+ * cmax_iwe returns for that reference time.  J_k = dI_k/dm with the bilinear cells held fixed.
+ * All four run on weighted and unweighted handles, in un-binned / binned / slab order and on every segment layout; CMAX_EUNSUPPORTED on a
+ * deterministic handle and on one that holds a communicator; an empty handle gives exact zeros.
+ * STATE: none of the four relies on anything an earlier call left on the handle -- not on the windows and cell offsets a vote published
+ * (they belong to the last vote only), not on another cmax_iwes, cmax_objective, cmax_set_time_slabs / _bins or cmax_set_event_weights in
+ * between.  Each call RE-DERIVES what it needs from the motion it is given: the second-order kernels (k_vote_tan, k_grad_hvp) warp
+ * their segment and build their LDS window themselves, and the per-event interpolation behind grad_w runs behind a K1 launch that only
+ * publishes windows (no votes).  The price: a backward call warps the events again (one warp per reference time in the gather; with
+ * grad_w one windows-only K1 more) instead of re-using the forward's windows -- and the result is that of the handle's state (order,
+ * weights) AT THE TIME OF THE CALL.  Scratch on first use: 28 images.
+ * ============================================================================================= */
+typedef struct {
+    int32_t model;        /* CMAX_MODEL_* */
+    int32_t normalize_t;
+    int32_t n_ref;        /* 1..4 reference times */
+    int32_t ref_mode[4];  /* CMAX_REF_* */
+    double ref_frac[4];
+    double sigma;         /* 3-tap blur of every image (0 = none) */
+    int32_t T;            /* voxel time bins */
+    int32_t motion_dtype; /* as cmax_objective_t::motion_dtype */
+    int32_t with_orig;    /* 1: one more image behind the n_ref, the un-warped events (the reference's orig_iwe) */
+} cmax_iwes_t;
+int cmax_sizeof_iwes(void);
+/* images: fp32 [n_ref (+1), Hp, Wp], overwritten: images[k] = I_k(m); images[n_ref] = the un-warped image when with_orig.  Votes go
+ * straight into the caller's buffer (sigma > 0: into the library's scratch, the blur writes the caller's buffer); the handle's own
+ * double-buffered vote images are not touched.                                                                                     */
+int cmax_iwes(cmax_handle_t h, const cmax_iwes_t *desc_host, const void *motion, float *images, cmax_stream_t stream);
+/* grad_motion = sum_k J_k^T gimages[k]: fp64 [2] for 2-DoF, fp32 [2,H,W] / [T,2,H,W] otherwise, overwritten (like cmax_objective's grad).
+ * gimages: fp32, the shape of `images` -- the caller's dL/dI_k, the whole truth: no region mask, no chain factor; a corner outside the
+ * padded image reads 0; the blur's transpose is applied when sigma > 0.  The un-warped image does not depend on the motion.
+ * grad_w (NULL: skipped; else fp32 [n], n = the n given to cmax_set_events) = sum_k bilin(gimages[k]; x'_e,k) (+ bilin(gimages[n_ref]; x_e)
+ * with with_orig), in the CALLER'S event order, NOT multiplied by w, zeros for events that were not packed: cmax_objective_weight_grad's
+ * output with the caller's G.                                                                                                      */
+int cmax_iwes_vjp(cmax_handle_t h, const cmax_iwes_t *desc_host, const void *motion, const float *gimages, void *grad_motion,
+                  float *grad_w, int64_t n, cmax_stream_t stream);
+/* dimages[k] = J_k u, fp32 [n_ref, Hp, Wp], overwritten (the un-warped image has no tangent: with_orig is ignored).  tangent: fp32, the
+ * layout of the motion, SCALED TO UNIT MAX-NORM by the caller as for cmax_objective_hvp (fixed-point derivative votes, scale per
+ * reference time; on a weighted handle the votes are normalised by wmax as in K1).                                                  */
+int cmax_iwes_jvp(cmax_handle_t h, const cmax_iwes_t *desc_host, const void *motion, const float *tangent, float *dimages,
+                  cmax_stream_t stream);
+/* out = d/d(eps) [ J(m + eps u)^T (G + eps G') ] at eps = 0, summed over k; G = gimages, G' = gimages_tan (both the shape of `images`; the
+ * plane of the un-warped image is not read).  out has the shape and dtype of grad_motion, overwritten.  With G' = (d2 l / dI2) J u this is
+ * the exact Hessian-vector product of any loss l(I); with G' = 0 the mixed term alone.  tangent as for cmax_iwes_jvp.               */
+int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *desc_host, const void *motion, const float *tangent, const float *gimages,
+                      const float *gimages_tan, void *out, cmax_stream_t stream);
+
 /* The same evaluation with its results delivered TO THE HOST -- what an optimiser written in C calls once per iteration
  * (the reference's TorchWrapper.get_value_and_grad ends in .cpu().numpy(), src/solver/scipy_autograd/torch_wrapper.py:46-49):
  * enqueues the evaluation and the copies on `stream` and returns when result_host[8] and grad_host (double[2] for 2DOF, else

@@ -15,9 +15,11 @@ def parse(path):
     return rows
 a, b = parse(sys.argv[1]), parse(sys.argv[2])
 pat = re.compile(sys.argv[3]) if len(sys.argv) > 3 else None
-names = sorted(set(a) | set(b))
-dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
-for k, d in zip(names, dem):
-    d = d.split("(")[0].replace("void cmax::", "")
+def demangled(rows):  # keyed by the demangled name without its parameter list: a kernel that only gained a trailing (empty) parameter pack keeps its key
+    names = list(rows)
+    dem = subprocess.run(["c++filt"], input="\n".join(names), capture_output=True, text=True).stdout.split("\n")
+    return {d.split("(")[0].replace("void cmax::", ""): rows[k] for k, d in zip(names, dem)}
+a, b = demangled(a), demangled(b)
+for d in sorted(set(a) | set(b)):
     if pat and not pat.search(d): continue
-    if a.get(k) != b.get(k): print(f"{d:56s} {a.get(k)} -> {b.get(k)}")
+    if a.get(d) != b.get(d): print(f"{d:56s} {a.get(d)} -> {b.get(d)}")
