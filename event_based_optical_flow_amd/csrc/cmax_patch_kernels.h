@@ -68,7 +68,9 @@ k_patch_to_dense_adj(const T *__restrict__ gflow, int ph, int pw, int pad_h, int
     const int Clo = pc == 0 ? 0 : pc + pad_w, Chi = pc == pw - 1 ? gw - 1 : pc + pad_w;
     const int i_lo = max((Rlo - 1) * sw_h - h1 - 1, 0), i_hi = min((Rhi + 2) * sw_h - h1 + 1, H);
     const int j_lo = max((Clo - 1) * sw_w - w1 - 1, 0), j_hi = min((Chi + 2) * sw_w - w1 + 1, W);
-    const int bw = j_hi - j_lo, bh = i_hi - i_lo;
+    // a cell of a grid that reaches far beyond the sensor has no pixel on one axis or on both: an empty band, not a negative one
+    // (the product of two negative extents would walk rows and columns outside the image)
+    const int bw = max(j_hi - j_lo, 0), bh = max(i_hi - i_lo, 0);
     double acc[1] = {0.0};
     for (int t = threadIdx.x; t < bw * bh; t += blockDim.x) {
         const int i = i_lo + t / bw, j = j_lo + t % bw;

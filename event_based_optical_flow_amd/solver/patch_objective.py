@@ -52,8 +52,9 @@ class PatchFlowObjective:
                  patch_shift=(0, 0), cost="hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
                  blur_sigma: float = 1.0, time_aware: bool = False, time_bin: int = 10,
                  flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None,
-                 scale_later: bool = False):
-        """sliced: a distributed.TimeSlicedObjective around `handle` when the batch is time-sliced over ranks.  With the library's own
+                 scale_later: bool = False, omit_boundary: bool = True):
+        """omit_boundary: the reference's `arg["omit_boundary"]`, for the contrast terms and the total variation alike.
+        sliced: a distributed.TimeSlicedObjective around `handle` when the batch is time-sliced over ranks.  With the library's own
         communicator on the handle (RCCL) the native plan evaluates the whole batch (cmax_patch_plan_* exchange images + 2 n_patch
         numbers); otherwise -- torch.distributed collectives -- the autograd-chained path below does the same two exchanges.  That
         fall-back has no exact Hessian-vector product (TorchWrapper then takes a difference quotient of the gradient, which on this
@@ -78,7 +79,8 @@ class PatchFlowObjective:
         if self.time_aware and handle.time_bin != self.time_bin:
             handle.set_time_bins(self.time_bin)
         model = "dense-flow-voxel" if self.time_aware else "dense-flow"
-        self.contrast = ContrastObjective(handle, model, cost=cost, cost_with_weight=cost_with_weight, sigma=blur_sigma)
+        self.contrast = ContrastObjective(handle, model, cost=cost, cost_with_weight=cost_with_weight, sigma=blur_sigma,
+                                          omit_boundary=omit_boundary)
         self.device = handle.device  # read by scipy_autograd.TorchWrapper
         self.auto_slabs = True  # ensure_time_slabs: time-slab order of the batch follows the motion's size
         self._plan = None

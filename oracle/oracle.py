@@ -542,9 +542,12 @@ def gaussian_filter(img, sigma):
 def gradmag_reflect101(img):
     """GradientMagnitude.calculate_numpy with omit_boundary False (src/costs/gradient_magnitude.py:78-95), un-signed:
     mean(gx^2 + gy^2), gx = cv2.Sobel(img, CV_64F, 1, 0, ksize=3) / 8 (derivative along columns), gy = Sobel(0, 1) / 8,
-    OpenCV's default border BORDER_REFLECT_101 (numpy's pad mode 'reflect')."""
+    OpenCV's default border BORDER_REFLECT_101 (numpy's pad mode 'reflect'), per axis: an axis of one pixel has nothing to
+    reflect and repeats its line, the other axis of a 1 x n image still reflects."""
     img = _f64(img)
-    p = np.pad(img, 1, mode="reflect") if min(img.shape) > 1 else np.pad(img, 1, mode="edge")
+    p = img
+    for axis in (0, 1):
+        p = np.pad(p, [(1, 1) if k == axis else (0, 0) for k in (0, 1)], mode="reflect" if img.shape[axis] > 1 else "edge")
     gx = ((p[:-2, 2:] - p[:-2, :-2]) + 2.0 * (p[1:-1, 2:] - p[1:-1, :-2]) + (p[2:, 2:] - p[2:, :-2])) / 8.0
     gy = ((p[2:, :-2] - p[:-2, :-2]) + 2.0 * (p[2:, 1:-1] - p[:-2, 1:-1]) + (p[2:, 2:] - p[:-2, 2:])) / 8.0
     return float(np.mean(gx * gx + gy * gy))
