@@ -1969,22 +1969,41 @@ static void with_model(int model, F &&f) {
     else if (model == CMAX_MODEL_DENSE) f(int_c<CMAX_MODEL_DENSE>{});
     else f(int_c<CMAX_MODEL_VOXEL>{});
 }
+// f(int_c<COST>{}) for the contrast of an objective (check_objective_args: one of the two)
+template <class F>
+static void with_cost(int cost, F &&f) {
+    if (cost == CMAX_COST_VARIANCE) f(int_c<CMAX_COST_VARIANCE>{});
+    else f(int_c<CMAX_COST_GRADMAG>{});
+}
+// grid.x of a kernel that finds its segment with segment_of_block: one workgroup per segment, the same number on each of the 8 XCDs
+static int seg_blocks(int nseg) { return 8 * ((nseg + 7) / 8); }
+// the 6-byte events of the work list from segment seg0 on (one region per segment), or nullptr where the kernels read the 8-byte ones
+template <int MODEL>
+static const char *compact_events(const cmax_handle_s *h, int seg0 = 0) {
+    return (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
+}
 static int layout_threads(Layout id) {
     int thr = 0;
     with_layout<t256, t512, t1024, m512, b512, b1024>(id, [&](auto l) { thr = decltype(l)::kThr; });
     return thr;
 }
 
-template <int MODEL>
-static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, hipStream_t s, int nz = 1) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref, nz);  // z: candidate motions of cmax_objective_batch
+// the arguments every vote and gather of a weighted handle carries (cmax_set_event_weights): objective, cmax_iwe, the un-warped image
+static RefArgs weighted_args(const cmax_handle_s *h, const RefArgs &ra_in) {
     RefArgs ra = ra_in;
-    if (h->weighted) {  // every vote of a weighted handle is weighted: objective, cmax_iwe, the un-warped image
+    if (h->weighted) {
         ra.wgt = h->w_packed;
         ra.wnorm = h->d_wnorm;
     }
+    return ra;
+}
+
+template <int MODEL>
+static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, hipStream_t s, int nz = 1) {
+    const dim3 grid(seg_blocks(h->nseg), n_ref, nz);  // z: candidate motions of cmax_objective_batch
+    const RefArgs ra = weighted_args(h, ra_in);
     ProfScope prof(h, kProfVote, s);
-    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // 6-byte events, one region per segment
+    const char *cev = compact_events<MODEL>(h);
     for (int rep = 0; rep < h->prof_repeat; ++rep)
         with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
             using L = decltype(l);
@@ -2002,82 +2021,30 @@ static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
 
 // seg0 / seg_n: sub-range of the work list (a band of tile rows, see cmax_comm_set_c2_bands); seg_n < 0 = the whole list.  The
 // kernels only see a shifted list (RefArgs::win is shifted by the caller).
-// K3 of a weighted handle (cmax_set_event_weights): the same layouts and variants, the WEIGHTED instantiations, and only the folds of the
-// general path (eval_plan sends a weighted handle through K1 -> statistics -> K3; deterministic mode is refused)
+// A weighted handle (cmax_set_event_weights) runs the same layouts and variants in their WEIGHTED instantiations, and only the folds of
+// the general path (eval_plan sends it through K1 -> statistics -> K3; deterministic mode is refused): the other combinations are
+// not instantiated.
 template <int MODEL>
-static void launch_grad_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, int fold,
-                                 const ObjParams &op, double *gpart, float *gflow, double *result, bool owned, hipStream_t s, int seg0,
-                                 int seg_n, int nz) {
-    const int4 *segs = h->d_segs + seg0;
-    const int nseg = seg_n < 0 ? h->nseg : seg_n;
-    const dim3 grid(8 * ((nseg + 7) / 8), n_ref, nz);
-    if (fold == kFoldDeferred || fold == kFoldStatsInside || h->deterministic) std::abort();  // (eval_plan never asks for these)
-    ProfScope prof(h, kProfGrad, s);
-    RefArgs ra = ra_in;
-    ra.wgt = h->w_packed;
-    ra.wnorm = h->d_wnorm;
-    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
-    auto launch = [&](auto l, auto frac, auto fold_c, auto variant) {
-        using L = decltype(l);
-        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, true>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev, cev,
-                           (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
-    };
-    const bool strided = MODEL == CMAX_MODEL_DENSE && !(h->long_runs && h->n_time_bin == 0);
-    const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big;
-    auto body = [&](auto l) {
-        using L = decltype(l);
-        auto with_variant = [&](auto frac, auto fold_c) {
-            if constexpr (MODEL == CMAX_MODEL_DENSE) {
-                if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{});
-                else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{});
-                else launch(l, frac, fold_c, int_c<kGradRuns>{});
-            } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
-                if (owned && small) {
-                    if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{});
-                } else if (owned) {
-                    launch(l, frac, fold_c, int_c<kGradOwned>{});
-                } else {
-                    launch(l, frac, fold_c, int_c<kGradRuns>{});
-                }
-            } else {
-                launch(l, frac, fold_c, int_c<kGradRuns>{});
-            }
-        };
-        with_bool(h->has_frac, [&](auto frac) {
-            if (fold == kFoldStats) with_variant(frac, int_c<kFoldStats>{});
-            else if (fold == kFoldScale) with_variant(frac, int_c<kFoldScale>{});
-            else with_variant(frac, int_c<kFoldNone>{});
-        });
-    };
-    for (int rep = 0; rep < h->prof_repeat; ++rep) {
-        if constexpr (MODEL == CMAX_MODEL_VOXEL) with_layout<b1024, m512, t512, t1024, t256>(grad_layout(h, MODEL, owned), body);
-        else with_layout<b512, m512, t512, t256>(grad_layout(h, MODEL, owned), body);
-    }
-}
-
-template <int MODEL>
-static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_ref, int fold,
+static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, int fold,
                         const ObjParams &op, double *gpart, float *gflow, double *result, bool owned, hipStream_t s, int seg0 = 0,
                         int seg_n = -1, int nz = 1) {
-    if (h->weighted) {
-        launch_grad_weighted<MODEL>(h, ev, wp, ra, n_ref, fold, op, gpart, gflow, result, owned, s, seg0, seg_n, nz);
-        return;
-    }
+    if (h->weighted && (fold == kFoldDeferred || fold == kFoldStatsInside || h->deterministic)) std::abort();  // (eval_plan never asks for these)
     const int4 *segs = h->d_segs + seg0;
     const int nseg = seg_n < 0 ? h->nseg : seg_n;
-    const dim3 grid(8 * ((nseg + 7) / 8) + (fold == kFoldStatsInside ? ra.stat_blocks : 0), n_ref, nz);
+    const dim3 grid(seg_blocks(nseg) + (fold == kFoldStatsInside ? ra_in.stat_blocks : 0), n_ref, nz);
     ProfScope prof(h, kProfGrad, s);
-    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
-    auto launch = [&](auto l, auto frac, auto fold_c, auto variant) {
+    const RefArgs ra = weighted_args(h, ra_in);
+    const char *cev = compact_events<MODEL>(h, seg0);
+    auto launch = [&](auto l, auto frac, auto fold_c, auto variant, auto weighted) {
         using L = decltype(l);
-        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev, cev,
-                           (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
+        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, weighted.value>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev,
+                           cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
     };
     if (h->deterministic) {  // one workgroup size, two ways of obtaining dL/dIWE (objective_finish runs the unfused image path)
         with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
             with_bool(h->has_frac, [&](auto frac) {
-                if (fold == kFoldStats) launch(l, frac, int_c<kFoldStats>{}, int_c<kGradDet>{});
-                else launch(l, frac, int_c<kFoldNone>{}, int_c<kGradDet>{});
+                if (fold == kFoldStats) launch(l, frac, int_c<kFoldStats>{}, int_c<kGradDet>{}, std::false_type{});
+                else launch(l, frac, int_c<kFoldNone>{}, int_c<kGradDet>{}, std::false_type{});
             });
         });
         return;
@@ -2090,35 +2057,38 @@ static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
     const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big;
     auto body = [&](auto l) {
         using L = decltype(l);
-        auto with_variant = [&](auto frac, auto fold_c) {
-            if constexpr (MODEL == CMAX_MODEL_DENSE) {
-                if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{});
-                else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{});
-                else launch(l, frac, fold_c, int_c<kGradRuns>{});
-            } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
-                if (owned && small) {
-                    if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{});
-                } else if (owned) {
-                    launch(l, frac, fold_c, int_c<kGradOwned>{});
+        with_bool(h->weighted, [&](auto weighted) {
+            constexpr bool kWeighted = decltype(weighted)::value;
+            auto with_variant = [&](auto frac, auto fold_c) {
+                if constexpr (MODEL == CMAX_MODEL_DENSE) {
+                    if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{}, weighted);
+                    else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{}, weighted);
+                    else launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
+                } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
+                    if (owned && small) {
+                        if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{}, weighted);
+                    } else if (owned) {
+                        launch(l, frac, fold_c, int_c<kGradOwned>{}, weighted);
+                    } else {
+                        launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
+                    }
                 } else {
-                    launch(l, frac, fold_c, int_c<kGradRuns>{});
+                    launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
                 }
-            } else {
-                launch(l, frac, fold_c, int_c<kGradRuns>{});
-            }
-        };
-        with_bool(h->has_frac, [&](auto frac) {
-            if (fold == kFoldDeferred) {
-                if constexpr (MODEL == CMAX_MODEL_2DOF) with_variant(frac, int_c<kFoldDeferred>{});
-            } else if (fold == kFoldStatsInside) {
-                if constexpr (MODEL != CMAX_MODEL_2DOF) with_variant(frac, int_c<kFoldStatsInside>{});
-            } else if (fold == kFoldStats) {
-                with_variant(frac, int_c<kFoldStats>{});
-            } else if (fold == kFoldScale) {
-                with_variant(frac, int_c<kFoldScale>{});
-            } else {
-                with_variant(frac, int_c<kFoldNone>{});
-            }
+            };
+            with_bool(h->has_frac, [&](auto frac) {
+                if (fold == kFoldDeferred) {
+                    if constexpr (MODEL == CMAX_MODEL_2DOF && !kWeighted) with_variant(frac, int_c<kFoldDeferred>{});
+                } else if (fold == kFoldStatsInside) {
+                    if constexpr (MODEL != CMAX_MODEL_2DOF && !kWeighted) with_variant(frac, int_c<kFoldStatsInside>{});
+                } else if (fold == kFoldStats) {
+                    with_variant(frac, int_c<kFoldStats>{});
+                } else if (fold == kFoldScale) {
+                    with_variant(frac, int_c<kFoldScale>{});
+                } else {
+                    with_variant(frac, int_c<kFoldNone>{});
+                }
+            });
         });
     };
     for (int rep = 0; rep < h->prof_repeat; ++rep) {
@@ -2278,15 +2248,12 @@ static int launch_stats(cmax_handle_s *h, int cost, const float *img, int omit, 
     double *stat_slot = h->d_stat + slot * kStatStride;
     ProfScope prof(h, kProfStats, s);
     for (int rep = 0; rep < h->prof_repeat; ++rep) {
-        if (h->deterministic) {  // kStatSub workgroups of 1024 threads: every accumulator is written once, the summation order is fixed
-            if (cost == CMAX_COST_VARIANCE)
-                hipLaunchKernelGGL((k_stats<CMAX_COST_VARIANCE, 1024>), dim3(grid), dim3(1024), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
+        with_cost(cost, [&](auto c) {
+            if (h->deterministic)  // kStatSub workgroups of 1024 threads: every accumulator is written once, the summation order is fixed
+                hipLaunchKernelGGL((k_stats<c.value, 1024>), dim3(grid), dim3(1024), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
             else
-                hipLaunchKernelGGL((k_stats<CMAX_COST_GRADMAG, 1024>), dim3(grid), dim3(1024), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
-        } else if (cost == CMAX_COST_VARIANCE)
-            hipLaunchKernelGGL(k_stats<CMAX_COST_VARIANCE>, dim3(grid), dim3(256), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
-        else
-            hipLaunchKernelGGL(k_stats<CMAX_COST_GRADMAG>, dim3(grid), dim3(256), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
+                hipLaunchKernelGGL(k_stats<c.value>, dim3(grid), dim3(256), 0, s, img, h->Hp, h->Wp, omit, nsub, stat_slot, zero_img, (float4 *)zero_extra, n_extra / 4);
+        });
     }
     CMAX_CHECK_LAUNCH();
     return 0;
@@ -3633,12 +3600,10 @@ static int finish_gimage(cmax_handle_s *h, const cmax_objective_t *d, const Eval
             float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
             const dim3 igrid(div_up(npix, 256), d->n_ref);
             // the n_ref images are not contiguous (last_iwe[k] = blurred copies or the caller's buffer): one launch each
-            for (int k = 0; k < d->n_ref; ++k) {
-                if (d->cost == CMAX_COST_VARIANCE)
-                    hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-                else
-                    hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-            }
+            with_cost(d->cost, [&](auto c) {
+                for (int k = 0; k < d->n_ref; ++k)
+                    hipLaunchKernelGGL(k_gimage<c.value>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+            });
             if (d->sigma > 0) hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt_det, Hp, Wp, p.tap0, p.tap1, h->G, npix);
             CMAX_CHECK_LAUNCH();
         }
@@ -3828,7 +3793,7 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
     const WarpParams wp = warp_params(h, motion, 0, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
     if (h->n > 0) {
         const EvView ev = ev_view(h);
-        const dim3 grid(8 * ((h->nseg + 7) / 8), nr);
+        const dim3 grid(seg_blocks(h->nseg), nr);
         ProfScope prof(h, kProfVote, s);
         for (int rep = 0; rep < h->prof_repeat; ++rep) {
             with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
@@ -3969,17 +3934,22 @@ __global__ void __launch_bounds__(256) k_weight_grad_scatter(const float *__rest
     grad_w[src[i]] = a;
 }
 
+// The launch form of the per-event gathers (K3w, K3e) over n_img images: K1's grid, events and layout (launch_vote), whose windows
+// they read.  f(L{}, frac, grid, cev) launches the kernel.
+template <int MODEL, class F>
+static void launch_gather(cmax_handle_s *h, int n_img, F &&f) {
+    const dim3 grid(seg_blocks(h->nseg), n_img);
+    const char *cev = compact_events<MODEL>(h);
+    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) { with_bool(h->has_frac, [&](auto frac) { f(l, frac, grid, cev); }); });
+}
+
 // K3w of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
 template <int MODEL>
 static void launch_weight_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_img, int plane0, hipStream_t s) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_img);
-    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // as K1 (launch_vote)
-    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+    launch_gather<MODEL>(h, n_img, [&](auto l, auto frac, dim3 grid, const char *cev) {
         using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            hipLaunchKernelGGL((k_weight_gather<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev, wp, ra,
-                               h->gw_packed + (int64_t)plane0 * h->gw_plane, h->gw_plane);
-        });
+        hipLaunchKernelGGL((k_weight_gather<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev, wp, ra,
+                           h->gw_packed + (int64_t)plane0 * h->gw_plane, h->gw_plane);
     });
 }
 
@@ -4039,19 +4009,54 @@ __global__ void __launch_bounds__(256) k_event_csum_finish(const double *__restr
 // K3e of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
 template <int MODEL>
 static void launch_event_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_img, int plane0, hipStream_t s) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_img);
-    const char *cev = (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev : nullptr;  // as K1 (launch_vote)
     RefArgs ra = ra_in;
     if (h->weighted) ra.wgt = h->w_packed;
-    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+    launch_gather<MODEL>(h, n_img, [&](auto l, auto frac, dim3 grid, const char *cev) {
         using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            with_bool(h->weighted, [&](auto wgt) {
-                hipLaunchKernelGGL((k_event_grad_gather<L, MODEL, frac.value, wgt.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev,
-                                   wp, ra, h->ge_packed + (int64_t)plane0 * h->ge_plane, h->ge_plane);
-            });
+        with_bool(h->weighted, [&](auto wgt) {
+            hipLaunchKernelGGL((k_event_grad_gather<L, MODEL, frac.value, wgt.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev,
+                               wp, ra, h->ge_packed + (int64_t)plane0 * h->ge_plane, h->ge_plane);
         });
     });
+}
+
+// the first n_planes of a packed per-event buffer (gw_packed: 5 planes, ge_packed: kEventGradPlanes), zeroed; a plane is sized like w_packed
+static int reserve_packed_planes(cmax_handle_s *h, float **packed, int64_t *plane_len, int capacity, int n_planes, hipStream_t s) {
+    if (h->n > *plane_len) {
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        dev_free(packed);
+        *plane_len = 0;
+        const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
+        int rc = dev_alloc(h, packed, capacity * plane);
+        if (rc) return rc;
+        *plane_len = plane;
+    }
+    CMAX_CHECK_HIP(hipMemsetAsync(*packed, 0, (size_t)n_planes * *plane_len * sizeof(float), s));
+    return 0;
+}
+
+// One more plane: the un-warped events against G_orig, behind a K1 launch that only publishes their windows.  gather(ev, wp, ra) launches
+// K3w / K3e of that one image into its plane.
+template <class Gather>
+static int gather_unwarped(cmax_handle_s *h, const float *G_orig, hipStream_t s, Gather &&gather) {
+    const EvView ev = ev_view(h);
+    RefArgs ra = {};
+    const int ref_mode = CMAX_REF_FIRST;
+    const double frac = 0.0;
+    fill_ref_times(ra, 1, &ref_mode, &frac);
+    ra.win = h->d_win;
+    ra.shifts = h->d_shifts;
+    ra.windows_only = 1;
+    const WarpParams wp = warp_params(h, nullptr, 0, CMAX_REF_FIRST, 0.0, 1);
+    launch_vote<-1>(h, ev, wp, ra, 1, s);
+    CMAX_CHECK_LAUNCH();
+    h->win_motion = nullptr;  // (the handle's windows are no evaluation's any more)
+    h->win_generation = ~(uint64_t)0;
+    ra.windows_only = 0;
+    ra.img[0] = const_cast<float *>(G_orig);  // (read only by the gather)
+    gather(ev, wp, ra);
+    CMAX_CHECK_LAUNCH();
+    return 0;
 }
 
 // behind objective_eval of the same call: its images, statistics, windows and cell offsets are the handle's current ones.
@@ -4069,17 +4074,8 @@ static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const f
         if (!rc) rc = dev_alloc(h, &h->gw_Gt, 5 * npix);
         if (rc) return rc;
     }
-    float **packed = events ? &h->ge_packed : &h->gw_packed;
-    int64_t *plane_len = events ? &h->ge_plane : &h->gw_plane;
-    if (h->n > *plane_len) {  // sized like w_packed
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(packed);
-        *plane_len = 0;
-        const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
-        rc = dev_alloc(h, packed, (events ? kEventGradPlanes : 5) * plane);
-        if (rc) return rc;
-        *plane_len = plane;
-    }
+    rc = events ? reserve_packed_planes(h, &h->ge_packed, &h->ge_plane, kEventGradPlanes, n_planes, s) : reserve_packed_planes(h, &h->gw_packed, &h->gw_plane, 5, n_planes, s);
+    if (rc) return rc;
     if (events) {  // per-workgroup partial sums of the scatter (csum), [4][blocks]
         const int64_t blocks = div_up(h->n, 256);
         if (blocks > h->ge_part_cap) {
@@ -4091,24 +4087,19 @@ static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const f
             h->ge_part_cap = blocks;
         }
     }
-    CMAX_CHECK_HIP(hipMemsetAsync(*packed, 0, (size_t)n_planes * *plane_len * sizeof(float), s));
     const ObjParams op = obj_params(h, d);
     double k0 = 0, k1 = 0;
     if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
     // G_k = dL/dIWE_k with its chain factor (multi-focal multipliers included), the blur transpose applied
     float *gdst = d->sigma > 0 ? h->gw_Gt : h->gw_G;
     const dim3 igrid(div_up(npix, 256));
-    for (int k = 0; k < nr; ++k) {
-        if (d->cost == CMAX_COST_VARIANCE)
-            hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-        else
-            hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-    }
-    if (d->normalized) {  // slot 4: G_orig on the (blurred) un-warped image
-        const float *img = d->sigma > 0 ? h->iweb[4] : orig_raw;
-        if (d->cost == CMAX_COST_VARIANCE) hipLaunchKernelGGL(k_gimage_orig<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, img, op, h->d_stat, gdst + 4 * npix);
-        else hipLaunchKernelGGL(k_gimage_orig<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, img, op, h->d_stat, gdst + 4 * npix);
-    }
+    with_cost(d->cost, [&](auto c) {
+        for (int k = 0; k < nr; ++k) hipLaunchKernelGGL(k_gimage<c.value>, igrid, dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+        if (d->normalized) {  // slot 4: G_orig on the (blurred) un-warped image
+            const float *img = d->sigma > 0 ? h->iweb[4] : orig_raw;
+            hipLaunchKernelGGL(k_gimage_orig<c.value>, igrid, dim3(256), 0, s, img, op, h->d_stat, gdst + 4 * npix);
+        }
+    });
     if (d->sigma > 0) {
         hipLaunchKernelGGL(k_blur3_adj<float>, dim3(igrid.x, nr), dim3(256), 0, s, h->gw_Gt, Hp, Wp, (float)k0, (float)k1, h->gw_G, npix);
         if (d->normalized)
@@ -4129,24 +4120,12 @@ static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const f
         });
         CMAX_CHECK_LAUNCH();
     }
-    if (d->normalized) {  // one more plane: the un-warped events against G_orig, behind a K1 launch that only publishes their windows
-        RefArgs ra = {};
-        const int ref_mode = CMAX_REF_FIRST;
-        const double frac = 0.0;
-        fill_ref_times(ra, 1, &ref_mode, &frac);
-        ra.win = h->d_win;
-        ra.shifts = h->d_shifts;
-        ra.windows_only = 1;
-        const WarpParams wp = warp_params(h, nullptr, 0, CMAX_REF_FIRST, 0.0, 1);
-        launch_vote<-1>(h, ev, wp, ra, 1, s);
-        CMAX_CHECK_LAUNCH();
-        h->win_motion = nullptr;  // (the handle's windows are no evaluation's any more)
-        h->win_generation = ~(uint64_t)0;
-        ra.windows_only = 0;
-        ra.img[0] = h->gw_G + 4 * npix;
-        if (events) launch_event_gather<-1>(h, ev, wp, ra, 1, 3 * nr, s);
-        else launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
-        CMAX_CHECK_LAUNCH();
+    if (d->normalized) {
+        rc = gather_unwarped(h, h->gw_G + 4 * npix, s, [&](const EvView &ev, const WarpParams &wp, const RefArgs &ra) {
+            if (events) launch_event_gather<-1>(h, ev, wp, ra, 1, 3 * nr, s);
+            else launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
+        });
+        if (rc) return rc;
     }
     if (events) {
         const int64_t blocks = div_up(h->n, 256);
@@ -4163,31 +4142,52 @@ static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const f
 
 extern "C" {
 
-int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad, float *grad_w,
-                               int64_t n, cmax_stream_t stream) {
-    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
-    int rc = check_objective_args(h, d, motion);
-    if (rc) return rc;
-    CMAX_REQUIRE(result && (grad_w || n == 0), "objective_weight_grad: result / grad_w (grad_w may be NULL only for n == 0)");
-    CMAX_REQUIRE(n == h->n_in, "objective_weight_grad: n must equal the n of the last cmax_set_events (one derivative per event, in the caller's order)");
+// the per-event derivatives and the IWE layer are not built for these two kinds of handle (`what`: the entry that was called)
+static int refuse_det_or_comm(const cmax_handle_s *h, const char *what) {
     if (h->deterministic) {
-        set_error("objective_weight_grad: not built for deterministic mode (cmax_set_deterministic)");
+        set_error("%s: not built for deterministic mode (cmax_set_deterministic)", what);
         return CMAX_EUNSUPPORTED;
     }
     if (h->comm) {
-        set_error("objective_weight_grad: not built for a handle with a communicator (cmax_comm_init)");
+        set_error("%s: not built for a handle with a communicator (cmax_comm_init)", what);
         return CMAX_EUNSUPPORTED;
     }
-    hipStream_t s = (hipStream_t)stream;
-    if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
-    // the general path (K1 -> statistics / image kernel -> K3) on any handle, and the un-warped image voted again: G_orig needs the image
-    // itself, the per-batch cache keeps its statistics only
+    return 0;
+}
+
+// what cmax_objective_weight_grad and _event_grad check alike (`what`: the entry that was called)
+static int per_event_check(cmax_handle_t h, const cmax_objective_t *d, const float *motion, int64_t n, const char *what) {
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    if (n != h->n_in) {
+        set_error("%s:%d bad argument: %s: n must equal the n of the last cmax_set_events (one row of the result per event, in the caller's order)", __FILE__, __LINE__, what);
+        return CMAX_EINVAL;
+    }
+    return refuse_det_or_comm(h, what);
+}
+
+// The evaluation in front of per_event_finish: the general path (K1 -> statistics / image kernel -> K3) on any handle, and the un-warped
+// image voted again into *orig_raw: G_orig needs the image itself, the per-batch cache keeps its statistics only
+static int per_event_eval(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s, const float **orig_raw) {
     const int64_t npix = (int64_t)h->Hp * h->Wp;
-    const float *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
+    *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
     h->general_only = true;
     if (d->normalized) h->orig_valid = false;
-    rc = objective_eval(h, d, motion, result, grad, s, nullptr);
+    const int rc = objective_eval(h, d, motion, result, grad, s, nullptr);
     h->general_only = false;
+    return rc;
+}
+
+int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad, float *grad_w,
+                               int64_t n, cmax_stream_t stream) {
+    const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
+    CMAX_REQUIRE(result && (grad_w || n == 0), "objective_weight_grad: result / grad_w (grad_w may be NULL only for n == 0)");
+    int rc = per_event_check(h, d, motion, n, "objective_weight_grad");
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
+    const float *orig_raw = nullptr;
+    rc = per_event_eval(h, d, motion, result, grad, s, &orig_raw);
     if (rc || h->n == 0) return rc;
     return per_event_finish(h, d, motion, orig_raw, grad_w, nullptr, nullptr, s);
 }
@@ -4195,28 +4195,14 @@ int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const
 int cmax_objective_event_grad(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result, void *grad, float *grad_events,
                               int64_t n, double *csum, cmax_stream_t stream) {
     const float *motion = static_cast<const float *>(motion_v);  // double theta[2] when d->motion_dtype == CMAX_F64
-    int rc = check_objective_args(h, d, motion);
-    if (rc) return rc;
     CMAX_REQUIRE(result && csum && (grad_events || n == 0), "objective_event_grad: result / csum / grad_events (grad_events may be NULL only for n == 0)");
-    CMAX_REQUIRE(n == h->n_in, "objective_event_grad: n must equal the n of the last cmax_set_events (one row per event, in the caller's order)");
-    if (h->deterministic) {
-        set_error("objective_event_grad: not built for deterministic mode (cmax_set_deterministic)");
-        return CMAX_EUNSUPPORTED;
-    }
-    if (h->comm) {
-        set_error("objective_event_grad: not built for a handle with a communicator (cmax_comm_init)");
-        return CMAX_EUNSUPPORTED;
-    }
+    int rc = per_event_check(h, d, motion, n, "objective_event_grad");
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_events, 0, (size_t)n * 3 * sizeof(float), s));
     CMAX_CHECK_HIP(hipMemsetAsync(csum, 0, 4 * sizeof(double), s));
-    // the general path and the un-warped image voted again, as cmax_objective_weight_grad
-    const int64_t npix = (int64_t)h->Hp * h->Wp;
-    const float *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
-    h->general_only = true;
-    if (d->normalized) h->orig_valid = false;
-    rc = objective_eval(h, d, motion, result, grad, s, nullptr);
-    h->general_only = false;
+    const float *orig_raw = nullptr;
+    rc = per_event_eval(h, d, motion, result, grad, s, &orig_raw);
     if (rc || h->n == 0) return rc;
     return per_event_finish(h, d, motion, orig_raw, nullptr, grad_events, csum, s);
 }
@@ -4538,34 +4524,93 @@ int cmax_comm_allreduce(cmax_handle_t h, void *buf, int64_t count, int dtype, in
 
 namespace cmax {
 
-// tangent votes of every reference time (blockIdx.y) into draw + k * tp.bs (zeroed by the caller)
+// tangent votes of every reference time (blockIdx.y) into draw + k * tp.bs (zeroed by the caller); draw64: the integer images of
+// deterministic mode.  A weighted handle passes its weights behind them (a weighted deterministic handle is refused at every entry).
 template <int MODEL>
 static void launch_vote_tan(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, float *draw, hipStream_t s,
                             long long *draw64 = nullptr) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
+    if (h->weighted && draw64) std::abort();
+    const dim3 grid(seg_blocks(h->nseg), n_ref);
     with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
         using L = decltype(l);
         with_bool(h->has_frac, [&](auto frac) {
-            hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
+            if (h->weighted)
+                hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw,
+                                   h->d_stat_tan, draw64, (const float *)h->w_packed, (const float *)h->d_wnorm);
+            else
+                hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
         });
     });
 }
 
+// det: the integer accumulators of deterministic mode (HvpDet{} otherwise); weights as launch_vote_tan
 template <int MODEL>
 static void launch_grad_hvp(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, const float *G,
                             const float *Gp, double *gpart, float *hflow, hipStream_t s, const HvpDet &det) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
+    if (h->weighted && h->deterministic) std::abort();
+    const dim3 grid(seg_blocks(h->nseg), n_ref);
     with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
         using L = decltype(l);
         with_bool(h->has_frac, [&](auto frac) {
-            hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
+            if (h->weighted)
+                hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det,
+                                   (const float *)h->w_packed);
+            else
+                hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
         });
     });
+}
+
+// scratch of the second-order path and of the IWE layer: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
+static int tangent_scratch(cmax_handle_s *h) {
+    if (h->hvp_img) return 0;
+    const int64_t npix = (int64_t)h->Hp * h->Wp;
+    int rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
+    if (!rc) rc = dev_alloc(h, &h->d_stat_tan, 4 * kStatStride);
+    if (!rc) {
+        dev_free(&h->Gt);
+        rc = dev_alloc(h, &h->Gt, 4 * npix);
+    }
+    return rc;
+}
+
+// derivative votes are bounded by 2 |dt|_max (the tangent has unit max-norm): fixed-point scale per reference time
+static TanParams tangent_params(const cmax_handle_s *h, const cmax_objective_t *d, const float *tangent) {
+    const double period = d->normalize_t ? 1.0 : (h->tmax_host - h->tmin_host);
+    TanParams tp = {};
+    tp.u = tangent;
+    tp.bs = (int64_t)h->Hp * h->Wp;
+    for (int k = 0; k < d->n_ref; ++k) {
+        const double dref = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
+        double dtmax = fabs(dref) > fabs(1.0 - dref) ? fabs(dref) : fabs(1.0 - dref);
+        dtmax *= period > 0 ? period : 1.0;
+        if (dtmax < 1e-30) dtmax = 1e-30;
+        tp.d[k] = (float)dref;
+        tp.fixk[k] = (float)(1073741824.0 / ((double)h->seg_max * 2.0 * dtmax));  // 2^30 / (events * max |derivative vote|)
+    }
+    tp.fix = tp.fixk[0];
+    tp.inv_fix = 1.f / tp.fix;
+    return tp;
 }
 
 }  // namespace cmax
 
 extern "C" {
+
+// T3 against the images G (current) and Gp (tangent) into `out` (zeroed by the caller): 2-DoF partials folded by k_finish, flow models
+// added per event; in deterministic mode both accumulate the integers of `det` and launch_finish_det rounds them once
+static int second_order_gather(cmax_handle_s *h, const cmax_objective_t *d, const EvView &ev, const WarpParams &wp, const TanParams &tp, const float *G,
+                               const float *Gp, void *out, const HvpDet &det, hipStream_t s) {
+    const bool two_dof = d->model == CMAX_MODEL_2DOF;
+    with_model(d->model, [&](auto m) { launch_grad_hvp<m.value>(h, ev, wp, tp, d->n_ref, G, Gp, two_dof ? h->d_gpart : nullptr, two_dof ? nullptr : (float *)out, s, det); });
+    CMAX_CHECK_LAUNCH();
+    if (h->deterministic) return launch_finish_det(h, d, out, s);
+    if (two_dof) {
+        hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, s, h->d_gpart, d->n_ref * h->nseg, (double *)out);
+        CMAX_CHECK_LAUNCH();
+    }
+    return 0;
+}
 
 // comm: the handle holds a time slice of the batch -- the images and the tangent images are all-reduced (ONE grouped call: both are
 // sums over events), everything in image space runs redundantly on every rank, the second-order gather covers this rank's events;
@@ -4580,15 +4625,8 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     const GradExtent g = grad_extent(h, d);
     CMAX_CHECK_HIP(hipMemsetAsync(hv, 0, g.bytes, s));
     if (h->n == 0 && !dist) return 0;
-    if (!h->hvp_img) {
-        rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
-        if (!rc) rc = dev_alloc(h, &h->d_stat_tan, 4 * kStatStride);
-        if (!rc) {
-            dev_free(&h->Gt);
-            rc = dev_alloc(h, &h->Gt, 4 * npix);
-        }
-        if (rc) return rc;
-    }
+    rc = tangent_scratch(h);
+    if (rc) return rc;
     // [6 kinds][4 reference times][npix]: every kernel of the chain covers all reference times in one launch
     // (blockIdx.y, element stride npix)
     const int64_t bs = npix;
@@ -4611,25 +4649,11 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
         if (rc) return rc;
     }
 
-    // derivative votes are bounded by 2 |dt|_max (the tangent has unit max-norm): fixed-point scale per reference time
-    const double period = d->normalize_t ? 1.0 : (h->tmax_host - h->tmin_host);
     const EvView ev = ev_view(h);
     double k0 = 0, k1 = 0;
     if (d->sigma > 0) blur_taps(d->sigma, k0, k1);
     const dim3 igrid(div_up(npix, 256), nr), sgrid(stat_blocks(h), nr);
-    TanParams tp = {};
-    tp.u = tangent;
-    tp.bs = bs;
-    for (int k = 0; k < nr; ++k) {
-        const double dref = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        double dtmax = fabs(dref) > fabs(1.0 - dref) ? fabs(dref) : fabs(1.0 - dref);
-        dtmax *= period > 0 ? period : 1.0;
-        if (dtmax < 1e-30) dtmax = 1e-30;
-        tp.d[k] = (float)dref;
-        tp.fixk[k] = (float)(1073741824.0 / ((double)h->seg_max * 2.0 * dtmax));  // 2^30 / (events * max |derivative vote|)
-    }
-    tp.fix = tp.fixk[0];
-    tp.inv_fix = 1.f / tp.fix;
+    const TanParams tp = tangent_params(h, d, tangent);
     const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
     // images, their blur and statistics (slots 0 .. nr-1)
     CMAX_CHECK_HIP(hipMemsetAsync(I, 0, (size_t)nr * npix * sizeof(float), s));
@@ -4678,10 +4702,9 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
         hipLaunchKernelGGL(k_blur3<float>, igrid, dim3(256), 0, s, I, Hp, Wp, (float)k0, (float)k1, Ib, bs);
         img = Ib;
     }
-    if (d->cost == CMAX_COST_VARIANCE)
-        hipLaunchKernelGGL(k_stats<CMAX_COST_VARIANCE>, sgrid, dim3(256), 0, s, img, Hp, Wp, d->omit_boundary, nsub, h->d_stat, (float *)nullptr, (float4 *)nullptr, (int64_t)0, bs);
-    else
-        hipLaunchKernelGGL(k_stats<CMAX_COST_GRADMAG>, sgrid, dim3(256), 0, s, img, Hp, Wp, d->omit_boundary, nsub, h->d_stat, (float *)nullptr, (float4 *)nullptr, (int64_t)0, bs);
+    with_cost(d->cost, [&](auto c) {
+        hipLaunchKernelGGL(k_stats<c.value>, sgrid, dim3(256), 0, s, img, Hp, Wp, d->omit_boundary, nsub, h->d_stat, (float *)nullptr, (float4 *)nullptr, (int64_t)0, bs);
+    });
     CMAX_CHECK_LAUNCH();
     // (the tangent images were voted above, next to the images)
     if (d->sigma > 0) {
@@ -4690,15 +4713,11 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     }
     // T2: tangent statistics, G (current) and G' (tangent), blur transposes
     float *Gk = d->sigma > 0 ? h->Gt : h->G, *Gpk = d->sigma > 0 ? Gpt : Gp;
-    if (d->cost == CMAX_COST_VARIANCE) {
-        hipLaunchKernelGGL(k_stats_tan<CMAX_COST_VARIANCE>, sgrid, dim3(256), 0, s, img, dimg, Hp, Wp, d->omit_boundary, nsub, h->d_stat_tan, bs);
-        hipLaunchKernelGGL(k_gimage<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, img, op, 0, h->d_stat, Gk, bs);
-        hipLaunchKernelGGL(k_gimage_tan<CMAX_COST_VARIANCE>, igrid, dim3(256), 0, s, img, dimg, op, 0, h->d_stat, h->d_stat_tan, Gpk, bs);
-    } else {
-        hipLaunchKernelGGL(k_stats_tan<CMAX_COST_GRADMAG>, sgrid, dim3(256), 0, s, img, dimg, Hp, Wp, d->omit_boundary, nsub, h->d_stat_tan, bs);
-        hipLaunchKernelGGL(k_gimage<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, img, op, 0, h->d_stat, Gk, bs);
-        hipLaunchKernelGGL(k_gimage_tan<CMAX_COST_GRADMAG>, igrid, dim3(256), 0, s, img, dimg, op, 0, h->d_stat, h->d_stat_tan, Gpk, bs);
-    }
+    with_cost(d->cost, [&](auto c) {
+        hipLaunchKernelGGL(k_stats_tan<c.value>, sgrid, dim3(256), 0, s, img, dimg, Hp, Wp, d->omit_boundary, nsub, h->d_stat_tan, bs);
+        hipLaunchKernelGGL(k_gimage<c.value>, igrid, dim3(256), 0, s, img, op, 0, h->d_stat, Gk, bs);
+        hipLaunchKernelGGL(k_gimage_tan<c.value>, igrid, dim3(256), 0, s, img, dimg, op, 0, h->d_stat, h->d_stat_tan, Gpk, bs);
+    });
     if (d->sigma > 0) {
         hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt, Hp, Wp, (float)k0, (float)k1, h->G, bs);
         hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, Gpt, Hp, Wp, (float)k0, (float)k1, Gp, bs);
@@ -4728,15 +4747,8 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
         hd.n_events = h->n;
         hd.n_ref = nr;
     }
-    with_model(d->model, [&](auto m) { launch_grad_hvp<m.value>(h, ev, wp, tp, nr, h->G, Gp, two_dof ? h->d_gpart : nullptr, two_dof ? nullptr : (float *)hv, s, hd); });
-    CMAX_CHECK_LAUNCH();
-    if (det) {
-        rc = launch_finish_det(h, d, hv, s);
-        if (rc) return rc;
-    } else if (two_dof) {
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, s, h->d_gpart, d->n_ref * h->nseg, (double *)hv);
-        CMAX_CHECK_LAUNCH();
-    }
+    rc = second_order_gather(h, d, ev, wp, tp, h->G, Gp, hv, hd, s);
+    if (rc) return rc;
     if (dist && reduce_hv) {
         ProfScope prof(h, kProfComm, s);
         rc = comm_allreduce(comm, hv, (size_t)g.count, g.type, kCommSum, s);
@@ -4770,31 +4782,6 @@ int cmax_objective_hvp_dist(cmax_handle_t h, const cmax_objective_t *d, const vo
 // ---- the image of warped events as a differentiable layer (cmax_iwes, _vjp, _jvp, _vjp_tan) --------------------------------------------
 namespace cmax {
 
-template <int MODEL>
-static void launch_vote_tan_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, float *draw, hipStream_t s) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
-    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-        using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw,
-                               h->d_stat_tan, (long long *)nullptr, (const float *)h->w_packed, (const float *)h->d_wnorm);
-        });
-    });
-}
-
-template <int MODEL>
-static void launch_grad_hvp_weighted(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, const float *G, const float *Gp,
-                                     double *gpart, float *hflow, hipStream_t s) {
-    const dim3 grid(8 * ((h->nseg + 7) / 8), n_ref);
-    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-        using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow,
-                               HvpDet{}, (const float *)h->w_packed);
-        });
-    });
-}
-
 // the part of an objective descriptor the event side reads (argument checks, warp parameters, windows)
 static cmax_objective_t iwes_as_objective(const cmax_iwes_t *d) {
     cmax_objective_t o = {};
@@ -4819,47 +4806,7 @@ static int iwes_check(cmax_handle_t h, const cmax_iwes_t *d, const void *motion,
     *o = iwes_as_objective(d);
     int rc = check_objective_args(h, o, static_cast<const float *>(motion));
     if (rc) return rc;
-    if (h->deterministic) {
-        set_error("%s: not built for deterministic mode (cmax_set_deterministic)", what);
-        return CMAX_EUNSUPPORTED;
-    }
-    if (h->comm) {
-        set_error("%s: not built for a handle with a communicator (cmax_comm_init)", what);
-        return CMAX_EUNSUPPORTED;
-    }
-    return 0;
-}
-
-// scratch shared with cmax_objective_hvp: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
-static int iwes_scratch(cmax_handle_s *h) {
-    if (h->hvp_img) return 0;
-    const int64_t npix = (int64_t)h->Hp * h->Wp;
-    int rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
-    if (!rc) rc = dev_alloc(h, &h->d_stat_tan, 4 * kStatStride);
-    if (!rc) {
-        dev_free(&h->Gt);
-        rc = dev_alloc(h, &h->Gt, 4 * npix);
-    }
-    return rc;
-}
-
-// fixed-point scale of the derivative votes per reference time, as objective_hvp_impl
-static TanParams iwes_tan_params(const cmax_handle_s *h, const cmax_objective_t *d, const float *tangent) {
-    const double period = d->normalize_t ? 1.0 : (h->tmax_host - h->tmin_host);
-    TanParams tp = {};
-    tp.u = tangent;
-    tp.bs = (int64_t)h->Hp * h->Wp;
-    for (int k = 0; k < d->n_ref; ++k) {
-        const double dref = ref_fraction(d->ref_mode[k], d->ref_frac[k]);
-        double dtmax = fabs(dref) > fabs(1.0 - dref) ? fabs(dref) : fabs(1.0 - dref);
-        dtmax *= period > 0 ? period : 1.0;
-        if (dtmax < 1e-30) dtmax = 1e-30;
-        tp.d[k] = (float)dref;
-        tp.fixk[k] = (float)(1073741824.0 / ((double)h->seg_max * 2.0 * dtmax));  // 2^30 / (events * max |derivative vote|)
-    }
-    tp.fix = tp.fixk[0];
-    tp.inv_fix = 1.f / tp.fix;
-    return tp;
+    return refuse_det_or_comm(h, what);
 }
 
 // the caller's n planes as the event kernels read them: the planes themselves, or their blur transpose in `stage`
@@ -4875,25 +4822,11 @@ static int iwes_stage(cmax_handle_s *h, double sigma, const float *planes, int n
     return 0;
 }
 
-// T3 with the caller's images (out zeroed by the caller): 2-DoF partials folded by k_finish, flow models added per event
+// T3 with the caller's images (out zeroed by the caller)
 static int iwes_gather(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *tangent, const float *G, const float *Gp, void *out,
                        hipStream_t s) {
-    const bool two_dof = d->model == CMAX_MODEL_2DOF;
-    const EvView ev = ev_view(h);
-    const TanParams tp = iwes_tan_params(h, d, tangent);
     const WarpParams wp = warp_params(h, motion, d->T, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
-    double *gpart = two_dof ? h->d_gpart : nullptr;
-    float *hflow = two_dof ? nullptr : (float *)out;
-    with_model(d->model, [&](auto m) {
-        if (h->weighted) launch_grad_hvp_weighted<m.value>(h, ev, wp, tp, d->n_ref, G, Gp, gpart, hflow, s);
-        else launch_grad_hvp<m.value>(h, ev, wp, tp, d->n_ref, G, Gp, gpart, hflow, s, HvpDet{});
-    });
-    CMAX_CHECK_LAUNCH();
-    if (two_dof) {
-        hipLaunchKernelGGL(k_finish, dim3(1), dim3(256), 0, s, h->d_gpart, d->n_ref * h->nseg, (double *)out);
-        CMAX_CHECK_LAUNCH();
-    }
-    return 0;
+    return second_order_gather(h, d, ev_view(h), wp, tangent_params(h, d, tangent), G, Gp, out, HvpDet{}, s);
 }
 
 // grad_w (zeroed by the caller) from finished planes G[0 .. n_ref) (+ G[n_ref] at the un-warped positions): per_event_finish's gather and
@@ -4901,17 +4834,8 @@ static int iwes_gather(cmax_handle_s *h, const cmax_objective_t *d, const float 
 static int iwes_weight_grad(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *G, bool with_orig, float *grad_w, hipStream_t s) {
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = d->n_ref, n_planes = nr + (with_orig ? 1 : 0);
-    int rc = 0;
-    if (h->n > h->gw_plane) {  // sized like w_packed
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->gw_packed);
-        h->gw_plane = 0;
-        const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
-        rc = dev_alloc(h, &h->gw_packed, 5 * plane);
-        if (rc) return rc;
-        h->gw_plane = plane;
-    }
-    CMAX_CHECK_HIP(hipMemsetAsync(h->gw_packed, 0, (size_t)n_planes * h->gw_plane * sizeof(float), s));
+    int rc = reserve_packed_planes(h, &h->gw_packed, &h->gw_plane, 5, n_planes, s);
+    if (rc) return rc;
     const EvView ev = ev_view(h);
     rc = publish_windows(h, d, motion, s);
     if (rc) return rc;
@@ -4926,21 +4850,10 @@ static int iwes_weight_grad(cmax_handle_s *h, const cmax_objective_t *d, const f
         with_model(d->model, [&](auto m) { launch_weight_gather<m.value>(h, ev, wp, ra, nr, 0, s); });
         CMAX_CHECK_LAUNCH();
     }
-    if (with_orig) {  // the un-warped events, behind a K1 launch that only publishes their windows (as per_event_finish)
-        RefArgs ra = {};
-        const int ref_mode = CMAX_REF_FIRST;
-        const double frac = 0.0;
-        fill_ref_times(ra, 1, &ref_mode, &frac);
-        ra.win = h->d_win;
-        ra.shifts = h->d_shifts;
-        ra.windows_only = 1;
-        const WarpParams wp = warp_params(h, nullptr, 0, CMAX_REF_FIRST, 0.0, 1);
-        launch_vote<-1>(h, ev, wp, ra, 1, s);
-        CMAX_CHECK_LAUNCH();
-        ra.windows_only = 0;
-        ra.img[0] = const_cast<float *>(G) + nr * npix;
-        launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s);
-        CMAX_CHECK_LAUNCH();
+    if (with_orig) {
+        rc = gather_unwarped(h, G + nr * npix, s,
+                             [&](const EvView &ev, const WarpParams &wp, const RefArgs &ra) { launch_weight_gather<-1>(h, ev, wp, ra, 1, nr, s); });
+        if (rc) return rc;
     }
     hipLaunchKernelGGL(k_weight_grad_scatter, dim3(div_up(h->n, 256)), dim3(256), 0, s, (const float *)h->gw_packed, h->gw_plane, n_planes, (const int *)h->src, h->n, grad_w);
     CMAX_CHECK_LAUNCH();
@@ -4968,7 +4881,7 @@ int cmax_iwes(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, float
     }
     float *raw = images;
     if (o.sigma > 0) {  // votes into the scratch (five consecutive images), the blur writes the caller's buffer
-        rc = iwes_scratch(h);
+        rc = tangent_scratch(h);
         if (rc) return rc;
         raw = h->hvp_img;
     }
@@ -5003,7 +4916,7 @@ int cmax_iwes_vjp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
     CMAX_CHECK_HIP(hipMemsetAsync(grad_motion, 0, g.bytes, s));
     if (grad_w && n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
     if (h->n == 0) return 0;
-    rc = iwes_scratch(h);
+    rc = tangent_scratch(h);
     if (rc) return rc;
     if (g.count > h->iw_zero_cap) {  // the zero tangent (once per motion size)
         CMAX_CHECK_HIP(hipStreamSynchronize(s));
@@ -5037,17 +4950,14 @@ int cmax_iwes_jvp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
         CMAX_CHECK_HIP(hipMemsetAsync(dimages, 0, (size_t)nr * npix * sizeof(float), s));
         return 0;
     }
-    rc = iwes_scratch(h);
+    rc = tangent_scratch(h);
     if (rc) return rc;
     float *draw = o.sigma > 0 ? h->hvp_img + 8 * npix : dimages;
     CMAX_CHECK_HIP(hipMemsetAsync(draw, 0, (size_t)nr * npix * sizeof(float), s));
     const EvView ev = ev_view(h);
-    const TanParams tp = iwes_tan_params(h, &o, tangent);
+    const TanParams tp = tangent_params(h, &o, tangent);
     const WarpParams wp = warp_params(h, motion, o.T, o.ref_mode[0], o.ref_frac[0], o.normalize_t, o.motion_dtype == CMAX_F64);
-    with_model(o.model, [&](auto m) {
-        if (h->weighted) launch_vote_tan_weighted<m.value>(h, ev, wp, tp, nr, draw, s);
-        else launch_vote_tan<m.value>(h, ev, wp, tp, nr, draw, s);
-    });
+    with_model(o.model, [&](auto m) { launch_vote_tan<m.value>(h, ev, wp, tp, nr, draw, s); });
     CMAX_CHECK_LAUNCH();
     if (o.sigma > 0) {
         double k0 = 0, k1 = 0;
@@ -5070,7 +4980,7 @@ int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_
     const GradExtent g = grad_extent(h, &o);
     CMAX_CHECK_HIP(hipMemsetAsync(out, 0, g.bytes, s));
     if (h->n == 0) return 0;
-    rc = iwes_scratch(h);
+    rc = tangent_scratch(h);
     if (rc) return rc;
     const float *G = nullptr, *Gp = nullptr;
     rc = iwes_stage(h, o.sigma, gimages, o.n_ref, h->hvp_img, &G, s);
@@ -5292,7 +5202,7 @@ int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start
 int cmax_debug_launch_floor(cmax_handle_t h, int pairs, cmax_stream_t stream) {
     CMAX_REQUIRE(h != nullptr && pairs > 0, "debug_launch_floor");
     CMAX_REQUIRE(h->n > 0 && h->nseg > 0, "debug_launch_floor: no events set");
-    const dim3 grid(8 * ((h->nseg + 7) / 8));
+    const dim3 grid(seg_blocks(h->nseg));
     const int k1 = layout_threads(vote_layout(h)), k3 = layout_threads(grad_layout(h, CMAX_MODEL_2DOF, false));
     for (int i = 0; i < pairs; ++i) {
         hipLaunchKernelGGL(k_empty, grid, dim3(k1), 0, (hipStream_t)stream, h->d_segs);
