@@ -1937,7 +1937,7 @@ __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, 
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
-    wp.d_lo = 0.f;
+    wp.d_lo = tp.d_lo[blockIdx.y];
     // (the by-value parameter block is only read: writing to it would move it to scratch memory for the indexing)
     const float wn0 = WEIGHTED ? pack_ptr(1, wargs...)[0] : 1.f, wn1 = WEIGHTED ? pack_ptr(1, wargs...)[1] : 1.f;
     // weighted: an event's votes are round(w d fix / wmax), the flush multiplies by wmax / fix
@@ -2030,7 +2030,7 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
     constexpr bool WEIGHTED = sizeof...(WGT) > 0;
     static_assert(sizeof...(WGT) <= 1, "k_grad_hvp: w_packed or nothing");
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
-    wp.d_lo = 0.f;
+    wp.d_lo = tp.d_lo[blockIdx.y];
     G += blockIdx.y * tp.bs;
     Gp += blockIdx.y * tp.bs;
     if (gpart) gpart += (int64_t)blockIdx.y * nseg * 2;

@@ -1509,6 +1509,7 @@ struct TanParams {
     float fix, inv_fix;  // fixed-point scale of the derivative votes (set per workgroup from the arrays below)
     // one launch covers the reference times of the objective (blockIdx.y):
     float d[4], fixk[4];  // reference time as a fraction of the batch period, its fixed-point scale
+    float d_lo[4];        // ... what fp32 lost of d (read by warp_exact only: these kernels decide the cells K1 decides, from d + d_lo)
     int64_t bs;           // element stride between the per-reference-time images
 };
 
@@ -4586,6 +4587,7 @@ static TanParams tangent_params(const cmax_handle_s *h, const cmax_objective_t *
         dtmax *= period > 0 ? period : 1.0;
         if (dtmax < 1e-30) dtmax = 1e-30;
         tp.d[k] = (float)dref;
+        tp.d_lo[k] = ref_fraction_lo(d->ref_mode[k], d->ref_frac[k]);
         tp.fixk[k] = (float)(1073741824.0 / ((double)h->seg_max * 2.0 * dtmax));  // 2^30 / (events * max |derivative vote|)
     }
     tp.fix = tp.fixk[0];
