@@ -352,13 +352,15 @@ class CMaxHandle:
     def _motion32(self, motion) -> torch.Tensor:
         return to_device_tensor(motion, "motion").detach().to(torch.float32).contiguous()
 
-    def _motion_arg(self, desc: CmaxObjective, motion):
+    def _motion_arg(self, desc: CmaxObjective, motion, exact_flow: bool = False):
         """(device tensor, descriptor) for one objective call.  A 2-DoF theta that arrives in fp64 -- the dtype the
         reference's solver optimises in (src/solver/patch_contrast_pyramid.py:186) -- is handed over as it is
         (cmax_objective_t::motion_dtype = CMAX_F64): the kernels round it to fp32 for the bulk arithmetic and keep the
-        doubles for the events that lie on a cell border.  Everything else is fp32 on the device."""
+        doubles for the events that lie on a cell border.  So is an fp64 flow / voxel with `exact_flow=True` (the keyword of
+        every method that takes a motion): the library splits it into (float)flow, which all the arithmetic reads, and the
+        remainder, which only those border events read.  Everything else is fp32 on the device."""
         m = to_device_tensor(motion, "motion").detach()
-        want = _lib.F64 if (desc.model == _lib.MODEL_2DOF and m.dtype == torch.float64) else _lib.F32
+        want = _lib.F64 if (m.dtype == torch.float64 and (desc.model == _lib.MODEL_2DOF or exact_flow)) else _lib.F32
         m = m.contiguous() if want == _lib.F64 else m.to(torch.float32).contiguous()
         if desc.motion_dtype != want:
             desc = CmaxObjective.from_buffer_copy(desc)
@@ -380,10 +382,10 @@ class CMaxHandle:
                                  out.data_ptr(), F._stream()))
         return out
 
-    def evaluate(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def evaluate(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective call.  Returns (result double[8] on device, grad or None).
         result[0] = loss, result[1..n_ref] = raw contrasts, result[5] = contrast of orig_iwe."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
         if want_grad:
@@ -395,13 +397,13 @@ class CMaxHandle:
                                        grad.data_ptr() if grad is not None else None, F._stream()))
         return result, grad
 
-    def evaluate_weight_grad(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def evaluate_weight_grad(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective_weight_grad call: (result, grad or None, grad_w).  result and grad as `evaluate` returns them;
         grad_w is dL/dw, float32 [n] on the device in the order of the events handed to set_events -- the reference's `weight.grad`
         after `backward()` through create_image_from_events_*(weight=w) (src/event_image_converter.py:316-372).  It is not multiplied
         by w (an event of weight 0 has a derivative), an unweighted handle means w = 1, and events that were not packed get 0.
         Deterministic handles and handles with a communicator raise NotImplementedError with the library's text."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
         if want_grad:
@@ -416,7 +418,7 @@ class CMaxHandle:
                                                    grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, F._stream()))
         return result, grad, grad_w
 
-    def evaluate_event_grad(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def evaluate_event_grad(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective_event_grad call: (result, grad or None, grad_events, csum).  result and grad as `evaluate` returns them;
         grad_events is float32 [n, 3] on the device in the order of the events handed to set_events: (dL/dx, dL/dy, C = sum_k dL/d dt_k),
         dt_k the event's time offset as the warp uses it -- the first two are the reference's `events.grad[:, :2]`
@@ -424,7 +426,7 @@ class CMaxHandle:
         time column; csum is float64 [4]: sum_e dL/d dt_{e,k} per reference time.  An unweighted handle means w = 1, events that were not
         packed keep a row of zeros.  Deterministic handles and handles with a communicator raise NotImplementedError with the
         library's text."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
         if want_grad:
@@ -439,14 +441,14 @@ class CMaxHandle:
                                                   grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, csum.data_ptr(), F._stream()))
         return result, grad, buf[:n], csum
 
-    def events_grad(self, desc: CmaxObjective, motion) -> torch.Tensor:
+    def events_grad(self, desc: CmaxObjective, motion, exact_flow: bool = False) -> torch.Tensor:
         """The reference's `events.grad`, float64 [n, 4] on the device: evaluate_event_grad composed with the batch's times
         (compose_events_grad; not a hot path).  The handle keeps a VIEW of the time column handed to set_events: the batch must not
         have been modified in place since."""
-        _, _, ge, csum = self.evaluate_event_grad(desc, motion, want_grad=False)
+        _, _, ge, csum = self.evaluate_event_grad(desc, motion, want_grad=False, exact_flow=exact_flow)
         return compose_events_grad(ge, csum, self._batch_t, ref_fractions(desc), bool(desc.normalize_t), self._batch_t_range)
 
-    def prepare(self, desc: CmaxObjective, motion, want_grad: bool = True, dist: bool = False):
+    def prepare(self, desc: CmaxObjective, motion, want_grad: bool = True, dist: bool = False, exact_flow: bool = False):
         """A prepared cmax_objective (dist: cmax_objective_dist) call for an inner loop that evaluates the SAME motion
         buffer again and again (an optimiser updating it in place, a benchmark): outputs allocated once, pointers
         resolved once.  Returns (call, result, grad); `call()` enqueues one evaluation on the current stream and
@@ -454,7 +456,7 @@ class CMaxHandle:
         tensor of the dtype the kernels take (fp32; fp64 for a 2-DoF theta) -- otherwise it is a private converted copy, and an
         optimiser that updates its own tensor in place must write into `call.motion` instead (call.motion_is_callers tells).  `evaluate` spends ~6 us per call in Python (two allocations, tensor checks) -- as
         much as the three launches of a 1M-event 2-DoF evaluation leave the host to spare (profiles/r02_ablation.txt)."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
         if want_grad:
@@ -474,12 +476,12 @@ class CMaxHandle:
         return call, result, grad
 
     # -- results on the host / raw sums (no finishing kernel) ---------------------------------------------------
-    def evaluate_host(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def evaluate_host(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective_host call: the evaluation with its results delivered to the host, the way an optimiser
         consumes them (the reference's wrapper ends in .cpu().numpy()).  Returns (result float64[8], grad ndarray or None);
         blocks.  For the 2-DoF image-variance objective the finishing kernel writes into pinned host memory and the call polls a
         run counter behind the results: no copy engine, no driver call on the way back."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = np.empty(8, dtype=np.float64)
         grad = None
         if want_grad:
@@ -488,10 +490,10 @@ class CMaxHandle:
                                             grad.ctypes.data if grad is not None else None, F._stream()))
         return result, grad
 
-    def prepare_host(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def prepare_host(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """Prepared cmax_objective_host call: (call, result, grad) with `result` / `grad` numpy arrays that every `call()`
         overwrites (it returns when they are filled)."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = np.empty(8, dtype=np.float64)
         grad = None
         if want_grad:
@@ -545,15 +547,15 @@ class CMaxHandle:
         call.motion = m
         return call, raw, finalize
 
-    def prepare_batch(self, desc: CmaxObjective, motions):
+    def prepare_batch(self, desc: CmaxObjective, motions, exact_flow: bool = False):
         """Prepared cmax_objective_batch call: (call, results, grads) for K candidate motions `motions` [K, ...] (2-DoF: [K, 2]; an
-        fp64 theta crosses the ABI in fp64 like in `evaluate`).  results float64 [K, 8], grads float64 [K, 2] | float32 [K, ...].
+        fp64 theta crosses the ABI in fp64 like in `evaluate`, and so do fp64 flows with exact_flow=True).  results float64 [K, 8], grads float64 [K, 2] | float32 [K, ...].
         The reference's gradient-free paths evaluate batches of sampled motions (src/solver/base.py:738-758); for the 2-DoF
         image-variance objective the K evaluations share one launch of each kernel (blockIdx.z = candidate)."""
         mt = to_device_tensor(motions, "motions").detach()
         K = int(mt.shape[0])
         desc = CmaxObjective.from_buffer_copy(desc)
-        if desc.model == _lib.MODEL_2DOF and mt.dtype == torch.float64:
+        if mt.dtype == torch.float64 and (desc.model == _lib.MODEL_2DOF or exact_flow):
             desc.motion_dtype = _lib.F64
             m = mt.contiguous()
         else:
@@ -574,24 +576,28 @@ class CMaxHandle:
         call.keepalive = (m, desc, results, grads)
         return call, results, grads
 
-    def evaluate_batch(self, desc: CmaxObjective, motions):
+    def evaluate_batch(self, desc: CmaxObjective, motions, exact_flow: bool = False):
         """(results [K, 8], grads [K, ...]) of K candidate motions: one cmax_objective_batch call."""
-        call, results, grads = self.prepare_batch(desc, motions)
+        call, results, grads = self.prepare_batch(desc, motions, exact_flow)
         call()
         return results, grads
 
-    def hvp(self, desc: CmaxObjective, motion, tangent) -> torch.Tensor:
+    def hvp(self, desc: CmaxObjective, motion, tangent, exact_flow: bool = False) -> torch.Tensor:
         """Exact Hessian-vector product H @ tangent of the objective w.r.t. the motion (cmax_objective_hvp):
         what torch.autograd.functional.vhp gives the reference's Newton-CG.  Returns fp64 [2] (2-DoF) or
-        fp32 with the motion's shape."""
-        m = self._motion32(motion)
-        if desc.motion_dtype != _lib.F32:
-            desc = CmaxObjective.from_buffer_copy(desc)
-            desc.motion_dtype = _lib.F32
+        fp32 with the motion's shape.  The motion crosses in fp32 unless exact_flow=True, which keeps the dtype it is given (an
+        fp64 flow / voxel or theta then decides the border cells, as in `evaluate`)."""
+        if exact_flow:
+            m, desc = self._motion_arg(desc, motion, True)
+        else:
+            m = self._motion32(motion)
+            if desc.motion_dtype != _lib.F32:
+                desc = CmaxObjective.from_buffer_copy(desc)
+                desc.motion_dtype = _lib.F32
         u = to_device_tensor(tangent, "tangent").detach().to(torch.float64)
         umax = u.abs().max()
         if float(umax) == 0.0:
-            return torch.zeros(2, dtype=torch.float64, device=self.device) if desc.model == _lib.MODEL_2DOF else torch.zeros_like(m)
+            return torch.zeros(2, dtype=torch.float64, device=self.device) if desc.model == _lib.MODEL_2DOF else torch.zeros_like(m, dtype=torch.float32)
         un = (u / umax).to(torch.float32).contiguous()  # unit max-norm: the derivative votes are fixed point
         if desc.model == _lib.MODEL_2DOF:
             hv = torch.empty(2, dtype=torch.float64, device=self.device)
@@ -601,13 +607,15 @@ class CMaxHandle:
         return hv * umax.to(hv.dtype)
 
     # -- the image of warped events as a differentiable layer (cmax_iwes*, see fused_iwes) ---------------------------
-    def _iwes_args(self, motion, motion_model: str, directions, sigma: float, normalize_t: bool, with_orig: bool):
+    def _iwes_args(self, motion, motion_model: str, directions, sigma: float, normalize_t: bool, with_orig: bool, exact_flow: bool = False):
         if motion_model not in F.MODEL_CODES:
             raise KeyError(motion_model)
         directions = (directions,) if isinstance(directions, (str, int, float)) else tuple(directions)
         if not 1 <= len(directions) <= 4:
             raise ValueError(f"1 to 4 reference times, got {len(directions)}")
-        m = self._motion32(motion)
+        m = to_device_tensor(motion, "motion").detach()
+        f64 = bool(exact_flow) and m.dtype == torch.float64 and F.MODEL_CODES[motion_model] != _lib.MODEL_2DOF  # (see _motion_arg)
+        m = m.contiguous() if f64 else m.to(torch.float32).contiguous()
         d = CmaxIwes()
         d.model = F.MODEL_CODES[motion_model]
         d.normalize_t = int(bool(normalize_t))
@@ -616,7 +624,7 @@ class CMaxHandle:
             d.ref_mode[k], d.ref_frac[k] = F.direction_to_ref(ref_dir)
         d.sigma = float(sigma)
         d.T = int(m.shape[0]) if d.model == _lib.MODEL_VOXEL else 0
-        d.motion_dtype = _lib.F32
+        d.motion_dtype = _lib.F64 if f64 else _lib.F32
         d.with_orig = int(bool(with_orig))
         return m, d
 
@@ -632,22 +640,22 @@ class CMaxHandle:
         return torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
 
     def iwes(self, motion, motion_model: str, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
-             with_orig: bool = False) -> torch.Tensor:
+             with_orig: bool = False, exact_flow: bool = False) -> torch.Tensor:
         """The images of warped events at every reference time in `directions` in one call (cmax_iwes): fp32 [K, Hp, Wp], K =
         len(directions) (+ 1 with_orig: the un-warped image last) -- image k is what `iwe(motion, motion_model, directions[k], ...)`
         returns, the weighted image on a weighted handle."""
-        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig, exact_flow)
         out = torch.empty((d.n_ref + d.with_orig,) + self.padded_size, dtype=torch.float32, device=self.device)
         check(self._lib.cmax_iwes(self._h, ctypes.byref(d), m.data_ptr(), out.data_ptr(), F._stream()))
         return out
 
     def iwes_vjp(self, motion, motion_model: str, gimages, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
-                 with_orig: bool = False, want_grad_w: bool = False):
+                 with_orig: bool = False, want_grad_w: bool = False, exact_flow: bool = False):
         """(sum_k J_k^T gimages[k], grad_w or None) -- cmax_iwes_vjp: the motion gradient of <gimages, iwes(motion)> with the cells
         held fixed (fp64 [2] for 2-DoF, else fp32 with the motion's shape) and, on request, its derivative with respect to the
         per-event weights (fp32 [n] in the order of the events handed to set_events, not multiplied by w).  gimages: the shape of
         `iwes`' result, the caller's dL/dI.  The result is that of the handle's state (order, weights) at the time of THIS call."""
-        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig, exact_flow)
         g = self._iwes_planes(gimages, d.n_ref + d.with_orig, "gimages")
         grad = self._iwes_grad_like(d, m)
         n = int(getattr(self, "_n_in", 0))
@@ -657,10 +665,10 @@ class CMaxHandle:
         return grad, (buf[:n] if want_grad_w else None)
 
     def iwes_jvp(self, motion, motion_model: str, tangent, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
-                 with_orig: bool = False) -> torch.Tensor:
+                 with_orig: bool = False, exact_flow: bool = False) -> torch.Tensor:
         """J_k tangent per reference time, fp32 [len(directions), Hp, Wp] (cmax_iwes_jvp).  The tangent is brought to unit max-norm
         for the fixed-point derivative votes and the result scaled back, as `hvp` does."""
-        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, False)
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, False, exact_flow)
         out = torch.zeros((d.n_ref,) + self.padded_size, dtype=torch.float32, device=self.device)
         u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
         umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
@@ -671,18 +679,18 @@ class CMaxHandle:
         return out * umax.to(torch.float32)
 
     def iwes_vjp_tan(self, motion, motion_model: str, tangent, gimages, gimages_tan=None, directions=("first",), sigma: float = 0.0,
-                     normalize_t: bool = True, with_orig: bool = False) -> torch.Tensor:
+                     normalize_t: bool = True, with_orig: bool = False, exact_flow: bool = False) -> torch.Tensor:
         """d/d(eps) [ J(motion + eps tangent)^T (gimages + eps gimages_tan) ] at eps = 0, summed over the reference times
         (cmax_iwes_vjp_tan); gimages_tan None = 0: the mixed term alone.  With gimages_tan = (d2 l / dI2) J tangent this is the exact
         Hessian-vector product of a loss l(iwes(motion)).  Shape and dtype of `iwes_vjp`'s gradient."""
-        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig)
+        m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig, exact_flow)
         n_planes = d.n_ref + d.with_orig
         g = self._iwes_planes(gimages, n_planes, "gimages")
         gt = torch.zeros_like(g) if gimages_tan is None else self._iwes_planes(gimages_tan, n_planes, "gimages_tan")
         u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
         umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
         if float(umax) == 0.0:  # what is left is J^T gimages_tan
-            return self.iwes_vjp(motion, motion_model, gt, directions, sigma, normalize_t, with_orig)[0]
+            return self.iwes_vjp(motion, motion_model, gt, directions, sigma, normalize_t, with_orig, exact_flow=exact_flow)[0]
         un = (u / umax).to(torch.float32).contiguous()
         gt = (gt / umax.to(torch.float32)).contiguous()  # linear in (tangent, gimages_tan) jointly
         out = self._iwes_grad_like(d, m)
@@ -691,21 +699,21 @@ class CMaxHandle:
         return out * umax.to(out.dtype)
 
     # -- phase-split form (time-sliced multi-GPU, see distributed.py) --------------------------------
-    def objective_vote(self, desc: CmaxObjective, motion) -> torch.Tensor:
+    def objective_vote(self, desc: CmaxObjective, motion, exact_flow: bool = False) -> torch.Tensor:
         """Raw votes of this handle's events: fp32 [n_images, Hp, Wp] (n_ref images, plus the un-warped
         image when a normalised cost needs it).  To be all-reduced (sum) across time slices."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         images = torch.empty((5,) + self.padded_size, dtype=torch.float32, device=self.device)
         n_images = ctypes.c_int(0)
         check(self._lib.cmax_objective_vote(self._h, ctypes.byref(desc), m.data_ptr(), images.data_ptr(),
                                             ctypes.byref(n_images), F._stream()))
         return images[: n_images.value]
 
-    def objective_finish(self, desc: CmaxObjective, motion, images: torch.Tensor, want_grad: bool = True):
+    def objective_finish(self, desc: CmaxObjective, motion, images: torch.Tensor, want_grad: bool = True, exact_flow: bool = False):
         """Loss from the (globally reduced) images, gradient contribution of this handle's events.
         Without a blur (sigma == 0) the handle keeps pointers into `images` instead of a copy: a later last_iwe() reads that
         tensor's memory, so keep the tensor alive (and unchanged) until then -- a freed one gives stale values with no error."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         images = images.contiguous()
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
@@ -843,10 +851,10 @@ class CMaxHandle:
         check(self._lib.cmax_comm_allreduce(self._h, t.data_ptr(), t.numel(), F._code(t), {"sum": 0, "min": 1, "max": 2}[op], F._stream()))
         return t
 
-    def evaluate_dist(self, desc: CmaxObjective, motion, want_grad: bool = True):
+    def evaluate_dist(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective_dist call: the evaluation of the whole time-sliced batch, both all-reduces enqueued
         by the library between its kernels.  Same returns as `evaluate`, the same on every rank."""
-        m, desc = self._motion_arg(desc, motion)
+        m, desc = self._motion_arg(desc, motion, exact_flow)
         result = torch.empty(8, dtype=torch.float64, device=self.device)
         grad = None
         if want_grad:
@@ -903,9 +911,9 @@ class CMaxHandle:
 
 class _FusedFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, motion, handle, desc):
+    def forward(ctx, motion, handle, desc, exact_flow=False):
         need = motion.requires_grad
-        result, grad = handle.evaluate(desc, motion, want_grad=need)
+        result, grad = handle.evaluate(desc, motion, want_grad=need, exact_flow=exact_flow)
         ctx.grad = grad
         ctx.mdtype = motion.dtype
         ctx.mdevice = motion.device
@@ -915,9 +923,9 @@ class _FusedFn(torch.autograd.Function):
     def backward(ctx, gout):
         g = ctx.grad
         if g is None:
-            return None, None, None
+            return None, None, None, None
         g = g.to(ctx.mdtype) * gout.to(g.device).to(ctx.mdtype)
-        return g.to(ctx.mdevice), None, None
+        return g.to(ctx.mdevice), None, None, None
 
 
 class _FusedWeightedFn(torch.autograd.Function):
@@ -925,8 +933,8 @@ class _FusedWeightedFn(torch.autograd.Function):
     `weights` (ContrastObjective.__call__ set them)."""
 
     @staticmethod
-    def forward(ctx, motion, weights, handle, desc):
-        result, grad, grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=motion.requires_grad)
+    def forward(ctx, motion, weights, handle, desc, exact_flow=False):
+        result, grad, grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=motion.requires_grad, exact_flow=exact_flow)
         ctx.grad = grad
         ctx.grad_w = grad_w if weights.requires_grad else None
         ctx.mdtype, ctx.mdevice = motion.dtype, motion.device
@@ -940,7 +948,7 @@ class _FusedWeightedFn(torch.autograd.Function):
             gm = (ctx.grad.to(ctx.mdtype) * gout.to(ctx.grad.device).to(ctx.mdtype)).to(ctx.mdevice)
         if ctx.grad_w is not None:
             gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
-        return gm, gw, None, None
+        return gm, gw, None, None, None
 
 
 class _FusedEventsFn(torch.autograd.Function):
@@ -948,15 +956,15 @@ class _FusedEventsFn(torch.autograd.Function):
     given, the per-event weights (one cmax_objective_weight_grad call more); the handle already holds the batch and the weights."""
 
     @staticmethod
-    def forward(ctx, motion, events, weights, handle, desc):
-        result, grad, ge, csum = handle.evaluate_event_grad(desc, motion, want_grad=motion.requires_grad)
+    def forward(ctx, motion, events, weights, handle, desc, exact_flow=False):
+        result, grad, ge, csum = handle.evaluate_event_grad(desc, motion, want_grad=motion.requires_grad, exact_flow=exact_flow)
         ctx.grad = grad
         ctx.grad_ev = None
         if events.requires_grad:
             ctx.grad_ev = compose_events_grad(ge, csum, handle._batch_t, ref_fractions(desc), bool(desc.normalize_t), handle._batch_t_range)
         ctx.grad_w = None
         if weights is not None and weights.requires_grad:
-            ctx.grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=False)[2]
+            ctx.grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=False, exact_flow=exact_flow)[2]
             ctx.wdtype, ctx.wdevice = weights.dtype, weights.device
         ctx.mdtype, ctx.mdevice = motion.dtype, motion.device
         ctx.edtype, ctx.edevice = events.dtype, events.device
@@ -971,7 +979,7 @@ class _FusedEventsFn(torch.autograd.Function):
             ge = (ctx.grad_ev * gout.to(ctx.grad_ev.device).to(torch.float64)).to(ctx.edtype).to(ctx.edevice)
         if ctx.grad_w is not None:
             gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
-        return gm, ge, gw, None, None
+        return gm, ge, gw, None, None, None
 
 
 class _IwesVjpFn(torch.autograd.Function):
@@ -1038,7 +1046,7 @@ class _IwesFn(torch.autograd.Function):
 
 def fused_iwes(handle: "CMaxHandle", motion: torch.Tensor, motion_model: str, directions=("first",), sigma: float = 0.0,
                normalize_t: bool = True, with_orig: bool = False, weights: Optional[torch.Tensor] = None,
-               _weights_on_handle: bool = False) -> torch.Tensor:
+               _weights_on_handle: bool = False, exact_flow: bool = False) -> torch.Tensor:
     """The images of warped events of the handle's batch ON THE AUTOGRAD TAPE: fp32 [K, Hp, Wp] (one image per reference time in
     `directions`, then the un-warped image when with_orig) -- what the reference's `arg["iwe"]` is to its costs, so that any torch
     expression on it (a CostBase subclass, a robust or learned loss, a loss against a frame) runs on the fused path.
@@ -1049,7 +1057,9 @@ def fused_iwes(handle: "CMaxHandle", motion: torch.Tensor, motion_model: str, di
     not on the tape.
     The graph remembers the batch it was recorded on: backward raises RuntimeError after another set_events.  Anything else that
     happened to the handle in between (time slabs, other weights, other evaluations) is allowed, and a backward pass then computes
-    with the handle's state AT BACKWARD TIME (the library re-derives windows and cells from the motion in every call)."""
+    with the handle's state AT BACKWARD TIME (the library re-derives windows and cells from the motion in every call).
+    exact_flow: a float64 flow / voxel crosses into the library as it is, in the forward pass, the backward and the double backward
+    (CMaxHandle._motion_arg); the default casts it to fp32."""
     if weights is not None:
         if not isinstance(weights, torch.Tensor):
             raise TypeError(f"weights must be a torch tensor, got {type(weights)}")
@@ -1057,6 +1067,8 @@ def fused_iwes(handle: "CMaxHandle", motion: torch.Tensor, motion_model: str, di
             handle.set_event_weights(weights.detach())
     directions = (directions,) if isinstance(directions, (str, int, float)) else tuple(directions)
     cfg = dict(motion_model=motion_model, directions=directions, sigma=float(sigma), normalize_t=bool(normalize_t), with_orig=bool(with_orig))
+    if exact_flow:  # (only then a key of cfg: the handle methods' default otherwise)
+        cfg["exact_flow"] = True
     motion = to_device_tensor(motion, "motion")
     return _IwesFn.apply(motion, weights, handle, cfg)
 
@@ -1087,9 +1099,9 @@ class _CustomTerm:
         self.with_orig = "orig_iwe" in self.keys
         self.sigma, self.normalize_t = float(sigma), bool(normalize_t)
 
-    def value(self, handle, motion, motion_model, omit_boundary, coarse_flow=None, weights=None):
+    def value(self, handle, motion, motion_model, omit_boundary, coarse_flow=None, weights=None, exact_flow=False):
         imgs = fused_iwes(handle, motion, motion_model, tuple(self.directions), self.sigma, self.normalize_t, self.with_orig, weights,
-                          _weights_on_handle=weights is not None)
+                          _weights_on_handle=weights is not None, exact_flow=exact_flow)
         arg = {k: imgs[i] for k, i in self.index.items()}
         if self.with_orig:
             arg["orig_iwe"] = imgs[len(self.directions)]
@@ -1108,13 +1120,16 @@ class ContrastObjective:
     A cost WITHOUT a fused kernel -- a CostBase instance, a callable arg_dict -> 0-dim tensor, or a name registered in
     costs.functions that is not among FUSED_COSTS -- is evaluated in torch on `fused_iwes` (the images its `required_keys` name, in the
     reference's `arg` dict with `omit_boundary`; padded images, cropped only by the cost itself); its gradient and `hvp` are torch's
-    backward and double backward through that layer.  Names unknown to costs.functions raise KeyError."""
+    backward and double backward through that layer.  Names unknown to costs.functions raise KeyError.
+    exact_flow: a float64 dense flow / voxel is handed to the library unchanged (the cells of events on a cell border are then
+    decided from the doubles, as for a float64 2-DoF theta); the gradient comes back in float64, cast from the fp32 output."""
 
     def __init__(self, handle: CMaxHandle, motion_model: str, cost: str = "image_variance",
                  cost_with_weight: Optional[Dict[str, Union[float, str]]] = None, direction: str = "minimize",
                  sigma: float = 0.0, omit_boundary: bool = True, normalize_t: bool = True,
-                 warp_direction: Union[str, float] = "first"):
+                 warp_direction: Union[str, float] = "first", exact_flow: bool = False):
         self.handle = handle
+        self.exact_flow = bool(exact_flow)  # a float64 flow / voxel crosses into the library as it is (CMaxHandle._motion_arg)
         self.motion_model = motion_model
         self.direction = direction
         self.omit_boundary = omit_boundary
@@ -1142,7 +1157,7 @@ class ContrastObjective:
         """H v of combine(weight, cost(fused_iwes(motion))): torch's double backward through the layer."""
         m = to_device_tensor(motion, "motion").detach().clone().requires_grad_()
         with torch.enable_grad():
-            value = combine(weight, term.value(self.handle, m, self.motion_model, self.omit_boundary))
+            value = combine(weight, term.value(self.handle, m, self.motion_model, self.omit_boundary, exact_flow=self.exact_flow))
             (g,) = torch.autograd.grad(value, m, create_graph=True)
             if not g.requires_grad:
                 return torch.zeros_like(v64)
@@ -1164,9 +1179,9 @@ class ContrastObjective:
                 hv = self._custom_hvp(desc, weight, motion, v64)
                 out = hv if out is None else out + hv.reshape(out.shape)
                 continue
-            hv = self.handle.hvp(desc, motion, vector).to(torch.float64)
+            hv = self.handle.hvp(desc, motion, vector, exact_flow=self.exact_flow).to(torch.float64)
             if weight == "inv":
-                res, grad = self.handle.evaluate(desc, motion, want_grad=True)
+                res, grad = self.handle.evaluate(desc, motion, want_grad=True, exact_flow=self.exact_flow)
                 p1, p2 = combine_derivatives("inv", res[0])
                 g64 = grad.to(torch.float64).reshape(v64.shape)
                 hv = p1 * hv + p2 * (g64 * v64).sum() * g64.reshape(hv.shape)
@@ -1197,10 +1212,10 @@ class ContrastObjective:
                     value = -value
             elif isinstance(desc, _CustomTerm):
                 with torch.no_grad():
-                    value = torch.stack([torch.as_tensor(desc.value(self.handle, mt[k], self.motion_model, self.omit_boundary)).to(torch.float64)
+                    value = torch.stack([torch.as_tensor(desc.value(self.handle, mt[k], self.motion_model, self.omit_boundary, exact_flow=self.exact_flow)).to(torch.float64)
                                          for k in range(K)]).to(self.handle.device)
             else:
-                results, _ = self.handle.evaluate_batch(desc, mt)
+                results, _ = self.handle.evaluate_batch(desc, mt, exact_flow=self.exact_flow)
                 value = results[:, 0]
             loss = loss + combine(weight, value)
         return loss
@@ -1235,14 +1250,14 @@ class ContrastObjective:
             elif isinstance(desc, _CustomTerm):
                 if events is not None:
                     raise NotImplementedError("dL/d(event) of a cost without a fused kernel is not built")
-                value = desc.value(self.handle, motion, self.motion_model, self.omit_boundary, coarse_flow, weights)
+                value = desc.value(self.handle, motion, self.motion_model, self.omit_boundary, coarse_flow, weights, self.exact_flow)
             else:
                 if events is not None:
-                    value = _FusedEventsFn.apply(motion, events, weights, self.handle, desc)
+                    value = _FusedEventsFn.apply(motion, events, weights, self.handle, desc, self.exact_flow)
                 elif weights is None:
-                    value = _FusedFn.apply(motion, self.handle, desc)
+                    value = _FusedFn.apply(motion, self.handle, desc, self.exact_flow)
                 else:
-                    value = _FusedWeightedFn.apply(motion, weights, self.handle, desc)
+                    value = _FusedWeightedFn.apply(motion, weights, self.handle, desc, self.exact_flow)
             value = value.to(motion.device) if isinstance(motion, torch.Tensor) else value
             loss = loss + combine(weight, value)
         return loss

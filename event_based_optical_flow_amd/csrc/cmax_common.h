@@ -43,6 +43,14 @@ static inline int stream_grid(int64_t n, int block) {
     return (int)g;
 }
 
+// An fp64 motion value as the event kernels read it: hi = (float)v for all the arithmetic, lo = (float)(v - hi) for the events whose
+// cell is decided in fp64 (hi + lo = v to 2^-48 relative); lo = 0 where hi is not finite.
+__device__ __forceinline__ void split_f64(double v, float &hi, float &lo) {
+    hi = (float)v;
+    const float l = (float)(v - (double)hi);
+    lo = fabsf(hi) <= 3.402823466e+38f ? l : 0.f;
+}
+
 // ---- library-internal view of the host-side state of a handle that changes from one evaluation to the next
 // (not exported: cmax_solver.hip replays captured hipGraphs and must advance this state the way the eager
 // launch sequence would have)
@@ -78,6 +86,12 @@ __attribute__((visibility("hidden"))) int objective_dist_local_grad(cmax_handle_
                                                                  void *grad, hipStream_t s);
 __attribute__((visibility("hidden"))) int objective_hvp_dist_local(cmax_handle_t h, const cmax_objective_t *d, const float *motion,
                                                                 const float *tangent, void *hv, hipStream_t s);
+// cmax_objective / cmax_objective_hvp on a motion the caller has split already (the patch plan's conversion kernels write both planes):
+// with d->motion_dtype == CMAX_F64 on a dense / voxel model `motion` is the high plane and the low plane lies behind it
+__attribute__((visibility("hidden"))) int objective_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad,
+                                                          hipStream_t s);
+__attribute__((visibility("hidden"))) int objective_hvp_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *tangent,
+                                                              void *hv, hipStream_t s);
 __attribute__((visibility("hidden"))) int handle_allreduce_sum(cmax_handle_t h, void *buf, size_t count, bool f64, hipStream_t s);
 __attribute__((visibility("hidden"))) int handle_allreduce_sum_with_scalars(cmax_handle_t h, void *buf, size_t count, bool f64, double *scalars, int n_scalars, hipStream_t s);
 

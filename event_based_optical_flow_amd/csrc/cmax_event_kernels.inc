@@ -213,7 +213,10 @@ __global__ void __launch_bounds__(L::kThr) k_pack_compact(const int4 *__restrict
     if (wrong) atomicOr(bad, 1);  // (never: a segment lies in one tile row and spans <= 6 tiles; checked by the host in debug runs)
 }
 
-template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, typename Init>
+// F64FLOW (dense / voxel): the motion is the caller's fp64 flow, split -- wp.motion is its high plane, the low plane lies behind the field
+// (k_split_motion); read by the border branch only.  A template argument, not a branch on wp.motion_f64: the kernels of an fp32 call
+// are the ones they were (profiles/flow64_resources.txt).
+template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, bool F64FLOW = false, typename Init>
 __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams &wp, int4 sg, EventLoads<L> &el, unsigned (&rc)[L::kEPT],
                                               float (&fa)[L::kEPT], float (&fb)[L::kEPT], float (&fdt)[L::kEPT], int (&fsrc)[L::kEPT],
                                               uint4 *s_box, const int4 *known, const unsigned *__restrict__ shifts, Init init, bool &wave_live,
@@ -221,6 +224,7 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     constexpr bool kExact = MODEL >= 0;  // cells of events on a cell border are decided in fp64 (warp_exact); the un-warped image has no motion
     constexpr bool kFlow = MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL;
     static_assert(!(KNOWN && !WANT_DT), "K3 re-uses K1's windows");
+    static_assert(!F64FLOW || (kFlow && !KNOWN), "the low plane of an fp64 flow is read where a cell is decided");
     auto local_index = [](int u) { return STRIDED ? 2 * ((u >> 1) * L::kThr + (int)threadIdx.x) + (u & 1) : L::kEPT * (int)threadIdx.x + u; };
     const int odd = sg.x & 1, cnt = sg.y;
     const int64_t first = (int64_t)sg.x - odd;
@@ -444,6 +448,11 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
                     m0 = (double)f0;
                     m1 = (double)f1;
                     if (!(fau < me || fau > ehi || fbu < me || fbu > ehi)) continue;
+                    if constexpr (F64FLOW) {  // the caller's fp64 flow: f0 / f1 are its high parts, the low plane lies behind the field (k_split_motion)
+                        const int64_t lo = src + (int64_t)(MODEL == CMAX_MODEL_VOXEL ? wp.T : 1) * 2 * hw;
+                        m0 += (double)wp.motion[lo];
+                        m1 += (double)wp.motion[lo + hw];
+                    }
                 }
                 const Warped w = warp_exact<MODEL, FRAC>(ev, ex, first + l, tau, period, wp, m0, m1);
                 const unsigned packed = ((unsigned)(w.row + 16384) << 16) | (unsigned)(w.col + 16384);
@@ -584,8 +593,12 @@ __device__ __forceinline__ int fast_index(unsigned rc, unsigned neg_origin, int 
 // WEIGHTED (cmax_set_event_weights): an event votes round(w / wmax * K) instead of K, split over its four cells from the row totals as
 // before (the four integers add up to it exactly); wmax is folded back in by the flush.  The window, the cells and the offsets
 // published for K3 do not depend on w.
-template <class L, int MODEL, bool FRAC, bool MU = false, bool WEIGHTED = false>
-__global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra) {
+// EXACT = called with an ExactFlow behind ra (dense / voxel, cmax_objective_t::motion_dtype == CMAX_F64): phase_warp's F64FLOW -- instantiations
+// of their own, the ones without the argument are untouched.
+template <class L, int MODEL, bool FRAC, bool MU = false, bool WEIGHTED = false, class... EXACT>
+__global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra, EXACT...) {
+    constexpr bool F64FLOW = sizeof...(EXACT) > 0;
+    static_assert(sizeof...(EXACT) <= 1 && (std::is_same_v<EXACT, ExactFlow> && ...), "k_vote: an ExactFlow or nothing");
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
     CMAX_STAMP(0, 0);
@@ -620,7 +633,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
     int fsrc[L::kEPT];
     bool live;  // this wave holds events (wave-uniform)
     unsigned nibbles;  // cell offsets of the events this thread decided in fp64 (phase_warp)
-    const Window win = phase_warp<L, MODEL, FRAC, false>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, MODEL, FRAC, false, false, false, F64FLOW>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
         for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
     }, live, nibbles);
@@ -1921,6 +1934,7 @@ k_event_grad_gather(const int4 *__restrict__ segs, int nseg, const uint2 *__rest
 
 // trailing kernel arguments of the WEIGHTED instantiations (a parameter pack: the unweighted kernels keep their argument block)
 __device__ __forceinline__ const float *pack_ptr(int) { return nullptr; }
+__device__ __forceinline__ const float *pack_ptr(int, ExactFlow) { return nullptr; }  // (the tag of an fp64 flow ends the pack)
 template <class... R>
 __device__ __forceinline__ const float *pack_ptr(int i, const float *a, R... r) { return i == 0 ? a : pack_ptr(i - 1, r...); }
 
@@ -1932,8 +1946,10 @@ __device__ __forceinline__ const float *pack_ptr(int i, const float *a, R... r) 
 template <class L, int MODEL, bool FRAC, class... WGT>
 __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg,
                                                   float *__restrict__ dimg, double *__restrict__ stat_zero, long long *__restrict__ dimg64, WGT... wargs) {
-    constexpr bool WEIGHTED = sizeof...(WGT) > 0;
-    static_assert(sizeof...(WGT) == 0 || sizeof...(WGT) == 2, "k_vote_tan: (w_packed, d_wnorm) or nothing");
+    constexpr bool F64FLOW = (std::is_same_v<WGT, ExactFlow> || ...);  // an ExactFlow ends the arguments: phase_warp's F64FLOW, as in k_vote
+    constexpr int kWgtArgs = (int)sizeof...(WGT) - (F64FLOW ? 1 : 0);
+    constexpr bool WEIGHTED = kWgtArgs > 0;
+    static_assert(kWgtArgs == 0 || kWgtArgs == 2, "k_vote_tan: (w_packed, d_wnorm) or nothing");
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
@@ -1956,7 +1972,7 @@ __global__ void __launch_bounds__(L::kThr) k_vote_tan(EvView ev, WarpParams wp, 
     int fsrc[L::kEPT];
     bool live;
     unsigned nib_unused;
-    const Window win = phase_warp<L, MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, MODEL, FRAC, true, false, false, F64FLOW>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
         for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
     }, live, nib_unused);
@@ -2027,8 +2043,10 @@ template <class L, int MODEL, bool FRAC, class... WGT>
 __global__ void __launch_bounds__(L::kThr)
 k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs, int nseg, const float *__restrict__ G,
            const float *__restrict__ Gp, double *__restrict__ gpart, float *__restrict__ hflow, HvpDet det, WGT... wargs) {
-    constexpr bool WEIGHTED = sizeof...(WGT) > 0;
-    static_assert(sizeof...(WGT) <= 1, "k_grad_hvp: w_packed or nothing");
+    constexpr bool F64FLOW = (std::is_same_v<WGT, ExactFlow> || ...);  // an ExactFlow ends the arguments, as in k_vote_tan
+    constexpr int kWgtArgs = (int)sizeof...(WGT) - (F64FLOW ? 1 : 0);
+    constexpr bool WEIGHTED = kWgtArgs > 0;
+    static_assert(kWgtArgs <= 1, "k_grad_hvp: w_packed or nothing");
     wp.d = tp.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = tp.d_lo[blockIdx.y];
     G += blockIdx.y * tp.bs;
@@ -2049,7 +2067,7 @@ k_grad_hvp(EvView ev, WarpParams wp, TanParams tp, const int4 *__restrict__ segs
     const int lane = threadIdx.x & (kWave - 1);
     bool live;
     unsigned nib_unused;
-    const Window win = phase_warp<L, MODEL, FRAC, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
+    const Window win = phase_warp<L, MODEL, FRAC, true, false, false, F64FLOW>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         for (int r = threadIdx.x / kWave; r < w.h; r += L::kNW)
             for (int c = lane; c < w.w; c += kWave) {
                 const int64_t q = (int64_t)(w.r0 + r) * wp.Wp + w.c0 + c;

@@ -94,9 +94,17 @@ struct WarpParams {
     float d;                   // reference time as a fraction of the batch period
     float d_lo;                // ... what fp32 could not hold of it (d64 = (double)d + (double)d_lo): read only by warp_exact
     int normalize;             // normalize_t
-    int motion_f64;            // 2-DoF only: `motion` points to double[2] (cmax_objective_t::motion_dtype == CMAX_F64)
+    int motion_f64;            // cmax_objective_t::motion_dtype == CMAX_F64.  2-DoF: `motion` points to double[2].  Dense / voxel: `motion` is the high
+                               // plane of the caller's doubles and the low plane lies behind it (k_split_motion); read by the HOST only, which
+                               // launches the deciding kernels' ExactFlow instantiations (phase_warp's F64FLOW)
     const double *tmm;         // device (tmin, tmax)
     const float *motion;       // theta[2] | flow[2,H,W] | voxel[T,2,H,W]
+};
+
+// Trailing kernel argument of K1, k_vote_tan and k_grad_hvp for a dense / voxel motion that crossed the boundary in fp64: selects the
+// instantiation whose border branch reads the low plane (nothing is read from the value)
+struct ExactFlow {
+    int on;
 };
 
 // One launch of an event kernel covers every reference time of the objective (blockIdx.y): a multi-focal cost
@@ -333,6 +341,11 @@ struct cmax_handle_s {
     int64_t g64_cap = 0;
     double *d_det_inv_scale = nullptr;  // [4]
     float *Gt_det = nullptr;      // [4][npix] dL/d(blurred image) of the unfused image path
+    // an fp64 flow / voxel at the boundary (cmax_objective_t::motion_dtype == CMAX_F64, dense / voxel): hi plane | lo plane of the
+    // caller's doubles (k_split_motion), allocated on first use
+    float *m64 = nullptr;
+    int64_t m64_cap = 0;            // floats
+    const void *m64_src = nullptr;  // whose split the planes hold (cmax_objective_finish: the windows of a vote are another motion's otherwise)
 };
 
 namespace cmax {
@@ -623,12 +636,41 @@ __device__ __forceinline__ Warped warp_exact(const EvView &ev, unsigned ex, int6
 // of the event (a function of the EVENT alone, so that nothing depends on how threads and events are matched).  Fractional sources add
 // the rounding of rx and the fma's on a sum of magnitude up to 1.  Everything else is RELATIVE to the motion: a zero motion -- the
 // optimiser's usual starting point, where every event sits ON a border -- has no candidates.
+// An fp64 flow / voxel (WarpParams::motion_f64): the bulk warp reads hi = fl(f), off from the caller's f by at most eps / 2 |f|, so
+// dx gains eps / 2 |dt f| against the fp64 arithmetic on f itself -- the term listed for theta above, which the flow models had
+// no use for while the flow was the device's own fp32.  The count is the 2-DoF model's, 3.5 |dt f| (4 with d = 0 counted in full)
+// against the 6 |dt f| the coefficient grants, and fm = max |hi| is |f| to within 1 + eps: the coefficient stands, and an fp32 call
+// selects the candidates it selected before.
 __device__ __forceinline__ float exact_margin_coef(float d, float tscale) {
     const float kappa = d == 0.f ? 0.f : (1.f + 0.5f * fabsf(d)) * tscale;
     return 0x1.8p-24f * (4.f * tscale * fmaxf(fabsf(d), fabsf(1.f - d)) + kappa);
 }
 template <bool FRAC>
 __device__ __forceinline__ float exact_margin(float coef, float fm) { return fmaf(coef, fm, FRAC ? 0x1p-21f : 0.f); }
+
+// An fp64 flow / voxel at the boundary: out[i] = hi = (float)v[i] -- the value an fp32 caller passes, read by every kernel -- and
+// out[count + i] = lo = (float)(v[i] - hi), read only where K1 decides a cell in fp64 (hi + lo = v to 2^-48 relative, what the source
+// residual rx + rxl has); lo = 0 where hi is not finite (split_f64, cmax_common.h).  Streaming: 2 x 16-byte loads, 2 x 16-byte stores per thread and step
+// (`vec`: count is a multiple of 4 and v is 16-byte aligned), one value per thread otherwise.
+__global__ void __launch_bounds__(256) k_split_motion(const double *__restrict__ v, int64_t count, int vec, float *__restrict__ out) {
+    const int64_t step = (int64_t)gridDim.x * blockDim.x, t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (vec) {
+        const double2 *v2 = reinterpret_cast<const double2 *>(v);
+        float4 *hi4 = reinterpret_cast<float4 *>(out), *lo4 = reinterpret_cast<float4 *>(out + count);
+        for (int64_t i = t; i < count / 4; i += step) {
+            const double2 a = v2[2 * i], b = v2[2 * i + 1];
+            float4 hi, lo;
+            split_f64(a.x, hi.x, lo.x);
+            split_f64(a.y, hi.y, lo.y);
+            split_f64(b.x, hi.z, lo.z);
+            split_f64(b.y, hi.w, lo.w);
+            hi4[i] = hi;
+            lo4[i] = lo;
+        }
+    } else {
+        for (int64_t i = t; i < count; i += step) split_f64(v[i], out[i], out[count + i]);
+    }
+}
 
 __device__ __forceinline__ float time_scale(const WarpParams &wp) {
     return wp.normalize ? 1.0f : (float)(wp.tmm[1] - wp.tmm[0]);
@@ -2005,19 +2047,30 @@ static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp
     const RefArgs ra = weighted_args(h, ra_in);
     ProfScope prof(h, kProfVote, s);
     const char *cev = compact_events<MODEL>(h);
-    for (int rep = 0; rep < h->prof_repeat; ++rep)
-        with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
-            using L = decltype(l);
-            with_bool(h->has_frac, [&](auto frac) {
-                if (ra.wgt) {  // weighted handle (never with the vote sums: eval_plan)
-                    hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);
-                    return;
-                }
-                with_bool(ra.musum[0] != nullptr, [&](auto mu) {
-                    hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp, ra);
+    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing)
+        for (int rep = 0; rep < h->prof_repeat; ++rep)
+            with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
+                using L = decltype(l);
+                with_bool(h->has_frac, [&](auto frac) {
+                    if (ra.wgt) {  // weighted handle (never with the vote sums: eval_plan)
+                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp,
+                                           ra, exact...);
+                        return;
+                    }
+                    with_bool(ra.musum[0] != nullptr, [&](auto mu) {
+                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value, false, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev,
+                                           wp, ra, exact...);
+                    });
                 });
             });
-        });
+    };
+    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
+        if (wp.motion_f64) {  // the caller's fp64 flow, split: the instantiation whose border branch reads the low plane
+            launch(ExactFlow{1});
+            return;
+        }
+    }
+    launch();
 }
 
 // seg0 / seg_n: sub-range of the work list (a band of tile rows, see cmax_comm_set_c2_bands); seg_n < 0 = the whole list.  The
@@ -2911,6 +2964,7 @@ int cmax_destroy(cmax_handle_t h) {
     dev_free(&h->g64);
     dev_free(&h->d_det_inv_scale);
     dev_free(&h->Gt_det);
+    dev_free(&h->m64);
     dev_free(&h->imgs);
     for (int k = 0; k < 5; ++k) dev_free(&h->iweb[k]);
     dev_free(&h->G);
@@ -3187,8 +3241,7 @@ static int check_objective_args(cmax_handle_t h, const cmax_objective_t *d, cons
     CMAX_REQUIRE(d->model >= CMAX_MODEL_2DOF && d->model <= CMAX_MODEL_VOXEL, "objective: model");
     CMAX_REQUIRE(d->cost == CMAX_COST_VARIANCE || d->cost == CMAX_COST_GRADMAG, "objective: cost");
     CMAX_REQUIRE(d->n_ref >= 1 && d->n_ref <= 4, "objective: n_ref");
-    CMAX_REQUIRE(d->motion_dtype == CMAX_F32 || (d->motion_dtype == CMAX_F64 && d->model == CMAX_MODEL_2DOF),
-                 "objective: motion_dtype must be CMAX_F32, or CMAX_F64 for the 2-DoF model");
+    CMAX_REQUIRE(d->motion_dtype == CMAX_F32 || d->motion_dtype == CMAX_F64, "objective: motion_dtype must be CMAX_F32 or CMAX_F64");
     CMAX_REQUIRE(d->model != CMAX_MODEL_VOXEL || (d->T > 0 && d->T == h->n_time_bin), "objective: voxel T must match the handle's time bins");
     CMAX_REQUIRE(d->model != CMAX_MODEL_VOXEL || !h->slab_major, "objective: a voxel motion needs time BINS (cmax_set_time_bins), this handle is in slab order");
     CMAX_REQUIRE(d->model == CMAX_MODEL_2DOF || h->n_outside == 0,
@@ -3241,6 +3294,32 @@ static GradExtent grad_extent(const cmax_handle_s *h, const cmax_objective_t *d)
     if (d->model == CMAX_MODEL_2DOF) return {2, 2 * sizeof(double), kCommF64};
     const int64_t count = (int64_t)(d->model == CMAX_MODEL_VOXEL ? d->T : 1) * 2 * h->H * h->W;
     return {count, (size_t)count * sizeof(float), kCommF32};
+}
+
+// The motion as the kernels read it (behind check_objective_args).  fp32, or the 2-DoF model's double theta[2]: the caller's pointer.
+// An fp64 flow / voxel: the high plane of its split in the handle's scratch, the low plane behind it (k_split_motion) -- one launch
+// on the caller's stream in front of the evaluation; everything but K1's fp64 cell decisions then runs what an fp32 call on
+// (float)flow runs.  The scratch grows on first use (with a synchronisation: not inside a stream capture).
+static int kernel_motion(cmax_handle_s *h, const cmax_objective_t *d, const void *motion_v, hipStream_t s, const float **motion) {
+    *motion = static_cast<const float *>(motion_v);
+    if (d->motion_dtype != CMAX_F64 || d->model == CMAX_MODEL_2DOF) return 0;
+    const int64_t count = grad_extent(h, d).count;
+    if (2 * count > h->m64_cap) {
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        if (h->win_motion == h->m64) h->win_motion = nullptr;
+        dev_free(&h->m64);
+        h->m64_cap = 0;
+        int rc = dev_alloc(h, &h->m64, 2 * count);
+        if (rc) return rc;
+        h->m64_cap = 2 * count;
+    }
+    const int vec = (count % 4 == 0 && (reinterpret_cast<uintptr_t>(motion_v) & 15u) == 0) ? 1 : 0;
+    const int64_t items = vec ? count / 4 : count;
+    hipLaunchKernelGGL(k_split_motion, dim3(stream_grid(items, 256)), dim3(256), 0, s, static_cast<const double *>(motion_v), count, vec, h->m64);
+    CMAX_CHECK_LAUNCH();
+    h->m64_src = motion_v;
+    *motion = h->m64;
+    return 0;
 }
 
 // C2 in row bands (cmax_comm_set_c2_bands).  WHETHER the gradient is exchanged in bands, and in which, must not depend on anything a
@@ -3487,6 +3566,8 @@ int cmax_objective_vote(cmax_handle_t h, const cmax_objective_t *d, const void *
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     CMAX_REQUIRE(images && n_images_host, "objective_vote: images / n_images_host");
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     VoteJobs jobs;
     jobs.publish_windows = true;
     return objective_vote(h, d, motion, images, 0u, n_images_host, (hipStream_t)stream, jobs);
@@ -3767,6 +3848,10 @@ int cmax_objective_finish(cmax_handle_t h, const cmax_objective_t *d, const void
     if (rc) return rc;
     CMAX_REQUIRE(images && result, "objective_finish: images / result");
     CMAX_REQUIRE(n_images == d->n_ref || n_images == d->n_ref + 1, "objective_finish: n_images");
+    // (an fp64 flow is split into the scratch every vote's split went to: the handle's windows are this motion's only if that vote's was)
+    if (h->m64 && h->win_motion == h->m64 && h->m64_src != motion_v) h->win_motion = nullptr;
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     return objective_finish(h, d, eval_plan(h, d, grad, false), motion, images, n_images, nullptr, result, grad, (hipStream_t)stream);
 }
 
@@ -3887,6 +3972,8 @@ int cmax_objective(cmax_handle_t h, const cmax_objective_t *d, const void *motio
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     CMAX_REQUIRE(result, "objective: result");
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, nullptr);
 }
 
@@ -4186,6 +4273,8 @@ int cmax_objective_weight_grad(cmax_handle_t h, const cmax_objective_t *d, const
     int rc = per_event_check(h, d, motion, n, "objective_weight_grad");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    rc = kernel_motion(h, d, motion_v, s, &motion);
+    if (rc) return rc;
     if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
     const float *orig_raw = nullptr;
     rc = per_event_eval(h, d, motion, result, grad, s, &orig_raw);
@@ -4200,6 +4289,8 @@ int cmax_objective_event_grad(cmax_handle_t h, const cmax_objective_t *d, const 
     int rc = per_event_check(h, d, motion, n, "objective_event_grad");
     if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
+    rc = kernel_motion(h, d, motion_v, s, &motion);
+    if (rc) return rc;
     if (n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_events, 0, (size_t)n * 3 * sizeof(float), s));
     CMAX_CHECK_HIP(hipMemsetAsync(csum, 0, 4 * sizeof(double), s));
     const float *orig_raw = nullptr;
@@ -4215,6 +4306,8 @@ int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     CMAX_REQUIRE(result, "objective_dist: result");
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, h->comm);
 }
 
@@ -4234,11 +4327,13 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
     hipStream_t s = (hipStream_t)stream;
     const bool two_dof = d->model == CMAX_MODEL_2DOF;
     const GradExtent g = grad_extent(h, d);
-    const int64_t mfloats = two_dof ? (d->motion_dtype == CMAX_F64 ? 4 : 2) : g.count;  // floats per candidate motion
+    const int64_t mfloats = (two_dof ? 2 : g.count) * (d->motion_dtype == CMAX_F64 ? 2 : 1);  // floats per candidate motion
     const bool fast = K > 1 && grads && deferred_applies(h, d, grads) && !d->normalized && !h->comm && !h->profiling;
     if (!fast) {
         for (int z = 0; z < K; ++z) {
-            rc = objective_eval(h, d, motions + z * mfloats, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
+            const float *motion = nullptr;  // (an fp64 flow: every candidate is split in front of its evaluation, stream-ordered in the one scratch)
+            rc = kernel_motion(h, d, motions + z * mfloats, s, &motion);
+            if (!rc) rc = objective_eval(h, d, motion, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
             if (rc) return rc;
         }
         return 0;
@@ -4375,6 +4470,8 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
     if (rc) return rc;
     CMAX_REQUIRE(result_host, "objective_host: result_host");
     hipStream_t s = (hipStream_t)stream;
+    rc = kernel_motion(h, d, motion_v, s, &motion);
+    if (rc) return rc;
     if (grad_host && two_dof_lines(h, d, grad_host)) {
         // 2-DoF objectives: K1 [-> image kernel] -> K3 -> the one-wave finishing kernel, which writes (loss and) gradient STRAIGHT INTO PINNED HOST
         // MEMORY and then a run counter behind them; the host polls that word.  No copy engine and no driver call between the
@@ -4532,16 +4629,26 @@ static void launch_vote_tan(cmax_handle_s *h, const EvView &ev, const WarpParams
                             long long *draw64 = nullptr) {
     if (h->weighted && draw64) std::abort();
     const dim3 grid(seg_blocks(h->nseg), n_ref);
-    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-        using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            if (h->weighted)
-                hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw,
-                                   h->d_stat_tan, draw64, (const float *)h->w_packed, (const float *)h->d_wnorm);
-            else
-                hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan, draw64);
+    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing, as in launch_vote)
+        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+            using L = decltype(l);
+            with_bool(h->has_frac, [&](auto frac) {
+                if (h->weighted)
+                    hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs,
+                                       h->nseg, draw, h->d_stat_tan, draw64, (const float *)h->w_packed, (const float *)h->d_wnorm, exact...);
+                else
+                    hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan,
+                                       draw64, exact...);
+            });
         });
-    });
+    };
+    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
+        if (wp.motion_f64) {
+            launch(ExactFlow{1});
+            return;
+        }
+    }
+    launch();
 }
 
 // det: the integer accumulators of deterministic mode (HvpDet{} otherwise); weights as launch_vote_tan
@@ -4550,16 +4657,26 @@ static void launch_grad_hvp(cmax_handle_s *h, const EvView &ev, const WarpParams
                             const float *Gp, double *gpart, float *hflow, hipStream_t s, const HvpDet &det) {
     if (h->weighted && h->deterministic) std::abort();
     const dim3 grid(seg_blocks(h->nseg), n_ref);
-    with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-        using L = decltype(l);
-        with_bool(h->has_frac, [&](auto frac) {
-            if (h->weighted)
-                hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det,
-                                   (const float *)h->w_packed);
-            else
-                hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det);
+    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing, as in launch_vote)
+        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
+            using L = decltype(l);
+            with_bool(h->has_frac, [&](auto frac) {
+                if (h->weighted)
+                    hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart,
+                                       hflow, det, (const float *)h->w_packed, exact...);
+                else
+                    hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det,
+                                       exact...);
+            });
         });
-    });
+    };
+    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
+        if (wp.motion_f64) {
+            launch(ExactFlow{1});
+            return;
+        }
+    }
+    launch();
 }
 
 // scratch of the second-order path and of the IWE layer: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
@@ -4766,6 +4883,8 @@ int cmax_objective_hvp(cmax_handle_t h, const cmax_objective_t *d, const void *m
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     CMAX_REQUIRE(tangent && hv, "objective_hvp: tangent / hv");
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     return objective_hvp_impl(h, d, motion, tangent, hv, (hipStream_t)stream, nullptr, false);
 }
 
@@ -4776,6 +4895,8 @@ int cmax_objective_hvp_dist(cmax_handle_t h, const cmax_objective_t *d, const vo
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     CMAX_REQUIRE(tangent && hv, "objective_hvp_dist: tangent / hv");
+    rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
+    if (rc) return rc;
     return objective_hvp_impl(h, d, motion, tangent, hv, (hipStream_t)stream, h->comm, true);
 }
 
@@ -4873,8 +4994,10 @@ int cmax_iwes(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, float
     int rc = iwes_check(h, d, motion_v, "iwes", &o);
     if (rc) return rc;
     CMAX_REQUIRE(images != nullptr, "iwes: images");
-    const float *motion = static_cast<const float *>(motion_v);
     hipStream_t s = (hipStream_t)stream;
+    const float *motion = nullptr;
+    rc = kernel_motion(h, &o, motion_v, s, &motion);
+    if (rc) return rc;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = o.n_ref, n_img = nr + (d->with_orig ? 1 : 0);
     if (h->n == 0) {
@@ -4911,8 +5034,10 @@ int cmax_iwes_vjp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
     if (rc) return rc;
     CMAX_REQUIRE(gimages && grad_motion, "iwes_vjp: gimages / grad_motion");
     CMAX_REQUIRE(!grad_w || n == h->n_in, "iwes_vjp: n must equal the n of the last cmax_set_events (one derivative per event, in the caller's order)");
-    const float *motion = static_cast<const float *>(motion_v);
     hipStream_t s = (hipStream_t)stream;
+    const float *motion = nullptr;
+    rc = kernel_motion(h, &o, motion_v, s, &motion);
+    if (rc) return rc;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const GradExtent g = grad_extent(h, &o);
     CMAX_CHECK_HIP(hipMemsetAsync(grad_motion, 0, g.bytes, s));
@@ -4944,8 +5069,10 @@ int cmax_iwes_jvp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
     int rc = iwes_check(h, d, motion_v, "iwes_jvp", &o);
     if (rc) return rc;
     CMAX_REQUIRE(tangent && dimages, "iwes_jvp: tangent / dimages");
-    const float *motion = static_cast<const float *>(motion_v);
     hipStream_t s = (hipStream_t)stream;
+    const float *motion = nullptr;
+    rc = kernel_motion(h, &o, motion_v, s, &motion);
+    if (rc) return rc;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = o.n_ref;
     if (h->n == 0) {
@@ -4976,8 +5103,10 @@ int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_
     int rc = iwes_check(h, d, motion_v, "iwes_vjp_tan", &o);
     if (rc) return rc;
     CMAX_REQUIRE(tangent && gimages && gimages_tan && out, "iwes_vjp_tan: tangent / gimages / gimages_tan / out");
-    const float *motion = static_cast<const float *>(motion_v);
     hipStream_t s = (hipStream_t)stream;
+    const float *motion = nullptr;
+    rc = kernel_motion(h, &o, motion_v, s, &motion);
+    if (rc) return rc;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const GradExtent g = grad_extent(h, &o);
     CMAX_CHECK_HIP(hipMemsetAsync(out, 0, g.bytes, s));
@@ -5009,6 +5138,17 @@ int objective_hvp_dist_local(cmax_handle_t h, const cmax_objective_t *d, const f
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
     return objective_hvp_impl(h, d, motion, tangent, hv, s, h->comm, false);
+}
+int objective_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s) {
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    return objective_eval(h, d, motion, result, grad, s, nullptr);
+}
+int objective_hvp_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *tangent, void *hv, hipStream_t s) {
+    CMAX_REFUSE_WEIGHTED(h, "patch plan product");
+    int rc = check_objective_args(h, d, motion);
+    if (rc) return rc;
+    return objective_hvp_impl(h, d, motion, tangent, hv, s, nullptr, false);
 }
 int handle_allreduce_sum(cmax_handle_t h, void *buf, size_t count, bool f64, hipStream_t s) {
     if (!h || !h->comm) return 0;

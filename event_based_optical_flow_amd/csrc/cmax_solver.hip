@@ -34,6 +34,23 @@ k_convert_scale(const TI *__restrict__ in, int64_t n, double scale, const double
     if (i < n) out[i] = (TO)((double)in[i] * sc);
 }
 
+// ... for a plan whose terms take the fp64 motion (cmax_objective_t::motion_dtype == CMAX_F64): hi = what k_convert_scale<float, double>
+// writes, lo = what fp32 lost of the scaled value (split_f64), in the same launch
+__global__ void __launch_bounds__(256)
+k_convert_split(const double *__restrict__ in, int64_t n, double scale, const double *__restrict__ scale_dev, float *__restrict__ hi, float *__restrict__ lo) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const double sc = scale_dev ? scale * scale_dev[0] : scale;
+    if (i < n) split_f64(in[i] * sc, hi[i], lo[i]);
+}
+// ... and of k_patch_to_dense<double, float>: the patch grid -> both planes of flow * scale
+__global__ void __launch_bounds__(256)
+k_patch_to_dense_split(const double *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, float *__restrict__ hi,
+                       float *__restrict__ lo, double scale) {
+    const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p >= 2 * (int64_t)H * W) return;
+    split_f64(patch_interp<double>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p) * scale, hi[p], lo[p]);
+}
+
 // acc (=, +=) w [* *w_dev] * g
 __global__ void __launch_bounds__(256)
 k_accumulate(const float *__restrict__ g, int64_t n, double w, int first, double *__restrict__ acc, const double *__restrict__ w_dev = nullptr) {
@@ -163,6 +180,16 @@ k_sl_motion_tangent(const double *__restrict__ V, const double *__restrict__ Wt,
     const double s = sl[0], sd = sl[2], v = V[i];
     Md[i] = sd * v + s * Wt[i];
     motion32[i] = (float)(s * v);
+}
+// ... of a plan whose terms take the fp64 motion: both planes of s V (k_convert_split)
+__global__ void __launch_bounds__(256)
+k_sl_motion_tangent_split(const double *__restrict__ V, const double *__restrict__ Wt, int64_t n, const double *__restrict__ sl,
+                          double *__restrict__ Md, float *__restrict__ hi, float *__restrict__ lo) {
+    const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (i >= n) return;
+    const double s = sl[0], sd = sl[2], v = V[i];
+    Md[i] = sd * v + s * Wt[i];
+    split_f64(s * v, hi[i], lo[i]);
 }
 
 struct DotJobs {
@@ -342,6 +369,9 @@ struct cmax_patch_plan_s {
     // time-aware Hessian-vector product (allocated on first use): tangent flow / voxel, tangent of dL/dvoxel, scalars
     double *dflow64 = nullptr, *dvox64 = nullptr, *dgacc64 = nullptr, *dgflow64 = nullptr, *scal = nullptr;
     float *motion32 = nullptr, *grad32 = nullptr, *tan32 = nullptr, *gx32 = nullptr;
+    // the terms carry motion_dtype == CMAX_F64: motion32 is [2][nmotion], the high plane (the fp32 motion of every other plan) and the low
+    // plane of the fp64 flow / voxel the plan holds anyway, written by the same conversion launches and read by K1's fp64 cell decisions
+    bool exact = false;
     // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
     double *dense64 = nullptr, *sl = nullptr, *sl_partial = nullptr;
     double *h_out_dev = nullptr;  // device view of the pinned output: the tail kernel writes the result there
@@ -387,10 +417,12 @@ int plan_alloc(T **p, int64_t count) {
 // total variation and everything derived from x are computed redundantly and identically on every rank.
 int plan_objective(cmax_patch_plan_s *p, const cmax_objective_t *term, double *result, void *grad, hipStream_t s) {
     if (handle_has_comm(p->handle)) return objective_dist_local_grad(p->handle, term, p->motion32, result, grad, s);
+    if (p->exact) return objective_presplit(p->handle, term, p->motion32, result, grad, s);  // (the planes are split already)
     return cmax_objective(p->handle, term, p->motion32, result, grad, s);
 }
 int plan_objective_hvp(cmax_patch_plan_s *p, const cmax_objective_t *term, void *hv, hipStream_t s) {
     if (handle_has_comm(p->handle)) return objective_hvp_dist_local(p->handle, term, p->motion32, p->tan32, hv, s);
+    if (p->exact) return objective_hvp_presplit(p->handle, term, p->motion32, p->tan32, hv, s);
     return cmax_objective_hvp(p->handle, term, p->motion32, p->tan32, hv, s);
 }
 // C2 of the plan: the gradient (or product) w.r.t. the patch motion, summed over the ranks (a no-op without a communicator)
@@ -413,6 +445,13 @@ int plan_reduce_gx_and_results(cmax_patch_plan_s *p, const double *gx64, const f
 int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
     const int grid = div_up(p->nflow, 256);
+    const bool split = p->exact && dst32 == p->motion32;  // the motion of an exact plan (not its tangent): both planes, in the launches below
+    float *lo32 = dst32 + p->nmotion;
+    if (!d.time_aware && !scale_dev && split) {
+        hipLaunchKernelGGL(k_patch_to_dense_split, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
+        CMAX_CHECK_LAUNCH();
+        return 0;
+    }
     if (!d.time_aware && !scale_dev) {  // patch grid -> fp32 flow * scale in one kernel
         hipLaunchKernelGGL((k_patch_to_dense<double, float>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
                            d.H, d.W, dst32, scale);
@@ -428,7 +467,8 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
         CMAX_CHECK_LAUNCH();
         int rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, nullptr, nullptr, s);
         if (rc) return rc;
-        hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)p->sl, dst32);
+        if (split) hipLaunchKernelGGL(k_convert_split, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)p->sl, dst32, lo32);
+        else hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)p->sl, dst32);
         CMAX_CHECK_LAUNCH();
         return 0;
     }
@@ -439,9 +479,13 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
                            d.H, d.W, p->flow64, scale);
         CMAX_CHECK_LAUNCH();
         bool wrote32 = false;
-        int rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, dst32, &wrote32, s);
+        // (an exact plan: the chain kernel writes no low plane -- where it would have written the fp32 copy itself, the conversion is this plan's one launch more)
+        int rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, split ? nullptr : dst32, split ? nullptr : &wrote32, s);
         if (rc) return rc;
-        if (!wrote32) {
+        if (split) {
+            hipLaunchKernelGGL(k_convert_split, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32, lo32);
+            CMAX_CHECK_LAUNCH();
+        } else if (!wrote32) {
             hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32);
             CMAX_CHECK_LAUNCH();
         }
@@ -450,7 +494,8 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
     int rc = cmax_patch_to_dense(src64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->flow64, s);
     if (rc) return rc;
     if (!d.time_aware) {
-        hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(grid), dim3(256), 0, s, p->flow64, p->nflow, scale, scale_dev, dst32);
+        if (split) hipLaunchKernelGGL(k_convert_split, dim3(grid), dim3(256), 0, s, p->flow64, p->nflow, scale, scale_dev, dst32, lo32);
+        else hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(grid), dim3(256), 0, s, p->flow64, p->nflow, scale, scale_dev, dst32);
         CMAX_CHECK_LAUNCH();
         return 0;
     }
@@ -458,7 +503,8 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
     CMAX_CHECK_LAUNCH();
     rc = cmax_voxel_construct(p->flow64, CMAX_F64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, s);
     if (rc) return rc;
-    hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32);
+    if (split) hipLaunchKernelGGL(k_convert_split, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32, lo32);
+    else hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32);
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -572,7 +618,8 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     CMAX_CHECK_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_absmax, dim3(mgrid < 256 ? mgrid : 256), dim3(256), 0, s, p->dvox64, p->nmotion, bits);
     hipLaunchKernelGGL(k_absmax_finish, dim3(1), dim3(1), 0, s, bits, p->scal);
-    hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, p->motion32);
+    if (p->exact) hipLaunchKernelGGL(k_convert_split, dim3(mgrid), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, p->motion32, p->motion32 + p->nmotion);
+    else hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, p->motion32);
     hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, p->dvox64, p->nmotion, 1.0, p->scal + 1, p->tan32);
     CMAX_CHECK_LAUNCH();
     for (int i = 0; i < d.n_terms; ++i) {
@@ -627,7 +674,10 @@ int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
     rc = cmax_voxel_construct_tan(p->flow64, p->dflow64, CMAX_F64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, p->dvox64, s);
     if (rc) return rc;
     // fp32 motion s V; tangent Md = sd V + s W (staged in dgacc64, free until the first product lands there), scaled to unit max-norm
-    hipLaunchKernelGGL(k_sl_motion_tangent, dim3(mgrid), dim3(256), 0, s, p->vox64, p->dvox64, p->nmotion, p->sl, p->dgacc64, p->motion32);
+    if (p->exact)
+        hipLaunchKernelGGL(k_sl_motion_tangent_split, dim3(mgrid), dim3(256), 0, s, p->vox64, p->dvox64, p->nmotion, p->sl, p->dgacc64, p->motion32,
+                           p->motion32 + p->nmotion);
+    else hipLaunchKernelGGL(k_sl_motion_tangent, dim3(mgrid), dim3(256), 0, s, p->vox64, p->dvox64, p->nmotion, p->sl, p->dgacc64, p->motion32);
     unsigned long long *bits = reinterpret_cast<unsigned long long *>(p->scal + 2);
     CMAX_CHECK_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned long long), s));
     hipLaunchKernelGGL(k_absmax, dim3(mgrid < 256 ? mgrid : 256), dim3(256), 0, s, p->dgacc64, p->nmotion, bits);
@@ -835,6 +885,7 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     for (int i = 0; i < d.n_terms; ++i) {
         CMAX_REQUIRE(d.term[i].model == (d.time_aware ? CMAX_MODEL_VOXEL : CMAX_MODEL_DENSE), "patch_plan_create: term model must match time_aware");
         CMAX_REQUIRE(!d.time_aware || d.term[i].T == d.T, "patch_plan_create: term T");
+        CMAX_REQUIRE(d.term[i].motion_dtype == d.term[0].motion_dtype, "patch_plan_create: the terms must agree on motion_dtype");
     }
     if (d.time_aware && d.scale_later && handle_has_comm(h)) {
         set_error("patch_plan_create: scale_later is not built for time-sliced batches (the handle holds a communicator)");
@@ -851,6 +902,7 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     if (const char *e = getenv("CMAX_PLAN_GRAPHS")) p->graphs_ok = atoi(e) != 0;
     p->nflow = 2 * (int64_t)d.H * d.W;
     p->nmotion = d.time_aware ? (int64_t)d.T * p->nflow : p->nflow;
+    p->exact = d.term[0].motion_dtype == CMAX_F64;
     int rc = 0;
     if (!rc) rc = plan_alloc(&p->x64, 2 * (int64_t)p->nx + 2);  // x | v | 2 scalars, filled by one copy
     if (!rc) p->v64 = p->x64 + p->nx;
@@ -865,7 +917,7 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     }
     if (!rc) rc = plan_alloc(&p->gx64, p->nx);
     if (!rc) rc = plan_alloc(&p->results, 8 * 4);
-    if (!rc) rc = plan_alloc(&p->motion32, p->nmotion);
+    if (!rc) rc = plan_alloc(&p->motion32, (p->exact ? 2 : 1) * p->nmotion);
     if (!rc) rc = plan_alloc(&p->grad32, p->nmotion);
     if (!rc) rc = plan_alloc(&p->tan32, p->nmotion);
     if (!rc) rc = plan_alloc(&p->gx32, p->nx);

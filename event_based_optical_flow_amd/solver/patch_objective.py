@@ -26,11 +26,11 @@ class _SlicedFusedFn(torch.autograd.Function):
     patch interpolation -- 2 n_patch numbers cross the fabric instead of the flow gradient, like in the library's own plan."""
 
     @staticmethod
-    def forward(ctx, motion, sliced, desc):
+    def forward(ctx, motion, sliced, desc, exact_flow=False):
         local = sliced.local
-        images = local.objective_vote(desc, motion)
+        images = local.objective_vote(desc, motion, exact_flow=exact_flow)
         sliced._all_reduce(images)
-        result, grad = local.objective_finish(desc, motion, images, want_grad=motion.requires_grad)
+        result, grad = local.objective_finish(desc, motion, images, want_grad=motion.requires_grad, exact_flow=exact_flow)
         sliced._rank0_value(result)  # the term's scalars as rank 0 summed them, on every rank (TimeSlicedObjective._rank0_value)
         ctx.grad, ctx.mdtype = grad, motion.dtype
         return result[0].to(motion.dtype)
@@ -38,8 +38,8 @@ class _SlicedFusedFn(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gout):
         if ctx.grad is None:
-            return None, None, None
-        return ctx.grad.to(ctx.mdtype) * gout.to(ctx.mdtype), None, None
+            return None, None, None, None
+        return ctx.grad.to(ctx.mdtype) * gout.to(ctx.mdtype), None, None, None
 
 
 def patch_pad(patch_size, sliding_window, patch_shift=(0, 0)) -> Tuple[int, int]:
@@ -52,7 +52,7 @@ class PatchFlowObjective:
                  patch_shift=(0, 0), cost="hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
                  blur_sigma: float = 1.0, time_aware: bool = False, time_bin: int = 10,
                  flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None,
-                 scale_later: bool = False, omit_boundary: bool = True):
+                 scale_later: bool = False, omit_boundary: bool = True, exact_flow: bool = False):
         """omit_boundary: the reference's `arg["omit_boundary"]`, for the contrast terms and the total variation alike.
         sliced: a distributed.TimeSlicedObjective around `handle` when the batch is time-sliced over ranks.  With the library's own
         communicator on the handle (RCCL) the native plan evaluates the whole batch (cmax_patch_plan_* exchange images + 2 n_patch
@@ -61,7 +61,10 @@ class PatchFlowObjective:
         piecewise-smooth objective is dominated by the kinks at cell borders): prefer a first-order method there, or the RCCL plan.
         scale_later: the reference's `solver.scale_later` (src/solver/base.py:219-224, patch_contrast_pyramid.py:489-515): the flow is
         divided by its signed maximum before the Burgers / upwind propagation and the voxel multiplied by it afterwards; the maximum is
-        differentiated like torch.Tensor.max().  Ignored unless `time_aware`.  Not built for time-sliced batches."""
+        differentiated like torch.Tensor.max().  Ignored unless `time_aware`.  Not built for time-sliced batches.
+        exact_flow: the fused terms receive the float64 dense flow / voxel this objective computes from x instead of its fp32 rounding
+        (ContrastObjective(exact_flow=True); the native plan's terms carry motion_dtype = CMAX_F64 and the plan hands over the
+        fp64 field it holds): the cells of events on a cell border are then the ones the reference's float64 solver takes."""
         if filter_type != "bilinear":
             raise NotImplementedError("only the bilinear patch filter (the shipped configs) is built")
         self.handle = handle
@@ -79,8 +82,9 @@ class PatchFlowObjective:
         if self.time_aware and handle.time_bin != self.time_bin:
             handle.set_time_bins(self.time_bin)
         model = "dense-flow-voxel" if self.time_aware else "dense-flow"
+        self.exact_flow = bool(exact_flow)
         self.contrast = ContrastObjective(handle, model, cost=cost, cost_with_weight=cost_with_weight, sigma=blur_sigma,
-                                          omit_boundary=omit_boundary)
+                                          omit_boundary=omit_boundary, exact_flow=self.exact_flow)
         self.device = handle.device  # read by scipy_autograd.TorchWrapper
         self.auto_slabs = True  # ensure_time_slabs: time-slab order of the batch follows the motion's size
         self._plan = None
@@ -118,6 +122,7 @@ class PatchFlowObjective:
         for i, (w, desc) in enumerate(fused):
             d.weight[i] = float(w)
             d.term[i] = desc
+            d.term[i].motion_dtype = _lib.F64 if self.exact_flow else _lib.F32  # (a copy: the ContrastObjective's descriptors stay as they are)
         sign = 1.0 if self.contrast.direction == "minimize" else -1.0
         d.tv_weight = sign * float(sum(tv)) if tv else 0.0
         plan = ctypes.c_void_p()
@@ -231,9 +236,9 @@ class PatchFlowObjective:
             if desc is None:
                 continue
             if isinstance(desc, _CustomTerm):
-                value = desc.value(self.handle, self.dense_flow(xt), self.contrast.motion_model, self.contrast.omit_boundary)
+                value = desc.value(self.handle, self.dense_flow(xt), self.contrast.motion_model, self.contrast.omit_boundary, exact_flow=self.exact_flow)
             else:
-                value = _FusedFn.apply(self.dense_flow(xt), self.handle, desc)
+                value = _FusedFn.apply(self.dense_flow(xt), self.handle, desc, self.exact_flow)
             loss = loss + combine(weight, value)
         (g,) = torch.autograd.grad(loss, xt)
         return g
@@ -301,6 +306,6 @@ class PatchFlowObjective:
                 if self.contrast.direction != "minimize":
                     value = -value
             else:
-                value = _SlicedFusedFn.apply(dense, self.sliced, desc)
+                value = _SlicedFusedFn.apply(dense, self.sliced, desc, self.exact_flow)
             loss = loss + combine(weight, value)
         return loss

@@ -97,6 +97,9 @@ class PyramidalPatchContrastMaximization:
         else:
             self.time_bin, self.flow_interpolation, self.t0_flow_location = 0, "burgers", "middle"
             self.scale_later = False  # (the reference never reads the key without time_aware)
+        # optional, absent = False: the fused terms see the float64 flow / voxel this solver optimises in, not its fp32 rounding
+        # (PatchFlowObjective(exact_flow=True): the border cells of the reference's float64 arithmetic)
+        self.exact_flow = _check_key_and_bool(solver_config, "exact_flow")
         # pyramid (patch_contrast_pyramid.py:50-61)
         patch = solver_config["patch"]
         self.filter_type = patch["filter_type"]
@@ -158,7 +161,8 @@ class PyramidalPatchContrastMaximization:
                     handle, t_scale, pis, self.scaled_patch_size[s], self.scaled_patch_size[s], self.patch_shift,
                     cost=self.cost_name, cost_with_weight=self.cost_weight, blur_sigma=self.iwe_config["blur_sigma"],
                     time_aware=self.is_time_aware, time_bin=self.time_bin, flow_interpolation=self.flow_interpolation,
-                    t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=self.scale_later)
+                    t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=self.scale_later,
+                    exact_flow=self.exact_flow)
             else:
                 objective.set_t_scale(t_scale)
             if self.previous_frame_best_estimation is not None and s == self.coarest_scale:

@@ -263,16 +263,23 @@ typedef struct {
     double mult[4];       /* e.g. forward 1, backward 1, middle 2 */
     double sigma;         /* blur (0 = none) */
     int32_t T;            /* voxel time bins */
-    int32_t motion_dtype; /* CMAX_F32 (0): `motion` is fp32.  CMAX_F64: 2-DoF only -- `motion` points to double theta[2], the
-                             optimiser's own fp64 parameters (src/solver/patch_contrast_pyramid.py:186): the bulk arithmetic stays
-                             fp32, but the cell floor(x' + 1e-6) of an event that lies within fp32 rounding of a cell border is
-                             decided in fp64 from this theta, like the reference does (src/event_image_converter.py:340) */
+    int32_t motion_dtype; /* CMAX_F32 (0): `motion` is fp32.  CMAX_F64: `motion` points to doubles of the same layout -- double theta[2],
+                             double flow[2,H,W] or double voxel[T,2,H,W], the optimiser's own fp64 parameters
+                             (src/solver/patch_contrast_pyramid.py:186): the bulk arithmetic stays fp32, on (float)motion -- what an fp32
+                             call on the rounded motion runs --, but the cell floor(x' + 1e-6) of an event that lies within fp32
+                             rounding of a cell border is decided in fp64 from these doubles, like the reference does
+                             (src/event_image_converter.py:340).  A flow / voxel is split once per call into (float)v and
+                             (float)(v - (float)v) in scratch of the handle (one streaming launch; the scratch grows on the first such
+                             call, with a stream synchronisation -- not inside a stream capture).  Accepted by every entry that takes a
+                             descriptor with this field: cmax_objective, _host, _vote, _finish, _batch, _dist, _weight_grad,
+                             _event_grad, _hvp, _hvp_dist and (cmax_iwes_t) cmax_iwes, _vjp, _jvp, _vjp_tan.  Outputs keep their
+                             dtypes (the gradient and the product of a flow model are fp32), tangents stay fp32. */
 } cmax_objective_t;
 
 /* One evaluation.  result[0] = loss, result[1..n_ref] = v_k, result[5] = v_orig (device
  * doubles, result has 8 entries).  grad: fp64 [2] for 2DOF, fp32 [2,H,W] / [T,2,H,W] otherwise
  * (overwritten); NULL skips the gradient pass.  motion: fp32 theta[2] | flow[2,H,W] | voxel[T,2,H,W]
- * (or double theta[2], see cmax_objective_t::motion_dtype).                                    */
+ * (or doubles of the same layout, see cmax_objective_t::motion_dtype).                         */
 int cmax_objective(cmax_handle_t h, const cmax_objective_t *desc_host, const void *motion,
                    double *result, void *grad, cmax_stream_t stream);
 
@@ -381,8 +388,8 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *desc_host, cons
 
 /* K candidate motions in one call (the reference's gradient-free paths evaluate the objective for batches of sampled motions:
  * src/solver/base.py:738-758 run_optuna, src/solver/patch_contrast_pyramid.py:363-415; a line search asks for several steps along one
- * direction).  motions: K consecutive motions as cmax_objective takes one (fp32 theta[2] | double theta[2] with motion_dtype CMAX_F64 |
- * flow[2,H,W] | voxel[T,2,H,W]); results: device double[K][8]; grads: device double[K][2] (2DOF) or fp32 [K][...] (NULL: values only).
+ * direction).  motions: K consecutive motions as cmax_objective takes one (fp32 theta[2] | flow[2,H,W] | voxel[T,2,H,W], or -- motion_dtype
+ * CMAX_F64 -- doubles of the same layout); results: device double[K][8]; grads: device double[K][2] (2DOF) or fp32 [K][...] (NULL: values only).
  * For the 2-DoF image-variance objective (sigma 0, not normalised, default mode, no communicator) the K evaluations share ONE
  * launch of each kernel: blockIdx.z is the candidate -- its own vote image, sums and windows -- so the launch structure that is 40 %
  * of a single 1M-event evaluation is paid once per batch.  Every other objective is evaluated candidate by candidate inside the call
@@ -604,6 +611,9 @@ int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start
  *   Hessian-vector product follow the whole map.  s lives in device memory: no host read-back inside a call.
  *   max D == 0 (x = 0) or not finite: loss, gradient and product are NaN, as the reference's 0/0 -- the event
  *   kernels are given a finite motion all the same.
+ * Terms with motion_dtype == CMAX_F64 (all of them or none): the fused terms decide the cells of events on a cell border from the
+ *   fp64 flow / voxel the plan holds, not from its fp32 rounding -- the conversion launches write both planes (see
+ *   cmax_objective_t::motion_dtype), evaluate, product and graph replay alike.
  * ============================================================================================= */
 typedef struct {
     int32_t n_terms;          /* 1..4 fused contrast terms of a hybrid cost (src/costs/hybrid.py:48-57) */
