@@ -79,6 +79,7 @@ class CmaxPatchObjective(ctypes.Structure):
         ("pad_w", ctypes.c_int32),
         ("tv_omit_boundary", ctypes.c_int32),
         ("scale_later", ctypes.c_int32),
+        ("filter_type", ctypes.c_int32),  # the former padding in front of t_scale: the size is unchanged
         ("t_scale", ctypes.c_double),
         ("weight", ctypes.c_double * 4),
         ("tv_weight", ctypes.c_double),
@@ -92,6 +93,7 @@ MODEL_2DOF, MODEL_DENSE, MODEL_VOXEL = 0, 1, 2
 REF_FIRST, REF_LAST, REF_FRAC = 0, 1, 2
 COST_VARIANCE, COST_GRADMAG = 0, 1
 SCHEME_BURGERS, SCHEME_UPWIND = 0, 1
+FILTER_BILINEAR, FILTER_NEAREST = 0, 1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 RAW_LINES = 32
@@ -124,6 +126,7 @@ SIGNATURES = {
     "cmax_voxel_construct_tan": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp]),
     "cmax_voxel_construct_adj_tan": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_to_dense": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "cmax_patch_to_dense_filter": (c_int, [c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "cmax_create": (c_int, [c_int, c_int, c_int, c_int, ctypes.POINTER(c_vp)]),
     "cmax_destroy": (c_int, [c_vp]),
     "cmax_set_events": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_dbl, c_dbl, c_int, c_vp]),

@@ -589,6 +589,16 @@ int voxel_construct_adj_tan_f64(const double *V, const double *dV, int Tn, int t
 }
 }  // namespace cmax
 
+namespace {
+template <typename T, int F>
+void launch_patch_to_dense(const void *motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, int adjoint, void *out, hipStream_t s) {
+    if (!adjoint)
+        hipLaunchKernelGGL((k_patch_to_dense<T, T, F>), dim3(div_up(2 * (int64_t)H * W, 256)), dim3(256), 0, s, (const T *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (T *)out, (T)1);
+    else
+        hipLaunchKernelGGL((k_patch_to_dense_adj<T, F>), dim3(2 * ph * pw), dim3(256), 0, s, (const T *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (T *)out);
+}
+}  // namespace
+
 extern "C" {
 
 int cmax_flow_step(const void *F, int dtype, int H, int W, double dt, int scheme, void *out, cmax_stream_t stream) {
@@ -655,19 +665,26 @@ int cmax_voxel_construct_adj_tan(const void *V, const void *dV, int dtype, int T
 
 int cmax_patch_to_dense(const void *motion, int dtype, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
                         int adjoint, void *out, cmax_stream_t stream) {
+    return cmax_patch_to_dense_filter(motion, dtype, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, CMAX_FILTER_BILINEAR, adjoint, out, stream);
+}
+
+int cmax_patch_to_dense_filter(const void *motion, int dtype, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
+                               int filter, int adjoint, void *out, cmax_stream_t stream) {
     CMAX_REQUIRE(motion && out && ph > 0 && pw > 0 && pad_h >= 0 && pad_w >= 0 && sw_h > 0 && sw_w > 0 && H > 0 && W > 0, "patch_to_dense");
     CMAX_REQUIRE((ph + 2 * pad_h) * sw_h >= H && (pw + 2 * pad_w) * sw_w >= W, "patch_to_dense: up-sampled grid smaller than the image");
+    if (filter != CMAX_FILTER_BILINEAR && filter != CMAX_FILTER_NEAREST) {
+        set_error("patch_to_dense: unknown filter %d (CMAX_FILTER_BILINEAR or CMAX_FILTER_NEAREST)", filter);
+        return CMAX_EINVAL;
+    }
+    if (dtype != CMAX_F32 && dtype != CMAX_F64) { set_error("patch_to_dense: dtype"); return CMAX_EINVAL; }
     hipStream_t s = (hipStream_t)stream;
-    if (!adjoint) {
-        const int grid = div_up(2 * (int64_t)H * W, 256);
-        if (dtype == CMAX_F32) hipLaunchKernelGGL(k_patch_to_dense<float>, dim3(grid), dim3(256), 0, s, (const float *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (float *)out);
-        else if (dtype == CMAX_F64) hipLaunchKernelGGL(k_patch_to_dense<double>, dim3(grid), dim3(256), 0, s, (const double *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (double *)out);
-        else { set_error("patch_to_dense: dtype"); return CMAX_EINVAL; }
+    const bool nearest = filter == CMAX_FILTER_NEAREST;
+    if (dtype == CMAX_F32) {
+        if (nearest) launch_patch_to_dense<float, CMAX_FILTER_NEAREST>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, adjoint, out, s);
+        else launch_patch_to_dense<float, CMAX_FILTER_BILINEAR>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, adjoint, out, s);
     } else {
-        const int grid = 2 * ph * pw;
-        if (dtype == CMAX_F32) hipLaunchKernelGGL(k_patch_to_dense_adj<float>, dim3(grid), dim3(256), 0, s, (const float *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (float *)out);
-        else if (dtype == CMAX_F64) hipLaunchKernelGGL(k_patch_to_dense_adj<double>, dim3(grid), dim3(256), 0, s, (const double *)motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, (double *)out);
-        else { set_error("patch_to_dense: dtype"); return CMAX_EINVAL; }
+        if (nearest) launch_patch_to_dense<double, CMAX_FILTER_NEAREST>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, adjoint, out, s);
+        else launch_patch_to_dense<double, CMAX_FILTER_BILINEAR>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, adjoint, out, s);
     }
     CMAX_CHECK_LAUNCH();
     return 0;

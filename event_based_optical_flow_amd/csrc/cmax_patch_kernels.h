@@ -9,6 +9,10 @@ namespace cmax {
 // Patch grid -> dense flow and its adjoint (interpolate_dense_flow_from_patch_tensor,
 // src/solver/patch_contrast_base.py:462-506): negate, replicate-pad by (pad_h, pad_w), bilinear x
 // (sw_h, sw_w) with align_corners=False, centre-crop to [H, W].
+// patch.filter_type "nearest" (lines 494-495, template argument F = CMAX_FILTER_NEAREST): the resize takes, for pixel (r, c) of
+// the up-sampled array, padded cell (r / sw_h, c / sw_w) -- the index rule of nearest-neighbour resizing by an integer factor.
+// The forward is a negated copy (exact in both dtypes); in the adjoint a cell owns ONE clipped rectangle of the output.
+// F = CMAX_FILTER_BILINEAR compiles to the code these kernels had before the argument existed.
 // ---------------------------------------------------------------------------------------------
 template <typename T>
 __device__ __forceinline__ void bilin_tap(int dst, int scale, int n_in, int &i0, int &i1, T &lam) {
@@ -24,7 +28,7 @@ __device__ __forceinline__ void bilin_tap(int dst, int scale, int n_in, int &i0,
 __device__ __forceinline__ int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 // value of the dense flow at flat index p of [2,H,W]
-template <typename T>
+template <typename T, int F = CMAX_FILTER_BILINEAR>
 __device__ __forceinline__ T patch_interp(const T *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
                                           int64_t p) {
     const int c = (int)(p / ((int64_t)H * W));
@@ -32,6 +36,11 @@ __device__ __forceinline__ T patch_interp(const T *__restrict__ motion, int ph, 
     const int i = (int)(q / W), j = (int)(q % W);
     const int gh = ph + 2 * pad_h, gw = pw + 2 * pad_w;
     const int h1 = (gh * sw_h) / 2 - H / 2, w1 = (gw * sw_w) / 2 - W / 2;  // lines 501-505
+    if constexpr (F == CMAX_FILTER_NEAREST) {
+        // padded cell of the pixel, then the replicate padding: the clamp onto the grid
+        const int R = clampi((i + h1) / sw_h, 0, gh - 1), C = clampi((j + w1) / sw_w, 0, gw - 1);
+        return -motion[(int64_t)c * ph * pw + (int64_t)clampi(R - pad_h, 0, ph - 1) * pw + clampi(C - pad_w, 0, pw - 1)];
+    }
     int r0, r1, c0, c1;
     T lr, lc;
     bilin_tap<T>(i + h1, sw_h, gh, r0, r1, lr);
@@ -42,19 +51,22 @@ __device__ __forceinline__ T patch_interp(const T *__restrict__ motion, int ph, 
 }
 
 // TOut / scale: the plan writes the fp32 motion of the fused objective (flow * t_scale) straight from the fp64 patch grid
-template <typename T, typename TOut = T>
+template <typename T, typename TOut = T, int F = CMAX_FILTER_BILINEAR>
 __global__ void __launch_bounds__(256)
 k_patch_to_dense(const T *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
                  TOut *__restrict__ flow, T scale = (T)1) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= 2 * (int64_t)H * W) return;
-    const T v = patch_interp<T>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
+    const T v = patch_interp<T, F>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
     flow[p] = (TOut)(v * scale);
 }
 
 // adjoint, gather form: one workgroup per patch cell sums the contributions of every output pixel
 // whose taps touch the cell (no atomics: the motion gradient has only 2*ph*pw entries).
-template <typename T>
+// Nearest filter: the cell's pixels are the rows [Rlo sw_h, (Rhi + 1) sw_h) x columns [Clo sw_w, (Chi + 1) sw_w) of the up-sampled
+// array (a border cell takes the replicate padding's share along), cropped to the sensor; each thread adds its pixels in index order
+// and block_sum adds the threads in a fixed order, so two runs agree bit for bit.
+template <typename T, int F = CMAX_FILTER_BILINEAR>
 __global__ void __launch_bounds__(256)
 k_patch_to_dense_adj(const T *__restrict__ gflow, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
                      T *__restrict__ gmotion) {
@@ -66,6 +78,18 @@ k_patch_to_dense_adj(const T *__restrict__ gflow, int ph, int pw, int pad_h, int
     // padded rows that map to patch row pr: [Rlo, Rhi]; output rows with a tap on them lie in a band around
     const int Rlo = pr == 0 ? 0 : pr + pad_h, Rhi = pr == ph - 1 ? gh - 1 : pr + pad_h;
     const int Clo = pc == 0 ? 0 : pc + pad_w, Chi = pc == pw - 1 ? gw - 1 : pc + pad_w;
+    if constexpr (F == CMAX_FILTER_NEAREST) {
+        const int i_lo = max(Rlo * sw_h - h1, 0), i_hi = min((Rhi + 1) * sw_h - h1, H);
+        const int j_lo = max(Clo * sw_w - w1, 0), j_hi = min((Chi + 1) * sw_w - w1, W);
+        // a cell off the sensor on either axis: an empty rectangle, never a negative extent (see the bilinear band below)
+        const int bw = max(j_hi - j_lo, 0), bh = max(i_hi - i_lo, 0);
+        double acc[1] = {0.0};
+        for (int t = threadIdx.x; t < bw * bh; t += blockDim.x)
+            acc[0] -= (double)gflow[(int64_t)c * H * W + (int64_t)(i_lo + t / bw) * W + (j_lo + t % bw)];
+        block_sum<1>(acc, smem);
+        if (threadIdx.x == 0) gmotion[cell] = (T)acc[0];
+        return;
+    }
     const int i_lo = max((Rlo - 1) * sw_h - h1 - 1, 0), i_hi = min((Rhi + 2) * sw_h - h1 + 1, H);
     const int j_lo = max((Clo - 1) * sw_w - w1 - 1, 0), j_hi = min((Chi + 2) * sw_w - w1 + 1, W);
     // a cell of a grid that reaches far beyond the sensor has no pixel on one axis or on both: an empty band, not a negative one

@@ -43,12 +43,13 @@ k_convert_split(const double *__restrict__ in, int64_t n, double scale, const do
     if (i < n) split_f64(in[i] * sc, hi[i], lo[i]);
 }
 // ... and of k_patch_to_dense<double, float>: the patch grid -> both planes of flow * scale
+template <int F = CMAX_FILTER_BILINEAR>
 __global__ void __launch_bounds__(256)
 k_patch_to_dense_split(const double *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, float *__restrict__ hi,
                        float *__restrict__ lo, double scale) {
     const int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
     if (p >= 2 * (int64_t)H * W) return;
-    split_f64(patch_interp<double>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p) * scale, hi[p], lo[p]);
+    split_f64(patch_interp<double, F>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p) * scale, hi[p], lo[p]);
 }
 
 // acc (=, +=) w [* *w_dev] * g
@@ -107,13 +108,14 @@ constexpr int kSlScalars = 4;
 static inline int sl_grid(int64_t n) { const int g = div_up(n, 256); return g < kSlBlocks ? g : kSlBlocks; }
 
 // D = P x and, per workgroup, its signed maximum (no atomics: ~700 same-address atomics would cost more than the pass itself)
+template <int F = CMAX_FILTER_BILINEAR>
 __global__ void __launch_bounds__(256)
 k_patch_to_dense_max(const double *__restrict__ motion, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
                      double *__restrict__ D, double *__restrict__ partial) {
     double m = -INFINITY;
     const int64_t n = 2 * (int64_t)H * W;
     for (int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; p < n; p += (int64_t)gridDim.x * blockDim.x) {
-        const double v = D[p] = patch_interp<double>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
+        const double v = D[p] = patch_interp<double, F>(motion, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W, p);
         m = fmax(m, v);
     }
     m = block_max(m);
@@ -440,28 +442,42 @@ int plan_reduce_gx_and_results(cmax_patch_plan_s *p, const double *gx64, const f
     return handle_allreduce_sum_with_scalars(p->handle, const_cast<float *>(gx32), gx32 ? (size_t)p->nx : 0, false, p->results, n_scalars, s);
 }
 
+// D = P x with the plan's filter, and the workgroups' maxima (scale_later)
+void launch_patch_to_dense_max(cmax_patch_plan_s *p, const double *src64, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    if (d.filter_type == CMAX_FILTER_NEAREST)
+        hipLaunchKernelGGL(k_patch_to_dense_max<CMAX_FILTER_NEAREST>, dim3(sl_grid(p->nflow)), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W,
+                           p->dense64, p->sl_partial);
+    else
+        hipLaunchKernelGGL(k_patch_to_dense_max<CMAX_FILTER_BILINEAR>, dim3(sl_grid(p->nflow)), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W,
+                           p->dense64, p->sl_partial);
+}
+
 // x (host) -> fp32 motion of the fused objective: flow [2,H,W] or voxel [T,2,H,W] in pixel per normalised time.
 // Leaves the fp64 flow (scaled) in flow64 and, when time-aware, the fp64 voxel in vox64.
 int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
     const int grid = div_up(p->nflow, 256);
     const bool split = p->exact && dst32 == p->motion32;  // the motion of an exact plan (not its tangent): both planes, in the launches below
+    const bool nearest = d.filter_type == CMAX_FILTER_NEAREST;
     float *lo32 = dst32 + p->nmotion;
     if (!d.time_aware && !scale_dev && split) {
-        hipLaunchKernelGGL(k_patch_to_dense_split, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
+        if (nearest) hipLaunchKernelGGL(k_patch_to_dense_split<CMAX_FILTER_NEAREST>, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
+        else hipLaunchKernelGGL(k_patch_to_dense_split<CMAX_FILTER_BILINEAR>, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
         CMAX_CHECK_LAUNCH();
         return 0;
     }
     if (!d.time_aware && !scale_dev) {  // patch grid -> fp32 flow * scale in one kernel
-        hipLaunchKernelGGL((k_patch_to_dense<double, float>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
-                           d.H, d.W, dst32, scale);
+        if (nearest) hipLaunchKernelGGL((k_patch_to_dense<double, float, CMAX_FILTER_NEAREST>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
+                                        d.H, d.W, dst32, scale);
+        else hipLaunchKernelGGL((k_patch_to_dense<double, float, CMAX_FILTER_BILINEAR>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
+                                d.H, d.W, dst32, scale);
         CMAX_CHECK_LAUNCH();
         return 0;
     }
     if (d.time_aware && d.scale_later && !scale_dev) {
         // D = P x and s = max D; u = t D / s (tie count on the way); V = C(u); fp32 motion s V, s read from device memory
-        hipLaunchKernelGGL(k_patch_to_dense_max, dim3(sl_grid(p->nflow)), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W,
-                           p->dense64, p->sl_partial);
+        launch_patch_to_dense_max(p, src64, s);
         hipLaunchKernelGGL(k_sl_scale, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->dense64, (const double *)nullptr, p->nflow, scale, sl_grid(p->nflow),
                            p->sl, p->flow64, p->sl_partial);
         CMAX_CHECK_LAUNCH();
@@ -475,8 +491,10 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
     if (d.time_aware && !scale_dev) {
         // patch grid -> fp64 displacement field (x t_scale) in one kernel; the voxel is built on the displacement
         // field (patch_contrast_pyramid.py:452, 499-515) and leaves the chain kernel in fp64 and fp32 at once
-        hipLaunchKernelGGL((k_patch_to_dense<double, double>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
-                           d.H, d.W, p->flow64, scale);
+        if (nearest) hipLaunchKernelGGL((k_patch_to_dense<double, double, CMAX_FILTER_NEAREST>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
+                                        d.H, d.W, p->flow64, scale);
+        else hipLaunchKernelGGL((k_patch_to_dense<double, double, CMAX_FILTER_BILINEAR>), dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w,
+                                d.H, d.W, p->flow64, scale);
         CMAX_CHECK_LAUNCH();
         bool wrote32 = false;
         // (an exact plan: the chain kernel writes no low plane -- where it would have written the fp32 copy itself, the conversion is this plan's one launch more)
@@ -491,7 +509,7 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
         }
         return 0;
     }
-    int rc = cmax_patch_to_dense(src64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->flow64, s);
+    int rc = cmax_patch_to_dense_filter(src64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->flow64, s);
     if (rc) return rc;
     if (!d.time_aware) {
         if (split) hipLaunchKernelGGL(k_convert_split, dim3(grid), dim3(256), 0, s, p->flow64, p->nflow, scale, scale_dev, dst32, lo32);
@@ -518,7 +536,7 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
     if (d.n_terms == 1 && !d.time_aware) {
         // one term on the dense flow: the adjoint of the interpolation reads the fp32 flow gradient as it is
         // (fp64 accumulation inside), the term's weight is applied by the tail
-        int rc = cmax_patch_to_dense(p->grad32, CMAX_F32, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 1, p->gx32, s);
+        int rc = cmax_patch_to_dense_filter(p->grad32, CMAX_F32, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx32, s);
         if (rc) return rc;
         *gx32 = p->gx32;
         *weight_scale = d.weight[0];
@@ -545,7 +563,7 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
         if (rc) return rc;
         gflow = p->gacc64 + (int64_t)d.t0 * p->nflow;
     }
-    int rc = cmax_patch_to_dense(gflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 1, p->gx64, s);
+    int rc = cmax_patch_to_dense_filter(gflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
     if (rc) return rc;
     *gx64 = p->gx64;
     return 0;
@@ -604,9 +622,9 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     const double *inv_vmax = p->x64 + 2 * p->nx, *vmax = inv_vmax + 1;
     const int fgrid = div_up(p->nflow, 256), mgrid = div_up(p->nmotion, 256);
     // F = t P x,  dF = t P v / |v|_inf
-    int rc = cmax_patch_to_dense(p->x64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->flow64, s);
+    int rc = cmax_patch_to_dense_filter(p->x64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->flow64, s);
     if (rc) return rc;
-    rc = cmax_patch_to_dense(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->dflow64, s);
+    rc = cmax_patch_to_dense_filter(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->dflow64, s);
     if (rc) return rc;
     hipLaunchKernelGGL((k_convert_scale<double, double>), dim3(fgrid), dim3(256), 0, s, p->flow64, p->nflow, d.t_scale, (const double *)nullptr, p->flow64);
     hipLaunchKernelGGL((k_convert_scale<double, double>), dim3(fgrid), dim3(256), 0, s, p->dflow64, p->nflow, d.t_scale, inv_vmax, p->dflow64);
@@ -635,7 +653,7 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     // the sweep leaves d(dL/dF) in bin t0 of the tangent gradient voxel: the interpolation adjoint reads it there
     rc = voxel_construct_adj_tan_f64(p->vox64, p->dvox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, p->dgacc64, s, handle_is_deterministic(p->handle));
     if (rc) return rc;
-    rc = cmax_patch_to_dense(p->dgacc64 + (int64_t)d.t0 * p->nflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 1, p->gx64, s);
+    rc = cmax_patch_to_dense_filter(p->dgacc64 + (int64_t)d.t0 * p->nflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
     if (!rc) rc = plan_reduce_gx(p, p->gx64, nullptr, s);
     if (rc) return rc;
     FinalParams fp;
@@ -661,10 +679,9 @@ int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
     const double *inv_vmax = p->x64 + 2 * p->nx, *vmax = inv_vmax + 1;
     const int fgrid = div_up(p->nflow, 256), mgrid = div_up(p->nmotion, 256);
     // D = P x, s = max D;  Dd = P v;  u = t D / s (flow64);  ud = (t Dd / |v|_inf - u sd) / s (dflow64)
-    hipLaunchKernelGGL(k_patch_to_dense_max, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->x64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, p->dense64,
-                       p->sl_partial);
+    launch_patch_to_dense_max(p, p->x64, s);
     CMAX_CHECK_LAUNCH();
-    int rc = cmax_patch_to_dense(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 0, p->dflow64, s);
+    int rc = cmax_patch_to_dense_filter(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->dflow64, s);
     if (rc) return rc;
     hipLaunchKernelGGL(k_sl_scale, dim3(sl_grid(p->nflow)), dim3(256), 0, s, p->dense64, (const double *)p->dflow64, p->nflow, d.t_scale, sl_grid(p->nflow),
                        p->sl, p->flow64, p->sl_partial);
@@ -706,7 +723,7 @@ int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
     SlCoef cf = {{1.0, 1.0, 0.0, -1.0, -1.0}, sl_grid(p->nmotion), sl_grid(p->nflow), sl_grid(p->nflow)};
     hipLaunchKernelGGL(k_sl_grad_dense, dim3(fgrid), dim3(256), 0, s, hd, p->dense64, p->nflow, d.t_scale, p->sl, p->sl_partial, cf, p->dgflow64);
     CMAX_CHECK_LAUNCH();
-    rc = cmax_patch_to_dense(p->dgflow64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, 1, p->gx64, s);
+    rc = cmax_patch_to_dense_filter(p->dgflow64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
     if (rc) return rc;
     FinalParams fp;
     fp.n_terms = 0;
@@ -882,6 +899,7 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     CMAX_REQUIRE(d.n_terms >= 1 && d.n_terms <= 4, "patch_plan_create: n_terms");
     CMAX_REQUIRE(d.H > 0 && d.W > 0 && d.ph > 0 && d.pw > 0 && d.sw_h > 0 && d.sw_w > 0 && d.pad_h >= 0 && d.pad_w >= 0, "patch_plan_create: sizes");
     CMAX_REQUIRE(!d.time_aware || (d.T > 0 && d.t0 >= 0 && d.t0 < d.T), "patch_plan_create: time bins");
+    CMAX_REQUIRE(d.filter_type == CMAX_FILTER_BILINEAR || d.filter_type == CMAX_FILTER_NEAREST, "patch_plan_create: filter_type (CMAX_FILTER_BILINEAR or CMAX_FILTER_NEAREST)");
     for (int i = 0; i < d.n_terms; ++i) {
         CMAX_REQUIRE(d.term[i].model == (d.time_aware ? CMAX_MODEL_VOXEL : CMAX_MODEL_DENSE), "patch_plan_create: term model must match time_aware");
         CMAX_REQUIRE(!d.time_aware || d.term[i].T == d.T, "patch_plan_create: term T");

@@ -347,34 +347,41 @@ def voxel_construct_adj_tan(V, dV, gV, dgV, scheme: str = "burgers", t0_location
 
 
 # ------------------------------------------------------------------------------------------------
+FILTER_CODES = {"bilinear": _lib.FILTER_BILINEAR, "nearest": _lib.FILTER_NEAREST}
+
+
 class _PatchToDenseFn(torch.autograd.Function):
     @staticmethod
-    def forward(ctx, motion, image_size, sliding_window, pad):
+    def forward(ctx, motion, image_size, sliding_window, pad, filt):
         _, ph, pw = motion.shape
         H, W = image_size
         flow = torch.empty((2, H, W), dtype=motion.dtype, device=motion.device)
-        check(_lib.load().cmax_patch_to_dense(_ptr(motion), _code(motion), ph, pw, pad[0], pad[1], sliding_window[0],
-                                              sliding_window[1], H, W, 0, _ptr(flow), _stream()))
-        ctx.meta = (ph, pw, H, W, sliding_window, pad)
+        check(_lib.load().cmax_patch_to_dense_filter(_ptr(motion), _code(motion), ph, pw, pad[0], pad[1], sliding_window[0],
+                                                     sliding_window[1], H, W, filt, 0, _ptr(flow), _stream()))
+        ctx.meta = (ph, pw, H, W, sliding_window, pad, filt)
         return flow
 
     @staticmethod
     def backward(ctx, gflow):
-        ph, pw, H, W, sliding_window, pad = ctx.meta
+        ph, pw, H, W, sliding_window, pad, filt = ctx.meta
         gflow = gflow.contiguous()
         gm = torch.empty((2, ph, pw), dtype=gflow.dtype, device=gflow.device)
-        check(_lib.load().cmax_patch_to_dense(_ptr(gflow), _code(gflow), ph, pw, pad[0], pad[1], sliding_window[0],
-                                              sliding_window[1], H, W, 1, _ptr(gm), _stream()))
-        return gm, None, None, None
+        check(_lib.load().cmax_patch_to_dense_filter(_ptr(gflow), _code(gflow), ph, pw, pad[0], pad[1], sliding_window[0],
+                                                     sliding_window[1], H, W, filt, 1, _ptr(gm), _stream()))
+        return gm, None, None, None, None
 
 
-def patch_to_dense(motion, image_size, sliding_window, pad):
-    """interpolate_dense_flow_from_patch_tensor for a [2,ph,pw] patch motion (bilinear filter)
-    (src/solver/patch_contrast_base.py:462-506)."""
+def patch_to_dense(motion, image_size, sliding_window, pad, filter_type="bilinear"):
+    """interpolate_dense_flow_from_patch_tensor for a [2,ph,pw] patch motion (src/solver/patch_contrast_base.py:462-506).
+    filter_type: the reference's `patch.filter_type` (lines 492-495), "bilinear" or "nearest" -- nearest-neighbour resizing by the
+    integer factors: pixel (r, c) of the up-sampled padded grid takes padded cell (r // sw_h, c // sw_w).  The backward is the
+    adjoint under the same filter."""
     _lib.require_gpu()
+    if filter_type not in FILTER_CODES:
+        raise ValueError(f"filter_type {filter_type!r}: 'bilinear' or 'nearest'")
     motion = _cuda(motion, "motion")
     return _PatchToDenseFn.apply(motion, (int(image_size[0]), int(image_size[1])),
-                                 (int(sliding_window[0]), int(sliding_window[1])), (int(pad[0]), int(pad[1])))
+                                 (int(sliding_window[0]), int(sliding_window[1])), (int(pad[0]), int(pad[1])), FILTER_CODES[filter_type])
 
 
 class _FieldMaxFn(torch.autograd.Function):

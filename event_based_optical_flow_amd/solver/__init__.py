@@ -1,11 +1,15 @@
-"""Optimiser-side boundary of the path: `scipy_autograd.minimize` and the GPU objective for
-patch-based flow.  The pyramid driver, Optuna initialisers and metrics of the reference's solver
-classes are outside the hot path."""
+"""Optimiser-side boundary of the path: `scipy_autograd.minimize`, the GPU objective for patch-based flow and the solver
+classes of the reference's registry built on it."""
 from . import scipy_autograd
+from .mixed import MixedPatchContrastMaximization, TimeAwarePatchContrastMaximization
 from .patch_objective import PatchFlowObjective, patch_pad
 from .pyramid import PyramidalPatchContrastMaximization
 
-# registry name of the reference (src/solver/__init__.py:14-19)
-collections = {"pyramidal_patch_contrast_maximization": PyramidalPatchContrastMaximization}
+# registry names of the reference (src/solver/__init__.py:14-19); MixedPatchContrastMaximization is importable but, as there, not registered
+collections = {
+    "pyramidal_patch_contrast_maximization": PyramidalPatchContrastMaximization,
+    "time_aware_mixed_patch_contrast_maximization": TimeAwarePatchContrastMaximization,
+}
 
-__all__ = ["scipy_autograd", "PatchFlowObjective", "patch_pad", "PyramidalPatchContrastMaximization", "collections"]
+__all__ = ["scipy_autograd", "PatchFlowObjective", "patch_pad", "PyramidalPatchContrastMaximization",
+           "MixedPatchContrastMaximization", "TimeAwarePatchContrastMaximization", "collections"]

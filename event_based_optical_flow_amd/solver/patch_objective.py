@@ -62,11 +62,14 @@ class PatchFlowObjective:
         scale_later: the reference's `solver.scale_later` (src/solver/base.py:219-224, patch_contrast_pyramid.py:489-515): the flow is
         divided by its signed maximum before the Burgers / upwind propagation and the voxel multiplied by it afterwards; the maximum is
         differentiated like torch.Tensor.max().  Ignored unless `time_aware`.  Not built for time-sliced batches.
+        filter_type: the reference's `patch.filter_type`, "bilinear" or "nearest" (patch_contrast_base.py:492-495), through the native
+        plan (cmax_patch_objective_t::filter_type) and the autograd-chained path (functional.patch_to_dense) alike.
         exact_flow: the fused terms receive the float64 dense flow / voxel this objective computes from x instead of its fp32 rounding
         (ContrastObjective(exact_flow=True); the native plan's terms carry motion_dtype = CMAX_F64 and the plan hands over the
         fp64 field it holds): the cells of events on a cell border are then the ones the reference's float64 solver takes."""
-        if filter_type != "bilinear":
-            raise NotImplementedError("only the bilinear patch filter (the shipped configs) is built")
+        if filter_type not in F.FILTER_CODES:
+            raise ValueError(f"patch filter_type {filter_type!r}: 'bilinear' or 'nearest' (patch_contrast_base.py:492-495)")
+        self.filter_type = filter_type
         self.handle = handle
         self.t_scale = float(t_scale)
         self.patch_image_size = (int(patch_image_size[0]), int(patch_image_size[1]))
@@ -118,6 +121,7 @@ class PatchFlowObjective:
         d.pad_h, d.pad_w = self.pad
         d.tv_omit_boundary = int(self.contrast.omit_boundary)
         d.scale_later = int(self.scale_later)
+        d.filter_type = F.FILTER_CODES[self.filter_type]
         d.t_scale = self.t_scale
         for i, (w, desc) in enumerate(fused):
             d.weight[i] = float(w)
@@ -204,7 +208,7 @@ class PatchFlowObjective:
     def dense_flow(self, x: torch.Tensor) -> torch.Tensor:
         """[2*ph*pw] patch motion -> [2,H,W] (or [T,2,H,W]) flow in pixel per NORMALISED time."""
         motion = x.reshape((2,) + self.patch_image_size)
-        dense = F.patch_to_dense(motion, self.handle.image_size, self.sliding_window, self.pad)
+        dense = F.patch_to_dense(motion, self.handle.image_size, self.sliding_window, self.pad, self.filter_type)
         if self.scale_later:
             scale = F.field_max(dense)  # one signed scalar over both components (patch_contrast_pyramid.py:489-490)
             voxel = F.construct_dense_flow_voxel(dense * self.t_scale / scale, self.time_bin, self.flow_interpolation, self.t0_flow_location)
@@ -275,12 +279,12 @@ class PatchFlowObjective:
             return (self._smooth_grad(x + h * v) - self._smooth_grad(x - h * v)) / (2.0 * h) + tv_part
         shape = (2,) + self.patch_image_size
         size, sw, pad = self.handle.image_size, self.sliding_window, self.pad
-        dense = F.patch_to_dense(x.detach().reshape(shape), size, sw, pad) * self.t_scale
-        vdense = F.patch_to_dense(v.detach().reshape(shape).to(x.dtype), size, sw, pad) * self.t_scale
+        dense = F.patch_to_dense(x.detach().reshape(shape), size, sw, pad, self.filter_type) * self.t_scale
+        vdense = F.patch_to_dense(v.detach().reshape(shape).to(x.dtype), size, sw, pad, self.filter_type) * self.t_scale
         hflow = self.contrast.hvp(dense, vdense).to(x.dtype)  # [2,H,W]
         # adjoint of the (linear) interpolation: the backward of patch_to_dense applied to hflow
         probe = x.detach().reshape(shape).clone().requires_grad_()
-        out = F.patch_to_dense(probe, size, sw, pad)
+        out = F.patch_to_dense(probe, size, sw, pad, self.filter_type)
         (hx,) = torch.autograd.grad(out, probe, grad_outputs=hflow.contiguous())
         return (hx * self.t_scale).reshape(x.shape) + tv_part
 

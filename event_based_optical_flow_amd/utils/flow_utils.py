@@ -36,8 +36,9 @@ def construct_dense_flow_voxel_torch(dense_flow: torch.Tensor, time_bin: int, sc
                                      t0_location: str = "middle", clamp: Optional[int] = None) -> torch.Tensor:
     """[(b,) 2,H,W] flow at t0 -> [(b,) time_bin, 2, H, W] voxel, differentiable.
 
-    Schemes "burgers" and "upwind" (the two the shipped configs can select); the
-    nearest/griddata propagators need torch_scatter in the reference and are out of scope."""
+    Schemes "burgers" and "upwind" (the two the shipped configs can select).  The reference's other schemes ("bilinear", "max",
+    "same") are not a gap: its construct_dense_flow_voxel_* hands a 4-D array to propagate_flow_to_voxel_*, which unpacks three
+    dimensions -- the call raises ValueError in the reference itself."""
     t = to_device_tensor(dense_flow, "dense_flow")
     if t.dim() == 4:
         v = torch.stack([F.construct_dense_flow_voxel(t[i], time_bin, scheme, t0_location) for i in range(t.shape[0])])

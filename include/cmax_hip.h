@@ -174,6 +174,17 @@ int cmax_voxel_construct_adj_tan(const void *V, const void *dV, int dtype, int T
 int cmax_patch_to_dense(const void *motion, int dtype, int ph, int pw, int pad_h, int pad_w, int sw_h,
                         int sw_w, int H, int W, int adjoint, void *out, cmax_stream_t stream);
 
+/* ... with the resize filter of `patch.filter_type` (src/solver/patch_contrast_base.py:49, 434-437, 492-495).
+ * CMAX_FILTER_BILINEAR: cmax_patch_to_dense itself.  CMAX_FILTER_NEAREST: pixel (r, c) of the up-sampled padded
+ * grid takes padded cell (r / sw_h, c / sw_w) -- nearest-neighbour resizing by an integer factor; the forward is a
+ * negated copy, exact in both dtypes.  The adjoint sums each cell's one clipped rectangle of dL/dflow (a border
+ * cell's includes the pixels of the replicate padding) in a fixed order without atomics: bit-identical from run
+ * to run; a cell with no pixel on the sensor gets 0.  Any other filter: CMAX_EINVAL.                          */
+#define CMAX_FILTER_BILINEAR 0
+#define CMAX_FILTER_NEAREST 1
+int cmax_patch_to_dense_filter(const void *motion, int dtype, int ph, int pw, int pad_h, int pad_w, int sw_h,
+                               int sw_w, int H, int W, int filter, int adjoint, void *out, cmax_stream_t stream);
+
 /* =============================================================================================
  * Fused objective (the hot path): events are packed + sorted once per batch, then every
  * evaluation runs  warp+vote -> contrast -> gather-gradient  without materialising warped events.
@@ -625,6 +636,8 @@ typedef struct {
     int32_t pad_h, pad_w;     /* replicate padding of the grid (patch_contrast_base.py:470-479) */
     int32_t tv_omit_boundary;
     int32_t scale_later;      /* time_aware only (ignored otherwise): propagate t_scale * D / max(D), multiply the voxel by max(D) */
+    int32_t filter_type;      /* CMAX_FILTER_* of the patch grid -> dense flow map (0 = bilinear).  Sits in what was the padding in
+                                 front of t_scale: sizeof and every other offset are unchanged */
     double t_scale;           /* pixel per time unit -> pixel per normalised batch period */
     double weight[4];
     double tv_weight;         /* 0 = no total_variation term; sign of the cost direction included */
