@@ -1,10 +1,11 @@
 """Builds libcmax_hip.so (gfx950) in-tree with hipcc.  No GPU needed (cross-compiles).
 
-Every translation unit is compiled to its own object (in parallel, re-used while neither it nor a header
-changed) and the objects are linked into the shared library.
+Every translation unit is compiled to its own object (in parallel, re-used while none of the files the compiler
+read for it changed: its -MD dependency file says which) and the objects are linked into the shared library.
 """
 import hashlib
 import os
+import shlex
 import subprocess
 import sys
 from concurrent.futures import ThreadPoolExecutor
@@ -13,10 +14,10 @@ PKG_DIR = os.path.dirname(os.path.abspath(__file__))
 CSRC = os.path.join(PKG_DIR, "csrc")
 # CMAX_LIB: alternative output / load path (tuning experiments build variants side by side)
 LIB_PATH = os.environ.get("CMAX_LIB", os.path.join(PKG_DIR, "libcmax_hip.so"))
-OBJ_DIR = os.path.join(PKG_DIR, "_obj")  # objects: git-ignored (*.o) and not shipped to the GPU box (.gpurunignore)
-SOURCES = ["cmax_leaf.hip", "cmax_flow.hip", "cmax_fused.hip", "cmax_solver.hip", "cmax_comm.hip"]
-HEADERS = ["cmax_common.h", "cmax_image_kernels.h", "cmax_patch_kernels.h", "cmax_flow_dual.h", "cmax_search_kernels.h",
-           "cmax_sort_kernels.h", "cmax_radix_sort.h", "cmax_event_kernels.inc", "cmax_comm.h", os.path.join("..", "..", "include", "cmax_hip.h")]
+OBJ_DIR = os.path.join(PKG_DIR, "_obj")  # objects and their dependency files (git-ignored)
+# every *.hip of csrc/ (tests/test_host_logic.py checks it); all are compiled at once, cmax_event_launch.hip is the long pole
+SOURCES = ["cmax_leaf.hip", "cmax_flow.hip", "cmax_event_launch.hip", "cmax_fused.hip", "cmax_solver.hip", "cmax_comm.hip"]
+PUBLIC_HEADER = os.path.join(PKG_DIR, "..", "include", "cmax_hip.h")
 # -munsafe-fp-atomics: fp32/fp64 atomicAdd lower to global_atomic_add_f32/_f64 and ds_add_f32
 # (hardware atomics) instead of compare-and-swap loops.
 # -amdgpu-kernarg-preload-count=16: the first 16 dwords of a kernel's arguments arrive in SGPRs at wave launch (gfx940+) instead
@@ -35,7 +36,8 @@ def hipcc_path() -> str:
 
 
 def _deps():
-    return [os.path.join(CSRC, f) for f in SOURCES + HEADERS] + [os.path.abspath(__file__)]
+    """Every file a translation unit may read: all of csrc/ (sources, headers, .inc), the public header, this script."""
+    return [os.path.join(CSRC, f) for f in sorted(os.listdir(CSRC))] + [PUBLIC_HEADER, os.path.abspath(__file__)]
 
 
 def needs_build() -> bool:
@@ -50,12 +52,22 @@ def _object_path(src: str, flags) -> str:
     return os.path.join(OBJ_DIR, f"{os.path.splitext(src)[0]}.{tag}.o")
 
 
+def _object_inputs(obj: str):
+    """The files the compiler read for `obj`, from the make rule it left in <obj>.d (-MD -MF); None without one."""
+    try:
+        with open(obj + ".d") as f:
+            rule = f.read().replace("\\\n", " ")
+    except OSError:
+        return None
+    return shlex.split(rule.partition(": ")[2])
+
+
 def _compile(src: str, flags, force: bool, verbose: bool) -> str:
     obj = _object_path(src, flags)
-    inputs = [os.path.join(CSRC, src)] + [os.path.join(CSRC, h) for h in HEADERS]
-    if not force and os.path.exists(obj) and all(os.path.getmtime(i) <= os.path.getmtime(obj) for i in inputs if os.path.exists(i)):
+    inputs = _object_inputs(obj)
+    if not force and inputs and os.path.exists(obj) and all(os.path.exists(i) and os.path.getmtime(i) <= os.path.getmtime(obj) for i in inputs):
         return obj
-    cmd = [hipcc_path()] + flags + ["-c", os.path.join(CSRC, src), "-o", obj]
+    cmd = [hipcc_path()] + flags + ["-MD", "-MF", obj + ".d", "-c", os.path.join(CSRC, src), "-o", obj]
     if verbose:
         print(" ".join(cmd), file=sys.stderr)
     subprocess.check_call(cmd)

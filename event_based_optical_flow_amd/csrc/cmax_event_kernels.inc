@@ -1,7 +1,8 @@
 // Event kernels of the fused objective, templates over the segment layout L (EventLayout below: workgroup size, event slots,
 // LDS window).  A segment of up to 2040 events is processed by 256 threads x 8 events (t256), 512 x 4 (t512) or 1024 x 2 (t1024);
 // the mid (m512) and big (b512, b1024) layouts hold longer segments.  Which layout a launch takes is decided on the host, once per
-// kernel family (vote_layout, grad_layout, plain_layout in cmax_fused.hip).  Shared helpers live in cmax_fused.hip.
+// kernel family (vote_layout, grad_layout, plain_layout in cmax_event_launch.hip, which includes this file).  Shared helpers live
+// there and in cmax_fused_device.h.
 
 template <int THREADS, int SLOTS, int WINCAP, int ACC_TILES, int ACC_SMALL_GROUPS>
 struct EventLayout {
@@ -39,8 +40,8 @@ struct EventLayout {
     static constexpr int kTanCap = kWinCap == 8192 ? 2720 : kWinCap / 3 - 8;
     static constexpr float kTanFix = kBig ? 131072.f : 262144.f, kTanInvFix = 1.f / kTanFix;
 };
-// The layouts: distinct types, so that a kernel's name says which one it was compiled for (cmax::k_grad<cmax::t512, ...>).
-enum class Layout { t256, t512, t1024, m512, b512, b1024 };
+// The layouts: distinct types, so that a kernel's name says which one it was compiled for (cmax::k_grad<cmax::t512, ...>); their
+// ids (enum class Layout) are declared in cmax_fused_internal.h.
 struct t256 : EventLayout<256, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t256; };
 struct t512 : EventLayout<512, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t512; };
 struct t1024 : EventLayout<1024, 2048, 8192, 3, 3> { static constexpr Layout kId = Layout::t1024; };

@@ -28,23 +28,17 @@
 //                   reduced in registers + one segmented scan, one atomic per run; voxel: LDS
 //                   accumulators in block-scaled fixed point)
 //   k_finish / k_finish_deferred   sum the per-segment partials (2-DoF), write loss + gradient
-// Every launch covers all reference times of the objective (blockIdx.y).  The event kernels live in
-// cmax_event_kernels.inc, templates over the segment layout (EventLayout: t256 / t512 / t1024 for segments of
-// up to 2040 events, m512 for mid and b512 / b1024 for big segments).  The layout of a launch is chosen in one
-// function per kernel family: vote_layout (K1: 512 threads above 512 segments), grad_layout (K3: the same, 1024
-// for the voxel K3 above 1024 segments) and plain_layout (deterministic K3 and the tangent kernels).
+// Every launch covers all reference times of the objective (blockIdx.y).  The event kernels (K1, K3, the tangent and per-event
+// gathers: cmax_event_kernels.inc) and their launch layer are a translation unit of their own, cmax_event_launch.hip; this unit
+// holds the handle, the per-batch preparation, the image-side kernels and the orchestration of an evaluation, and reaches the
+// event kernels through the launchers declared in cmax_fused_internal.h (launch_vote, launch_grad, ...) alone.
 //
 // fp32 per event with the integer source pixel split from the fp32 displacement (keeps the
 // bilinear fractions accurate to ulp(displacement) instead of ulp(coordinate)); fp64 reductions.
 #include <algorithm>
 #include <atomic>
-#include <cstdlib>
-#include <cstring>
-#include <type_traits>
-#include <vector>
 
-#include "cmax_comm.h"
-#include "cmax_common.h"
+#include "cmax_fused_device.h"
 #include "cmax_image_kernels.h"
 #include "cmax_search_kernels.h"
 #include "cmax_sort_kernels.h"
@@ -64,338 +58,6 @@
 //   CMAX_DEBUG_COMPACT=1 cmax_set_events synchronises behind k_pack_compact and fails if an event did not fit its region's coordinates
 //   CMAX_SORT=radix | bucket   per-batch order by the stable radix sort (cmax_radix_sort.h) / the two-level counting sort, whatever the size
 namespace cmax {
-
-constexpr int kSparseSegment = 512;  // voxel K3: segments below this many events add straight to memory (no LDS accumulators)
-constexpr int kTile = 16;  // source-pixel tile edge of the counting sort
-constexpr int kSegMax = 2040;                 // events per segment (+1 for the even-aligned start still fits 2048);
-                                              // |sum of votes| <= 2040 * 2^20 < 2^31
-constexpr int kAccCells = 3072;               // flow-gradient accumulator cells per channel in LDS (voxel K3): 12 (tile, bin) groups
-constexpr int kAccCellsDense = 768;           // the same for the dense K3 with owned tiles: 3 source tiles
-constexpr int kWinMaxW = 128;                 // widest window when the bounding box has to be clipped
-constexpr int64_t kRadixMinEvents = 8000000;  // batches from here on are ordered by the stable radix sort (cmax_radix_sort.h): 8M events 550 vs 556 us,
-                                              // 12M 765 vs 875, 20M 1177 vs 1419, 64M 3483 vs 4754 (profiles/r05_set_events.txt); below, the counting sort's fewer launches win
-constexpr int kShiftWordsMax = 512;           // words of cell offsets per (reference time, segment): 4 bits per slot of a big segment
-// (votes are accumulated as signed fixed point in the LDS windows: 12.20, big segments 13.19 -- kFixNS of cmax_event_kernels.inc)
-
-struct EvView {
-    const uint2 *ev;      // .x = row | col << 12 | bin << 24 ; .y = bits of fp32 tau = (t - tmin) / (tmax - tmin)
-    const float *rx;      // fractional residual of the source coordinate (nullptr if integral)
-    const float *ry;
-    const float2 *rl;     // ... its low part (rxl, ryl): residual = (double)rx + (double)rxl -- read only by warp_exact (events on a cell border)
-    const double *tau64;  // BINNED handles (the packed word's top byte holds the voxel bin): normalised time in fp64, same order as `ev` --
-                          // read only for the few events whose cell is decided in fp64 (warp_exact); null on un-binned handles, whose
-                          // packed word carries the time's residual beyond fp32 (tau_refined)
-};
-
-struct WarpParams {
-    int H, W, Hp, Wp, ph, pw;  // un-padded sensor, padded image, padding
-    int T;                     // voxel bins
-    int ntc;                   // source tiles per tile row
-    float d;                   // reference time as a fraction of the batch period
-    float d_lo;                // ... what fp32 could not hold of it (d64 = (double)d + (double)d_lo): read only by warp_exact
-    int normalize;             // normalize_t
-    int motion_f64;            // cmax_objective_t::motion_dtype == CMAX_F64.  2-DoF: `motion` points to double[2].  Dense / voxel: `motion` is the high
-                               // plane of the caller's doubles and the low plane lies behind it (k_split_motion); read by the HOST only, which
-                               // launches the deciding kernels' ExactFlow instantiations (phase_warp's F64FLOW)
-    const double *tmm;         // device (tmin, tmax)
-    const float *motion;       // theta[2] | flow[2,H,W] | voxel[T,2,H,W]
-};
-
-// Trailing kernel argument of K1, k_vote_tan and k_grad_hvp for a dense / voxel motion that crossed the boundary in fp64: selects the
-// instantiation whose border branch reads the low plane (nothing is read from the value)
-struct ExactFlow {
-    int on;
-};
-
-// One launch of an event kernel covers every reference time of the objective (blockIdx.y): a multi-focal cost
-// warps the same events to 3 reference times, and on the solver's small batches three dependent launches per
-// kernel class were three times the launch latency.
-struct RefArgs {
-    float d[4];       // reference time as a fraction of the batch period
-    float d_lo[4];    // ... its fp32 remainder (K1's fp64 cell decisions: a reference time need not be a dyadic fraction -- "random" / float directions)
-    float *img[4];    // K1: vote image to fill; K3: image to gather from (dL/dIWE or the IWE itself)
-    double *stat[4];  // K1: statistics accumulators to reset (or null)
-    double *raw_zero; // K1: [n_ref][kRawStride] gradient-sum lines of the 2-DoF K3 of the same evaluation to reset (or null)
-    float *zero[4];   // K3, deferred statistics: vote image of the NEXT evaluation to clear (or null)
-    int k0;           // index of the first reference time of this launch (statistics slot, partial-sum offset)
-    int4 *win;        // [n_ref][nseg] LDS windows: written by K1, read by K3 of the same evaluation (or null)
-    unsigned *shifts; // [n_ref][nseg][kSlots / 8] cell offsets of the events K1 decided in fp64 (phase_warp), 8 slots per word; valid where Window::bmask says so
-    int windows_only; // K1: publish the windows (and offsets) and return -- for a K3 whose vote this was not (cmax_objective_finish)
-    // cmax_objective_batch: blockIdx.z = candidate motion.  Element strides between consecutive candidates (0 for every other launch):
-    int64_t z_img;    // floats between their vote images (img[k] / zero[k] are candidate 0's)
-    int64_t z_raw;    // doubles between their raw-sum lines (stat[k] of K1, gpart of K3)
-    int z_motion;     // floats between their motions
-    // K1, blurred variance with a gradient: sum_p I[p] B[p] (B = blur^T 1_Omega = b(r) b(c)) = the sum of the blurred image over
-    // Omega, accumulated while the votes are flushed -- the image kernel then knows the mean before it has blurred anything
-    double *musum[4];        // kMuLines accumulators (one 128-byte line each) per reference time, or null
-    // K3, kFoldStatsInside: musum[k] is READ (the mean), and
-    int stat_blocks;         // leading workgroups of the grid that run the statistics (a multiple of 8: the XCD map of the others holds)
-    int *ticket;             // their arrival counters (kTicketLines lines, zero between launches): the last one writes the loss
-    double *musum_next;      // the other buffer of the vote sums: cleared for the next evaluation
-    float band_b0, band_b1;  // b(0) = b(n - 1) and b(1) = b(n - 2) of border_weight (b = 1 elsewhere)
-    // deterministic mode (cmax_set_deterministic): order-free integer accumulation
-    long long *img64[4];       // K1: 2^-20 fixed-point vote image, 64-bit integer atomics instead of fp32 ones (or null)
-    const unsigned *imax;      // K3: bits of max |image k| per statistics slot (the bound the fixed-point scale is derived from)
-    long long *g64;            // K3: 2-DoF per-segment partial sums [n_ref][nseg][2] / flow-gradient accumulators, fixed point
-    double *det_inv_scale;     // K3: [4] 1 / scale used by reference time k (2-DoF) or by all of them ([0], flow gradient)
-    long long n_events;        // K3: events behind one accumulator at most (fixed-point headroom)
-    // K1: the flow-gradient buffer the K3 of this evaluation ADDS into (work lists that are not group-aligned), cleared slice by slice
-    // behind the event loads -- so that the statistics can run inside the K3 launch there too (kFoldStatsInside) instead of in a
-    // launch of their own whose second job this was
-    float4 *grad_zero;
-    int64_t n_grad_zero4;
-    // weighted handles (cmax_set_event_weights; the WEIGHTED instantiations of K1 / K3 only): per-event weights in packed order and
-    // (1 / wmax, wmax) in device memory -- K1 votes round(w / wmax * K) and folds wmax back in when it flushes, K3 multiplies dt by w
-    const float *wgt;
-    const float *wnorm;
-};
-
-// the image-space kernels of an evaluation cover all reference times in one launch as well (blockIdx.y)
-struct ImgArgs {
-    const float *in[4];  // raw votes or blurred image, per reference time
-    float *blurred[4];   // blurred image to write (kernels that blur)
-    float *zero[4];      // vote image of the next evaluation to clear (or null)
-    float *G[4];         // dL/dIWE to write
-    float chain[4];      // fused statistics + G kernels: chain factor to fold into G (a constant of a cost that is not normalised;
-                         // 1 when it depends on the finished statistics and K3 applies it: kFoldScale)
-};
-
-}  // namespace cmax
-
-// Phase timeline of the event kernels (builds with -DCMAX_TIMELINE only, tools/timeline.py): thread 0 of the first 4096 workgroups of
-// reference time 0 stamps the 100 MHz wall clock at the phase boundaries of K1 (kernel 0) and K3 (kernel 1) into
-// g_timeline[kernel][workgroup][8] (round 6: kernel 2 = the fused image kernel between them); a stamp that is to follow the arrival of
-// loaded data is handed a value computed from it.
-#ifdef CMAX_TIMELINE
-namespace cmax {
-__device__ unsigned long long *g_timeline = nullptr;
-__device__ __forceinline__ void timeline_stamp(int kernel, int idx) {
-    if (g_timeline && threadIdx.x == 0 && blockIdx.y == 0 && blockIdx.x < 4096u) g_timeline[((size_t)kernel * 4096 + blockIdx.x) * 8 + idx] = wall_clock64();
-}
-template <typename T>
-__device__ __forceinline__ void timeline_stamp_after(int kernel, int idx, T dep) {
-    asm volatile("" ::"v"(dep));
-    timeline_stamp(kernel, idx);
-}
-}  // namespace cmax
-#define CMAX_STAMP(K, I) cmax::timeline_stamp(K, I)
-#define CMAX_STAMP_AFTER(K, I, DEP) cmax::timeline_stamp_after(K, I, DEP)
-#else
-#define CMAX_STAMP(K, I) do { } while (0)
-#define CMAX_STAMP_AFTER(K, I, DEP) do { } while (0)
-#endif
-
-struct cmax_handle_s {
-    int H = 0, W = 0, ph = 0, pw = 0, Hp = 0, Wp = 0;
-    int device = 0;
-    int64_t n = 0, cap = 0;
-    int64_t n_dropped = 0;  // events of the last batch whose source pixel was off the sensor (or NaN): not packed
-    bool keep_outside = true;  // cmax_set_keep_outside (default since round 5): finite events off the sensor are packed (nearest sensor pixel + residual)
-    int64_t n_outside = 0;      // ... how many of the last batch (2-DoF objectives only: a flow has no value there)
-    bool has_frac = false;
-    int n_time_bin = 0;
-    bool slab_major = false;  // the (tile, bin) groups are ordered (tile row, time slab, tile column): cmax_set_time_slabs (large motions)
-    // packed, sorted events
-    uint2 *evp = nullptr;  // packed events, 8 B each, 16-byte aligned base (+2 elements of padding)
-    float *rx = nullptr, *ry = nullptr;
-    float2 *rl = nullptr;  // low parts of (rx, ry): written and read only for batches with fractional sources
-    double *tau64 = nullptr;
-    int *src = nullptr, *src_alt = nullptr;  // index of every packed event in the caller's array, carried through every re-ordering
-    // per-event weights (cmax_set_event_weights): the caller's values in the caller's order, the same gathered into packed order (slot l of a
-    // segment reads w_packed[first + l]; padded with zeros so that the event kernels load unconditionally), and the normalisation
-    float *w_user = nullptr, *w_packed = nullptr;
-    int64_t w_user_cap = 0, w_packed_cap = 0;
-    float *d_wnorm = nullptr;  // [0] = 1 / wmax (0 when wmax == 0), [1] = wmax = max |w|, [2] = bits of wmax (reduction), [3] = non-finite flag
-    bool weighted = false;
-    double wmax_host = 0.0;
-    int64_t n_in = 0;          // events handed to the last cmax_set_events
-    // cmax_objective_weight_grad: finished dL/dIWE images ([5][npix]: reference times 0..3, slot 4 = the un-warped image) and their
-    // blur-transpose input, the per-event interpolations in packed order (one plane of gw_plane floats per image), all allocated on first use;
-    // general_only: the evaluation inside that call takes the general K1 -> statistics / image kernel -> K3 path on any handle
-    float *gw_G = nullptr, *gw_Gt = nullptr, *gw_packed = nullptr;
-    int64_t gw_plane = 0;
-    bool general_only = false;
-    // cmax_objective_event_grad: (gx, gy, c) per packed event, three planes of ge_plane floats per reference time + two for the un-warped image,
-    // and the scatter's per-workgroup partial sums of c ([4][ge_part_cap]); allocated on first use, grown on demand
-    float *ge_packed = nullptr;
-    int64_t ge_plane = 0;
-    double *ge_part = nullptr;
-    int64_t ge_part_cap = 0;
-    // staging SoA of the two-level sort (tile buckets before the per-tile ordering)
-    uint2 *evp_alt = nullptr;
-    float *rx_alt = nullptr, *ry_alt = nullptr;
-    float2 *rl_alt = nullptr;
-    double *tau64_alt = nullptr;
-    int64_t cap_alt = 0;
-    // sort scratch
-    int *counts = nullptr;  // [nkeys + 1] events per tile -> tile offsets after the scan
-    int *cursor = nullptr;  // [nkeys] per-tile cursor of the bucket pass, then active source pixels per tile
-    int *scan_tmp = nullptr;  // [ceil(nkeys / 2048)] chunk sums of the scan
-    int *rs_hist = nullptr;   // radix sort (large batches): [digits][workgroups] + 1 histogram / offsets of one pass
-    int *rs_tmp = nullptr;    // ... chunk sums of its scan
-    int64_t rs_hist_cap = 0;
-    int nkeys = 0, ntr = 0, ntc = 0;
-    int *d_flags = nullptr;  // [0] any fractional source coordinate, [1] dropped events, [2] events kept from off the sensor (cmax_set_keep_outside)
-    bool long_runs = false;  // >= 8 events per active source pixel on average: the dense K3 reduces runs serially per thread
-    bool mid = false;        // MID segments: up to 3064 events, four source tiles (five (tile, bin) groups) wide, event kernels of the m512 namespace -- when the
-                             // standard cut would need more workgroups than the chip holds at once and this one does not (build_segments)
-    bool big = false;        // BIG segments: up to 4088 events each, event kernels of the b512 / b1024 namespaces (batches of >= 8M events)
-    int seg_max = 2040;      // events per segment of the current work list (kSegMax, or 4088 for big segments)
-    bool small_acc = false;  // binned handle, owned groups of <= 3 groups per segment: the voxel K3 with kAccCellsDense accumulator cells (kGradOwnedSmall)
-    bool owned = false;      // the work list gives every group (empty ones included) to exactly one segment, <= kAccCells / 256 groups each
-    int *d_tile_start = nullptr;  // [ngroups + 1] first sorted event of every group (source tile, or (tile, time bin))
-    // What the host reads back once per batch lives in ONE allocation, in this order: d_tmm (2 doubles) | d_flags (4 ints) |
-    // d_active (ntiles ints) | d_tile_start (...): one device-to-host copy instead of four (each ~4 us of copy latency)
-    int *d_batch = nullptr;   // base of that allocation (as ints)
-    int *d_active = nullptr;  // [ntiles] source pixels that hold events, per tile (un-binned order; written by k_tile_sort)
-    int4 *d_segs = nullptr;       // [nseg] (begin, count, first source tile, tiles spanned): work items of the event kernels
-    int4 *d_win = nullptr;        // [4][nseg] LDS windows of the last objective vote (K1 -> K3 of the same evaluation)
-    // compact copy of the sorted events, one region per segment of the work list (EventLoads in cmax_event_kernels.inc): big segments of
-    // un-binned handles; valid for the current work list only (build_segments)
-    char *cev = nullptr;
-    int64_t cev_cap = 0;          // regions allocated
-    bool compact = false;
-    // cmax_objective_batch: K candidate motions per launch (allocated on first use, sized for batch_cap candidates)
-    float *bimg = nullptr;        // [2 buffers][batch_cap][n_ref <= 4][npix] vote images
-    double *braw = nullptr;       // [batch_cap][4][kRawStride] raw sums
-    int4 *bwin = nullptr;         // [batch_cap][4][nseg] windows
-    unsigned *bshifts = nullptr;  // [batch_cap][4][nseg][kShiftWordsMax]
-    int batch_cap = 0, batch_seg_cap = 0, batch_cur = 0;
-    int batch_zero[2] = {0, 0};  // the first batch_zero[b] images of buffer b are zero
-    unsigned *d_shifts = nullptr; // [4][nseg][kShiftWordsMax] cell offsets of the events that vote decided in fp64 (RefArgs::shifts)
-    // what those windows were computed for: K3 reuses them only for the same motion / model / reference times
-    const float *win_motion = nullptr;
-    int win_model = -2, win_nref = 0, win_T = 0, win_normalize = 0;
-    float win_d[4] = {0.f, 0.f, 0.f, 0.f};
-    uint64_t win_generation = ~(uint64_t)0;
-    int nseg = 0, seg_cap = 0;
-    // images
-    float *imgs = nullptr;                                  // [2 buffers][5, Hp, Wp] raw votes: one per reference time + un-warped
-    float *iweb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // blurred copies
-    float *G = nullptr, *Gt = nullptr;
-    const float *last_iwe[4] = {nullptr, nullptr, nullptr, nullptr};
-    // device scalars
-    double *d_tmm = nullptr;  // [2]
-    double *d_stat = nullptr;   // [5 slots][32 sub-accumulators][2] contrast statistics (slot 4 = un-warped image)
-    // the handle's own vote images are double-buffered: k_stats of evaluation e zeroes the images of
-    // evaluation e+1, so the steady state needs no memset node.  zero_mask[b] bit k: image k of buffer b is zero
-    int cur_buf = 0;
-    unsigned zero_mask[2] = {0u, 0u};
-    double *d_gpart = nullptr;  // [4 reference times][nseg][2] per-segment 2-DoF partials
-    double *d_raw = nullptr;    // [4 reference times][kRawStride] raw sums of the deferred 2-DoF K3 (cmax_objective's own copy)
-    // cmax_objective_host: device outputs + pinned staging of one evaluation whose results go straight to the host
-    double *d_host_result = nullptr;  // [8]
-    void *d_host_grad = nullptr;
-    int64_t host_grad_bytes = 0;
-    double *hp_out = nullptr;  // pinned
-    int64_t hp_out_cap = 0;
-    unsigned long long host_seq = 0;  // run counter of the finishing kernel that writes into hp_out (polled by cmax_objective_host)
-    int *d_ticket = nullptr;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches
-    double *d_musum = nullptr;  // [2 buffers][4 reference times][kMuStride] K1's sums for the blurred variance (RefArgs::musum)
-    int mu_buf = 0;             // buffer the next evaluation adds into (the other one is being cleared / is clear); flipped by the launch that reads the sums
-    // orig-IWE cache key
-    bool orig_valid = false;
-    double orig_sigma = -1;
-    int orig_cost = -1, orig_omit = -1;
-    double tmin_host = 0.0, tmax_host = 0.0;  // batch extremes (copied once per batch)
-    float *hvp_img = nullptr;                 // [6 kinds][4 reference times][Hp, Wp] scratch of cmax_objective_hvp (allocated on first use)
-    float *iw_zero = nullptr;                 // cmax_iwes_vjp: a zero tangent of the motion's size (the gather of J^T G is T3 with u = 0, G' = G)
-    int64_t iw_zero_cap = 0;
-    double *d_stat_tan = nullptr;             // [4][kStatStride] tangent statistics
-    // pinned host staging of the per-batch read-back (group starts, active pixels per tile, flags, time extremes) and
-    // of the work list: copies to / from pageable memory are staged by the runtime and cost a synchronisation each
-    int *hp_read = nullptr;
-    int64_t hp_read_cap = 0;
-    int4 *hp_segs = nullptr;
-    int64_t hp_segs_cap = 0;
-    hipEvent_t segs_copied = nullptr;  // the last upload of hp_segs has left the host buffer
-    hipEvent_t read_done = nullptr;    // the per-batch read-back has arrived (the stream may still be busy behind it)
-    float2 *search_range = nullptr;           // [search_cap] (tau_min, tau_max) per patch of cmax_patch_search
-    int search_cap = 0;
-    int64_t bytes = 0;
-    uint64_t generation = 0;  // bumped by set_events / set_time_bins (device pointers and the work list change)
-    uint64_t generation_counted = ~(uint64_t)0;
-    // optional per-kernel-class timing with HIP events (cmax_set_profiling)
-    bool profiling = false;
-    int prof_repeat = 1;  // > 1: every hot launch is issued this many times inside its event bracket (timing only)
-    std::vector<hipEvent_t> prof_ev[CMAX_PROF_CLASSES];  // class -> [start0, stop0, start1, stop1, ...]
-    // 2-DoF tangent images (k_vote_tan2): [2 buffers][4 reference times][I: Hp Wp | E0: (Hp + 1) Wp | F1: Hp (Wp + 1)]
-    float *tan = nullptr;
-    int tan_cur = 0;
-    unsigned tan_zero_mask[2] = {0u, 0u};  // bit k: planes of reference time k of buffer b are zero
-    double *d_tanpart = nullptr;           // [4][kTanBlocks][6] partial sums of k_tan_stats_var
-    // time-sliced multi-GPU evaluation: this rank's RCCL communicator (cmax_comm_init), or null
-    cmax::Comm *comm = nullptr;
-    // C2 in row bands behind K3 (cmax_comm_set_c2_bands): the owned-group K3 of a dense objective is launched band by band (whole
-    // tile rows) and every band's rows of the gradient are all-reduced on a second stream while the next band's K3 runs
-    int c2_bands = 1;
-    std::vector<int> row_seg_start;  // [ntr + 1] first segment of every source tile row (owned work lists only)
-    hipStream_t comm_stream = nullptr;
-    std::vector<hipEvent_t> band_ev;  // [bands + 1]
-    // deterministic mode (cmax_set_deterministic): every accumulation that depends on the order of events, workgroups or
-    // atomics is done in integers (exact, associative) -- bit-identical IWE, loss and gradient from run to run
-    bool deterministic = false;
-    long long *img64 = nullptr;   // [5][npix] fixed-point vote images, all zero between evaluations
-    unsigned *d_imax = nullptr;   // [kStatSlots] bits of max |image| per statistics slot
-    long long *g64 = nullptr;     // fixed-point gradient accumulators (zero between evaluations)
-    int64_t g64_cap = 0;
-    double *d_det_inv_scale = nullptr;  // [4]
-    float *Gt_det = nullptr;      // [4][npix] dL/d(blurred image) of the unfused image path
-    // an fp64 flow / voxel at the boundary (cmax_objective_t::motion_dtype == CMAX_F64, dense / voxel): hi plane | lo plane of the
-    // caller's doubles (k_split_motion), allocated on first use
-    float *m64 = nullptr;
-    int64_t m64_cap = 0;            // floats
-    const void *m64_src = nullptr;  // whose split the planes hold (cmax_objective_finish: the windows of a vote are another motion's otherwise)
-};
-
-namespace cmax {
-
-// kernel classes for cmax_set_profiling / cmax_read_profile
-enum { kProfVote = 0, kProfStats = 1, kProfGimage = 2, kProfGrad = 3, kProfFinish = 4, kProfComm = 5 };
-static_assert(kProfComm + 1 == CMAX_PROF_CLASSES, "profile classes");
-constexpr size_t kProfMaxPairs = 16384;
-
-// RAII: records a HIP event on the launch stream before and after the enclosed launch
-struct ProfScope {
-    cmax_handle_s *h;
-    int cls;
-    hipStream_t s;
-    hipEvent_t stop = nullptr;
-    ProfScope(cmax_handle_s *h_, int cls_, hipStream_t s_) : h(h_), cls(cls_), s(s_) {
-        if (!h->profiling || h->prof_ev[cls].size() >= 2 * kProfMaxPairs) return;
-        hipEvent_t start = nullptr;
-        if (hipEventCreate(&start) != hipSuccess || hipEventCreate(&stop) != hipSuccess) {
-            stop = nullptr;
-            return;
-        }
-        (void)hipEventRecord(start, s);
-        h->prof_ev[cls].push_back(start);
-        h->prof_ev[cls].push_back(stop);
-    }
-    ~ProfScope() {
-        if (stop) (void)hipEventRecord(stop, s);
-    }
-};
-
-// ---------------------------------------------------------------------------------------------
-// memory helpers
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-static int dev_alloc(cmax_handle_s *h, T **p, int64_t count) {
-    if (count <= 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(T));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(count * sizeof(T)), hipGetErrorString(e));
-        return CMAX_ENOMEM;
-    }
-    h->bytes += count * (int64_t)sizeof(T);
-    return 0;
-}
-template <typename T>
-static void dev_free(T **p) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-}
 
 // ---------------------------------------------------------------------------------------------
 // set_events: pack + two-level sort (cmax_sort_kernels.h); the scan of the tile counts lives here
@@ -517,137 +179,6 @@ __global__ void __launch_bounds__(1024) k_scan_small(int *__restrict__ counts, i
     if (t == 1023) counts[m] = run;
 }
 
-// ---------------------------------------------------------------------------------------------
-// per-event warp shared by K1 and K3
-// ---------------------------------------------------------------------------------------------
-// v_cvt_flr_i32_f32: (int)floor(x) in one instruction, saturating
-__device__ __forceinline__ int cvt_flr(float x) {
-    int r;
-    asm("v_cvt_flr_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-
-struct Warped {
-    int row, col;  // top-left corner in the padded image
-    float a, b;    // row / column fractions
-    float dt;
-    int src;       // source pixel linear index (un-padded), + bin * 2HW for voxel
-    float f0, f1;  // dense / voxel: the flow at the source pixel (phase_warp bounds the rounding of dt * f with it)
-};
-
-// One event as the warp sees it, whichever way it was stored (plain 8-byte event: absolute coordinates, zero bases; compact event of a
-// big segment: coordinates relative to the segment's tile strip, bases from the region's header -- cmax_event_kernels.inc).
-struct EvDec {
-    unsigned ixr, iyr;  // source row / column minus EvBase::row / col
-    unsigned top;       // top byte of the plain packed word (voxel: the time bin)
-    unsigned key;       // (row | col << 12 [| bin << 24]) absolute: the run key of the flow-gradient reduction (K3)
-    float tmd;          // tau - d: calculate_dt before the time scale, rounded once
-};
-struct EvBase {  // workgroup-uniform
-    unsigned row, col;  // what ixr / iyr are relative to (0 for plain events)
-    unsigned src;       // row * W + col
-};
-
-// MODEL: -1 none (orig_iwe), 0 2-DoF, 1 dense, 2 voxel
-template <int MODEL, bool FRAC>
-__device__ __forceinline__ Warped warp_one(const EvView &ev, const EvDec &e, const EvBase &eb, int64_t i, bool valid, const WarpParams &wp, float tscale, float th0,
-                                           float th1) {
-    Warped w;
-    const int ix = (int)e.ixr, iy = (int)e.iyr;
-    w.dt = e.tmd * tscale;  // calculate_dt, src/warp.py:254-259
-    float dx = 0.f, dy = 0.f;
-    if (FRAC && valid) {  // `valid` false: an empty slot of the caller (zero event), i may be outside the arrays
-        dx = ev.rx[i];
-        dy = ev.ry[i];
-    }
-    w.src = (int)(__umul24((unsigned)ix, (unsigned)wp.W & 0xFFFFFFu) + (unsigned)iy + eb.src);  // 12-bit x 13-bit: v_mul_u32_u24 (full rate; v_mul_lo_u32 runs at a quarter)
-    if (MODEL == CMAX_MODEL_2DOF) {
-        dx = fmaf(w.dt, th0, dx);  // x' = x + dt*theta0, src/warp.py:506-515
-        dy = fmaf(w.dt, th1, dy);
-    } else if (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
-        const int hw = wp.H * wp.W;
-        if (MODEL == CMAX_MODEL_VOXEL) w.src += (int)e.top * 2 * hw;  // (2 HW can exceed 24 bits: a full 32-bit multiply)
-        // uniform base + unsigned 32-bit BYTE offset: one address instruction per event and a `global_load_dword v, voff, s[base]`
-        // per channel, instead of 64-bit per-lane pointer arithmetic (the field is < 4 GiB: checked by the host)
-        const unsigned off = (unsigned)w.src * 4u;
-        const char *m0 = reinterpret_cast<const char *>(wp.motion), *m1 = reinterpret_cast<const char *>(wp.motion + hw);
-        w.f0 = *reinterpret_cast<const float *>(m0 + off);
-        w.f1 = *reinterpret_cast<const float *>(m1 + off);
-        dx = fmaf(-w.dt, w.f0, dx);  // x' = x - dt*F[0,ix,iy], src/warp.py:305-306
-        dy = fmaf(-w.dt, w.f1, dy);
-    }
-    // floor(x' + 1e-6) = ix + floor(dx + 1e-6) exactly because ix is an integer
-    // (bilinear_vote_tensor, src/event_image_converter.py:340-345)
-    // Round 6 (VALU diet): v_floor_f32 + v_cvt_i32_f32 per coordinate; the v_med3_f32 between them (a clamp to +-8192) is gone:
-    // a displacement beyond +-8192 px (a diverged or non-finite motion) now lands on whatever cell the saturated conversion names --
-    // (v_cvt_i32_f32 saturates) -- its packed (row, col) word may wrap, but every consumer derives box, window and indices from the SAME word, so such an event
-    // is either outside every window of the fast path's 8192 words (-> the clipped path, whose every corner is tested against window
-    // and image) or votes in bounds; it was never defined where.
-    const float fx = floorf(dx + 1e-6f), fy = floorf(dy + 1e-6f);
-    const int fxi = (int)fx, fyi = (int)fy;  // (v_cvt_i32_f32 saturates; through inline asm v_cvt_flr_i32_f32 + v_cvt_f32_i32 are two instructions as well, but
-    w.a = dx - fx;                           // the asm operands cost the 512 x 8 K3 eleven VGPRs, i.e. a wave per SIMD)
-    w.b = dy - fy;
-    w.row = ix + fxi + (int)(eb.row + (unsigned)wp.ph);
-    w.col = iy + fyi + (int)(eb.col + (unsigned)wp.pw);
-    return w;
-}
-
-// EXACT CELLS (round 3: 2-DoF; round 4: every model).  The image is continuous across a cell border, the gradient is not (it takes
-// its differences of dL/dIWE from the event's own cell): an event whose displacement lies within fp32 rounding of a border falls
-// on the other side in any fp32 evaluation, and its term of the gradient then comes from the wrong side of the kink -- ~70 of a
-// million events moved the 2-DoF gradient (ONE sum over all events) by 6e-4 relative against the reference's fp64 value (the
-// reference's own fp32 path: 1.3e-3, tests/golden/cfg2_fp32_reference.npz), and a flow gradient by more than 1e-4 in the pixels
-// such events come from (2-5 of 0.6-1.8M entries at the BASELINE sizes).  The fp32 displacement of warp_one is off by at most
-// 7 * 2^-24 |motion| max(period, 1) max(1, |d|, |1 - d|) (rounding of tau, of tau - d, of the time scale, of the product, of the
-// + 1e-6); an event whose fraction a or b comes closer than exact_margin to 0 or 1 is warped again here BY K1, with the arithmetic of
-// src/warp.py:304-307 / 506-515 + src/event_image_converter.py:340 in fp64: the fp64 normalised time (EvView::tau64, a load only
-// these events make), the caller's fp64 theta (2-DoF), the flow as the device holds it (fp32 values, fp64 arithmetic) -- 1e-5 ..
-// 1e-4 of the events -- and K1 publishes the cell's offset from the fp32 one for K3 (phase_warp).
-template <int MODEL, bool FRAC>
-__device__ __forceinline__ Warped warp_exact(const EvView &ev, unsigned ex, int64_t i, double tau, double period, const WarpParams &wp, double m0, double m1) {
-    Warped w;
-    const int ix = (int)(ex & 0xFFFu), iy = (int)((ex >> 12) & 0xFFFu);
-    const double dtd = (tau - ((double)wp.d + (double)wp.d_lo)) * period;
-    const double sgn = MODEL == CMAX_MODEL_2DOF ? 1.0 : -1.0;  // x' = x + dt theta (warp.py:514)  |  x' = x - dt F (warp.py:305)
-    double srx = 0.0, sry = 0.0;  // the source coordinate's residual as the reference's fp64 arithmetic sees it
-    if (FRAC) {
-        const float2 lo = ev.rl[i];
-        srx = (double)ev.rx[i] + (double)lo.x;
-        sry = (double)ev.ry[i] + (double)lo.y;
-    }
-    const double ddx = fma(sgn * dtd, m0, srx), ddy = fma(sgn * dtd, m1, sry);
-    const double fxd = fmin(fmax(floor(ddx + 1e-6), -8192.0), 8192.0), fyd = fmin(fmax(floor(ddy + 1e-6), -8192.0), 8192.0);
-    w.a = (float)(ddx - fxd);
-    w.b = (float)(ddy - fyd);
-    w.row = ix + (int)fxd + wp.ph;
-    w.col = iy + (int)fyd + wp.pw;
-    w.dt = 0.f;
-    w.src = 0;
-    w.f0 = 0.f;
-    w.f1 = 0.f;
-    return w;
-}
-// The margin m of an event: it is a candidate for warp_exact when a + 1e-6 or b + 1e-6 lies in [0, m) or (1 - m, 1).  With eps = 2^-24
-// the fp32 displacement dx = fl(rx -/+ dt32 f), dt32 = fl(fl(tau32 - d32) period32), is off by at most
-//   eps (3.5 |dt f| + kappa |f|),   kappa = 0 for the reference time "first" (d = 0: the rounding of tau is then relative to dt itself),
-//                                   else (1 + |d| / 2) period (roundings of tau and d: absolute in dt, so they scale with |f| alone)
-// -- 3.5: the subtraction, the period, the product, the fma and the `+ 1e-6` at eps / 2 each, tau at eps (d = 0), theta at eps / 2
-// (2-DoF) -- and |dt| <= period max(|d|, |1 - d|).  m = 1.5 eps (4 period max(|d|, |1 - d|) + kappa) fm with fm = max |motion component|
-// of the event (a function of the EVENT alone, so that nothing depends on how threads and events are matched).  Fractional sources add
-// the rounding of rx and the fma's on a sum of magnitude up to 1.  Everything else is RELATIVE to the motion: a zero motion -- the
-// optimiser's usual starting point, where every event sits ON a border -- has no candidates.
-// An fp64 flow / voxel (WarpParams::motion_f64): the bulk warp reads hi = fl(f), off from the caller's f by at most eps / 2 |f|, so
-// dx gains eps / 2 |dt f| against the fp64 arithmetic on f itself -- the term listed for theta above, which the flow models had
-// no use for while the flow was the device's own fp32.  The count is the 2-DoF model's, 3.5 |dt f| (4 with d = 0 counted in full)
-// against the 6 |dt f| the coefficient grants, and fm = max |hi| is |f| to within 1 + eps: the coefficient stands, and an fp32 call
-// selects the candidates it selected before.
-__device__ __forceinline__ float exact_margin_coef(float d, float tscale) {
-    const float kappa = d == 0.f ? 0.f : (1.f + 0.5f * fabsf(d)) * tscale;
-    return 0x1.8p-24f * (4.f * tscale * fmaxf(fabsf(d), fabsf(1.f - d)) + kappa);
-}
-template <bool FRAC>
-__device__ __forceinline__ float exact_margin(float coef, float fm) { return fmaf(coef, fm, FRAC ? 0x1p-21f : 0.f); }
-
 // An fp64 flow / voxel at the boundary: out[i] = hi = (float)v[i] -- the value an fp32 caller passes, read by every kernel -- and
 // out[count + i] = lo = (float)(v[i] - hi), read only where K1 decides a cell in fp64 (hi + lo = v to 2^-48 relative, what the source
 // residual rx + rxl has); lo = 0 where hi is not finite (split_f64, cmax_common.h).  Streaming: 2 x 16-byte loads, 2 x 16-byte stores per thread and step
@@ -672,75 +203,6 @@ __global__ void __launch_bounds__(256) k_split_motion(const double *__restrict__
     }
 }
 
-__device__ __forceinline__ float time_scale(const WarpParams &wp) {
-    return wp.normalize ? 1.0f : (float)(wp.tmm[1] - wp.tmm[0]);
-}
-
-// Workgroup -> segment, XCD-aware: the dispatcher places block b on XCD b % 8, so giving XCD x the
-// contiguous range [x * per, (x+1) * per) keeps neighbouring tiles (shared halo rows of the IWE / G
-// windows, neighbouring flow pixels) in one XCD's L2.  Placement only affects speed.
-__device__ __forceinline__ int segment_of_block(int nseg, unsigned bx = blockIdx.x) {
-    const int per = (nseg + 7) >> 3;
-    return (int)(bx & 7u) * per + (int)(bx >> 3);
-}
-
-// Row stride of an LDS window of width w.  With a power-of-two stride (the first version: a shift per index) the bank of a
-// cell is its COLUMN modulo 32 whatever its row -- a 20-pixel-wide window used 20 of the 32 banks, and the two rows of a
-// 2 x 2 footprint always collided (SQ_LDS_BANK_CONFLICT / SQ_LDS_IDX_ACTIVE = 0.55-0.70 in K1 and K3, profiles/r02_sq_*).  An odd
-// stride walks the banks row by row; the index costs one v_mad_u32_u24 instead of a shift + add.
-__host__ __device__ inline int window_stride(int w) { return (w < 15 ? 15 : w) | 1; }
-
-struct Window {
-    int r0, c0, h, w;  // top-left corner in the padded image, extent (clipped to the image and to LDS)
-    int stride;        // LDS row stride in words: odd (window_stride), so that the rows of a window start in different banks
-    bool clipped;      // the bounding box did not fit: votes / reads outside the window but inside the image exist
-    bool border;       // the segment holds an event within fp32 rounding of a cell border (K1's verdict, re-used by K3)
-    unsigned long long bmask;  // ... and where: bit q = such an event among the segment's slots [q * kSlots / 64, (q + 1) * kSlots / 64)
-};
-// A window as K1 publishes it for K3 of the same evaluation (RefArgs::win): position | geometry + flags | the 64 bits of bmask
-// (the LDS row stride follows from the width)
-__device__ __forceinline__ int4 pack_window(const Window &w) {
-    return make_int4((int)(((unsigned)(w.r0 + 16384) << 16) | (unsigned)(w.c0 + 16384)),
-                     w.h | (w.w << 12) | (w.clipped ? (1 << 28) : 0) | (w.border ? (1 << 29) : 0),
-                     (int)(unsigned)w.bmask, (int)(unsigned)(w.bmask >> 32));
-}
-__device__ __forceinline__ Window unpack_window(int4 kw) {
-    Window w;
-    w.r0 = (int)((unsigned)kw.x >> 16) - 16384;
-    w.c0 = (int)((unsigned)kw.x & 0xFFFFu) - 16384;
-    w.h = kw.y & 0xFFF;
-    w.w = (kw.y >> 12) & 0xFF;
-    w.stride = window_stride(w.w);
-    w.clipped = ((kw.y >> 28) & 1) != 0;
-    w.border = ((kw.y >> 29) & 1) != 0;
-    w.bmask = (unsigned long long)(unsigned)kw.z | ((unsigned long long)(unsigned)kw.w << 32);
-    return w;
-}
-// how K3 obtains dL/dIWE: from a materialised G image; folded G = c2 (IWE - mu) with the statistics K2 left in
-// `stat`; or (2-DoF) deferred -- K3 gathers the raw image and the image statistics itself, the chain factors are
-// applied by k_finish_deferred, and K2 is not launched at all
-// Linear index of pixel (r, c) of an image that is W wide, r >= 0: one full-rate v_mad_u32_u24 (rows and widths are < 2^13;
-// a 64-bit r * W + c is a quarter-rate v_mad_u64_u32, a 32-bit one a quarter-rate v_mul_lo_u32 -- and the event kernels are
-// VALU-bound on the large configurations: SQ_ACTIVE_INST_VALU x 8 waves ~ 0.8 of the SIMD cycles in K1 / K3 of cfg3).
-__device__ __forceinline__ int pix_index(int r, int c, int W) { return (int)__umul24((unsigned)r, (unsigned)W & 0xFFFFFFu) + c; }
-
-
-constexpr int kFoldNone = 0, kFoldStats = 1, kFoldDeferred = 2, kFoldScale = 3;  // kFoldScale: G image stored without its chain factor
-// kFoldStatsInside: kFoldStats for a plain (not normalised) variance whose K2 runs INSIDE the K3 launch -- the first
-// RefArgs::stat_blocks workgroups of the grid are k_stats (they also write the loss), the others gather; nothing in the
-// gradient waits for the statistics: the chain factor is a constant and the mean comes from K1's vote sums (RefArgs::musum)
-constexpr int kFoldStatsInside = 4;
-constexpr int kGradRuns = 0, kGradStrided = 1, kGradOwned = 2, kGradDet = 3, kGradOwnedSmall = 4;  // k_grad's VARIANT (see cmax_event_kernels.inc)
-constexpr int kScratch = 200;       // scratch words behind the window; the fast path sends the 2x2 footprint of an
-                                    // empty slot to kWinCap + lane + {0, 1, stride, stride + 1}, stride <= 128
-static_assert(kScratch >= 64 + kWinMaxW + 2, "scratch must hold a per-lane 2x2 footprint at the widest stride");
-
-// Compiler barrier on a loaded value.  `x = cond ? p[i] : 0` -- and even an unconditional load whose only use is such a
-// select -- is compiled into an exec-masked block that holds the load AND its s_waitcnt: a thread that wants four loads in flight
-// gets four dependent round trips to memory (found in round 3 in the ISA of K1 / K3 / k_stats: profiles/r03_ablation.txt).  Load
-// unconditionally (clamped index), pin() every value, select afterwards: the loads are then issued back to back.
-__device__ __forceinline__ void pin(float &v) { asm volatile("" : "+v"(v)); }
-
 // Stage the ROWS x COLS window of `img` whose top-left pixel is (r0, c0) into an LDS tile of row pitch LD floats, zero outside
 // the image.  All of a thread's loads are issued before its first LDS store (see pin(): `in ? img[..] : 0` per iteration is one
 // memory round trip per iteration).  256 threads.
@@ -764,114 +226,6 @@ __device__ __forceinline__ void stage_tile(float (*tile)[LD], const float *__res
     }
 }
 
-// 16 bytes of zeros, written through the L2 (sc1): see the deferred-statistics K3
-typedef float float4_v __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ void store_zero4_sc1(float *p) {
-    const float4_v z = {0.f, 0.f, 0.f, 0.f};
-    asm volatile("global_store_dwordx4 %0, %1, off sc1" ::"v"(p), "v"(z) : "memory");
-}
-
-// Clears n floats at `base`, the launch's threads striding over it (tid of nthreads), with write-through stores:
-// buffers that the NEXT kernels fill with device-scope atomics (vote images, the flow gradient) must not stay
-// parked in an XCD's L2.  16-byte stores when the buffer allows it.
-__device__ __forceinline__ void zero_fill_sc1(float *base, int64_t n, int64_t tid, int64_t nthreads) {
-    if (!base) return;
-    if ((n & 3) == 0 && (reinterpret_cast<uintptr_t>(base) & 15u) == 0) {
-        for (int64_t q = tid; q < (n >> 2); q += nthreads) store_zero4_sc1(base + 4 * q);
-    } else {
-        for (int64_t q = tid; q < n; q += nthreads) __hip_atomic_store(&base[q], 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-}
-
-// v_cvt_rpi_i32_f32: floor(x + 0.5) in one instruction (rndne + cvt are two)
-__device__ __forceinline__ int cvt_rpi(float x) {
-    int r;
-    asm("v_cvt_rpi_i32_f32 %0, %1" : "=v"(r) : "v"(x));
-    return r;
-}
-// v_mad_u32_u16 with the HIGH half of `packed` as first factor: (packed >> 16) * factor + addend in one instruction (`factor` wave-uniform,
-// below 2^16), and v_add_u32 with the LOW half of `packed` through SDWA: the LDS word of a packed (row, col) in two instructions where
-// shift, mask, multiply-add and add were four
-__device__ __forceinline__ unsigned mad_hi16_u(unsigned packed, unsigned factor, unsigned addend) {
-    unsigned r;
-    asm("v_mad_u32_u16 %0, %1, %2, %3 op_sel:[1,0,0,0]" : "=v"(r) : "v"(packed), "s"(factor), "v"(addend));
-    return r;
-}
-__device__ __forceinline__ unsigned add_lo16_u(unsigned a, unsigned packed) {
-    unsigned r;
-    asm("v_add_u32_sdwa %0, %1, %2 dst_sel:DWORD dst_unused:UNUSED_PAD src0_sel:DWORD src1_sel:WORD_0" : "=v"(r) : "v"(a), "v"(packed));
-    return r;
-}
-// 24-bit multiplies with a UNIFORM second factor, spelled out: the compiler takes v_mul_lo_u32 / v_mul_hi_u32 whenever it cannot
-// prove both factors below 2^24 (a run-time window stride: K1's vote index, one per event).  `b` must be wave-uniform.
-__device__ __forceinline__ unsigned mul24_u(unsigned a, unsigned b) {
-    unsigned r;
-    asm("v_mul_u32_u24 %0, %1, %2" : "=v"(r) : "s"(b), "v"(a));
-    return r;
-}
-__device__ __forceinline__ unsigned mad24_u(unsigned a, unsigned b, unsigned c) {
-    unsigned r;
-    asm("v_mad_u32_u24 %0, %1, %2, %3" : "=v"(r) : "v"(a), "s"(b), "v"(c));
-    return r;
-}
-typedef unsigned short ushort2_v __attribute__((ext_vector_type(2)));
-__device__ __forceinline__ unsigned pk_min_u16(unsigned a, unsigned b) {  // v_pk_min_u16: both 16-bit halves at once
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_min(__builtin_bit_cast(ushort2_v, a), __builtin_bit_cast(ushort2_v, b)));
-}
-__device__ __forceinline__ unsigned pk_max_u16(unsigned a, unsigned b) {
-    return __builtin_bit_cast(unsigned, __builtin_elementwise_max(__builtin_bit_cast(ushort2_v, a), __builtin_bit_cast(ushort2_v, b)));
-}
-
-// ---- wave64 segmented inclusive scan without LDS traffic -------------------------------------------
-// ds_bpermute-based __shfl_up costs ~16 cycles per wave instruction on gfx950 and the 6-step scan of
-// (x, y, flag) was 60 % of the dense K3 (profiles/r01_ablation.txt).  DPP row shifts run on the VALU:
-// 4 steps inside each 16-lane row, then three v_readlane carries across the rows.
-template <int CTRL>
-__device__ __forceinline__ float dpp_f(float v) {  // lanes whose source is outside the row / wave read 0
-    return __int_as_float(__builtin_amdgcn_update_dpp(0, __float_as_int(v), CTRL, 0xF, 0xF, false));
-}
-template <int CTRL>
-__device__ __forceinline__ int dpp_i(int old, int v) {
-    return __builtin_amdgcn_update_dpp(old, v, CTRL, 0xF, 0xF, false);
-}
-template <int CTRL>
-__device__ __forceinline__ unsigned dpp_u0(unsigned v) {  // lanes without a source read 0 (bound_ctrl: no move of the identity first)
-    return (unsigned)__builtin_amdgcn_update_dpp(0, (int)v, CTRL, 0xF, 0xF, true);
-}
-constexpr int kDppRowShr1 = 0x111, kDppRowShr2 = 0x112, kDppRowShr4 = 0x114, kDppRowShr8 = 0x118;
-constexpr int kDppWaveShl1 = 0x130, kDppWaveShr1 = 0x138, kDppRowBcast15 = 0x142, kDppRowBcast31 = 0x143;
-
-// head: 1 on the first lane of every run.  On return (vx, vy) of the LAST lane of a run hold the run's sums.
-__device__ __forceinline__ void seg_scan64(int head, float &vx, float &vy, int lane) {
-    int f = head;  // "a run starts between my row's first lane and me"
-#define CMAX_SEG_STEP(CTRL)                                   \
-    {                                                         \
-        const float x2 = dpp_f<CTRL>(vx), y2 = dpp_f<CTRL>(vy); \
-        const int f2 = dpp_i<CTRL>(0, f);                     \
-        if (!f) {                                             \
-            vx += x2;                                         \
-            vy += y2;                                         \
-            f |= f2;                                          \
-        }                                                     \
-    }
-    CMAX_SEG_STEP(kDppRowShr1)
-    CMAX_SEG_STEP(kDppRowShr2)
-    CMAX_SEG_STEP(kDppRowShr4)
-    CMAX_SEG_STEP(kDppRowShr8)
-#undef CMAX_SEG_STEP
-    // carry the run that crosses a row boundary: lanes of row r without a head before them continue
-    // the run ending at the last lane of row r-1 (whose value already contains earlier carries)
-#pragma unroll
-    for (int r = 1; r < 4; ++r) {
-        const float cx = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vx), 16 * r - 1));
-        const float cy = __int_as_float(__builtin_amdgcn_readlane(__float_as_int(vy), 16 * r - 1));
-        if ((lane >> 4) == r && !f) {
-            vx += cx;
-            vy += cy;
-        }
-    }
-}  // 64 scratch words behind the window: target of masked lanes (branch-free phase B)
-
 // ---------------------------------------------------------------------------------------------
 // K2: contrast statistics of one image (+ zeroing of the NEXT evaluation's vote image).
 //     Workgroup b adds its fp64 partials to sub-accumulator b % 32 of its slot:
@@ -880,150 +234,6 @@ __device__ __forceinline__ void seg_scan64(int head, float &vx, float &vy, int l
 //     they are spread over 32 addresses and consumers add the 32 values.  The accumulators are zeroed
 //     by workgroup 0 of the K1 launch that fills the image (stream order), so no memset node exists.
 // ---------------------------------------------------------------------------------------------
-constexpr int kStatBlocksMax = 512;
-constexpr int kStatSlots = 5;  // reference times 0..3, slot 4 = un-warped image
-constexpr int kStatSub = 32;   // sub-accumulators per slot
-// Every sub-accumulator sits on its OWN 128-byte line: atomics to one cache line serialise in the L2 atomic unit whatever
-// their address inside it (~7 ns each).  Packed 16 bytes apart, the up to 32 sub-accumulators of a slot shared 1-4 lines, and
-// the 363 workgroups of a 260 x 346 image kernel spent 5 of their 9.8 us queueing on ONE line (profiles/r02_ablation.txt).
-constexpr int kSubStride = 16;  // doubles between sub-accumulators
-constexpr int kStatStride = kStatSub * kSubStride;
-// raw sums of the deferred 2-DoF K3 (S1x, S1y, S2x, S2y, sum I, sum I^2): kRawLines accumulators per reference time, one line each
-constexpr int kRawLines = CMAX_RAW_LINES, kRawStride = CMAX_RAW_DOUBLES;
-static_assert(kRawLines == kStatSub && kRawStride == kStatStride && (kRawLines & (kRawLines - 1)) == 0, "K1 resets either with the same pattern");
-
-struct ObjParams {
-    int cost, normalized, minimize, negate, omit, n_ref;
-    double mult[4];
-    int H, W;  // padded image
-    int nsub;  // sub-accumulators in use (<= kStatSub), grows with the number of k_stats workgroups
-};
-
-// raw contrast from the summed accumulators (variance: unbiased like torch.var, image_variance.py:55)
-__device__ __forceinline__ double contrast_value(int cost, const double *acc, double npix, double *mu_out) {
-    if (cost == CMAX_COST_VARIANCE) {
-        const double mu = acc[0] / npix;
-        if (mu_out) *mu_out = mu;
-        return (acc[1] - acc[0] * mu) / (npix - 1.0);
-    }
-    return acc[0] / npix;
-}
-
-__device__ __forceinline__ double region_pixels(int H, int W, int omit) {
-    const int i0 = omit ? 1 : 0;
-    return (double)(H - 2 * i0) * (double)(W - 2 * i0);
-}
-
-// sum of the sub-accumulators of one slot.  WAVE: called by a whole converged wave -- lane u loads accumulator u,
-// DPP reduction, broadcast from lane 63 (a serial walk over up to 32 addresses costs the event kernels 2-4 us of
-// dependent scalar-load latency at the head of every workgroup).
-template <bool WAVE = false>
-__device__ __forceinline__ void stat_sum(const double *__restrict__ stat, int slot, int nsub, double (&acc)[2]) {
-    if (WAVE) {
-        const int lane = threadIdx.x & (kWave - 1);
-        double a0 = 0.0, a1 = 0.0;
-        if (lane < nsub) {
-            a0 = stat[slot * kStatStride + kSubStride * lane];
-            a1 = stat[slot * kStatStride + kSubStride * lane + 1];
-        }
-        a0 = wave_sum_lane63(a0);
-        a1 = wave_sum_lane63(a1);
-        acc[0] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a0), kWave - 1), __builtin_amdgcn_readlane(__double2loint(a0), kWave - 1));
-        acc[1] = __hiloint2double(__builtin_amdgcn_readlane(__double2hiint(a1), kWave - 1), __builtin_amdgcn_readlane(__double2loint(a1), kWave - 1));
-        return;
-    }
-    acc[0] = 0.0;
-    acc[1] = 0.0;
-    for (int u = 0; u < nsub; ++u) {
-        acc[0] += stat[slot * kStatStride + kSubStride * u];
-        acc[1] += stat[slot * kStatStride + kSubStride * u + 1];
-    }
-}
-
-template <bool WAVE = false>
-__device__ __forceinline__ double orig_value(const ObjParams &op, const double *stat) {
-    // orig_iwe is NOT boundary-cropped for the variance (normalized_image_variance.py:40-41)
-    const int omit_o = op.cost == CMAX_COST_VARIANCE ? 0 : op.omit;
-    double acc[2];
-    stat_sum<WAVE>(stat, 4, op.nsub, acc);
-    return contrast_value(op.cost, acc, region_pixels(op.H, op.W, omit_o), nullptr);
-}
-
-// dL/dv_k: chain factor of reference time k, and the mean of its image (variance)
-template <bool WAVE = false>
-__device__ __forceinline__ double chain_coef(const ObjParams &op, const double *stat, int k, double *mu_out) {
-    const double npix = region_pixels(op.H, op.W, op.omit);
-    if (!op.normalized && op.cost != CMAX_COST_VARIANCE) {  // constant factor, no mean: the statistics are not needed
-        const double c = op.mult[k] * (op.minimize ? -1.0 : 1.0);
-        return op.negate ? -c : c;
-    }
-    double acc[2];
-    stat_sum<WAVE>(stat, k, op.nsub, acc);
-    const double v = contrast_value(op.cost, acc, npix, mu_out);
-    double coef;
-    if (!op.normalized) coef = op.mult[k] * (op.minimize ? -1.0 : 1.0);
-    else {
-        const double v_orig = orig_value<WAVE>(op, stat);
-        coef = op.mult[k] * (op.minimize ? -v_orig / (v * v) : 1.0 / v_orig);
-    }
-    return op.negate ? -coef : coef;
-}
-
-// Arrival ticket of a group of workgroups inside one launch: called by ONE thread of workgroup `wg` of `total` after its
-// device-scope atomics; true for exactly one caller, the last to arrive, and every other workgroup's atomics have been
-// performed by then (the caller waits for its own acknowledgements first).  The counters are left at zero.  Same-line atomics
-// serialise, hence kTicketSubs lines + one.  Four dependent fabric round trips (~5 us, profiles/r02_ablation.txt): only for work
-// that is NOT at the end of its kernel.
-constexpr int kTicketSubs = 16, kTicketLines = kTicketSubs + 1, kTicketLineInts = 32;
-__device__ __forceinline__ bool arrive_last(int *ticket, int wg, int total) {
-    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    const int nsub = total < kTicketSubs ? total : kTicketSubs;
-    const int sub = wg % kTicketSubs, per = (total - sub + kTicketSubs - 1) / kTicketSubs;
-    int *line = ticket + sub * kTicketLineInts;
-    if (__hip_atomic_fetch_add(line, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != per - 1) return false;
-    __hip_atomic_store(line, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);  // nobody else arrives on this line any more
-    int *master = ticket + kTicketSubs * kTicketLineInts;
-    if (__hip_atomic_fetch_add(master, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != nsub - 1) return false;
-    __hip_atomic_store(master, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    return true;
-}
-
-// loss of a plain variance objective with ONE reference time from accumulators that other workgroups of the same launch
-// filled with device-scope atomics: device-scope loads (a plain load may be served from this XCD's L2)
-__device__ __forceinline__ void write_result_variance_agent(const ObjParams &op, const double *stat, double *__restrict__ result) {
-    double acc[2] = {0.0, 0.0};
-    for (int u = 0; u < op.nsub; ++u) {
-        acc[0] += __hip_atomic_load(&stat[kSubStride * u], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-        acc[1] += __hip_atomic_load(&stat[kSubStride * u + 1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-    }
-    const double v = contrast_value(CMAX_COST_VARIANCE, acc, region_pixels(op.H, op.W, op.omit), nullptr);
-    const double loss = op.mult[0] * (op.minimize ? -v : v);
-    result[0] = op.negate ? -loss : loss;
-    result[1] = v;
-    result[5] = 0.0;
-}
-
-// loss and per-reference-time contrasts -> result[0..5].  WAVE: called by a whole converged wave (the accumulators of a slot
-// are gathered in ONE round trip instead of a serial walk over their cache lines); its first lane writes.
-template <bool WAVE = false>
-__device__ __forceinline__ void write_result(const ObjParams &op, const double *stat, double *__restrict__ result) {
-    const double npix = region_pixels(op.H, op.W, op.omit);
-    const double v_orig = op.normalized ? orig_value<WAVE>(op, stat) : 0.0;
-    const bool writer = !WAVE || (threadIdx.x & (kWave - 1)) == 0;
-    double loss = 0.0;
-    for (int k = 0; k < op.n_ref; ++k) {
-        double acc[2];
-        stat_sum<WAVE>(stat, k, op.nsub, acc);
-        const double v = contrast_value(op.cost, acc, npix, nullptr);
-        if (writer) result[1 + k] = v;
-        if (!op.normalized) loss += op.mult[k] * (op.minimize ? -v : v);
-        else loss += op.mult[k] * (op.minimize ? v_orig / v : v / v_orig);
-    }
-    if (writer) {
-        result[0] = op.negate ? -loss : loss;
-        result[5] = v_orig;
-    }
-}
 
 // THR: 256, or 1024 in deterministic mode (kStatSub workgroups, one per accumulator: they have to be large)
 template <int COST, int THR = 256>
@@ -1303,8 +513,6 @@ k_blur_stats_gimage_gm(const float *__restrict__ in0, int64_t in_stride, int H, 
 // "four weights add up to 1" is immaterial.  So this kernel reads mu, blurs, sums (for the loss) and writes
 // G' = 2 / (n - 1) blur3^T [ (Ib - mu) 1_Omega ]; K3 (kFoldScale) multiplies by coef once the statistics are complete.
 // One 8 x 32 output tile per workgroup, halo 2 -> 1 -> 0 in LDS; arithmetic of the blur as in k_blur3.
-constexpr int kMuLines = 32;                       // accumulators of K1's sum (same-line atomics serialise: one line each)
-constexpr int kMuStride = kMuLines * kSubStride;   // doubles per reference time
 __global__ void __launch_bounds__(256)
 k_blur_stats_adj_var(const float *__restrict__ in0, int64_t in_stride, int H, int W, ImgArgs ia, float k0, float k1, int omit, int nsub, double *__restrict__ stat_base,
                      float4 *__restrict__ zero_extra, int64_t n_extra4, const double *__restrict__ musum, double *__restrict__ musum_next,
@@ -1536,50 +744,6 @@ k_gimage_blur_adj_var(ImgArgs ia, ObjParams op, const double *__restrict__ stat,
     G[p] = blur_adj_1d<float>(i, H, k0, k1, [&](int r) { return blur_adj_1d<float>(j, W, k0, k1, [&](int c) { return g(r, c); }); });
 }
 
-// =============================================================================================
-// Exact Hessian-vector product (a18): what torch.autograd.functional.vhp returns for the
-// objective (src/solver/scipy_autograd/torch_wrapper.py:51-73) -- the derivative of the analytic
-// gradient along a tangent motion u with the pixel cells held fixed (floor has zero derivative):
-//   H u = sum_k [ phi_k'' dv_k J^T G0_k + phi_k' ( (dJ^T/dtheta u) G0_k + J^T (dG0_k/dI) J u ) ]
-//   T1 k_vote_tan   tangent image dI = J u        (votes with the derivatives of the 4 bilinear weights)
-//   T2 k_stats_tan  <G0, dI> and mean(dI)  ;  k_gimage_tan  G' = phi' dG0 + phi'' dv G0
-//   T3 k_grad_hvp   per event: mixed term M (da, db) with the current G + gather of G' -> J^T
-// The tangent is scaled to unit max-norm by the caller so the derivative votes fit fixed point.
-// =============================================================================================
-struct TanParams {
-    const float *u;      // tangent motion, same layout as the motion, scaled to |u|_inf = 1
-    float fix, inv_fix;  // fixed-point scale of the derivative votes (set per workgroup from the arrays below)
-    // one launch covers the reference times of the objective (blockIdx.y):
-    float d[4], fixk[4];  // reference time as a fraction of the batch period, its fixed-point scale
-    float d_lo[4];        // ... what fp32 lost of d (read by warp_exact only: these kernels decide the cells K1 decides, from d + d_lo)
-    int64_t bs;           // element stride between the per-reference-time images
-};
-
-// deterministic mode of the second-order gather (k_grad_hvp): all null / zero in the default mode
-struct HvpDet {
-    long long *g64;        // 2-DoF: per-segment partial sums [n_ref][nseg][2]; flow models: fixed-point accumulators of the product
-    const unsigned *imax;  // bits of max |G_k| at [k], of max |G'_k| at [4 + k]
-    double *inv_scale;     // [4] 1 / scale of reference time k (2-DoF) or of the whole launch ([0])
-    long long n_events;
-    int n_ref;
-};
-
-// (da, db) of cached event slot: d(x', y')/d(motion) . u
-template <int MODEL>
-__device__ __forceinline__ void tangent_delta(const WarpParams &wp, const TanParams &tp, float dt, unsigned key, float u0, float u1,
-                                              float &da, float &db) {
-    if (MODEL == CMAX_MODEL_2DOF) {
-        da = dt * u0;  // x' = x + dt * theta0
-        db = dt * u1;
-    } else {
-        const int hw = wp.H * wp.W;
-        const int ix = (int)(key & 0xFFFu), iy = (int)((key >> 12) & 0xFFFu), bin = (int)(key >> 24);
-        const int src = bin * 2 * hw + ix * wp.W + iy;
-        da = -dt * tp.u[src];  // x' = x - dt * F[0, ix, iy]
-        db = -dt * tp.u[src + hw];
-    }
-}
-
 // T2a: st[0] += sum_Omega dI (variance) or sum_Omega (gx dgx + gy dgy) (grad-mag); st[1] += sum_Omega I dI
 template <int COST>
 __global__ void __launch_bounds__(256)
@@ -1663,34 +827,7 @@ k_gimage_tan(const float *__restrict__ img, const float *__restrict__ dimg, ObjP
     }
 }
 
-// ---------------------------------------------------------------------------------------------
-// deterministic mode: fixed-point conversions
-// ---------------------------------------------------------------------------------------------
-// power-of-two scale s with  bound * n * s < 2^61: n terms of magnitude <= bound fit a 64-bit accumulator
-// (n counted as at least 2048: a single term then stays below 2^50 and det_fixed's conversion is exact)
-__device__ __forceinline__ double det_scale(double bound, long long n) {
-    int e = 0;
-    (void)frexp(bound * (double)(n > 2048 ? n : 2048), &e);  // bound n = f 2^e, f in [0.5, 1); 0 -> e = 0
-    if (!(bound >= 0.0) || e > 1000) e = 1000;         // NaN / inf: any finite scale
-    return ldexp(1.0, 60 - e);
-}
-// rint(x * s) as a 64-bit integer for |x s| < 2^51: x s + 1.5 2^52 carries the rounded integer in its low mantissa bits (one fma
-// + a 64-bit subtraction; __double2ll_rn is a ~25-instruction sequence on gfx950, twice per event in the deterministic K3)
-__device__ __forceinline__ long long det_fixed(double x, double s) {
-    const double magic = 6755399441055744.0;  // 1.5 * 2^52
-    return __double_as_longlong(fma(x, s, magic)) - __double_as_longlong(magic);
-}
-__device__ __forceinline__ void atomic_add_i64(long long *p, long long v) {
-    atomicAdd(reinterpret_cast<unsigned long long *>(p), (unsigned long long)v);  // two's complement: wrap-around add
-}
-
 // fixed-point vote images -> fp32 images (blockIdx.y = image), the integer image is left zero for the next evaluation
-struct FixedArgs {
-    long long *src[5];
-    float *dst[5];
-    double inv_fix;  // 1 / the vote fixed point of the kernels that filled src: 2^-20, big segments 2^-19
-    double inv_fixk[5];  // != 0: per-image scale instead (tangent votes: one fixed point per reference time)
-};
 __global__ void __launch_bounds__(256) k_fixed_to_image(FixedArgs fa, int64_t npix) {
     long long *__restrict__ src = fa.src[blockIdx.y];
     float *__restrict__ dst = fa.dst[blockIdx.y];
@@ -1791,14 +928,6 @@ k_finish_lines(const double *__restrict__ raw, int n_ref, double *__restrict__ g
         if (lane == kWave - 1) *flag = seq;
     }
 }
-
-}  // namespace cmax
-
-// the event kernels
-namespace cmax {
-#include "cmax_event_kernels.inc"
-
-__global__ void k_empty(const int4 *) {}  // cmax_debug_launch_floor
 
 // 2-DoF only: gradient = sum of the per-segment partials of every K3 launch (one workgroup).
 __global__ void __launch_bounds__(256)
@@ -1965,46 +1094,6 @@ static void fill_ref_times(RefArgs &ra, int n_ref, const int *ref_mode, const do
     }
 }
 
-// The layout of the event kernels, chosen ONCE per kernel family (each family is instantiated for the layouts its function returns).
-// A work list of big / mid segments (up to 4088 / 3064 events) can only be run by the big / mid layouts.
-// K1: 512 threads (4 events per thread) once the work list exceeds what the chip holds at once -- as for K3: cfg2 (704 half-tile
-// segments) K1 6.35 -> 5.97 us, evaluation 18.06 -> 17.38
-static Layout vote_layout(const cmax_handle_s *h) {
-    if (h->big) return Layout::b512;
-    if (h->mid) return Layout::m512;
-    return h->nseg > 512 ? Layout::t512 : Layout::t256;
-}
-// K3 (not deterministic): as K1, with the voxel K3 at 1024 threads on big segments and above 1024 segments (cfg4: 22.1 us with 512
-// threads -> 19.3 us), and at 512 threads with the small accumulator array on owned groups of <= 3 groups per segment (build_segments)
-static Layout grad_layout(const cmax_handle_s *h, int model, bool owned) {
-    const bool voxel = model == CMAX_MODEL_VOXEL;
-    if (h->big) return voxel ? Layout::b1024 : Layout::b512;
-    if (h->mid) return Layout::m512;
-    if (voxel && owned && h->small_acc) return Layout::t512;
-    if (voxel && h->nseg > 1024) return Layout::t1024;
-    return h->nseg > 512 ? Layout::t512 : Layout::t256;  // K3 hides its latencies better with 8 waves per workgroup (cfg2: 7.5 -> 7.1 us)
-}
-// deterministic K3, the tangent votes (k_vote_tan, k_vote_tan2) and the second-order gather (k_grad_hvp)
-static Layout plain_layout(const cmax_handle_s *h) {
-    if (h->big) return Layout::b512;
-    if (h->mid) return Layout::m512;
-    return Layout::t256;
-}
-
-// f(L{}) for the layout L among Ls whose id is `id`
-template <class... Ls, class F>
-static void with_layout(Layout id, F &&f) {
-    const bool found = ((Ls::kId == id ? (f(Ls{}), true) : false) || ...);
-    if (!found) std::abort();  // (a choice function returned a layout its family is not instantiated for)
-}
-// f(std::true_type{}) or f(std::false_type{}): a run-time flag as a template argument
-template <class F>
-static void with_bool(bool b, F &&f) {
-    if (b) f(std::true_type{});
-    else f(std::false_type{});
-}
-template <int V>
-using int_c = std::integral_constant<int, V>;  // (fold / variant of k_grad)
 // f(int_c<MODEL>{}) for the motion model of an objective (check_objective_args: one of the three)
 template <class F>
 static void with_model(int model, F &&f) {
@@ -2017,138 +1106,6 @@ template <class F>
 static void with_cost(int cost, F &&f) {
     if (cost == CMAX_COST_VARIANCE) f(int_c<CMAX_COST_VARIANCE>{});
     else f(int_c<CMAX_COST_GRADMAG>{});
-}
-// grid.x of a kernel that finds its segment with segment_of_block: one workgroup per segment, the same number on each of the 8 XCDs
-static int seg_blocks(int nseg) { return 8 * ((nseg + 7) / 8); }
-// the 6-byte events of the work list from segment seg0 on (one region per segment), or nullptr where the kernels read the 8-byte ones
-template <int MODEL>
-static const char *compact_events(const cmax_handle_s *h, int seg0 = 0) {
-    return (h->compact && h->big && MODEL != CMAX_MODEL_VOXEL) ? h->cev + (int64_t)seg0 * b512::kCompactStride : nullptr;
-}
-static int layout_threads(Layout id) {
-    int thr = 0;
-    with_layout<t256, t512, t1024, m512, b512, b1024>(id, [&](auto l) { thr = decltype(l)::kThr; });
-    return thr;
-}
-
-// the arguments every vote and gather of a weighted handle carries (cmax_set_event_weights): objective, cmax_iwe, the un-warped image
-static RefArgs weighted_args(const cmax_handle_s *h, const RefArgs &ra_in) {
-    RefArgs ra = ra_in;
-    if (h->weighted) {
-        ra.wgt = h->w_packed;
-        ra.wnorm = h->d_wnorm;
-    }
-    return ra;
-}
-
-template <int MODEL>
-static void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, hipStream_t s, int nz = 1) {
-    const dim3 grid(seg_blocks(h->nseg), n_ref, nz);  // z: candidate motions of cmax_objective_batch
-    const RefArgs ra = weighted_args(h, ra_in);
-    ProfScope prof(h, kProfVote, s);
-    const char *cev = compact_events<MODEL>(h);
-    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing)
-        for (int rep = 0; rep < h->prof_repeat; ++rep)
-            with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) {
-                using L = decltype(l);
-                with_bool(h->has_frac, [&](auto frac) {
-                    if (ra.wgt) {  // weighted handle (never with the vote sums: eval_plan)
-                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp,
-                                           ra, exact...);
-                        return;
-                    }
-                    with_bool(ra.musum[0] != nullptr, [&](auto mu) {
-                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value, false, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev,
-                                           wp, ra, exact...);
-                    });
-                });
-            });
-    };
-    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
-        if (wp.motion_f64) {  // the caller's fp64 flow, split: the instantiation whose border branch reads the low plane
-            launch(ExactFlow{1});
-            return;
-        }
-    }
-    launch();
-}
-
-// seg0 / seg_n: sub-range of the work list (a band of tile rows, see cmax_comm_set_c2_bands); seg_n < 0 = the whole list.  The
-// kernels only see a shifted list (RefArgs::win is shifted by the caller).
-// A weighted handle (cmax_set_event_weights) runs the same layouts and variants in their WEIGHTED instantiations, and only the folds of
-// the general path (eval_plan sends it through K1 -> statistics -> K3; deterministic mode is refused): the other combinations are
-// not instantiated.
-template <int MODEL>
-static void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, int fold,
-                        const ObjParams &op, double *gpart, float *gflow, double *result, bool owned, hipStream_t s, int seg0 = 0,
-                        int seg_n = -1, int nz = 1) {
-    if (h->weighted && (fold == kFoldDeferred || fold == kFoldStatsInside || h->deterministic)) std::abort();  // (eval_plan never asks for these)
-    const int4 *segs = h->d_segs + seg0;
-    const int nseg = seg_n < 0 ? h->nseg : seg_n;
-    const dim3 grid(seg_blocks(nseg) + (fold == kFoldStatsInside ? ra_in.stat_blocks : 0), n_ref, nz);
-    ProfScope prof(h, kProfGrad, s);
-    const RefArgs ra = weighted_args(h, ra_in);
-    const char *cev = compact_events<MODEL>(h, seg0);
-    auto launch = [&](auto l, auto frac, auto fold_c, auto variant, auto weighted) {
-        using L = decltype(l);
-        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, weighted.value>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev,
-                           cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
-    };
-    if (h->deterministic) {  // one workgroup size, two ways of obtaining dL/dIWE (objective_finish runs the unfused image path)
-        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-            with_bool(h->has_frac, [&](auto frac) {
-                if (fold == kFoldStats) launch(l, frac, int_c<kFoldStats>{}, int_c<kGradDet>{}, std::false_type{});
-                else launch(l, frac, int_c<kFoldNone>{}, int_c<kGradDet>{}, std::false_type{});
-            });
-        });
-        return;
-    }
-    // dense model: runs of equal source pixel are reduced serially per thread when they are long (pixel-sorted
-    // handle, >= 8 events per active pixel), else with a segmented scan per slot over lanes holding consecutive events;
-    // owned groups (dense / voxel, one reference time, group-aligned work list): LDS accumulators + plain stores
-    const bool strided = MODEL == CMAX_MODEL_DENSE && !(h->long_runs && h->n_time_bin == 0);
-    // voxel, owned groups of <= 3 groups per segment: the small accumulator array (grad_layout: 512 threads x 4 events, or mid segments)
-    const bool small = MODEL == CMAX_MODEL_VOXEL && owned && h->small_acc && !h->big;
-    auto body = [&](auto l) {
-        using L = decltype(l);
-        with_bool(h->weighted, [&](auto weighted) {
-            constexpr bool kWeighted = decltype(weighted)::value;
-            auto with_variant = [&](auto frac, auto fold_c) {
-                if constexpr (MODEL == CMAX_MODEL_DENSE) {
-                    if (owned) launch(l, frac, fold_c, int_c<kGradOwned>{}, weighted);
-                    else if (strided) launch(l, frac, fold_c, int_c<kGradStrided>{}, weighted);
-                    else launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
-                } else if constexpr (MODEL == CMAX_MODEL_VOXEL) {
-                    if (owned && small) {
-                        if constexpr (L::kThr == 512 && L::kSlots <= 3072) launch(l, frac, fold_c, int_c<kGradOwnedSmall>{}, weighted);
-                    } else if (owned) {
-                        launch(l, frac, fold_c, int_c<kGradOwned>{}, weighted);
-                    } else {
-                        launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
-                    }
-                } else {
-                    launch(l, frac, fold_c, int_c<kGradRuns>{}, weighted);
-                }
-            };
-            with_bool(h->has_frac, [&](auto frac) {
-                if (fold == kFoldDeferred) {
-                    if constexpr (MODEL == CMAX_MODEL_2DOF && !kWeighted) with_variant(frac, int_c<kFoldDeferred>{});
-                } else if (fold == kFoldStatsInside) {
-                    if constexpr (MODEL != CMAX_MODEL_2DOF && !kWeighted) with_variant(frac, int_c<kFoldStatsInside>{});
-                } else if (fold == kFoldStats) {
-                    with_variant(frac, int_c<kFoldStats>{});
-                } else if (fold == kFoldScale) {
-                    with_variant(frac, int_c<kFoldScale>{});
-                } else {
-                    with_variant(frac, int_c<kFoldNone>{});
-                }
-            });
-        });
-    };
-    for (int rep = 0; rep < h->prof_repeat; ++rep) {
-        if constexpr (MODEL == CMAX_MODEL_VOXEL) with_layout<b1024, m512, t512, t1024, t256>(grad_layout(h, MODEL, owned), body);
-        else with_layout<b512, m512, t512, t256>(grad_layout(h, MODEL, owned), body);
-    }
 }
 
 static EvView ev_view(const cmax_handle_s *h) {
@@ -2339,24 +1296,6 @@ struct BatchReadback {
 //   * smaller batches are latency-bound: small groups are merged while they fit, a group with more than
 //     kSegMax events is split into EQUAL parts -- group-aligned windows are tighter and no workgroup is left
 //     with a small remainder (cfg2: 2040 + 806 per tile -> 2 x 1423).
-template <typename T>
-static int pinned_reserve(T **p, int64_t *cap, int64_t count) {
-    if (count <= *cap) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const int64_t want = count + count / 2 + 64;
-    // coherent + mapped: kernels write results and run counters straight into these buffers and the host polls them
-    // (cmax_objective_host, the patch plan's tail) -- visibility must not hang on HIP_HOST_COHERENT; zeroed: a flag word is polled
-    // before anything ever wrote it
-    if (hipHostMalloc((void **)p, (size_t)want * sizeof(T), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        set_error("hipHostMalloc(%lld bytes) failed", (long long)(want * sizeof(T)));
-        return CMAX_ENOMEM;
-    }
-    std::memset((void *)*p, 0, (size_t)want * sizeof(T));
-    *cap = want;
-    return 0;
-}
 
 // overlap: launched (by the caller's functor) BEHIND the read-back copies and an event, i.e. work the GPU does while the host
 // waits for that event only, cuts the segments and uploads them -- the ordering of the pixel runs by time (k_run_time_sort),
@@ -2597,16 +1536,8 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
     // events -- K1 must then warp with the same fp32 time (K3 follows K1's cells and windows without tests), so such a handle gets no compact
     // copy at all (big segments + short runs = a sparse batch on a very large sensor, or CMAX_BIG_SEG=1).
     if (h->big && T == 1 && !slab && h->n_time_bin == 0 && h->nseg > 0 && compact_env != 0 && h->long_runs) {
-        if (h->nseg > h->cev_cap) {
-            dev_free(&h->cev);
-            h->cev_cap = 0;
-            rc = dev_alloc(h, &h->cev, (int64_t)h->nseg * b512::kCompactStride);
-            if (rc) return rc;
-            h->cev_cap = h->nseg;
-        }
-        hipLaunchKernelGGL((k_pack_compact<b512>), dim3(h->nseg), dim3(b512::kThr), 0, s, (const int4 *)h->d_segs, h->nseg, (const uint2 *)h->evp, h->ntc,
-                           h->cev, h->d_flags + 3);
-        CMAX_CHECK_HIP(hipGetLastError());
+        rc = pack_compact_events(h, s);  // (cmax_event_launch.hip: the kernel is a template over the event layouts)
+        if (rc) return rc;
         static const bool debug_compact = getenv("CMAX_DEBUG_COMPACT") != nullptr;
         if (debug_compact) {  // (k_pack_compact raises d_flags[3] when an event lies outside its segment's tile row / 8-tile span: never)
             int bad = 0;
@@ -2812,7 +1743,6 @@ __global__ void k_weights_norm(float *__restrict__ wnorm) {
     wnorm[0] = wmax > 0.f ? 1.f / wmax : 0.f;
     wnorm[1] = wmax;
 }
-constexpr int64_t kWeightPad = 4096 + 16;  // an event kernel's unconditional loads reach at most one segment's slots behind the last event
 
 // the packed-order copy of the kept weights for the CURRENT order of the batch (after cmax_set_event_weights and after every re-ordering)
 static int gather_weights(cmax_handle_s *h, hipStream_t s) {
@@ -2834,14 +1764,6 @@ static int gather_weights(cmax_handle_s *h, hipStream_t s) {
     h->win_generation = ~(uint64_t)0;
     return 0;
 }
-
-#define CMAX_REFUSE_WEIGHTED(h, what)                                                                                                 \
-    do {                                                                                                                              \
-        if ((h) && (h)->weighted) {                                                                                                   \
-            ::cmax::set_error("%s: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them", what); \
-            return CMAX_EUNSUPPORTED;                                                                                                 \
-        }                                                                                                                             \
-    } while (0)
 
 void handle_get_eval_state(cmax_handle_t h, HandleEvalState *out) {
     out->cur_buf = h->cur_buf;
@@ -3878,17 +2800,7 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
     h->tan_zero_mask[h->tan_cur] &= ~used;
     const WarpParams wp = warp_params(h, motion, 0, d->ref_mode[0], d->ref_frac[0], d->normalize_t, d->motion_dtype == CMAX_F64);
     if (h->n > 0) {
-        const EvView ev = ev_view(h);
-        const dim3 grid(seg_blocks(h->nseg), nr);
-        ProfScope prof(h, kProfVote, s);
-        for (int rep = 0; rep < h->prof_repeat; ++rep) {
-            with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-                using L = decltype(l);
-                with_bool(h->has_frac, [&](auto frac) {
-                    hipLaunchKernelGGL((k_vote_tan2<L, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev, wp, ra);
-                });
-            });
-        }
+        launch_vote_tan2(h, ev_view(h), wp, ra, nr, s);
         CMAX_CHECK_LAUNCH();
     }
     if (comm) {  // the ONE exchange of a 2-DoF evaluation: all planes of all reference times are contiguous
@@ -4022,25 +2934,6 @@ __global__ void __launch_bounds__(256) k_weight_grad_scatter(const float *__rest
     grad_w[src[i]] = a;
 }
 
-// The launch form of the per-event gathers (K3w, K3e) over n_img images: K1's grid, events and layout (launch_vote), whose windows
-// they read.  f(L{}, frac, grid, cev) launches the kernel.
-template <int MODEL, class F>
-static void launch_gather(cmax_handle_s *h, int n_img, F &&f) {
-    const dim3 grid(seg_blocks(h->nseg), n_img);
-    const char *cev = compact_events<MODEL>(h);
-    with_layout<b512, m512, t512, t256>(vote_layout(h), [&](auto l) { with_bool(h->has_frac, [&](auto frac) { f(l, frac, grid, cev); }); });
-}
-
-// K3w of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
-template <int MODEL>
-static void launch_weight_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_img, int plane0, hipStream_t s) {
-    launch_gather<MODEL>(h, n_img, [&](auto l, auto frac, dim3 grid, const char *cev) {
-        using L = decltype(l);
-        hipLaunchKernelGGL((k_weight_gather<L, MODEL, frac.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev, wp, ra,
-                           h->gw_packed + (int64_t)plane0 * h->gw_plane, h->gw_plane);
-    });
-}
-
 // cmax_objective_event_grad: grad_events[src[i]] = (sum_k gx, sum_k gy, sum_k c) over the planes of ge_packed in index order (+ the un-warped image's
 // x and y planes), behind a zero fill of grad_events.  csum[k] = sum_i c_{i,k} in fp64 without atomics: a fixed tree per workgroup into
 // part[k][block], folded by k_event_csum_finish in a fixed order -- the same bits on every run.
@@ -4092,20 +2985,6 @@ __global__ void __launch_bounds__(256) k_event_csum_finish(const double *__restr
         for (int64_t b = threadIdx.x; b < n_blocks; b += 256) a += part[(int64_t)k * n_blocks + b];
     const double tot = block_sum_256(a, s_red);
     if (threadIdx.x == 0) csum[k] = tot;
-}
-
-// K3e of n_img images (MODEL >= 0: the reference times of the objective; -1: the un-warped events) into planes plane0 ..
-template <int MODEL>
-static void launch_event_gather(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_img, int plane0, hipStream_t s) {
-    RefArgs ra = ra_in;
-    if (h->weighted) ra.wgt = h->w_packed;
-    launch_gather<MODEL>(h, n_img, [&](auto l, auto frac, dim3 grid, const char *cev) {
-        using L = decltype(l);
-        with_bool(h->weighted, [&](auto wgt) {
-            hipLaunchKernelGGL((k_event_grad_gather<L, MODEL, frac.value, wgt.value>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, (const int4 *)ra.win, ev,
-                               wp, ra, h->ge_packed + (int64_t)plane0 * h->ge_plane, h->ge_plane);
-        });
-    });
 }
 
 // the first n_planes of a packed per-event buffer (gw_packed: 5 planes, ge_packed: kEventGradPlanes), zeroed; a plane is sized like w_packed
@@ -4622,63 +3501,6 @@ int cmax_comm_allreduce(cmax_handle_t h, void *buf, int64_t count, int dtype, in
 
 namespace cmax {
 
-// tangent votes of every reference time (blockIdx.y) into draw + k * tp.bs (zeroed by the caller); draw64: the integer images of
-// deterministic mode.  A weighted handle passes its weights behind them (a weighted deterministic handle is refused at every entry).
-template <int MODEL>
-static void launch_vote_tan(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, float *draw, hipStream_t s,
-                            long long *draw64 = nullptr) {
-    if (h->weighted && draw64) std::abort();
-    const dim3 grid(seg_blocks(h->nseg), n_ref);
-    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing, as in launch_vote)
-        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-            using L = decltype(l);
-            with_bool(h->has_frac, [&](auto frac) {
-                if (h->weighted)
-                    hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, const float *, const float *, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs,
-                                       h->nseg, draw, h->d_stat_tan, draw64, (const float *)h->w_packed, (const float *)h->d_wnorm, exact...);
-                else
-                    hipLaunchKernelGGL((k_vote_tan<L, MODEL, frac.value, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, draw, h->d_stat_tan,
-                                       draw64, exact...);
-            });
-        });
-    };
-    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
-        if (wp.motion_f64) {
-            launch(ExactFlow{1});
-            return;
-        }
-    }
-    launch();
-}
-
-// det: the integer accumulators of deterministic mode (HvpDet{} otherwise); weights as launch_vote_tan
-template <int MODEL>
-static void launch_grad_hvp(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const TanParams &tp, int n_ref, const float *G,
-                            const float *Gp, double *gpart, float *hflow, hipStream_t s, const HvpDet &det) {
-    if (h->weighted && h->deterministic) std::abort();
-    const dim3 grid(seg_blocks(h->nseg), n_ref);
-    auto launch = [&](auto... exact) {  // (an ExactFlow or nothing, as in launch_vote)
-        with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {
-            using L = decltype(l);
-            with_bool(h->has_frac, [&](auto frac) {
-                if (h->weighted)
-                    hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, const float *, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart,
-                                       hflow, det, (const float *)h->w_packed, exact...);
-                else
-                    hipLaunchKernelGGL((k_grad_hvp<L, MODEL, frac.value, decltype(exact)...>), grid, dim3(L::kThr), 0, s, ev, wp, tp, h->d_segs, h->nseg, G, Gp, gpart, hflow, det,
-                                       exact...);
-            });
-        });
-    };
-    if constexpr (MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL) {
-        if (wp.motion_f64) {
-            launch(ExactFlow{1});
-            return;
-        }
-    }
-    launch();
-}
-
 // scratch of the second-order path and of the IWE layer: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
 static int tangent_scratch(cmax_handle_s *h) {
     if (h->hvp_img) return 0;
@@ -5126,6 +3948,9 @@ int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_
 // RANK'S SHARE -- the patch plan carries it through the (linear) adjoints of the voxel chain and of the patch interpolation and
 // all-reduces 2 n_patch numbers instead of 2 H W [T]
 namespace cmax {
+#ifdef CMAX_TIMELINE
+int image_timeline_set(unsigned long long *buffer) { return timeline_set(buffer); }
+#endif
 bool handle_has_comm(cmax_handle_t h) { return h && h->comm != nullptr; }
 int objective_dist_local_grad(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s) {
     CMAX_REFUSE_WEIGHTED(h, "patch plan evaluation");
@@ -5169,7 +3994,6 @@ int handle_allreduce_sum_with_scalars(cmax_handle_t h, void *buf, size_t count, 
 }  // namespace cmax
 
 extern "C" {
-
 
 int cmax_sizeof_objective(void) { return (int)sizeof(cmax_objective_t); }
 
@@ -5314,20 +4138,6 @@ int cmax_handle_info(cmax_handle_t h, int64_t *n_events, int64_t *workspace_byte
     return 0;
 }
 
-// tools/timeline.py: where the event kernels record their phase stamps (device buffer of 2 x 4096 x 8 u64; NULL: off).  Only
-// libraries built with -DCMAX_TIMELINE record anything; the others return CMAX_ESTATE.
-int cmax_debug_timeline(void *device_buffer) {
-#ifdef CMAX_TIMELINE
-    unsigned long long *p = static_cast<unsigned long long *>(device_buffer);
-    CMAX_CHECK_HIP(hipMemcpyToSymbol(HIP_SYMBOL(cmax::g_timeline), &p, sizeof(p)));
-    return 0;
-#else
-    (void)device_buffer;
-    set_error("debug_timeline: this library was built without -DCMAX_TIMELINE");
-    return CMAX_ESTATE;
-#endif
-}
-
 int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start_out, int *n_groups_host, cmax_stream_t stream) {
     CMAX_REQUIRE(h != nullptr && events_out != nullptr, "debug_packed_events");
     const int ngroups = h->ntr * h->ntc * (h->n_time_bin > 0 ? h->n_time_bin : 1);
@@ -5335,22 +4145,6 @@ int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start
     if (h->n > 0) CMAX_CHECK_HIP(hipMemcpyAsync(events_out, h->evp, (size_t)h->n * sizeof(uint2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
     if (group_start_out)
         CMAX_CHECK_HIP(hipMemcpyAsync(group_start_out, h->d_tile_start, (size_t)(ngroups + 1) * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
-}
-
-// Launch floor of the current work list: `pairs` times two dependent EMPTY launches with the grids of K1 and K3 of a single-reference
-// objective on this batch (the launch structure of the headline evaluation).  bench.py brackets it with events: what the evaluation
-// would cost if its kernels did nothing (profiles/r03_launch_floor.txt measured the same with tools/microbench_launch.hip).
-int cmax_debug_launch_floor(cmax_handle_t h, int pairs, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr && pairs > 0, "debug_launch_floor");
-    CMAX_REQUIRE(h->n > 0 && h->nseg > 0, "debug_launch_floor: no events set");
-    const dim3 grid(seg_blocks(h->nseg));
-    const int k1 = layout_threads(vote_layout(h)), k3 = layout_threads(grad_layout(h, CMAX_MODEL_2DOF, false));
-    for (int i = 0; i < pairs; ++i) {
-        hipLaunchKernelGGL(k_empty, grid, dim3(k1), 0, (hipStream_t)stream, h->d_segs);
-        hipLaunchKernelGGL(k_empty, grid, dim3(k3), 0, (hipStream_t)stream, h->d_segs);
-    }
-    CMAX_CHECK_LAUNCH();
     return 0;
 }
 

@@ -55,7 +55,7 @@ __device__ __forceinline__ int sort_voxel_bin(double tau, int T) {
 // The 8 bits above the source pixel of an UN-BINNED handle's packed word hold the residual of the normalised time that fp32
 // cannot: tau = (double)tau32 + q * ulp(tau32) / 256, q in [-128, 127] -- 32 significant bits, enough to decide on which
 // side of a cell border an event lies exactly like the reference's fp64 arithmetic does (see warp_one).  Binned handles keep
-// the voxel time bin there.
+// the voxel time bin there.  (The event kernels decode it: tau_refined, cmax_event_launch.hip.)
 __device__ __forceinline__ uint32_t tau_residual8(double tn) {
     const float hi = (float)tn;
     const uint32_t eb = __float_as_uint(hi) & 0x7F800000u;
@@ -64,12 +64,6 @@ __device__ __forceinline__ uint32_t tau_residual8(double tn) {
     int q = (int)rint((tn - (double)hi) / unit);
     q = q < -128 ? -128 : (q > 127 ? 127 : q);
     return (uint32_t)q & 0xFFu;
-}
-__device__ __forceinline__ double tau_refined(uint2 e) {
-    const uint32_t eb = e.y & 0x7F800000u;
-    const int q = (int)e.x >> 24;  // sign-extended
-    const double hi = (double)__uint_as_float(e.y);
-    return eb < (32u << 23) ? hi : hi + (double)q * (double)__uint_as_float(eb - (31u << 23));
 }
 
 // One event as the sort sees it.

@@ -14,7 +14,7 @@ plus a residual byte) and 0.25 ulp of the event's fp32 displac
 |delta| log-uniform from max(2^-28, LOWER) to 2^-12 px, both signs -- it asks whether exact_margin is wide enough wherever fp32 can still
 flip, without restating it.  An exact tie is not defined and not built.
 
-`fp32_cells` restates the device's split-base fp32 arithmetic (ix + floor(fl(rx +- dt32 f32) + 1e-6f), cmax_fused.hip warp_one) in numpy:
+`fp32_cells` restates the device's split-base fp32 arithmetic (ix + floor(fl(rx +- dt32 f32) + 1e-6f), cmax_event_launch.hip warp_one) in numpy:
 what a kernel WITHOUT exact cells computes.  tests/test_cell_reference.py asserts per case that it disagrees with the fp64 cell often
 enough, that reading the wrong cell moves the per-event gradient by far more than the gate, and that the checker the GPU test uses
 fails on a result composed from those cells."""

@@ -41,6 +41,13 @@ def test_header_symbols_are_bound_and_exported():
     assert lib.cmax_sizeof_objective() == ctypes.sizeof(_lib.CmaxObjective)
 
 
+def test_build_sources_are_the_translation_units_of_csrc():
+    # a unit missing from build.SOURCES would only show as undefined symbols when the library is linked or loaded
+    units = sorted(f for f in os.listdir(build.CSRC) if f.endswith(".hip"))
+    assert len(build.SOURCES) == len(set(build.SOURCES))
+    assert sorted(build.SOURCES) == units
+
+
 def test_header_constants_match_binding():
     text = open(HEADER).read()
     consts = dict(re.findall(r"#define\s+(CMAX_[A-Z0-9_]+)\s+(-?\d+)", text))

@@ -1,5 +1,5 @@
 #!/usr/bin/env python
-"""Phase timeline of the event kernels K1 / K3 for one bench workload (library built with -DCMAX_TIMELINE, see csrc/cmax_fused.hip):
+"""Phase timeline of the event kernels K1 / K3 for one bench workload (library built with -DCMAX_TIMELINE, see csrc/cmax_fused_device.h):
     CMAX_LIB=gpurun_variants/libtimeline.so python tools/timeline.py cfg2 [cfg4 cfg5 ...]
 Thread 0 of every workgroup stamps the 100 MHz wall clock at its phase boundaries; printed per kernel: when workgroups start
 (dispatch skew), how long each phase takes (median / p90 / max over the workgroups), when they end, and the kernel's span."""
