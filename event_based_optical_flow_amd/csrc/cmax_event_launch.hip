@@ -624,13 +624,8 @@ void launch_vote_tan2(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, 
 
 // the compact copy of the sorted events, one region per segment of the current work list (build_segments, cmax_fused.hip)
 int pack_compact_events(cmax_handle_s *h, hipStream_t s) {
-    if (h->nseg > h->cev_cap) {
-        dev_free(&h->cev);
-        h->cev_cap = 0;
-        int rc = dev_alloc(h, &h->cev, (int64_t)h->nseg * b512::kCompactStride);
-        if (rc) return rc;
-        h->cev_cap = h->nseg;
-    }
+    int rc = h->cev.reserve(&h->bytes, (int64_t)h->nseg * b512::kCompactStride, s);
+    if (rc) return rc;
     hipLaunchKernelGGL((k_pack_compact<b512>), dim3(h->nseg), dim3(b512::kThr), 0, s, (const int4 *)h->d_segs, h->nseg, (const uint2 *)h->evp, h->ntc,
                        h->cev, h->d_flags + 3);
     CMAX_CHECK_HIP(hipGetLastError());

@@ -1312,7 +1312,7 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
     // the pinned read-back mirrors the device allocation: [2 doubles] extremes | [4] flags | [ntiles] active pixels | [ngroups + 1] group starts
     const int64_t off_tmm = 0, off_flags = 4, off_active = 8, off_start = 8 + ntiles;
     (void)want_active;
-    int rc = pinned_reserve(&h->hp_read, &h->hp_read_cap, off_start + ngroups + 1);
+    int rc = h->hp_read.reserve(off_start + ngroups + 1);
     if (rc) return rc;
     const int *group_start = h->hp_read + off_start;
     CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_read, h->d_batch, (size_t)(off_start + ngroups + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
@@ -1497,32 +1497,25 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
     if (debug_segs)
         fprintf(stderr, "[cmax] work list: n=%lld groups=%d segments=%d owned=%d big=%d small_acc=%d\n", (long long)h->n, ngroups, h->nseg, (int)h->owned,
                 (int)h->big, (int)h->small_acc);
-    if (h->nseg > h->seg_cap) {
-        dev_free(&h->d_segs);
-        dev_free(&h->d_gpart);
-        dev_free(&h->d_win);
-        dev_free(&h->d_shifts);
-        // the workspace of cmax_objective_batch is sized by the work list too: allocated again on its next call
-        dev_free(&h->bimg);
-        dev_free(&h->braw);
-        dev_free(&h->bwin);
-        dev_free(&h->bshifts);
-        h->batch_cap = h->batch_seg_cap = 0;
-        h->seg_cap = 0;
-        int rc = dev_alloc(h, &h->d_segs, h->nseg);
-        if (!rc) rc = dev_alloc(h, &h->d_win, (int64_t)4 * h->nseg);
-        if (!rc) rc = dev_alloc(h, &h->d_shifts, (int64_t)4 * h->nseg * kShiftWordsMax);
-        if (!rc) rc = dev_alloc(h, &h->d_gpart, (int64_t)4 * h->nseg * 2);
+    if (h->nseg > h->d_segs.capacity()) {
+        // the workspace of cmax_objective_batch is sized by the work list too (its layout: batch_seg_cap): allocated again on its next call
+        rc = release_all(s, h->d_segs, h->d_gpart, h->d_win, h->d_shifts, h->bimg, h->braw, h->bwin, h->bshifts);
         if (rc) return rc;
-        // (K3 reads an offset word only where K1 flagged its block; cleared once so that no word ever holds allocator garbage)
-        CMAX_CHECK_HIP(hipMemsetAsync(h->d_shifts, 0, (size_t)4 * h->nseg * kShiftWordsMax * sizeof(unsigned), s));
-        h->seg_cap = h->nseg;
+        h->batch_cap = h->batch_seg_cap = 0;
     }
+    bool fresh = false;
+    rc = h->d_segs.reserve(&h->bytes, h->nseg, s);
+    if (!rc) rc = h->d_win.reserve(&h->bytes, (int64_t)4 * h->nseg, s);
+    if (!rc) rc = h->d_shifts.reserve(&h->bytes, (int64_t)4 * h->nseg * kShiftWordsMax, s, &fresh);
+    if (!rc) rc = h->d_gpart.reserve(&h->bytes, (int64_t)4 * h->nseg * 2, s);
+    if (rc) return rc;
+    // (K3 reads an offset word only where K1 flagged its block; cleared once so that no word ever holds allocator garbage)
+    if (fresh) CMAX_CHECK_HIP(hipMemsetAsync(h->d_shifts, 0, (size_t)h->d_shifts.capacity() * sizeof(unsigned), s));
     if (h->nseg > 0) {
         // upload from pinned memory, no wait: the buffer is only rewritten after the event below has passed
         if (h->segs_copied) CMAX_CHECK_HIP(hipEventSynchronize(h->segs_copied));
         else CMAX_CHECK_HIP(hipEventCreateWithFlags(&h->segs_copied, hipEventDisableTiming));
-        rc = pinned_reserve(&h->hp_segs, &h->hp_segs_cap, h->nseg);
+        rc = h->hp_segs.reserve(h->nseg);
         if (rc) return rc;
         std::memcpy(h->hp_segs, segs.data(), segs.size() * sizeof(int4));
         CMAX_CHECK_HIP(hipMemcpyAsync(h->d_segs, h->hp_segs, segs.size() * sizeof(int4), hipMemcpyHostToDevice, s));
@@ -1555,25 +1548,27 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
 
 // Order `n_in` events from `src` for h->n_time_bin (cmax_sort_kernels.h) into the handle's SoA, then build the work
 // list.  first_flag: d_flags[first_flag .. 3] are cleared (0 for a new batch; 1 keeps "fractional sources" when re-binning).
+// the handle's own event arrays and their staging copies change roles
+static void swap_event_arrays(cmax_handle_s *h) {
+    swap(h->evp, h->evp_alt);
+    swap(h->rx, h->rx_alt);
+    swap(h->ry, h->ry_alt);
+    swap(h->rl, h->rl_alt);
+    swap(h->tau64, h->tau64_alt);
+    swap(h->src, h->src_alt);
+}
+
 template <typename SRC>
 static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool reduce_time, int first_flag, hipStream_t s) {
     const int ntiles = h->ntr * h->ntc, T = h->n_time_bin;
-    if (h->cap_alt < h->cap) {  // staging SoA of the bucket pass
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->evp_alt);
-        dev_free(&h->rx_alt);
-        dev_free(&h->ry_alt);
-        dev_free(&h->rl_alt);
-        dev_free(&h->tau64_alt);
-        dev_free(&h->src_alt);
-        int rc = dev_alloc(h, &h->evp_alt, h->cap + 2);
-        if (!rc) rc = dev_alloc(h, &h->rx_alt, h->cap);
-        if (!rc) rc = dev_alloc(h, &h->ry_alt, h->cap);
-        if (!rc) rc = dev_alloc(h, &h->rl_alt, h->cap);
-        if (!rc) rc = dev_alloc(h, &h->tau64_alt, h->cap);
-        if (!rc) rc = dev_alloc(h, &h->src_alt, h->cap);
+    {  // staging SoA of the bucket pass: as large as the handle's own arrays (cmax_set_events releases it when those grow)
+        int rc = h->evp_alt.reserve(&h->bytes, h->evp.capacity(), s);
+        if (!rc) rc = h->rx_alt.reserve(&h->bytes, h->rx.capacity(), s);
+        if (!rc) rc = h->ry_alt.reserve(&h->bytes, h->ry.capacity(), s);
+        if (!rc) rc = h->rl_alt.reserve(&h->bytes, h->rl.capacity(), s);
+        if (!rc) rc = h->tau64_alt.reserve(&h->bytes, h->tau64.capacity(), s);
+        if (!rc) rc = h->src_alt.reserve(&h->bytes, h->src.capacity(), s);
         if (rc) return rc;
-        h->cap_alt = h->cap;
     }
 
     SortOut stage = {h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt, h->src_alt};
@@ -1625,28 +1620,17 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
         const int nwg = (int)std::min<int64_t>(kRsMaxGroups, std::max<int64_t>(1, div_up(n_in, (int64_t)kRsChunk)));
         const int64_t range = (int64_t)div_up(div_up(n_in, (int64_t)nwg), (int64_t)kRsThreads) * kRsThreads;
         const int64_t need = ((int64_t)1 << maxbits) * nwg + 1;
-        if (need > h->rs_hist_cap) {
-            CMAX_CHECK_HIP(hipStreamSynchronize(s));
-            dev_free(&h->rs_hist);
-            dev_free(&h->rs_tmp);
-            h->rs_hist_cap = 0;
-            int rc = dev_alloc(h, &h->rs_hist, need);
-            if (!rc) rc = dev_alloc(h, &h->rs_tmp, div_up(need, (int64_t)kScanChunk) + 2);
-            if (rc) return rc;
-            h->rs_hist_cap = need;
-        }
+        int rc = need > h->rs_hist.capacity() ? release_all(s, h->rs_hist, h->rs_tmp) : 0;
+        if (!rc) rc = h->rs_hist.reserve(&h->bytes, need, s);
+        if (!rc) rc = h->rs_tmp.reserve(&h->bytes, div_up(need, (int64_t)kScanChunk) + 2, s);
+        if (rc) return rc;
         hipLaunchKernelGGL(k_rs_clear, dim3(div_up(std::max(ntiles, 4), 256)), dim3(256), 0, s, h->d_active, ntiles, h->d_flags, first_flag, keys);
         if (!key.fine && keys)  // (the first digit needs the time bin: the batch's extremes first)
             hipLaunchKernelGGL((k_rs_time_extremes<SRC>), dim3(nwg), dim3(kRsThreads), 0, s, src, n_in, keys);
         // pass q writes buffer (P - 1 - q) % 2 (0: the handle's own arrays, 1: the staging copy), so that the last pass lands in the own arrays.
         // Re-binning reads the own arrays: when pass 0 would write them too, the two sets swap roles first (the source then IS the staging set).
         if (!std::is_same<SRC, RawSource<float>>::value && !std::is_same<SRC, RawSource<double>>::value && (P - 1) % 2 == 0) {
-            std::swap(h->evp, h->evp_alt);
-            std::swap(h->rx, h->rx_alt);
-            std::swap(h->ry, h->ry_alt);
-            std::swap(h->rl, h->rl_alt);
-            std::swap(h->tau64, h->tau64_alt);
-            std::swap(h->src, h->src_alt);
+            swap_event_arrays(h);
             std::swap(stage, fin);
         }
         // the number of packed events (every pass's scan writes it again): where the other pipeline keeps its total, outside the histogram
@@ -1682,12 +1666,7 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
         hipLaunchKernelGGL(k_slab_regroup, dim3(ngroups), dim3(256), 0, s, h->d_tile_start, h->cursor, h->ntc, T, fin, stage, h->d_flags);
         CMAX_CHECK_LAUNCH();
         CMAX_CHECK_HIP(hipMemcpyAsync(h->d_tile_start, h->cursor, (size_t)(ngroups + 1) * sizeof(int), hipMemcpyDeviceToDevice, s));
-        std::swap(h->evp, h->evp_alt);
-        std::swap(h->rx, h->rx_alt);
-        std::swap(h->ry, h->ry_alt);
-        std::swap(h->rl, h->rl_alt);
-        std::swap(h->tau64, h->tau64_alt);
-        std::swap(h->src, h->src_alt);
+        swap_event_arrays(h);
     }
     static const bool run_sort = !getenv("CMAX_NO_RUN_SORT");
     BatchReadback rb;
@@ -1698,12 +1677,7 @@ static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool redu
             // while the host cuts the segments: it needs nothing from the host and changes nothing the host reads back.
             hipLaunchKernelGGL(k_run_time_sort, dim3(div_up(n_in, kRunSortChunk)), dim3(256), 0, s, fin, stage, h->counts + ntiles, h->d_flags);
             CMAX_CHECK_LAUNCH();
-            std::swap(h->evp, h->evp_alt);
-            std::swap(h->rx, h->rx_alt);
-            std::swap(h->ry, h->ry_alt);
-            std::swap(h->rl, h->rl_alt);
-            std::swap(h->tau64, h->tau64_alt);
-            std::swap(h->src, h->src_alt);
+            swap_event_arrays(h);
         }
         return 0;
     });
@@ -1747,15 +1721,9 @@ __global__ void k_weights_norm(float *__restrict__ wnorm) {
 // the packed-order copy of the kept weights for the CURRENT order of the batch (after cmax_set_event_weights and after every re-ordering)
 static int gather_weights(cmax_handle_s *h, hipStream_t s) {
     const int64_t n_pad = h->n + kWeightPad;
-    if (n_pad > h->w_packed_cap) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->w_packed);
-        h->w_packed_cap = 0;
-        int rc = dev_alloc(h, &h->w_packed, n_pad);
-        if (rc) return rc;
-        h->w_packed_cap = n_pad;
-    }
-    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm);
+    int rc = h->w_packed.reserve(&h->bytes, n_pad, s);
+    if (rc) return rc;
+    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm.get());
     CMAX_CHECK_HIP(hipMemsetAsync(flags + 2, 0, sizeof(unsigned), s));
     hipLaunchKernelGGL(k_weights_gather, dim3(div_up(n_pad, 256)), dim3(256), 0, s, (const float *)h->w_user, (const int *)h->src, h->n, n_pad, h->w_packed, flags);
     hipLaunchKernelGGL(k_weights_norm, dim3(1), dim3(1), 0, s, h->d_wnorm);
@@ -1834,29 +1802,29 @@ int cmax_create(int H, int W, int ph, int pw, cmax_handle_t *out) {
     h->ntc = div_up(W, kTile);
     h->nkeys = h->ntr * h->ntc * kTile * kTile;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
-    int rc = dev_alloc(h, &h->imgs, 2 * 5 * npix);
-    for (int k = 0; k < 5 && !rc; ++k) rc = dev_alloc(h, &h->iweb[k], npix);
-    if (!rc) rc = dev_alloc(h, &h->G, 4 * npix);  // dL/dIWE of up to 4 reference times
-    if (!rc) rc = dev_alloc(h, &h->Gt, npix);
+    int rc = h->imgs.reserve(&h->bytes, 2 * 5 * npix, nullptr);
+    for (int k = 0; k < 5 && !rc; ++k) rc = h->iweb[k].reserve(&h->bytes, npix, nullptr);
+    if (!rc) rc = h->G.reserve(&h->bytes, 4 * npix, nullptr);  // dL/dIWE of up to 4 reference times
+    if (!rc) rc = h->Gt.reserve(&h->bytes, npix, nullptr);
     {
         const int ntiles = h->ntr * h->ntc;
         const int64_t nints = 4 /* tmm */ + 4 /* flags */ + ntiles + ((int64_t)ntiles * 256 + 1);  // tile starts: up to 255 time bins per tile
-        if (!rc) rc = dev_alloc(h, &h->d_batch, nints);
+        if (!rc) rc = h->d_batch.reserve(&h->bytes, nints, nullptr);
         if (!rc) {
-            h->d_tmm = reinterpret_cast<double *>(h->d_batch);
+            h->d_tmm = reinterpret_cast<double *>(h->d_batch.get());
             h->d_flags = h->d_batch + 4;
             h->d_active = h->d_batch + 8;
             h->d_tile_start = h->d_batch + 8 + ntiles;
         }
     }
-    if (!rc) rc = dev_alloc(h, &h->d_stat, kStatSlots * kStatStride);
-    if (!rc) rc = dev_alloc(h, &h->counts, h->nkeys + 1);
-    if (!rc) rc = dev_alloc(h, &h->cursor, h->nkeys);
-    if (!rc) rc = dev_alloc(h, &h->scan_tmp, div_up(h->nkeys, kScanChunk) + 1);
-    if (!rc) rc = dev_alloc(h, &h->d_raw, 4 * kRawStride);
-    if (!rc) rc = dev_alloc(h, &h->d_host_result, 8);
-    if (!rc) rc = dev_alloc(h, &h->d_musum, 2 * 4 * kMuStride);
-    if (!rc) rc = dev_alloc(h, &h->d_ticket, kTicketLines * kTicketLineInts);
+    if (!rc) rc = h->d_stat.reserve(&h->bytes, kStatSlots * kStatStride, nullptr);
+    if (!rc) rc = h->counts.reserve(&h->bytes, h->nkeys + 1, nullptr);
+    if (!rc) rc = h->cursor.reserve(&h->bytes, h->nkeys, nullptr);
+    if (!rc) rc = h->scan_tmp.reserve(&h->bytes, div_up(h->nkeys, kScanChunk) + 1, nullptr);
+    if (!rc) rc = h->d_raw.reserve(&h->bytes, 4 * kRawStride, nullptr);
+    if (!rc) rc = h->d_host_result.reserve(&h->bytes, 8, nullptr);
+    if (!rc) rc = h->d_musum.reserve(&h->bytes, 2 * 4 * kMuStride, nullptr);
+    if (!rc) rc = h->d_ticket.reserve(&h->bytes, kTicketLines * kTicketLineInts, nullptr);
     if (!rc && hipMemset(h->d_ticket, 0, kTicketLines * kTicketLineInts * sizeof(int)) != hipSuccess) {
         set_error("cmax_create: clearing the arrival counters failed");
         rc = CMAX_ENOMEM;
@@ -1879,74 +1847,11 @@ int cmax_destroy(cmax_handle_t h) {
     h->comm = nullptr;
     if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
     for (hipEvent_t e : h->band_ev) (void)hipEventDestroy(e);
-    dev_free(&h->tan);
-    dev_free(&h->d_tanpart);
-    dev_free(&h->img64);
-    dev_free(&h->d_imax);
-    dev_free(&h->g64);
-    dev_free(&h->d_det_inv_scale);
-    dev_free(&h->Gt_det);
-    dev_free(&h->m64);
-    dev_free(&h->imgs);
-    for (int k = 0; k < 5; ++k) dev_free(&h->iweb[k]);
-    dev_free(&h->G);
-    dev_free(&h->Gt);
-    dev_free(&h->d_batch);  // d_tmm, d_flags, d_active and d_tile_start live inside it
-    h->d_tmm = nullptr;
-    h->d_flags = nullptr;
-    h->d_tile_start = nullptr;
-    dev_free(&h->d_stat);
-    dev_free(&h->d_musum);
-    dev_free(&h->d_raw);
-    dev_free(&h->d_host_result);
-    if (h->d_host_grad) (void)hipFree(h->d_host_grad);
-    if (h->hp_out) (void)hipHostFree(h->hp_out);
-    dev_free(&h->d_ticket);
-    dev_free(&h->hvp_img);
-    dev_free(&h->d_stat_tan);
-    dev_free(&h->search_range);
-    if (h->hp_read) (void)hipHostFree(h->hp_read);
-    if (h->hp_segs) (void)hipHostFree(h->hp_segs);
     if (h->segs_copied) (void)hipEventDestroy(h->segs_copied);
     if (h->read_done) (void)hipEventDestroy(h->read_done);
-    dev_free(&h->d_gpart);
-    dev_free(&h->counts);
-    dev_free(&h->cursor);
-    dev_free(&h->scan_tmp);
-    dev_free(&h->rs_hist);
-    dev_free(&h->rs_tmp);
-    dev_free(&h->d_segs);
-    dev_free(&h->d_win);
-    dev_free(&h->d_shifts);
-    dev_free(&h->bimg);
-    dev_free(&h->braw);
-    dev_free(&h->bwin);
-    dev_free(&h->bshifts);
-    dev_free(&h->evp);
-    dev_free(&h->rx);
-    dev_free(&h->ry);
-    dev_free(&h->rl);
-    dev_free(&h->tau64);
-    dev_free(&h->src);
-    dev_free(&h->src_alt);
-    dev_free(&h->w_user);
-    dev_free(&h->w_packed);
-    dev_free(&h->d_wnorm);
-    dev_free(&h->gw_G);
-    dev_free(&h->gw_Gt);
-    dev_free(&h->gw_packed);
-    dev_free(&h->iw_zero);
-    dev_free(&h->ge_packed);
-    dev_free(&h->ge_part);
-    dev_free(&h->cev);
-    dev_free(&h->evp_alt);
-    dev_free(&h->rx_alt);
-    dev_free(&h->ry_alt);
-    dev_free(&h->rl_alt);
-    dev_free(&h->tau64_alt);
     for (int c = 0; c < CMAX_PROF_CLASSES; ++c)
         for (hipEvent_t e : h->prof_ev[c]) (void)hipEventDestroy(e);
-    delete h;
+    delete h;  // (the buffers free themselves)
     return 0;
 }
 
@@ -1966,30 +1871,19 @@ int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, i
     h->n_in = n;
     ++h->generation;
     h->generation_counted = ~(uint64_t)0;
-    if (n > h->cap) {
-        // the old buffers may still be in use by work queued on the stream
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->evp);
-        dev_free(&h->rx);
-        dev_free(&h->ry);
-        dev_free(&h->rl);
-        dev_free(&h->tau64);
-        dev_free(&h->src);
-        int rc = dev_alloc(h, &h->evp, n + 2);  // +2: the vector loads may touch one event past the end
-        if (!rc) rc = dev_alloc(h, &h->rx, n);
-        if (!rc) rc = dev_alloc(h, &h->ry, n);
-        if (!rc) rc = dev_alloc(h, &h->rl, n);
-        if (!rc) rc = dev_alloc(h, &h->tau64, n);
-        if (!rc) rc = dev_alloc(h, &h->src, n);
+    {
+        // All six arrays are freed before the first is allocated again.  Each one then answers for itself: an array that a failed
+        // growth left empty is allocated by the next call, whatever that call's n.
+        const bool grow = n > h->src.capacity();
+        int rc = grow ? release_all(s, h->evp, h->rx, h->ry, h->rl, h->tau64, h->src) : 0;
+        if (!rc) rc = h->evp.reserve(&h->bytes, n ? n + 2 : 0, s);  // +2: the vector loads may touch one event past the end
+        if (!rc) rc = h->rx.reserve(&h->bytes, n, s);
+        if (!rc) rc = h->ry.reserve(&h->bytes, n, s);
+        if (!rc) rc = h->rl.reserve(&h->bytes, n, s);
+        if (!rc) rc = h->tau64.reserve(&h->bytes, n, s);
+        if (!rc) rc = h->src.reserve(&h->bytes, n, s);
+        if (!rc && grow) rc = release_all(s, h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt, h->src_alt);  // the staging SoA follows (sort_events)
         if (rc) return rc;
-        h->cap = n;
-        dev_free(&h->evp_alt);  // the staging SoA follows (sort_events)
-        dev_free(&h->rx_alt);
-        dev_free(&h->ry_alt);
-        dev_free(&h->rl_alt);
-        dev_free(&h->tau64_alt);
-        dev_free(&h->src_alt);
-        h->cap_alt = 0;
     }
     // global time extremes: given (a time slice of a larger batch), or reduced by the first sort kernel
     if (have_tminmax) {
@@ -2082,24 +1976,15 @@ int cmax_set_event_weights(cmax_handle_t h, const void *weights, int dtype, int6
         h->wmax_host = 0.0;
         return 0;
     }
-    if (!h->d_wnorm) {
-        int rc = dev_alloc(h, &h->d_wnorm, 4);
-        if (rc) return rc;
-    }
-    if (n > h->w_user_cap) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->w_user);
-        h->w_user_cap = 0;
-        int rc = dev_alloc(h, &h->w_user, n);
-        if (rc) return rc;
-        h->w_user_cap = n;
-    }
-    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm);
+    int rc = h->d_wnorm.reserve(&h->bytes, 4, s);
+    if (!rc) rc = h->w_user.reserve(&h->bytes, n, s);
+    if (rc) return rc;
+    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm.get());
     CMAX_CHECK_HIP(hipMemsetAsync(h->d_wnorm, 0, 4 * sizeof(float), s));
     if (dtype == CMAX_F32) hipLaunchKernelGGL((k_weights_keep<float>), dim3(div_up(n, 256)), dim3(256), 0, s, (const float *)weights, n, h->w_user, flags);
     else hipLaunchKernelGGL((k_weights_keep<double>), dim3(div_up(n, 256)), dim3(256), 0, s, (const double *)weights, n, h->w_user, flags);
     CMAX_CHECK_LAUNCH();
-    int rc = gather_weights(h, s);
+    rc = gather_weights(h, s);
     if (rc) return rc;
     // blocks once, like cmax_set_events: the non-finite flag and wmax for cmax_batch_weighted
     float host[4];
@@ -2226,15 +2111,9 @@ static int kernel_motion(cmax_handle_s *h, const cmax_objective_t *d, const void
     *motion = static_cast<const float *>(motion_v);
     if (d->motion_dtype != CMAX_F64 || d->model == CMAX_MODEL_2DOF) return 0;
     const int64_t count = grad_extent(h, d).count;
-    if (2 * count > h->m64_cap) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        if (h->win_motion == h->m64) h->win_motion = nullptr;
-        dev_free(&h->m64);
-        h->m64_cap = 0;
-        int rc = dev_alloc(h, &h->m64, 2 * count);
-        if (rc) return rc;
-        h->m64_cap = 2 * count;
-    }
+    if (2 * count > h->m64.capacity() && h->win_motion == h->m64) h->win_motion = nullptr;  // (windows of a vote on planes that go away)
+    int rc = h->m64.reserve(&h->bytes, 2 * count, s);
+    if (rc) return rc;
     const int vec = (count % 4 == 0 && (reinterpret_cast<uintptr_t>(motion_v) & 15u) == 0) ? 1 : 0;
     const int64_t items = vec ? count / 4 : count;
     hipLaunchKernelGGL(k_split_motion, dim3(stream_grid(items, 256)), dim3(256), 0, s, static_cast<const double *>(motion_v), count, vec, h->m64);
@@ -2561,14 +2440,10 @@ static int finish_without_gather(cmax_handle_s *h, const EvalPlan &p, const ObjP
 
 // room for `count` fixed-point gradient accumulators (deterministic flow gradients; zero between evaluations)
 static int reserve_g64(cmax_handle_s *h, int64_t count, hipStream_t s) {
-    if (count <= h->g64_cap) return 0;
-    CMAX_CHECK_HIP(hipStreamSynchronize(s));
-    dev_free(&h->g64);
-    h->g64_cap = 0;
-    int rc = dev_alloc(h, &h->g64, count);
+    bool fresh = false;
+    int rc = h->g64.reserve(&h->bytes, count, s, &fresh);
     if (rc) return rc;
-    h->g64_cap = count;
-    CMAX_CHECK_HIP(hipMemsetAsync(h->g64, 0, (size_t)count * sizeof(long long), s));
+    if (fresh) CMAX_CHECK_HIP(hipMemsetAsync(h->g64, 0, (size_t)count * sizeof(long long), s));
     return 0;
 }
 
@@ -2576,7 +2451,7 @@ static int reserve_g64(cmax_handle_s *h, int64_t count, hipStream_t s) {
 static int launch_finish_det(cmax_handle_s *h, const cmax_objective_t *d, void *out, hipStream_t s) {
     const int64_t gcount = grad_extent(h, d).count;
     if (d->model == CMAX_MODEL_2DOF)
-        hipLaunchKernelGGL(k_finish_det, dim3(1), dim3(256), 0, s, reinterpret_cast<long long *>(h->d_gpart), h->nseg, d->n_ref, h->d_det_inv_scale, (double *)out);
+        hipLaunchKernelGGL(k_finish_det, dim3(1), dim3(256), 0, s, reinterpret_cast<long long *>(h->d_gpart.get()), h->nseg, d->n_ref, h->d_det_inv_scale, (double *)out);
     else
         hipLaunchKernelGGL(k_fixed_to_grad, dim3(stream_grid(gcount, 256)), dim3(256), 0, s, h->g64, (float *)out, gcount, h->d_det_inv_scale);
     CMAX_CHECK_LAUNCH();
@@ -2597,8 +2472,8 @@ static int finish_gimage(cmax_handle_s *h, const cmax_objective_t *d, const Eval
         hipLaunchKernelGGL(k_image_absmax, dim3(std::min(stream_grid(npix, 1024), 256), d->n_ref), dim3(256), 0, s, im, npix, 0, h->d_imax);
         CMAX_CHECK_LAUNCH();
         if (p.fold == kFoldNone) {  // dL/dIWE with its chain factor: k_gimage on the (blurred) image, then the blur transpose
-            if (d->sigma > 0 && !h->Gt_det) {
-                int rc = dev_alloc(h, &h->Gt_det, 4 * npix);
+            if (d->sigma > 0) {
+                int rc = h->Gt_det.reserve(&h->bytes, 4 * npix, s);
                 if (rc) return rc;
             }
             float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
@@ -2665,7 +2540,7 @@ static int finish_grad_args(cmax_handle_s *h, const cmax_objective_t *d, const E
     }
     if (h->deterministic) {  // the integer-accumulating K3
         ra.imax = h->d_imax;
-        ra.g64 = d->model == CMAX_MODEL_2DOF ? reinterpret_cast<long long *>(h->d_gpart) : h->g64;  // (d_gpart: [4][nseg][6] doubles, 2 used per segment)
+        ra.g64 = d->model == CMAX_MODEL_2DOF ? reinterpret_cast<long long *>(h->d_gpart.get()) : h->g64;  // (d_gpart: [4][nseg][6] doubles, 2 used per segment)
         ra.det_inv_scale = h->d_det_inv_scale;
     }
     return 0;
@@ -2783,12 +2658,11 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
     const int64_t tsize = (int64_t)3 * Hp * Wp + Hp + Wp;
     const int64_t tstride = (tsize + 3) & ~(int64_t)3;  // 16-byte aligned planes: the clearing stores are 16 bytes wide
     int rc = 0;
-    if (!h->tan) {
-        rc = dev_alloc(h, &h->tan, 2 * 4 * tstride);
-        if (!rc) rc = dev_alloc(h, &h->d_tanpart, 4 * kTanBlocks * 6);
-        if (rc) return rc;
-        h->tan_zero_mask[0] = h->tan_zero_mask[1] = 0u;
-    }
+    bool fresh = false;
+    rc = h->tan.reserve(&h->bytes, 2 * 4 * tstride, s, &fresh);
+    if (!rc) rc = h->d_tanpart.reserve(&h->bytes, 4 * kTanBlocks * 6, s);
+    if (rc) return rc;
+    if (fresh) h->tan_zero_mask[0] = h->tan_zero_mask[1] = 0u;
     float *cur = h->tan + (int64_t)h->tan_cur * 4 * tstride, *nxt = h->tan + (int64_t)(h->tan_cur ^ 1) * 4 * tstride;
     RefArgs ra = {};
     fill_ref_times(ra, nr, d->ref_mode, d->ref_frac);
@@ -2988,17 +2862,15 @@ __global__ void __launch_bounds__(256) k_event_csum_finish(const double *__restr
 }
 
 // the first n_planes of a packed per-event buffer (gw_packed: 5 planes, ge_packed: kEventGradPlanes), zeroed; a plane is sized like w_packed
-static int reserve_packed_planes(cmax_handle_s *h, float **packed, int64_t *plane_len, int capacity, int n_planes, hipStream_t s) {
-    if (h->n > *plane_len) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(packed);
+static int reserve_packed_planes(cmax_handle_s *h, DevBuf<float> &packed, int64_t *plane_len, int capacity, int n_planes, hipStream_t s) {
+    if (h->n > *plane_len) {  // (the plane's length is the layout of the buffer too: kept beside it)
         *plane_len = 0;
         const int64_t plane = (h->n + kWeightPad + 3) & ~(int64_t)3;
-        int rc = dev_alloc(h, packed, capacity * plane);
+        int rc = packed.reserve(&h->bytes, capacity * plane, s);
         if (rc) return rc;
         *plane_len = plane;
     }
-    CMAX_CHECK_HIP(hipMemsetAsync(*packed, 0, (size_t)n_planes * *plane_len * sizeof(float), s));
+    CMAX_CHECK_HIP(hipMemsetAsync(packed, 0, (size_t)n_planes * *plane_len * sizeof(float), s));
     return 0;
 }
 
@@ -3035,24 +2907,14 @@ static int per_event_finish(cmax_handle_s *h, const cmax_objective_t *d, const f
     const int64_t npix = (int64_t)Hp * Wp;
     const bool events = grad_events != nullptr;
     const int n_planes = events ? 3 * nr + (d->normalized ? 2 : 0) : nr + (d->normalized ? 1 : 0);
-    int rc = 0;
-    if (!h->gw_G) {
-        rc = dev_alloc(h, &h->gw_G, 5 * npix);
-        if (!rc) rc = dev_alloc(h, &h->gw_Gt, 5 * npix);
-        if (rc) return rc;
-    }
-    rc = events ? reserve_packed_planes(h, &h->ge_packed, &h->ge_plane, kEventGradPlanes, n_planes, s) : reserve_packed_planes(h, &h->gw_packed, &h->gw_plane, 5, n_planes, s);
+    int rc = h->gw_G.reserve(&h->bytes, 5 * npix, s);
+    if (!rc) rc = h->gw_Gt.reserve(&h->bytes, 5 * npix, s);
+    if (rc) return rc;
+    rc = events ? reserve_packed_planes(h, h->ge_packed, &h->ge_plane, kEventGradPlanes, n_planes, s) : reserve_packed_planes(h, h->gw_packed, &h->gw_plane, 5, n_planes, s);
     if (rc) return rc;
     if (events) {  // per-workgroup partial sums of the scatter (csum), [4][blocks]
-        const int64_t blocks = div_up(h->n, 256);
-        if (blocks > h->ge_part_cap) {
-            CMAX_CHECK_HIP(hipStreamSynchronize(s));
-            dev_free(&h->ge_part);
-            h->ge_part_cap = 0;
-            rc = dev_alloc(h, &h->ge_part, 4 * blocks);
-            if (rc) return rc;
-            h->ge_part_cap = blocks;
-        }
+        rc = h->ge_part.reserve(&h->bytes, (int64_t)4 * div_up(h->n, 256), s);
+        if (rc) return rc;
     }
     const ObjParams op = obj_params(h, d);
     double k0 = 0, k1 = 0;
@@ -3220,17 +3082,14 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = d->n_ref;
     if (K > h->batch_cap || h->nseg > h->batch_seg_cap) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->bimg);
-        dev_free(&h->braw);
-        dev_free(&h->bwin);
-        dev_free(&h->bshifts);
+        // the four buffers share one layout (batch_cap candidates, batch_seg_cap segments): all of them go, whichever grew
         const int cap = std::max(K, h->batch_cap), scap = std::max(h->nseg, h->batch_seg_cap);
         h->batch_cap = h->batch_seg_cap = 0;  // (a failed allocation below must not leave a later call believing the workspace is there)
-        rc = dev_alloc(h, &h->bimg, (int64_t)2 * cap * 4 * npix);
-        if (!rc) rc = dev_alloc(h, &h->braw, (int64_t)cap * 4 * kRawStride);
-        if (!rc) rc = dev_alloc(h, &h->bwin, (int64_t)cap * 4 * scap);
-        if (!rc) rc = dev_alloc(h, &h->bshifts, (int64_t)cap * 4 * scap * kShiftWordsMax);
+        rc = release_all(s, h->bimg, h->braw, h->bwin, h->bshifts);
+        if (!rc) rc = h->bimg.reserve(&h->bytes, (int64_t)2 * cap * 4 * npix, s);
+        if (!rc) rc = h->braw.reserve(&h->bytes, (int64_t)cap * 4 * kRawStride, s);
+        if (!rc) rc = h->bwin.reserve(&h->bytes, (int64_t)cap * 4 * scap, s);
+        if (!rc) rc = h->bshifts.reserve(&h->bytes, (int64_t)cap * 4 * scap * kShiftWordsMax, s);
         if (rc) return rc;
         CMAX_CHECK_HIP(hipMemsetAsync(h->bshifts, 0, (size_t)cap * 4 * scap * kShiftWordsMax * sizeof(unsigned), s));
         h->batch_cap = cap;
@@ -3356,7 +3215,7 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
         // MEMORY and then a run counter behind them; the host polls that word.  No copy engine and no driver call between the
         // last kernel and the caller (a 4 KB device-to-host copy of the raw sums + hipStreamQuery polling was 5-6 us slower per
         // evaluation, profiles/r03_ablation.txt 10).
-        rc = pinned_reserve(&h->hp_out, &h->hp_out_cap, (int64_t)4 * kRawStride);
+        rc = h->hp_out.reserve((int64_t)4 * kRawStride);
         if (rc) return rc;
         volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16);
         const unsigned long long seq = ++h->host_seq;
@@ -3385,18 +3244,10 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
         return 0;
     }
     const int64_t gbytes = grad_host ? (int64_t)grad_extent(h, d).bytes : 0;
-    if (gbytes > h->host_grad_bytes) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        if (h->d_host_grad) (void)hipFree(h->d_host_grad);
-        h->d_host_grad = nullptr;
-        h->host_grad_bytes = 0;
-        CMAX_CHECK_HIP(hipMalloc(&h->d_host_grad, (size_t)gbytes));
-        h->host_grad_bytes = gbytes;
-        h->bytes += gbytes;
-    }
-    rc = pinned_reserve(&h->hp_out, &h->hp_out_cap, 8 + (gbytes + 7) / 8);
+    rc = h->d_host_grad.reserve(&h->bytes, gbytes, s);
+    if (!rc) rc = h->hp_out.reserve(8 + (gbytes + 7) / 8);
     if (rc) return rc;
-    rc = objective_eval(h, d, motion, h->d_host_result, grad_host ? h->d_host_grad : nullptr, s, nullptr);
+    rc = objective_eval(h, d, motion, h->d_host_result, grad_host ? h->d_host_grad.get() : nullptr, s, nullptr);
     if (rc) return rc;
     CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out, h->d_host_result, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
     if (grad_host) CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out + 8, h->d_host_grad, (size_t)gbytes, hipMemcpyDeviceToHost, s));
@@ -3412,23 +3263,17 @@ int cmax_set_deterministic(cmax_handle_t h, int enable) {
     if (enable) CMAX_REFUSE_WEIGHTED(h, "set_deterministic");
     if (enable) {  // each buffer on its own: a failed allocation must not leave a later call believing everything is there
         const int64_t npix = (int64_t)h->Hp * h->Wp;
-        if (!h->img64) {
-            int rc = dev_alloc(h, &h->img64, 5 * npix);
-            if (rc) return rc;
-            if (hipMemset(h->img64, 0, (size_t)5 * npix * sizeof(long long)) != hipSuccess) {
-                dev_free(&h->img64);
-                set_error("set_deterministic: clearing the integer images failed");
-                return CMAX_ENOMEM;
-            }
+        bool fresh = false;
+        int rc = h->img64.reserve(&h->bytes, 5 * npix, nullptr, &fresh);
+        if (rc) return rc;
+        if (fresh && hipMemset(h->img64, 0, (size_t)5 * npix * sizeof(long long)) != hipSuccess) {
+            h->img64.release();
+            set_error("set_deterministic: clearing the integer images failed");
+            return CMAX_ENOMEM;
         }
-        if (!h->d_imax) {
-            int rc = dev_alloc(h, &h->d_imax, 8);  // [0..4]: images of the objective; HVP: [0..3] max |G_k|, [4..7] max |G'_k|
-            if (rc) return rc;
-        }
-        if (!h->d_det_inv_scale) {
-            int rc = dev_alloc(h, &h->d_det_inv_scale, 4);
-            if (rc) return rc;
-        }
+        rc = h->d_imax.reserve(&h->bytes, 8, nullptr);  // [0..4]: images of the objective; HVP: [0..3] max |G_k|, [4..7] max |G'_k|
+        if (!rc) rc = h->d_det_inv_scale.reserve(&h->bytes, 4, nullptr);
+        if (rc) return rc;
     }
     h->deterministic = enable != 0;
     h->win_generation = ~(uint64_t)0;  // windows published by the other mode's K1 stay valid, but keep the state simple
@@ -3502,15 +3347,11 @@ int cmax_comm_allreduce(cmax_handle_t h, void *buf, int64_t count, int dtype, in
 namespace cmax {
 
 // scratch of the second-order path and of the IWE layer: [6][4] images, the tangent statistics (k_vote_tan's first workgroup clears them) and Gt
-static int tangent_scratch(cmax_handle_s *h) {
-    if (h->hvp_img) return 0;
+static int tangent_scratch(cmax_handle_s *h, hipStream_t s) {
     const int64_t npix = (int64_t)h->Hp * h->Wp;
-    int rc = dev_alloc(h, &h->hvp_img, 6 * 4 * npix);
-    if (!rc) rc = dev_alloc(h, &h->d_stat_tan, 4 * kStatStride);
-    if (!rc) {
-        dev_free(&h->Gt);
-        rc = dev_alloc(h, &h->Gt, 4 * npix);
-    }
+    int rc = h->hvp_img.reserve(&h->bytes, 6 * 4 * npix, s);
+    if (!rc) rc = h->d_stat_tan.reserve(&h->bytes, 4 * kStatStride, s);
+    if (!rc) rc = h->Gt.reserve(&h->bytes, 4 * npix, s);  // (cmax_create's holds one image)
     return rc;
 }
 
@@ -3566,7 +3407,7 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
     const GradExtent g = grad_extent(h, d);
     CMAX_CHECK_HIP(hipMemsetAsync(hv, 0, g.bytes, s));
     if (h->n == 0 && !dist) return 0;
-    rc = tangent_scratch(h);
+    rc = tangent_scratch(h, s);
     if (rc) return rc;
     // [6 kinds][4 reference times][npix]: every kernel of the chain covers all reference times in one launch
     // (blockIdx.y, element stride npix)
@@ -3682,7 +3523,7 @@ static int objective_hvp_impl(cmax_handle_t h, const cmax_objective_t *d, const 
             rc = reserve_g64(h, g.count, s);
             if (rc) return rc;
         }
-        hd.g64 = two_dof ? reinterpret_cast<long long *>(h->d_gpart) : h->g64;  // (d_gpart: [4][nseg][2] doubles = as many 64-bit integers)
+        hd.g64 = two_dof ? reinterpret_cast<long long *>(h->d_gpart.get()) : h->g64;  // (d_gpart: [4][nseg][2] doubles = as many 64-bit integers)
         hd.imax = h->d_imax;
         hd.inv_scale = h->d_det_inv_scale;
         hd.n_events = h->n;
@@ -3779,7 +3620,7 @@ static int iwes_gather(cmax_handle_s *h, const cmax_objective_t *d, const float 
 static int iwes_weight_grad(cmax_handle_s *h, const cmax_objective_t *d, const float *motion, const float *G, bool with_orig, float *grad_w, hipStream_t s) {
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = d->n_ref, n_planes = nr + (with_orig ? 1 : 0);
-    int rc = reserve_packed_planes(h, &h->gw_packed, &h->gw_plane, 5, n_planes, s);
+    int rc = reserve_packed_planes(h, h->gw_packed, &h->gw_plane, 5, n_planes, s);
     if (rc) return rc;
     const EvView ev = ev_view(h);
     rc = publish_windows(h, d, motion, s);
@@ -3828,7 +3669,7 @@ int cmax_iwes(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, float
     }
     float *raw = images;
     if (o.sigma > 0) {  // votes into the scratch (five consecutive images), the blur writes the caller's buffer
-        rc = tangent_scratch(h);
+        rc = tangent_scratch(h, s);
         if (rc) return rc;
         raw = h->hvp_img;
     }
@@ -3865,17 +3706,12 @@ int cmax_iwes_vjp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
     CMAX_CHECK_HIP(hipMemsetAsync(grad_motion, 0, g.bytes, s));
     if (grad_w && n > 0) CMAX_CHECK_HIP(hipMemsetAsync(grad_w, 0, (size_t)n * sizeof(float), s));
     if (h->n == 0) return 0;
-    rc = tangent_scratch(h);
+    rc = tangent_scratch(h, s);
     if (rc) return rc;
-    if (g.count > h->iw_zero_cap) {  // the zero tangent (once per motion size)
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        dev_free(&h->iw_zero);
-        h->iw_zero_cap = 0;
-        rc = dev_alloc(h, &h->iw_zero, g.count);
-        if (rc) return rc;
-        CMAX_CHECK_HIP(hipMemset(h->iw_zero, 0, (size_t)g.count * sizeof(float)));
-        h->iw_zero_cap = g.count;
-    }
+    bool fresh = false;  // the zero tangent (once per motion size)
+    rc = h->iw_zero.reserve(&h->bytes, g.count, s, &fresh);
+    if (rc) return rc;
+    if (fresh) CMAX_CHECK_HIP(hipMemset(h->iw_zero, 0, (size_t)g.count * sizeof(float)));
     const int n_planes = o.n_ref + ((d->with_orig && grad_w) ? 1 : 0);
     const float *G = nullptr;
     rc = iwes_stage(h, o.sigma, gimages, n_planes, h->hvp_img + 16 * npix, &G, s);
@@ -3901,7 +3737,7 @@ int cmax_iwes_jvp(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_v, c
         CMAX_CHECK_HIP(hipMemsetAsync(dimages, 0, (size_t)nr * npix * sizeof(float), s));
         return 0;
     }
-    rc = tangent_scratch(h);
+    rc = tangent_scratch(h, s);
     if (rc) return rc;
     float *draw = o.sigma > 0 ? h->hvp_img + 8 * npix : dimages;
     CMAX_CHECK_HIP(hipMemsetAsync(draw, 0, (size_t)nr * npix * sizeof(float), s));
@@ -3933,7 +3769,7 @@ int cmax_iwes_vjp_tan(cmax_handle_t h, const cmax_iwes_t *d, const void *motion_
     const GradExtent g = grad_extent(h, &o);
     CMAX_CHECK_HIP(hipMemsetAsync(out, 0, g.bytes, s));
     if (h->n == 0) return 0;
-    rc = tangent_scratch(h);
+    rc = tangent_scratch(h, s);
     if (rc) return rc;
     const float *G = nullptr, *Gp = nullptr;
     rc = iwes_stage(h, o.sigma, gimages, o.n_ref, h->hvp_img, &G, s);
@@ -4072,12 +3908,9 @@ int cmax_patch_search(cmax_handle_t h, int n_patch, const int *boxes, int img_h,
         return CMAX_ESTATE;
     }
     hipStream_t s = (hipStream_t)stream;
-    if (n_patch > h->search_cap) {
-        dev_free(&h->search_range);
-        h->search_cap = 0;
-        int rc = dev_alloc(h, &h->search_range, (size_t)n_patch);
+    {
+        int rc = h->search_range.reserve(&h->bytes, n_patch, s);
         if (rc) return rc;
-        h->search_cap = n_patch;
     }
     CMAX_REQUIRE(h->n_outside == 0, "patch_search: the batch holds events off the sensor (cmax_set_keep_outside)");
     SearchArgs a;

@@ -11,6 +11,7 @@
 #include <type_traits>
 #include <vector>
 
+#include "cmax_buffers.h"
 #include "cmax_comm.h"
 #include "cmax_common.h"
 
@@ -116,7 +117,8 @@ struct ImgArgs {
 struct cmax_handle_s {
     int H = 0, W = 0, ph = 0, pw = 0, Hp = 0, Wp = 0;
     int device = 0;
-    int64_t n = 0, cap = 0;
+    int64_t bytes = 0;  // HBM held by the buffers below (cmax_handle_info): declared before them, their destructors take their bytes off
+    int64_t n = 0;
     int64_t n_dropped = 0;  // events of the last batch whose source pixel was off the sensor (or NaN): not packed
     bool keep_outside = true;  // cmax_set_keep_outside (default since round 5): finite events off the sensor are packed (nearest sensor pixel + residual)
     int64_t n_outside = 0;      // ... how many of the last batch (2-DoF objectives only: a flow has no value there)
@@ -124,44 +126,40 @@ struct cmax_handle_s {
     int n_time_bin = 0;
     bool slab_major = false;  // the (tile, bin) groups are ordered (tile row, time slab, tile column): cmax_set_time_slabs (large motions)
     // packed, sorted events
-    uint2 *evp = nullptr;  // packed events, 8 B each, 16-byte aligned base (+2 elements of padding)
-    float *rx = nullptr, *ry = nullptr;
-    float2 *rl = nullptr;  // low parts of (rx, ry): written and read only for batches with fractional sources
-    double *tau64 = nullptr;
-    int *src = nullptr, *src_alt = nullptr;  // index of every packed event in the caller's array, carried through every re-ordering
+    cmax::DevBuf<uint2> evp;  // packed events, 8 B each, 16-byte aligned base (+2 elements of padding)
+    cmax::DevBuf<float> rx, ry;
+    cmax::DevBuf<float2> rl;  // low parts of (rx, ry): written and read only for batches with fractional sources
+    cmax::DevBuf<double> tau64;
+    cmax::DevBuf<int> src, src_alt;  // index of every packed event in the caller's array, carried through every re-ordering
     // per-event weights (cmax_set_event_weights): the caller's values in the caller's order, the same gathered into packed order (slot l of a
     // segment reads w_packed[first + l]; padded with zeros so that the event kernels load unconditionally), and the normalisation
-    float *w_user = nullptr, *w_packed = nullptr;
-    int64_t w_user_cap = 0, w_packed_cap = 0;
-    float *d_wnorm = nullptr;  // [0] = 1 / wmax (0 when wmax == 0), [1] = wmax = max |w|, [2] = bits of wmax (reduction), [3] = non-finite flag
+    cmax::DevBuf<float> w_user, w_packed;
+    cmax::DevBuf<float> d_wnorm;  // [0] = 1 / wmax (0 when wmax == 0), [1] = wmax = max |w|, [2] = bits of wmax (reduction), [3] = non-finite flag
     bool weighted = false;
     double wmax_host = 0.0;
     int64_t n_in = 0;          // events handed to the last cmax_set_events
     // cmax_objective_weight_grad: finished dL/dIWE images ([5][npix]: reference times 0..3, slot 4 = the un-warped image) and their
     // blur-transpose input, the per-event interpolations in packed order (one plane of gw_plane floats per image), all allocated on first use;
     // general_only: the evaluation inside that call takes the general K1 -> statistics / image kernel -> K3 path on any handle
-    float *gw_G = nullptr, *gw_Gt = nullptr, *gw_packed = nullptr;
+    cmax::DevBuf<float> gw_G, gw_Gt, gw_packed;
     int64_t gw_plane = 0;
     bool general_only = false;
     // cmax_objective_event_grad: (gx, gy, c) per packed event, three planes of ge_plane floats per reference time + two for the un-warped image,
-    // and the scatter's per-workgroup partial sums of c ([4][ge_part_cap]); allocated on first use, grown on demand
-    float *ge_packed = nullptr;
+    // and the scatter's per-workgroup partial sums of c ([4][workgroups]); allocated on first use, grown on demand
+    cmax::DevBuf<float> ge_packed;
     int64_t ge_plane = 0;
-    double *ge_part = nullptr;
-    int64_t ge_part_cap = 0;
+    cmax::DevBuf<double> ge_part;
     // staging SoA of the two-level sort (tile buckets before the per-tile ordering)
-    uint2 *evp_alt = nullptr;
-    float *rx_alt = nullptr, *ry_alt = nullptr;
-    float2 *rl_alt = nullptr;
-    double *tau64_alt = nullptr;
-    int64_t cap_alt = 0;
+    cmax::DevBuf<uint2> evp_alt;
+    cmax::DevBuf<float> rx_alt, ry_alt;
+    cmax::DevBuf<float2> rl_alt;
+    cmax::DevBuf<double> tau64_alt;
     // sort scratch
-    int *counts = nullptr;  // [nkeys + 1] events per tile -> tile offsets after the scan
-    int *cursor = nullptr;  // [nkeys] per-tile cursor of the bucket pass, then active source pixels per tile
-    int *scan_tmp = nullptr;  // [ceil(nkeys / 2048)] chunk sums of the scan
-    int *rs_hist = nullptr;   // radix sort (large batches): [digits][workgroups] + 1 histogram / offsets of one pass
-    int *rs_tmp = nullptr;    // ... chunk sums of its scan
-    int64_t rs_hist_cap = 0;
+    cmax::DevBuf<int> counts;  // [nkeys + 1] events per tile -> tile offsets after the scan
+    cmax::DevBuf<int> cursor;  // [nkeys] per-tile cursor of the bucket pass, then active source pixels per tile
+    cmax::DevBuf<int> scan_tmp;  // [ceil(nkeys / 2048)] chunk sums of the scan
+    cmax::DevBuf<int> rs_hist;   // radix sort (large batches): [digits][workgroups] + 1 histogram / offsets of one pass
+    cmax::DevBuf<int> rs_tmp;    // ... chunk sums of its scan
     int nkeys = 0, ntr = 0, ntc = 0;
     int *d_flags = nullptr;  // [0] any fractional source coordinate, [1] dropped events, [2] events kept from off the sensor (cmax_set_keep_outside)
     bool long_runs = false;  // >= 8 events per active source pixel on average: the dense K3 reduces runs serially per thread
@@ -174,73 +172,65 @@ struct cmax_handle_s {
     int *d_tile_start = nullptr;  // [ngroups + 1] first sorted event of every group (source tile, or (tile, time bin))
     // What the host reads back once per batch lives in ONE allocation, in this order: d_tmm (2 doubles) | d_flags (4 ints) |
     // d_active (ntiles ints) | d_tile_start (...): one device-to-host copy instead of four (each ~4 us of copy latency)
-    int *d_batch = nullptr;   // base of that allocation (as ints)
+    cmax::DevBuf<int> d_batch;   // base of that allocation (as ints)
     int *d_active = nullptr;  // [ntiles] source pixels that hold events, per tile (un-binned order; written by k_tile_sort)
-    int4 *d_segs = nullptr;       // [nseg] (begin, count, first source tile, tiles spanned): work items of the event kernels
-    int4 *d_win = nullptr;        // [4][nseg] LDS windows of the last objective vote (K1 -> K3 of the same evaluation)
+    cmax::DevBuf<int4> d_segs;       // [nseg] (begin, count, first source tile, tiles spanned): work items of the event kernels
+    cmax::DevBuf<int4> d_win;        // [4][nseg] LDS windows of the last objective vote (K1 -> K3 of the same evaluation)
     // compact copy of the sorted events, one region per segment of the work list (EventLoads in cmax_event_kernels.inc): big segments of
     // un-binned handles; valid for the current work list only (build_segments)
-    char *cev = nullptr;
-    int64_t cev_cap = 0;          // regions allocated
+    cmax::DevBuf<char> cev;
     bool compact = false;
     // cmax_objective_batch: K candidate motions per launch (allocated on first use, sized for batch_cap candidates)
-    float *bimg = nullptr;        // [2 buffers][batch_cap][n_ref <= 4][npix] vote images
-    double *braw = nullptr;       // [batch_cap][4][kRawStride] raw sums
-    int4 *bwin = nullptr;         // [batch_cap][4][nseg] windows
-    unsigned *bshifts = nullptr;  // [batch_cap][4][nseg][kShiftWordsMax]
+    cmax::DevBuf<float> bimg;        // [2 buffers][batch_cap][n_ref <= 4][npix] vote images
+    cmax::DevBuf<double> braw;       // [batch_cap][4][kRawStride] raw sums
+    cmax::DevBuf<int4> bwin;         // [batch_cap][4][nseg] windows
+    cmax::DevBuf<unsigned> bshifts;  // [batch_cap][4][nseg][kShiftWordsMax]
     int batch_cap = 0, batch_seg_cap = 0, batch_cur = 0;
     int batch_zero[2] = {0, 0};  // the first batch_zero[b] images of buffer b are zero
-    unsigned *d_shifts = nullptr; // [4][nseg][kShiftWordsMax] cell offsets of the events that vote decided in fp64 (RefArgs::shifts)
+    cmax::DevBuf<unsigned> d_shifts; // [4][nseg][kShiftWordsMax] cell offsets of the events that vote decided in fp64 (RefArgs::shifts)
     // what those windows were computed for: K3 reuses them only for the same motion / model / reference times
     const float *win_motion = nullptr;
     int win_model = -2, win_nref = 0, win_T = 0, win_normalize = 0;
     float win_d[4] = {0.f, 0.f, 0.f, 0.f};
     uint64_t win_generation = ~(uint64_t)0;
-    int nseg = 0, seg_cap = 0;
+    int nseg = 0;
     // images
-    float *imgs = nullptr;                                  // [2 buffers][5, Hp, Wp] raw votes: one per reference time + un-warped
-    float *iweb[5] = {nullptr, nullptr, nullptr, nullptr, nullptr};  // blurred copies
-    float *G = nullptr, *Gt = nullptr;
+    cmax::DevBuf<float> imgs;                               // [2 buffers][5, Hp, Wp] raw votes: one per reference time + un-warped
+    cmax::DevBuf<float> iweb[5];                            // blurred copies
+    cmax::DevBuf<float> G, Gt;
     const float *last_iwe[4] = {nullptr, nullptr, nullptr, nullptr};
     // device scalars
     double *d_tmm = nullptr;  // [2]
-    double *d_stat = nullptr;   // [5 slots][32 sub-accumulators][2] contrast statistics (slot 4 = un-warped image)
+    cmax::DevBuf<double> d_stat;   // [5 slots][32 sub-accumulators][2] contrast statistics (slot 4 = un-warped image)
     // the handle's own vote images are double-buffered: k_stats of evaluation e zeroes the images of
     // evaluation e+1, so the steady state needs no memset node.  zero_mask[b] bit k: image k of buffer b is zero
     int cur_buf = 0;
     unsigned zero_mask[2] = {0u, 0u};
-    double *d_gpart = nullptr;  // [4 reference times][nseg][2] per-segment 2-DoF partials
-    double *d_raw = nullptr;    // [4 reference times][kRawStride] raw sums of the deferred 2-DoF K3 (cmax_objective's own copy)
+    cmax::DevBuf<double> d_gpart;  // [4 reference times][nseg][2] per-segment 2-DoF partials
+    cmax::DevBuf<double> d_raw;    // [4 reference times][kRawStride] raw sums of the deferred 2-DoF K3 (cmax_objective's own copy)
     // cmax_objective_host: device outputs + pinned staging of one evaluation whose results go straight to the host
-    double *d_host_result = nullptr;  // [8]
-    void *d_host_grad = nullptr;
-    int64_t host_grad_bytes = 0;
-    double *hp_out = nullptr;  // pinned
-    int64_t hp_out_cap = 0;
+    cmax::DevBuf<double> d_host_result;  // [8]
+    cmax::DevBuf<char> d_host_grad;
+    cmax::PinnedBuf<double> hp_out;
     unsigned long long host_seq = 0;  // run counter of the finishing kernel that writes into hp_out (polled by cmax_objective_host)
-    int *d_ticket = nullptr;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches
-    double *d_musum = nullptr;  // [2 buffers][4 reference times][kMuStride] K1's sums for the blurred variance (RefArgs::musum)
+    cmax::DevBuf<int> d_ticket;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches
+    cmax::DevBuf<double> d_musum;  // [2 buffers][4 reference times][kMuStride] K1's sums for the blurred variance (RefArgs::musum)
     int mu_buf = 0;             // buffer the next evaluation adds into (the other one is being cleared / is clear); flipped by the launch that reads the sums
     // orig-IWE cache key
     bool orig_valid = false;
     double orig_sigma = -1;
     int orig_cost = -1, orig_omit = -1;
     double tmin_host = 0.0, tmax_host = 0.0;  // batch extremes (copied once per batch)
-    float *hvp_img = nullptr;                 // [6 kinds][4 reference times][Hp, Wp] scratch of cmax_objective_hvp (allocated on first use)
-    float *iw_zero = nullptr;                 // cmax_iwes_vjp: a zero tangent of the motion's size (the gather of J^T G is T3 with u = 0, G' = G)
-    int64_t iw_zero_cap = 0;
-    double *d_stat_tan = nullptr;             // [4][kStatStride] tangent statistics
+    cmax::DevBuf<float> hvp_img;              // [6 kinds][4 reference times][Hp, Wp] scratch of cmax_objective_hvp (allocated on first use)
+    cmax::DevBuf<float> iw_zero;              // cmax_iwes_vjp: a zero tangent of the motion's size (the gather of J^T G is T3 with u = 0, G' = G)
+    cmax::DevBuf<double> d_stat_tan;          // [4][kStatStride] tangent statistics
     // pinned host staging of the per-batch read-back (group starts, active pixels per tile, flags, time extremes) and
     // of the work list: copies to / from pageable memory are staged by the runtime and cost a synchronisation each
-    int *hp_read = nullptr;
-    int64_t hp_read_cap = 0;
-    int4 *hp_segs = nullptr;
-    int64_t hp_segs_cap = 0;
+    cmax::PinnedBuf<int> hp_read;
+    cmax::PinnedBuf<int4> hp_segs;
     hipEvent_t segs_copied = nullptr;  // the last upload of hp_segs has left the host buffer
     hipEvent_t read_done = nullptr;    // the per-batch read-back has arrived (the stream may still be busy behind it)
-    float2 *search_range = nullptr;           // [search_cap] (tau_min, tau_max) per patch of cmax_patch_search
-    int search_cap = 0;
-    int64_t bytes = 0;
+    cmax::DevBuf<float2> search_range;        // (tau_min, tau_max) per patch of cmax_patch_search
     uint64_t generation = 0;  // bumped by set_events / set_time_bins (device pointers and the work list change)
     uint64_t generation_counted = ~(uint64_t)0;
     // optional per-kernel-class timing with HIP events (cmax_set_profiling)
@@ -248,10 +238,10 @@ struct cmax_handle_s {
     int prof_repeat = 1;  // > 1: every hot launch is issued this many times inside its event bracket (timing only)
     std::vector<hipEvent_t> prof_ev[CMAX_PROF_CLASSES];  // class -> [start0, stop0, start1, stop1, ...]
     // 2-DoF tangent images (k_vote_tan2): [2 buffers][4 reference times][I: Hp Wp | E0: (Hp + 1) Wp | F1: Hp (Wp + 1)]
-    float *tan = nullptr;
+    cmax::DevBuf<float> tan;
     int tan_cur = 0;
     unsigned tan_zero_mask[2] = {0u, 0u};  // bit k: planes of reference time k of buffer b are zero
-    double *d_tanpart = nullptr;           // [4][kTanBlocks][6] partial sums of k_tan_stats_var
+    cmax::DevBuf<double> d_tanpart;        // [4][kTanBlocks][6] partial sums of k_tan_stats_var
     // time-sliced multi-GPU evaluation: this rank's RCCL communicator (cmax_comm_init), or null
     cmax::Comm *comm = nullptr;
     // C2 in row bands behind K3 (cmax_comm_set_c2_bands): the owned-group K3 of a dense objective is launched band by band (whole
@@ -263,16 +253,14 @@ struct cmax_handle_s {
     // deterministic mode (cmax_set_deterministic): every accumulation that depends on the order of events, workgroups or
     // atomics is done in integers (exact, associative) -- bit-identical IWE, loss and gradient from run to run
     bool deterministic = false;
-    long long *img64 = nullptr;   // [5][npix] fixed-point vote images, all zero between evaluations
-    unsigned *d_imax = nullptr;   // [kStatSlots] bits of max |image| per statistics slot
-    long long *g64 = nullptr;     // fixed-point gradient accumulators (zero between evaluations)
-    int64_t g64_cap = 0;
-    double *d_det_inv_scale = nullptr;  // [4]
-    float *Gt_det = nullptr;      // [4][npix] dL/d(blurred image) of the unfused image path
+    cmax::DevBuf<long long> img64;   // [5][npix] fixed-point vote images, all zero between evaluations
+    cmax::DevBuf<unsigned> d_imax;   // [kStatSlots] bits of max |image| per statistics slot
+    cmax::DevBuf<long long> g64;     // fixed-point gradient accumulators (zero between evaluations)
+    cmax::DevBuf<double> d_det_inv_scale;  // [4]
+    cmax::DevBuf<float> Gt_det;      // [4][npix] dL/d(blurred image) of the unfused image path
     // an fp64 flow / voxel at the boundary (cmax_objective_t::motion_dtype == CMAX_F64, dense / voxel): hi plane | lo plane of the
     // caller's doubles (k_split_motion), allocated on first use
-    float *m64 = nullptr;
-    int64_t m64_cap = 0;            // floats
+    cmax::DevBuf<float> m64;
     const void *m64_src = nullptr;  // whose split the planes hold (cmax_objective_finish: the windows of a vote are another motion's otherwise)
 };
 
@@ -304,26 +292,6 @@ struct ProfScope {
         if (stop) (void)hipEventRecord(stop, s);
     }
 };
-
-// ---------------------------------------------------------------------------------------------
-// memory helpers
-// ---------------------------------------------------------------------------------------------
-template <typename T>
-static int dev_alloc(cmax_handle_s *h, T **p, int64_t count) {
-    if (count <= 0) count = 1;
-    hipError_t e = hipMalloc((void **)p, (size_t)count * sizeof(T));
-    if (e != hipSuccess) {
-        set_error("hipMalloc(%lld bytes) failed: %s", (long long)(count * sizeof(T)), hipGetErrorString(e));
-        return CMAX_ENOMEM;
-    }
-    h->bytes += count * (int64_t)sizeof(T);
-    return 0;
-}
-template <typename T>
-static void dev_free(T **p) {
-    if (*p) (void)hipFree(*p);
-    *p = nullptr;
-}
 
 // how K3 obtains dL/dIWE: from a materialised G image; folded G = c2 (IWE - mu) with the statistics K2 left in
 // `stat`; or (2-DoF) deferred -- K3 gathers the raw image and the image statistics itself, the chain factors are
@@ -397,26 +365,6 @@ struct FixedArgs {
 
 template <int V>
 using int_c = std::integral_constant<int, V>;  // (fold / variant of k_grad)
-
-// pinned host staging, grown on demand
-template <typename T>
-static int pinned_reserve(T **p, int64_t *cap, int64_t count) {
-    if (count <= *cap) return 0;
-    if (*p) (void)hipHostFree(*p);
-    *p = nullptr;
-    *cap = 0;
-    const int64_t want = count + count / 2 + 64;
-    // coherent + mapped: kernels write results and run counters straight into these buffers and the host polls them
-    // (cmax_objective_host, the patch plan's tail) -- visibility must not hang on HIP_HOST_COHERENT; zeroed: a flag word is polled
-    // before anything ever wrote it
-    if (hipHostMalloc((void **)p, (size_t)want * sizeof(T), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) {
-        set_error("hipHostMalloc(%lld bytes) failed", (long long)(want * sizeof(T)));
-        return CMAX_ENOMEM;
-    }
-    std::memset((void *)*p, 0, (size_t)want * sizeof(T));
-    *cap = want;
-    return 0;
-}
 
 constexpr int64_t kWeightPad = 4096 + 16;  // an event kernel's unconditional loads reach at most one segment's slots behind the last event
 

@@ -18,6 +18,7 @@
 #include <atomic>
 #include <vector>
 
+#include "cmax_buffers.h"
 #include "cmax_common.h"
 #include "cmax_image_kernels.h"
 #include "cmax_patch_kernels.h"
@@ -360,25 +361,25 @@ k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *_
 
 }  // namespace cmax
 
-struct cmax_patch_plan_s {
+struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: its implicit destructor is no export)
     cmax_handle_t handle = nullptr;
     cmax_patch_objective_t d;
     int nx = 0;            // 2 * ph * pw
     int64_t nflow = 0;     // 2 * H * W
     int64_t nmotion = 0;   // nflow or T * nflow
-    double *x64 = nullptr, *v64 = nullptr, *flow64 = nullptr, *vox64 = nullptr, *gacc64 = nullptr, *gflow64 = nullptr;
-    double *gx64 = nullptr, *results = nullptr;
+    cmax::DevBuf<double> x64, flow64, vox64, gacc64, gflow64, gx64, results;
+    double *v64 = nullptr;  // (inside x64)
     // time-aware Hessian-vector product (allocated on first use): tangent flow / voxel, tangent of dL/dvoxel, scalars
-    double *dflow64 = nullptr, *dvox64 = nullptr, *dgacc64 = nullptr, *dgflow64 = nullptr, *scal = nullptr;
-    float *motion32 = nullptr, *grad32 = nullptr, *tan32 = nullptr, *gx32 = nullptr;
+    cmax::DevBuf<double> dflow64, dvox64, dgacc64, dgflow64, scal;
+    cmax::DevBuf<float> motion32, grad32, tan32, gx32;
     // the terms carry motion_dtype == CMAX_F64: motion32 is [2][nmotion], the high plane (the fp32 motion of every other plan) and the low
     // plane of the fp64 flow / voxel the plan holds anyway, written by the same conversion launches and read by K1's fp64 cell decisions
     bool exact = false;
     // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
-    double *dense64 = nullptr, *sl = nullptr, *sl_partial = nullptr;
+    cmax::DevBuf<double> dense64, sl, sl_partial;
     double *h_out_dev = nullptr;  // device view of the pinned output: the tail kernel writes the result there
-    double *h_in = nullptr, *h_out = nullptr;  // pinned staging: x | v | 2 scalars, loss | grad | run counter
-    unsigned long long *seq_dev = nullptr;     // device-side run counter of the tail kernel
+    cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter
+    cmax::DevBuf<unsigned long long> seq_dev;  // device-side run counter of the tail kernel
     unsigned long long seq_seen = 0;           // its value after the last completed call
     // Captured launch sequences (hipGraph), replayed on the plan's own stream: an evaluation is ~25 small launches,
     // host-bound when issued one by one.  Keyed by everything that changes the sequence: the kind of call and the
@@ -400,16 +401,6 @@ struct cmax_patch_plan_s {
 using namespace cmax;
 
 namespace {
-
-template <typename T>
-int plan_alloc(T **p, int64_t count) {
-    hipError_t e = hipMalloc((void **)p, (size_t)(count > 0 ? count : 1) * sizeof(T));
-    if (e != hipSuccess) {
-        set_error("patch plan: hipMalloc(%lld bytes) failed: %s", (long long)(count * sizeof(T)), hipGetErrorString(e));
-        return CMAX_ENOMEM;
-    }
-    return 0;
-}
 
 // Time-sliced batches (the handle holds a communicator, cmax_comm_init): the solver's objective is evaluated the way
 // cmax_objective_dist evaluates a fused term -- K1 -> all-reduce(images) -> image kernels -> K3 on this rank's events -- but the
@@ -922,32 +913,32 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     p->nmotion = d.time_aware ? (int64_t)d.T * p->nflow : p->nflow;
     p->exact = d.term[0].motion_dtype == CMAX_F64;
     int rc = 0;
-    if (!rc) rc = plan_alloc(&p->x64, 2 * (int64_t)p->nx + 2);  // x | v | 2 scalars, filled by one copy
+    if (!rc) rc = p->x64.reserve(nullptr, 2 * (int64_t)p->nx + 2, nullptr);  // x | v | 2 scalars, filled by one copy
     if (!rc) p->v64 = p->x64 + p->nx;
-    if (!rc) rc = plan_alloc(&p->flow64, p->nflow);
-    if (!rc && d.time_aware) rc = plan_alloc(&p->vox64, p->nmotion);
-    if (!rc) rc = plan_alloc(&p->gacc64, p->nmotion);
-    if (!rc && d.time_aware) rc = plan_alloc(&p->gflow64, p->nflow);
+    if (!rc) rc = p->flow64.reserve(nullptr, p->nflow, nullptr);
+    if (!rc && d.time_aware) rc = p->vox64.reserve(nullptr, p->nmotion, nullptr);
+    if (!rc) rc = p->gacc64.reserve(nullptr, p->nmotion, nullptr);
+    if (!rc && d.time_aware) rc = p->gflow64.reserve(nullptr, p->nflow, nullptr);
     if (!rc && d.time_aware && d.scale_later) {
-        rc = plan_alloc(&p->dense64, p->nflow);
-        if (!rc) rc = plan_alloc(&p->sl, kSlScalars);
-        if (!rc) rc = plan_alloc(&p->sl_partial, kSlSlots * kSlBlocks);
+        rc = p->dense64.reserve(nullptr, p->nflow, nullptr);
+        if (!rc) rc = p->sl.reserve(nullptr, kSlScalars, nullptr);
+        if (!rc) rc = p->sl_partial.reserve(nullptr, kSlSlots * kSlBlocks, nullptr);
     }
-    if (!rc) rc = plan_alloc(&p->gx64, p->nx);
-    if (!rc) rc = plan_alloc(&p->results, 8 * 4);
-    if (!rc) rc = plan_alloc(&p->motion32, (p->exact ? 2 : 1) * p->nmotion);
-    if (!rc) rc = plan_alloc(&p->grad32, p->nmotion);
-    if (!rc) rc = plan_alloc(&p->tan32, p->nmotion);
-    if (!rc) rc = plan_alloc(&p->gx32, p->nx);
-    if (!rc && hipHostMalloc((void **)&p->h_in, (2 * (size_t)p->nx + 2) * sizeof(double)) != hipSuccess) rc = CMAX_ENOMEM;
+    if (!rc) rc = p->gx64.reserve(nullptr, p->nx, nullptr);
+    if (!rc) rc = p->results.reserve(nullptr, 8 * 4, nullptr);
+    if (!rc) rc = p->motion32.reserve(nullptr, (p->exact ? 2 : 1) * p->nmotion, nullptr);
+    if (!rc) rc = p->grad32.reserve(nullptr, p->nmotion, nullptr);
+    if (!rc) rc = p->tan32.reserve(nullptr, p->nmotion, nullptr);
+    if (!rc) rc = p->gx32.reserve(nullptr, p->nx, nullptr);
+    if (!rc) rc = p->h_in.reserve(2 * (int64_t)p->nx + 2);
     if (!rc && hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) rc = CMAX_ENOMEM;
     if (!rc && hipEventCreateWithFlags(&p->ev_caller, hipEventDisableTiming) != hipSuccess) rc = CMAX_ENOMEM;
-    if (!rc && hipHostMalloc((void **)&p->h_out, (2 + (size_t)p->nx) * sizeof(double), hipHostMallocCoherent | hipHostMallocMapped) != hipSuccess) rc = CMAX_ENOMEM;
+    if (!rc) rc = p->h_out.reserve(2 + (int64_t)p->nx);
     if (!rc && hipHostGetDevicePointer((void **)&p->h_out_dev, p->h_out, 0) != hipSuccess) {
         (void)hipGetLastError();
         p->h_out_dev = p->h_out;  // unified addressing: pinned host memory is addressable from the device as it is
     }
-    if (!rc) rc = plan_alloc(&p->seq_dev, 1);
+    if (!rc) rc = p->seq_dev.reserve(nullptr, 1, nullptr);
     if (!rc && hipMemset(p->seq_dev, 0, sizeof(unsigned long long)) != hipSuccess) rc = CMAX_ENOMEM;
     if (!rc) reinterpret_cast<unsigned long long *>(p->h_out + 1 + p->nx)[0] = 0ull;
     if (rc) {
@@ -981,17 +972,7 @@ int cmax_patch_plan_destroy(cmax_patch_plan_t p) {
     drop_graphs(p);
     if (p->own_stream) (void)hipStreamDestroy(p->own_stream);
     if (p->ev_caller) (void)hipEventDestroy(p->ev_caller);
-    double *d64[] = {p->x64, p->flow64, p->vox64, p->gacc64, p->gflow64, p->gx64, p->results, p->dflow64, p->dvox64, p->dgacc64, p->dgflow64, p->scal,
-                     p->dense64, p->sl, p->sl_partial};
-    for (double *q : d64)
-        if (q) (void)hipFree(q);
-    float *d32[] = {p->motion32, p->grad32, p->tan32, p->gx32};
-    for (float *q : d32)
-        if (q) (void)hipFree(q);
-    if (p->h_in) (void)hipHostFree(p->h_in);
-    if (p->h_out) (void)hipHostFree(p->h_out);
-    if (p->seq_dev) (void)hipFree(p->seq_dev);
-    delete p;
+    delete p;  // (the buffers free themselves)
     return 0;
 }
 
@@ -1019,12 +1000,13 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
         return CMAX_EUNSUPPORTED;
     }
     const cmax_patch_objective_t &d = p->d;
-    if (d.time_aware && !p->dvox64) {  // second-order buffers of the voxel chain, on first use
-        int rc = plan_alloc(&p->dflow64, p->nflow);
-        if (!rc) rc = plan_alloc(&p->dvox64, p->nmotion);
-        if (!rc) rc = plan_alloc(&p->dgacc64, p->nmotion);
-        if (!rc) rc = plan_alloc(&p->dgflow64, p->nflow);
-        if (!rc) rc = plan_alloc(&p->scal, 4);
+    if (d.time_aware) {  // second-order buffers of the voxel chain, on first use
+        hipStream_t s = (hipStream_t)stream;
+        int rc = p->dflow64.reserve(nullptr, p->nflow, s);
+        if (!rc) rc = p->dvox64.reserve(nullptr, p->nmotion, s);
+        if (!rc) rc = p->dgacc64.reserve(nullptr, p->nmotion, s);
+        if (!rc) rc = p->dgflow64.reserve(nullptr, p->nflow, s);
+        if (!rc) rc = p->scal.reserve(nullptr, 4, s);
         if (rc) return rc;
     }
     double vmax = 0.0;
