@@ -87,6 +87,33 @@ class CmaxPatchObjective(ctypes.Structure):
     ]
 
 
+class CmaxDescent(ctypes.Structure):
+    """Mirror of cmax_descent_t (include/cmax_hip.h): every value explicit, torch's defaults are filled by `descent_descriptor`."""
+
+    _fields_ = [
+        ("method", ctypes.c_int32),
+        ("n_iter", ctypes.c_int32),
+        ("lr", ctypes.c_double),
+        ("lr_step", ctypes.c_int32),
+        ("lr_decay", ctypes.c_double),
+        ("momentum", ctypes.c_double),
+        ("beta1", ctypes.c_double),
+        ("beta2", ctypes.c_double),
+        ("eps", ctypes.c_double),
+    ]
+
+
+class CmaxDescentResult(ctypes.Structure):
+    """Mirror of cmax_descent_result_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("best_loss", ctypes.c_double),
+        ("best_iter", ctypes.c_int32),
+        ("n_done", ctypes.c_int32),
+        ("last_lr", ctypes.c_double),
+    ]
+
+
 # constants (include/cmax_hip.h)
 F32, F64 = 0, 1
 MODEL_2DOF, MODEL_DENSE, MODEL_VOXEL = 0, 1, 2
@@ -94,6 +121,10 @@ REF_FIRST, REF_LAST, REF_FRAC = 0, 1, 2
 COST_VARIANCE, COST_GRADMAG = 0, 1
 SCHEME_BURGERS, SCHEME_UPWIND = 0, 1
 FILTER_BILINEAR, FILTER_NEAREST = 0, 1
+OPT_SGD, OPT_ADAM = 0, 1
+OPT_CODES = {"SGD": OPT_SGD, "Adam": OPT_ADAM}
+DESCENT_MAX_ITER = 4096
+EINVAL = -1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
 RAW_LINES = 32
@@ -182,6 +213,10 @@ SIGNATURES = {
     "cmax_patch_plan_evaluate": (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(c_dbl), c_vp, c_vp]),
     "cmax_patch_plan_hvp": (c_int, [c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_plan_set_t_scale": (c_int, [c_vp, c_dbl]),
+    "cmax_sizeof_descent": (c_int, []),
+    "cmax_patch_plan_descend": (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult), c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_objective_descend": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult),
+                                       c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_search": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_vp]),
@@ -227,6 +262,8 @@ def load():
             raise RuntimeError("cmax_iwes_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_patch_objective() != ctypes.sizeof(CmaxPatchObjective):
             raise RuntimeError("cmax_patch_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_descent() != ctypes.sizeof(CmaxDescent):
+            raise RuntimeError("cmax_descent_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libcmax_hip ABI {lib.cmax_abi_version()} != binding ABI {ABI_VERSION}")
         _lib = lib
@@ -239,6 +276,55 @@ def check(rc: int):
         if rc == EUNSUPPORTED:  # a call the library refuses in the handle's state (per-event weights): the library's own text
             raise NotImplementedError(msg.decode("utf-8", "replace") if msg else "unsupported")
         raise CmaxError(rc, msg.decode("utf-8", "replace") if msg else "")
+
+
+def descent_descriptor(method: str = "Adam", n_iter: int = 100, lr: float = 0.05, lr_step=None, lr_decay: float = 0.1, momentum: float = 0.0,
+                       betas=(0.9, 0.999), eps: float = 1e-8) -> CmaxDescent:
+    """cmax_descent_t with the reference's constants (src/solver/base.py:857-862: lr 0.05, StepLR(n_iter, 0.1)) and torch's defaults
+    for what it leaves to torch.optim (SGD: momentum 0; Adam: betas (0.9, 0.999), eps 1e-8).  lr_step None: n_iter."""
+    if method not in OPT_CODES:
+        raise NotImplementedError(f"descent method {method!r}: the device-resident loop is built for {sorted(OPT_CODES)}")
+    d = CmaxDescent()
+    d.method, d.n_iter, d.lr = OPT_CODES[method], int(n_iter), float(lr)
+    d.lr_step = int(n_iter if lr_step is None else lr_step)
+    d.lr_decay, d.momentum, d.beta1, d.beta2, d.eps = float(lr_decay), float(momentum), float(betas[0]), float(betas[1]), float(eps)
+    return d
+
+
+class DescentResult:
+    """What a device-resident descent returns (cmax_patch_plan_descend / cmax_objective_descend): x_best is the iterate of the lowest
+    loss, x_last the iterate after the last step taken (what the reference's run_torch returns as "param": its best_poses aliases the live
+    tensor, src/solver/base.py:871); loss_history[it] = L_it (NaN behind a stop); trace [n_iter + 1, nx] or None; n_done steps taken;
+    best_iter = -1 and best_loss = inf when no iteration had a finite loss.  `x` and `fun` name x_best / best_loss the way SciPy's result does."""
+
+    def __init__(self, x_best, x_last, best_loss, best_iter, n_done, last_lr, loss_history, trace):
+        self.x_best, self.x_last, self.best_loss, self.best_iter = x_best, x_last, float(best_loss), int(best_iter)
+        self.n_done, self.last_lr, self.loss_history, self.trace = int(n_done), float(last_lr), loss_history, trace
+
+    @property
+    def x(self):
+        return self.x_best
+
+    @property
+    def fun(self):
+        return self.best_loss
+
+    def __repr__(self):
+        return f"DescentResult(best_loss={self.best_loss!r}, best_iter={self.best_iter}, n_done={self.n_done}, nx={self.x_best.size})"
+
+
+def run_descent(call, nx: int, descent: CmaxDescent, trace: bool) -> DescentResult:
+    """Allocates the host outputs of a descend entry point, runs `call(descent*, result*, x_last, x_best, history, trace)`."""
+    import numpy as np
+
+    n_iter = max(int(descent.n_iter), 1)
+    res = CmaxDescentResult()
+    x_last, x_best = np.empty(nx, dtype=np.float64), np.empty(nx, dtype=np.float64)
+    hist = np.empty(n_iter, dtype=np.float64)
+    tr = np.empty((n_iter + 1, nx), dtype=np.float64) if trace else None
+    check(call(ctypes.byref(descent), ctypes.byref(res), x_last.ctypes.data, x_best.ctypes.data, hist.ctypes.data,
+               tr.ctypes.data if trace else None))
+    return DescentResult(x_best, x_last, res.best_loss, res.best_iter, res.n_done, res.last_lr, hist, tr)
 
 
 def require_gpu():

@@ -510,6 +510,20 @@ class CMaxHandle:
         call.motion = m
         return call, result, grad
 
+    def descend(self, desc: CmaxObjective, theta0, descent: "_lib.CmaxDescent", trace: bool = False) -> "_lib.DescentResult":
+        """One cmax_objective_descend call: descent.n_iter iterations of SGD / Adam on a 2-DoF objective (the reference's run_torch,
+        src/solver/base.py:840-881), theta and the optimiser's state resident in device memory, one wait at the end.  theta0: two
+        numbers (host); `descent`: _lib.descent_descriptor(...).  Blocks; returns a _lib.DescentResult of host arrays."""
+        theta0 = np.ascontiguousarray(np.asarray(theta0.detach().cpu() if isinstance(theta0, torch.Tensor) else theta0, dtype=np.float64).reshape(-1))
+        if theta0.size != 2:
+            raise ValueError(f"theta0 has {theta0.size} elements, a 2-DoF descent needs 2")
+        if desc.motion_dtype != _lib.F64:  # the iterate is fp64 in device memory
+            desc = CmaxObjective.from_buffer_copy(desc)
+            desc.motion_dtype = _lib.F64
+        fn, h, dref, stream = self._lib.cmax_objective_descend, self._h, ctypes.byref(desc), F._stream()
+        with torch.cuda.device(self.device):
+            return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(h, dref, theta0.ctypes.data, o, res, xl, xb, hist, tr, stream), 2, descent, trace)
+
     def has_raw(self, desc: CmaxObjective) -> bool:
         """Whether `desc` on the current batch has a raw form (cmax_objective_has_raw): every 2-DoF objective in the default
         (non-deterministic) mode on a non-empty batch, except a normalised plain variance."""
@@ -1191,6 +1205,22 @@ class ContrastObjective:
         if out is None:
             out = torch.zeros_like(vector, dtype=torch.float64)
         return out.reshape(vector.shape).to(vector.dtype if vector.dtype.is_floating_point else torch.float64)
+
+    def descend(self, theta0, method: str = "Adam", n_iter: int = 100, lr: float = 0.05, lr_step: Optional[int] = None, lr_decay: float = 0.1,
+                momentum: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, trace: bool = False):
+        """n_iter iterations of torch.optim.SGD / Adam with StepLR(lr_step, lr_decay) on this objective in ONE library call
+        (CMaxHandle.descend; the reference's run_torch with its constants as defaults, src/solver/base.py:857-862; lr_step None: n_iter).
+        2-DoF models with exactly one fused term of weight 1: a hybrid of several terms (or an "inv" weight, a total_variation member, a
+        cost without a fused kernel) has no single fused objective whose gradient the device-side step could read -- refused."""
+        if F.MODEL_CODES[self.motion_model] != _lib.MODEL_2DOF:
+            raise NotImplementedError(f"descend: 2-DoF motion models only, not {self.motion_model!r} (a patch grid descends through PatchFlowObjective.descend)")
+        if len(self.terms) != 1 or self.terms[0][2] is None or isinstance(self.terms[0][2], _CustomTerm):
+            raise NotImplementedError("descend: the device-resident loop steps on ONE fused term; this objective combines "
+                                      f"{[name for name, _, _ in self.terms]} (several terms, total_variation or a cost without a fused kernel)")
+        name, weight, desc = self.terms[0]
+        if weight == "inv" or float(weight) != 1.0:
+            raise NotImplementedError(f"descend: the term's weight must be 1 (got {weight!r}): the step reads the fused term's own gradient")
+        return self.handle.descend(desc, theta0, _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps), trace=trace)
 
     def evaluate_candidates(self, motions, coarse_flows=None) -> torch.Tensor:
         """Loss of K candidate motions `motions` [K, ...] -> float64 [K] on the device: one cmax_objective_batch call per fused term

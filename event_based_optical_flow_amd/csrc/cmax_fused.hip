@@ -38,6 +38,7 @@
 #include <algorithm>
 #include <atomic>
 
+#include "cmax_descent.h"
 #include "cmax_fused_device.h"
 #include "cmax_image_kernels.h"
 #include "cmax_search_kernels.h"
@@ -1053,6 +1054,72 @@ k_finish_raw(const double *__restrict__ raw, int n_ref, ObjParams op, const doub
         if (flag) {
             __threadfence_system();
             *flag = seq;
+        }
+    }
+}
+
+// k_finish_raw for an iteration of the device-resident descent (cmax_objective_descend, src/solver/base.py:840-881): the same wave, the
+// same three 16-byte loads per lane in flight, the same DPP sums and finalize_deferred -- and lane 63 then applies the optimiser's step to
+// theta in place (cmax_descent.h, nx = 2), so that an iteration stays at K1 -> K3 -> ONE finishing launch.  result / gtheta: device memory.
+__global__ void __launch_bounds__(64)
+k_finish_raw_step(const double *__restrict__ raw, int n_ref, ObjParams op, const double *__restrict__ stat, double *__restrict__ result, double *__restrict__ gtheta,
+                  DescentArgs step) {
+    const int lane = threadIdx.x;
+    double v[4][6];
+    typedef double double2_v __attribute__((ext_vector_type(2)));
+    const int line = lane < kRawLines ? lane : kRawLines - 1;  // unconditional loads, masked afterwards (see k_finish_raw)
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[k][q] = 0.0;
+        if (k < n_ref) {  // uniform
+            const double2_v *src = reinterpret_cast<const double2_v *>(raw + (int64_t)k * kRawStride + line * kSubStride);
+            const double2_v a = src[0], b = src[1], c = src[2];
+            v[k][0] = a.x;
+            v[k][1] = a.y;
+            v[k][2] = b.x;
+            v[k][3] = b.y;
+            v[k][4] = c.x;
+            v[k][5] = c.y;
+        }
+    }
+#pragma unroll
+    for (int k = 0; k < 4; ++k)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[k][q] = lane < kRawLines ? v[k][q] : 0.0;
+    const double v_orig = op.normalized ? orig_value<true>(op, stat) : 0.0;
+#pragma unroll
+    for (int k = 0; k < 4; ++k) {
+        if (k >= op.n_ref) break;  // (uniform)
+#pragma unroll
+        for (int q = 0; q < 6; ++q) v[k][q] = wave_sum_lane63(v[k][q]);
+    }
+    if (lane == kWave - 1) {
+        // (n_ref as a constant per branch: finalize_deferred's loop over the reference times unrolls and v[][] stays in registers -- indexed
+        // by a run-time k it is 208 bytes of scratch per lane)
+        ObjParams on = op;
+        double res[8], g[2];
+        switch (op.n_ref) {
+            case 1: on.n_ref = 1; finalize_deferred(on, v, v_orig, res, g); break;
+            case 2: on.n_ref = 2; finalize_deferred(on, v, v_orig, res, g); break;
+            case 3: on.n_ref = 3; finalize_deferred(on, v, v_orig, res, g); break;
+            default: on.n_ref = 4; finalize_deferred(on, v, v_orig, res, g); break;
+        }
+        result[0] = res[0];
+        result[5] = res[5];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < op.n_ref) result[1 + k] = res[1 + k];
+        gtheta[0] = g[0];
+        gtheta[1] = g[1];
+        const double L = res[0], g0 = g[0], g1 = g[1];
+        const DescentDecision d = descent_decide(step, L, !(isfinite(L) && isfinite(g0) && isfinite(g1)));
+        descent_element(step, d, 0, g0);
+        descent_element(step, d, 1, g1);
+        descent_publish(step, d, L);
+        if (step.it == step.n_iter - 1 && step.flag) {
+            __threadfence_system();
+            *step.flag = step.seq;
         }
     }
 }
@@ -2224,6 +2291,7 @@ struct EvalPlan {
     volatile unsigned long long *host_flag;  // cmax_objective_host: `result` and `grad` are pinned host memory, the finishing kernel writes the
     unsigned long long host_seq;             // run counter behind them
     GradExtent g;
+    const DescentArgs *step;  // cmax_objective_descend on the deferred path: the finishing launch is k_finish_raw_step, which also applies this step
     // ---- the path
     bool deferred;  // deferred_applies: no K2, K3 gathers the statistics, k_finish_raw applies the chain factors
     bool lines;     // two_dof_lines (includes the deferred case)
@@ -2572,7 +2640,9 @@ static int finish_grad_in_bands(cmax_handle_s *h, const cmax_objective_t *d, con
 static int finish_two_dof(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, double *result, void *grad, hipStream_t s) {
     if (!p.lines || p.raw_only) return 0;
     ProfScope prof(h, kProfFinish, s);
-    if (p.deferred)
+    if (p.deferred && p.step)
+        hipLaunchKernelGGL(k_finish_raw_step, dim3(1), dim3(64), 0, s, (const double *)p.raw, op.n_ref, op, h->d_stat, result, (double *)grad, *p.step);
+    else if (p.deferred)
         hipLaunchKernelGGL(k_finish_raw, dim3(1), dim3(64), 0, s, (const double *)p.raw, op.n_ref, op, h->d_stat, result, (double *)grad, p.host_flag, p.host_seq);
     else  // (host_flag: K3's first workgroup wrote the loss into the pinned `result`)
         hipLaunchKernelGGL(k_finish_lines, dim3(1), dim3(64), 0, s, p.raw, d->n_ref, (double *)grad, (const double *)nullptr, (double *)nullptr, p.host_flag, p.host_seq);
@@ -2705,8 +2775,11 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
 // raw_out: non-null = stop at the raw sums of the 2-DoF K3 (cmax_objective_raw; `grad` is then only a non-null marker)
 static int objective_eval(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s,
                           cmax::Comm *comm, double *raw_out = nullptr, volatile unsigned long long *host_flag = nullptr,
-                          unsigned long long host_seq = 0, bool skip_c2 = false) {
-    const EvalPlan p = eval_plan(h, d, grad, true, comm, skip_c2, raw_out, host_flag, host_seq);
+                          unsigned long long host_seq = 0, bool skip_c2 = false, const DescentArgs *step = nullptr, bool *stepped = nullptr) {
+    EvalPlan p = eval_plan(h, d, grad, true, comm, skip_c2, raw_out, host_flag, host_seq);
+    // (a descent's step rides on the deferred path's finishing launch; on every other path the caller launches it behind the evaluation)
+    p.step = (step && p.deferred && !p.tan2 && !p.empty) ? step : nullptr;
+    if (stepped) *stepped = p.step != nullptr;
     if (p.tan2) return objective_eval_tan2(h, d, motion, result, grad, s, comm);
     if (raw_out && !p.lines) {
         set_error("objective_raw: this objective has no raw form (2-DoF, a non-empty batch, not deterministic)");
@@ -3255,6 +3328,77 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
     if (rc) return rc;
     std::memcpy(result_host, h->hp_out, 8 * sizeof(double));
     if (grad_host) std::memcpy(grad_host, h->hp_out + 8, (size_t)gbytes);
+    return 0;
+}
+
+// SolverBase.run_torch (src/solver/base.py:840-881) on a 2-DoF fused objective: theta0 once, n_iter x (what cmax_objective runs from the
+// device-resident theta -> the step) eagerly on the caller's stream, ONE wait behind the last iteration's run counter, the copies out.
+int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, const cmax_descent_t *o, cmax_descent_result_t *res_host,
+                           double *x_last_host, double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream) {
+    static const bool no_fused_step = getenv("CMAX_DESCENT_NO_FUSED_STEP") != nullptr;  // (tools/probe_descent.py: the separate finish + step)
+    int rc = descent_check(o, "objective_descend");
+    if (rc) return rc;
+    CMAX_REQUIRE(h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, "objective_descend: null pointer");
+    CMAX_REQUIRE(d->model == CMAX_MODEL_2DOF, "objective_descend: 2-DoF descriptors only (a dense flow / voxel descends through a patch plan: cmax_patch_plan_descend)");
+    CMAX_REQUIRE(d->motion_dtype == CMAX_F64, "objective_descend: the iterate is fp64 in device memory: desc->motion_dtype must be CMAX_F64");
+    if (h->comm) {
+        set_error("objective_descend: not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nx = 2, n_iter = o->n_iter;
+    const bool trace = x_trace_host != nullptr;
+    constexpr int kHead = 16;  // theta[2] | grad[2] | pad[4] | result[8]
+    rc = h->descent.reserve(&h->bytes, kHead + descent_state_doubles(nx, n_iter, trace), s);
+    if (!rc) rc = h->hp_out.reserve((int64_t)4 * kRawStride);
+    if (rc) return rc;
+    double *theta = h->descent, *grad = theta + 2, *result = theta + 8, *st = theta + kHead;
+    rc = check_objective_args(h, d, reinterpret_cast<const float *>(theta));
+    if (rc) return rc;
+    double *hp_dev = nullptr;
+    if (hipHostGetDevicePointer((void **)&hp_dev, h->hp_out, 0) != hipSuccess) {
+        (void)hipGetLastError();
+        hp_dev = h->hp_out;  // unified addressing
+    }
+    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16);
+    const unsigned long long seq = ++h->host_seq;
+    h->hp_out[8] = theta0_host[0];  // (pinned staging of theta0; doubles 0..3 receive the result block, 16 the run counter)
+    h->hp_out[9] = theta0_host[1];
+    CMAX_CHECK_HIP(hipMemcpyAsync(theta, h->hp_out + 8, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int it = 0; it < n_iter; ++it) {
+        DescentArgs a = descent_args(*o, it, nx, trace, theta, st);
+        if (it == n_iter - 1) {
+            a.res_pinned = hp_dev;
+            a.flag = reinterpret_cast<volatile unsigned long long *>(hp_dev + 16);
+            a.seq = seq;
+        }
+        bool stepped = false;
+        rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, nullptr, nullptr, nullptr, 0, false, no_fused_step ? nullptr : &a, &stepped);
+        if (!rc && !stepped) rc = launch_descent_step(a, result, grad, s);
+        if (rc) return rc;
+    }
+    bool seen = false;
+    for (long spin = 0; spin < 20000000L; ++spin) {  // tens of ms at most, then ask the runtime
+        if (*flag == seq) {
+            seen = true;
+            break;
+        }
+        cpu_relax();
+    }
+    if (!seen) {
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        if (*flag != seq) {
+            set_error("objective_descend: the last step did not report (stream finished without its run counter)");
+            return CMAX_ESTATE;
+        }
+    }
+    std::atomic_thread_fence(std::memory_order_acquire);
+    descent_result(h->hp_out, res_host);
+    CMAX_CHECK_HIP(hipMemcpyAsync(x_best_host, st + kDcCtrl, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipMemcpyAsync(x_last_host, st + kDcCtrl + nx, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipMemcpyAsync(loss_history_host, st + kDcCtrl + 4 * nx, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (trace) CMAX_CHECK_HIP(hipMemcpyAsync(x_trace_host, st + kDcCtrl + 4 * nx + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

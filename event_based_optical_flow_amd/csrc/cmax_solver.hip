@@ -20,6 +20,7 @@
 
 #include "cmax_buffers.h"
 #include "cmax_common.h"
+#include "cmax_descent.h"
 #include "cmax_image_kernels.h"
 #include "cmax_patch_kernels.h"
 
@@ -359,6 +360,32 @@ k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *_
     }
 }
 
+// One iteration of the device-resident descent (cmax_descent.h; src/solver/base.py:840-881): loss and gradient are read where the
+// tail / the 2-DoF objective left them in device memory, the non-finite test covers ALL of g before any store, then m, v, x, x_best,
+// history and trace are updated grid-stride in fp64.  ONE workgroup: nx is 2 .. 8192 and every step depends on the last.  The last
+// iteration publishes the result block and, behind a system-wide fence, the run counter to pinned memory, as k_patch_tail does.
+__global__ void __launch_bounds__(256) k_descent_step(DescentArgs a, const double *__restrict__ loss, const double *__restrict__ grad) {
+    const double L = loss[0];
+    int bad = isfinite(L) ? 0 : 1;
+    for (int p = threadIdx.x; p < a.nx; p += blockDim.x) bad |= isfinite(grad[p]) ? 0 : 1;
+    bad = __syncthreads_or(bad);
+    const DescentDecision d = descent_decide(a, L, bad != 0);
+    for (int p = threadIdx.x; p < a.nx; p += blockDim.x) descent_element(a, d, p, grad[p]);
+    __syncthreads();  // (every thread has read the control block)
+    if (threadIdx.x == 0) descent_publish(a, d, L);
+    if (a.it == a.n_iter - 1 && a.flag) {
+        __threadfence_system();
+        __syncthreads();
+        if (threadIdx.x == 0) *a.flag = a.seq_src ? a.seq_src[0] : a.seq;
+    }
+}
+
+int launch_descent_step(const DescentArgs &a, const double *loss, const double *grad, hipStream_t s) {
+    hipLaunchKernelGGL(k_descent_step, dim3(1), dim3(256), 0, s, a, loss, grad);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace cmax
 
 struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: its implicit destructor is no export)
@@ -381,6 +408,10 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter
     cmax::DevBuf<unsigned long long> seq_dev;  // device-side run counter of the tail kernel
     unsigned long long seq_seen = 0;           // its value after the last completed call
+    // cmax_patch_plan_descend (reserved on first use): the tail's output in device memory (loss | grad | counter slot), the descent state
+    cmax::DevBuf<double> d_out, descent;
+    cmax::PinnedBuf<double> h_res;  // ... and the result block the last step writes (the run counter goes to h_out's slot, like every tail's)
+    double *h_res_dev = nullptr;
     // Captured launch sequences (hipGraph), replayed on the plan's own stream: an evaluation is ~25 small launches,
     // host-bound when issued one by one.  Keyed by everything that changes the sequence: the kind of call and the
     // handle's host-side state (which vote buffer is current, which images are already zero, whether the
@@ -560,10 +591,12 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
     return 0;
 }
 
-// Everything between the pinned input and the pinned output of one evaluation, enqueued on `s` (no synchronisation).
-int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t s) {
+// Everything between the input and the output of one evaluation, enqueued on `s` (no synchronisation).  x_src: pinned host memory the
+// leading copy brings x from (nullptr: x64 holds x already -- the descent's iterate); out: where the tail writes loss | gradient | run
+// counter (the device view of the pinned output, or the descent's device buffer).
+int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t s, const double *x_src, double *out) {
     const cmax_patch_objective_t &d = p->d;
-    CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (size_t)p->nx * sizeof(double), hipMemcpyHostToDevice, s));
+    if (x_src) CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, x_src, (size_t)p->nx * sizeof(double), hipMemcpyHostToDevice, s));
     int rc = forward_motion(p, p->x64, d.t_scale, nullptr, p->motion32, s);
     if (rc) return rc;
     const bool accumulate = want_grad && !(d.n_terms == 1 && !d.time_aware);
@@ -595,7 +628,7 @@ int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t 
     fp.gscale = d.t_scale * wscale;  // d(flow * t_scale) / d flow
     if (d.time_aware && d.scale_later) fp.gscale = 1.0;
     const double *ok_dev = d.time_aware && d.scale_later ? p->sl + 1 : nullptr;
-    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, (const double *)nullptr, p->h_out_dev, p->seq_dev, ok_dev);
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, (const double *)nullptr, out, p->seq_dev, ok_dev);
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -790,8 +823,8 @@ static volatile unsigned long long *plan_flag(cmax_patch_plan_s *p) {
     return reinterpret_cast<volatile unsigned long long *>(p->h_out + 1 + p->nx);
 }
 
-static int wait_for_tail(cmax_patch_plan_s *p, hipStream_t s, bool poll) {
-    const unsigned long long expected = p->seq_seen + 1ull;
+static int wait_for_tail(cmax_patch_plan_s *p, hipStream_t s, bool poll, unsigned long long n_tails = 1ull) {
+    const unsigned long long expected = p->seq_seen + n_tails;  // (a descent: one tail per iteration, the last step publishes the counter)
     if (poll) {
         volatile unsigned long long *flag = plan_flag(p);
         for (long spin = 0; spin < 4000000L; ++spin) {  // a few ms at most, then sleep like everybody else
@@ -986,10 +1019,70 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t p, const double *x_host, int with
     const bool tv = with_tv && p->d.tv_weight != 0.0;
     std::memcpy(p->h_in, x_host, (size_t)p->nx * sizeof(double));
     const int kind = (tv ? 1 : 0) | (grad_host ? 2 : 0);
-    int rc = run_sequence(p, kind, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_evaluate(p, tv, grad_host != nullptr, s); });
+    int rc = run_sequence(p, kind, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_evaluate(p, tv, grad_host != nullptr, s, p->h_in, p->h_out_dev); });
     if (rc) return rc;
     *loss_host = p->h_out[0];
     if (grad_host) std::memcpy(grad_host, p->h_out + 1, (size_t)p->nx * sizeof(double));
+    return 0;
+}
+
+int cmax_sizeof_descent(void) { return (int)sizeof(cmax_descent_t); }
+
+// SolverBase.run_torch (src/solver/base.py:840-881) on the plan's objective: x0 once, n_iter x (evaluate from the device-resident x -> tail
+// into a device buffer -> k_descent_step) eagerly on the caller's stream, ONE wait, the copies out.
+int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with_tv, const cmax_descent_t *o, cmax_descent_result_t *res_host,
+                            double *x_last_host, double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream) {
+    int rc = descent_check(o, "patch_plan_descend");
+    if (rc) return rc;
+    CMAX_REQUIRE(p && x0_host && res_host && x_last_host && x_best_host && loss_history_host, "patch_plan_descend: null pointer");
+    if (handle_has_comm(p->handle)) {
+        set_error("patch_plan_descend: not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (handle_is_weighted(p->handle)) {
+        set_error("patch_plan_descend: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool tv = with_tv && p->d.tv_weight != 0.0, trace = x_trace_host != nullptr;
+    const int nx = p->nx, n_iter = o->n_iter;
+    const int64_t n_state = descent_state_doubles(nx, n_iter, trace);
+    rc = p->d_out.reserve(nullptr, 2 + (int64_t)nx, s);
+    if (!rc) rc = p->descent.reserve(nullptr, n_state, s);
+    if (!rc && !p->h_res.get()) {
+        rc = p->h_res.reserve(4);
+        if (!rc && hipHostGetDevicePointer((void **)&p->h_res_dev, p->h_res, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            p->h_res_dev = p->h_res;  // unified addressing
+        }
+    }
+    if (rc) return rc;
+    std::memcpy(p->h_in, x0_host, (size_t)nx * sizeof(double));
+    CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int it = 0; it < n_iter; ++it) {
+        rc = enqueue_evaluate(p, tv, true, s, nullptr, p->d_out);
+        if (rc) return rc;
+        DescentArgs a = descent_args(*o, it, nx, trace, p->x64, p->descent);
+        if (it == n_iter - 1) {
+            a.res_pinned = p->h_res_dev;
+            a.flag = reinterpret_cast<volatile unsigned long long *>(p->h_out_dev + 1 + nx);
+            a.seq_src = p->seq_dev;
+        }
+        rc = launch_descent_step(a, p->d_out, p->d_out + 1, s);
+        if (rc) return rc;
+    }
+    ++p->eager_calls;
+    rc = wait_for_tail(p, s, p->eager_calls > 1, (unsigned long long)n_iter);
+    if (rc) return rc;
+    descent_result(p->h_res, res_host);
+    // (behind the wait: the state is final; x_best | x_last lead it, history and trace close it)
+    const double *st = p->descent;
+    CMAX_CHECK_HIP(hipMemcpyAsync(x_best_host, st + kDcCtrl, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipMemcpyAsync(x_last_host, st + kDcCtrl + nx, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipMemcpyAsync(loss_history_host, st + kDcCtrl + 4 * (int64_t)nx, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (trace)
+        CMAX_CHECK_HIP(hipMemcpyAsync(x_trace_host, st + kDcCtrl + 4 * (int64_t)nx + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
 }
 

@@ -14,6 +14,25 @@ logger = logging.getLogger(__name__)
 
 SCIPY_OPTIMIZERS = ["Nelder-Mead", "Powell", "CG", "BFGS", "Newton-CG", "L-BFGS-B", "TNC", "COBYLA", "SLSQP",
                     "trust-constr", "dogleg", "trust-ncg", "trust-exact", "trust-krylov"]
+# first-order methods of the reference's TORCH_OPTIMIZERS (src/solver/base.py:38-52) that run as a device-resident loop
+# (PatchFlowObjective.descend: n_iter iterations per library call); the other eleven names are not built
+DESCENT_OPTIMIZERS = ["SGD", "Adam"]
+
+
+def check_opt_method(method: str):
+    """The solver classes' `optimizer.method`: a SciPy method or a device-resident first-order method; everything else -- the rest of
+    the reference's TORCH_OPTIMIZERS, Optuna -- raises NotImplementedError with what is built."""
+    if method == "optuna":
+        raise NotImplementedError("opt_method 'optuna' is not built: Optuna is not a dependency of this package "
+                                  f"(SciPy methods and the device-resident {DESCENT_OPTIMIZERS})")
+    if method not in SCIPY_OPTIMIZERS and method not in DESCENT_OPTIMIZERS:
+        raise NotImplementedError(f"Optimizer {method} is not supported (SciPy methods, and of torch.optim the device-resident {DESCENT_OPTIMIZERS} only)")
+
+
+def run_descent(objective, x0: np.ndarray, method: str, opt_config: dict):
+    """SolverBase.run_torch (src/solver/base.py:840-881) with its constants: lr 0.05, StepLR(n_iter, 0.1), optimizer.n_iter iterations,
+    torch's defaults for the optimiser itself -- one PatchFlowObjective.descend call.  -> _lib.DescentResult (its x is x_best)."""
+    return objective.descend(x0, method=method, n_iter=int(opt_config["n_iter"]), lr=0.05, lr_step=None, lr_decay=0.1)
 
 
 def _check_key_and_bool(config: dict, key: str) -> bool:

@@ -19,7 +19,8 @@ import numpy as np
 
 from ..cmax import CMaxHandle
 from . import scipy_autograd
-from .common import SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, one_patch_guess, whole_image_guess
+from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, one_patch_guess, run_descent,
+                     whole_image_guess)
 from .patch_objective import PatchFlowObjective, patch_pad
 
 logger = logging.getLogger(__name__)
@@ -44,10 +45,7 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         self.out_config = output_config
         self.visualizer = visualize_module
         self.opt_method = optimizer_config["method"]
-        if self.opt_method == "optuna":
-            raise NotImplementedError("opt_method 'optuna' is not built: Optuna is not a dependency of this package (SciPy methods only)")
-        if self.opt_method not in SCIPY_OPTIMIZERS:
-            raise NotImplementedError(f"Optimizer {self.opt_method} is not supported (SciPy methods only)")
+        check_opt_method(self.opt_method)
         self.padding = solver_config["outer_padding"] if "outer_padding" in solver_config else 0
         self.iwe_config = solver_config["iwe"]
         if self.iwe_config["method"] != "bilinear_vote":
@@ -85,7 +83,7 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         self.n_patch = self.patch_image_size[0] * self.patch_image_size[1]
         self._patch_motion_model_keys = [f"patch{i}_{k}" for i in range(self.n_patch) for k in self.motion_model_keys]
         self.previous_frame_best_estimation: Optional[np.ndarray] = None
-        self.history = []         # OptimizeResult per frame
+        self.history = []         # OptimizeResult (optimizer.method "SGD" / "Adam": DescentResult) per frame
         self.search_history = []  # (initialiser, losses of every candidate, pick) per frame
         self._handle: Optional[CMaxHandle] = None
         self._search_handle: Optional[CMaxHandle] = None  # un-binned twin of a time-binned handle, for the 2-DoF grid search
@@ -190,11 +188,14 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         logger.info(f"DoF is {self.motion_vector_size * self.n_patch}")
         objective = self.prepare_objective(events)
         motion0 = self.initial_motion(events)
-        res = scipy_autograd.minimize(objective, motion0, method=self.opt_method, precision="float64",
-                                      torch_device=str(self._handle.device),
-                                      options={"gtol": 1e-7, "disp": False, "maxiter": self.opt_config["max_iter"]}
-                                      if self.opt_method in ("Newton-CG", "BFGS", "CG", "L-BFGS-B", "trust-ncg", "trust-krylov")
-                                      else {"maxiter": self.opt_config["max_iter"]})
+        if self.opt_method in DESCENT_OPTIMIZERS:  # run_torch's loop (src/solver/base.py:840-881), device-resident; the motion is x_best
+            res = run_descent(objective, motion0, self.opt_method, self.opt_config)
+        else:
+            res = scipy_autograd.minimize(objective, motion0, method=self.opt_method, precision="float64",
+                                          torch_device=str(self._handle.device),
+                                          options={"gtol": 1e-7, "disp": False, "maxiter": self.opt_config["max_iter"]}
+                                          if self.opt_method in ("Newton-CG", "BFGS", "CG", "L-BFGS-B", "trust-ncg", "trust-krylov")
+                                          else {"maxiter": self.opt_config["max_iter"]})
         logger.info(f"End optimization: loss {res.fun}")
         self.history.append(res)
         return np.asarray(res.x).reshape((self.motion_vector_size,) + self.patch_image_size)

@@ -183,6 +183,27 @@ class PatchFlowObjective:
                                                             grad.ctypes.data if want_grad else None, F._stream()))
         return loss.value, grad
 
+    def descend(self, x0: np.ndarray, method: str = "Adam", n_iter: int = 100, lr: float = 0.05, lr_step: Optional[int] = None,
+                lr_decay: float = 0.1, momentum: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, with_tv: bool = True, trace: bool = False):
+        """n_iter iterations of torch.optim.SGD / Adam with StepLR(lr_step, lr_decay) from x0 [2*ph*pw] in ONE cmax_patch_plan_descend
+        call: the reference's run_torch (src/solver/base.py:840-881; its constants are the defaults, lr_step None: n_iter) with the iterate
+        and the optimiser's state resident in device memory and one wait at the end.  Returns a _lib.DescentResult (host arrays).
+        Time slabs are a host decision and there is no host between the iterations: they are decided ONCE, from max|x0| + lr * n_iter --
+        Adam moves an entry by about lr per step at most, so that bounds its travel; SGD's steps scale with the gradient and have no such
+        bound: its slabs follow x0 alone."""
+        if self._plan is None:
+            raise NotImplementedError("descend needs the native plan (numeric hybrid weights, fused costs, no torch.distributed fall-back)")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if x0.size != self._nx:
+            raise ValueError(f"x0 has {x0.size} elements, the patch grid needs {self._nx}")
+        descent = _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps)
+        reach = float(np.abs(x0).max()) + (float(lr) * int(n_iter) if method == "Adam" else 0.0)
+        self.ensure_time_slabs(np.array([reach]))
+        fn, plan, stream = _lib.load().cmax_patch_plan_descend, self._plan, F._stream()
+        with torch.cuda.device(self.handle.device):
+            return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(plan, x0.ctypes.data, int(with_tv), o, res, xl, xb, hist, tr, stream),
+                                    self._nx, descent, trace)
+
     def hvp_numpy(self, x: np.ndarray, v: np.ndarray, disp_step: float = 0.05, exact: bool = True) -> np.ndarray:
         """Hessian-vector product on host arrays through cmax_patch_plan_hvp: exact, what the reference's
         torch.autograd.functional.vhp returns -- for time-aware objectives including the second-order adjoint of the

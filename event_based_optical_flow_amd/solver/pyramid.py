@@ -29,8 +29,8 @@ import scipy.ndimage as ndi
 from ..cmax import CMaxHandle
 from . import scipy_autograd
 from .patch_objective import PatchFlowObjective
-from .common import (SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, calculate_flow_error_numpy,  # noqa: F401
-                     one_patch_guess, whole_image_guess)
+from .common import (DESCENT_OPTIMIZERS, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, calculate_flow_error_numpy,  # noqa: F401
+                     check_opt_method, one_patch_guess, run_descent, whole_image_guess)
 
 logger = logging.getLogger(__name__)
 
@@ -70,8 +70,7 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
         self.out_config = output_config
         self.visualizer = visualize_module
         self.opt_method = optimizer_config["method"]
-        if self.opt_method not in SCIPY_OPTIMIZERS:
-            raise NotImplementedError(f"Optimizer {self.opt_method} is not supported (SciPy methods only)")
+        check_opt_method(self.opt_method)
         self.padding = solver_config["outer_padding"] if "outer_padding" in solver_config else 0
         self.iwe_config = solver_config["iwe"]
         if self.iwe_config["method"] != "bilinear_vote":
@@ -112,7 +111,7 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
             self.scaled_n_patch[s] = self.scaled_patch_image_size[s][0] * self.scaled_patch_image_size[s][1]
         self.total_n_patch = sum(self.scaled_n_patch.values())
         self.previous_frame_best_estimation: Optional[Dict[int, np.ndarray]] = None
-        self.history = []  # (scale, OptimizeResult)
+        self.history = []  # (scale, OptimizeResult -- or, optimizer.method "SGD" / "Adam", the DescentResult)
         self.search_history = []  # (scale, candidates, loss, picked index) of the per-patch re-initialisation
         self._handle: Optional[CMaxHandle] = None
         self._objectives: Dict[int, PatchFlowObjective] = {}
@@ -173,11 +172,14 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
                 x0 = np.tile(best_guess[None], (self.scaled_n_patch[s], 1)).T.reshape(-1)
             else:
                 x0 = self.initialize_random(self.scaled_n_patch[s]).reshape(-1)
-            res = scipy_autograd.minimize(objective, x0, method=self.opt_method, precision="float64",
-                                          torch_device=str(handle.device),
-                                          options={"gtol": 1e-5, "disp": False, "maxiter": self.opt_config["max_iter"]}
-                                          if self.opt_method in ("Newton-CG", "BFGS", "CG", "L-BFGS-B", "trust-ncg", "trust-krylov")
-                                          else {"maxiter": self.opt_config["max_iter"]})
+            if self.opt_method in DESCENT_OPTIMIZERS:  # run_torch's loop, device-resident, once per scale; the motion is x_best
+                res = run_descent(objective, x0, self.opt_method, self.opt_config)
+            else:
+                res = scipy_autograd.minimize(objective, x0, method=self.opt_method, precision="float64",
+                                              torch_device=str(handle.device),
+                                              options={"gtol": 1e-5, "disp": False, "maxiter": self.opt_config["max_iter"]}
+                                              if self.opt_method in ("Newton-CG", "BFGS", "CG", "L-BFGS-B", "trust-ncg", "trust-krylov")
+                                              else {"maxiter": self.opt_config["max_iter"]})
             logger.info(f"Scale {s}: loss {res.fun}")
             self.history.append((s, res))
             self.slab_history.append((s, handle.time_slabs))

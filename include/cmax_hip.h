@@ -672,6 +672,73 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t plan, const double *x_host, int w
 int cmax_patch_plan_hvp(cmax_patch_plan_t plan, const double *x_host, const double *v_host, double *hv_host,
                         cmax_stream_t stream);
 
+/* =============================================================================================
+ * Device-resident first-order descent: n_iter iterations of SGD (with momentum) or Adam in ONE call.  What
+ * SolverBase.run_torch runs (src/solver/base.py:840-881: torch.optim.__dict__[method]([poses], lr = 0.05),
+ * StepLR(n_iter, 0.1), a loop that keeps the lowest loss) -- without a host decision between two evaluations: the
+ * iterate, the optimiser's state, the loss history and the optional trace live in device memory, every iteration is
+ * enqueued eagerly on the caller's stream (evaluation from the device-resident x -> loss and gradient left in device
+ * memory -> one update launch), and the call waits ONCE, behind the last iteration.  All values of the descriptor are
+ * explicit (the Python layer fills torch's defaults).  cmax_descent_t is a new struct: the ABI version is unchanged.
+ *
+ * The rules are torch's.  Iteration `it` (0-based) evaluates L_it, g_it at x_it, then steps:
+ *   SGD      buf = g at the first step, afterwards buf = momentum * buf + g;  x <- x - lr_it * buf  (momentum = 0: x <- x - lr_it * g)
+ *   Adam     t = it + 1;  m = beta1 m + (1 - beta1) g;  v = beta2 v + (1 - beta2) g^2;
+ *            x <- x - (lr_it / (1 - beta1^t)) * m / (sqrt(v) / sqrt(1 - beta2^t) + eps)
+ *   StepLR   lr_it = lr * lr_decay^floor(it / lr_step)
+ *   best     if L_it < best_loss (strict; a NaN never wins): best_loss = L_it, best_iter = it, x_best = x_it.  No iteration won:
+ *            best_loss = +inf, best_iter = -1, x_best = x0.
+ *   x_last   the iterate after the last step taken; its loss is not evaluated, as in the reference.  The reference's
+ *            `best_poses = poses` aliases the live tensor, so what it returns as "param" is x_last, not the iterate of
+ *            best_iter: both are returned here.
+ *   stop     the device-side form of the reference's `break`: if L_it or any entry of g_it is not finite, no step is taken at `it`
+ *            or afterwards; n_done = it (n_iter when no iteration stopped); loss_history[it] = L_it and the entries of later
+ *            iterations are NaN.  The remaining evaluations still run, at the unchanged, finite x: the host cannot know -- the
+ *            price of not waiting.
+ *   outputs  loss_history[it] = L_it;  x_trace (optional) row it = x_it, row n_iter = x_last;
+ *            last_lr = lr_it of the last step taken (0: none was).
+ * ============================================================================================= */
+#define CMAX_OPT_SGD 0
+#define CMAX_OPT_ADAM 1
+#define CMAX_DESCENT_MAX_ITER 4096
+typedef struct {
+    int32_t method;   /* CMAX_OPT_* */
+    int32_t n_iter;   /* 1 .. CMAX_DESCENT_MAX_ITER */
+    double lr;        /* > 0 */
+    int32_t lr_step;  /* >= 1 (four bytes of padding behind it) */
+    double lr_decay;  /* > 0 */
+    double momentum;  /* SGD: [0, 1) */
+    double beta1;     /* Adam: [0, 1) */
+    double beta2;     /* Adam: [0, 1) */
+    double eps;       /* Adam: > 0 */
+} cmax_descent_t;
+typedef struct {
+    double best_loss;
+    int32_t best_iter; /* -1: no iteration had a loss below +inf */
+    int32_t n_done;    /* steps taken */
+    double last_lr;
+} cmax_descent_result_t;
+int cmax_sizeof_descent(void);
+/* The descent on a patch plan's objective (src/solver/base.py:840-881 on objective_scipy).  x0_host [nx = 2*ph*pw];
+ * res_host, x_last_host [nx], x_best_host [nx], loss_history_host [n_iter]: filled; x_trace_host [(n_iter + 1) * nx] or NULL.
+ * Refused before any launch: CMAX_EINVAL for an unknown method, n_iter outside 1 .. 4096, a non-finite or non-positive lr,
+ * lr_decay or eps, lr_step < 1, momentum / beta1 / beta2 outside [0, 1), null pointers; CMAX_EUNSUPPORTED for a handle with a
+ * communicator and for a weighted handle (as cmax_patch_plan_evaluate).  Deterministic handles are allowed.  The handle's
+ * host-side evaluation state advances as n_iter cmax_patch_plan_evaluate calls would advance it; never replayed from a graph.
+ * Blocks until the results are on the host.                                                                            */
+int cmax_patch_plan_descend(cmax_patch_plan_t plan, const double *x0_host, int with_tv, const cmax_descent_t *descent,
+                            cmax_descent_result_t *res_host, double *x_last_host, double *x_best_host,
+                            double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
+/* The descent on a 2-DoF fused objective (src/solver/base.py:840-881 on a "2d-translation" warp): what cmax_objective runs per
+ * iteration, theta in fp64 in device memory -- desc->motion_dtype must be CMAX_F64 and desc->model CMAX_MODEL_2DOF (CMAX_EINVAL
+ * with the reason otherwise).  nx = 2.  The plain variance without a blur on the deferred path ends every iteration in ONE
+ * one-wave launch that folds the raw sums AND applies the step (k_finish_raw_step); every other objective runs its normal
+ * sequence and the update launch behind it.  Weighted and deterministic handles are allowed; a handle with a communicator is
+ * CMAX_EUNSUPPORTED.  Same descriptor checks, outputs and blocking as cmax_patch_plan_descend.                          */
+int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *desc_host, const double *theta0_host,
+                           const cmax_descent_t *descent, cmax_descent_result_t *res_host, double *x_last_host,
+                           double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
+
 /* The reduction of the scale_later map as a leaf operator (the autograd-chained path chains it with cmax_patch_to_dense and
  * cmax_voxel_construct).  x: device fp32 / fp64 [n].  out: device double[4] -- out[0] = max x (signed), out[1] = number of
  * elements EQUAL to it (exact comparison of the values the device holds), out[2..3] scratch.  Asynchronous.                 */
