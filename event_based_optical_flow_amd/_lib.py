@@ -124,6 +124,7 @@ FILTER_BILINEAR, FILTER_NEAREST = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1
 OPT_CODES = {"SGD": OPT_SGD, "Adam": OPT_ADAM}
 DESCENT_MAX_ITER = 4096
+DESCENT_MAX_STARTS = 64  # CMAX_DESCENT_MAX_STARTS: trajectories per cmax_objective_descend_batch call
 EINVAL = -1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
@@ -217,6 +218,7 @@ SIGNATURES = {
     "cmax_patch_plan_descend": (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult), c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_descend": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult),
                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_objective_descend_batch": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_int, ctypes.POINTER(CmaxDescent), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_search": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_vp]),
@@ -325,6 +327,21 @@ def run_descent(call, nx: int, descent: CmaxDescent, trace: bool) -> DescentResu
     check(call(ctypes.byref(descent), ctypes.byref(res), x_last.ctypes.data, x_best.ctypes.data, hist.ctypes.data,
                tr.ctypes.data if trace else None))
     return DescentResult(x_best, x_last, res.best_loss, res.best_iter, res.n_done, res.last_lr, hist, tr)
+
+
+def run_descent_batch(call, K: int, nx: int, descent: CmaxDescent, trace: bool) -> list:
+    """The same for the K trajectories of cmax_objective_descend_batch: `call(descent*, results[K], x_last, x_best, history, trace)`
+    -> K DescentResults (views of the [K, ...] host arrays)."""
+    import numpy as np
+
+    n_iter = max(int(descent.n_iter), 1)
+    res = (CmaxDescentResult * K)()
+    x_last, x_best = np.empty((K, nx), dtype=np.float64), np.empty((K, nx), dtype=np.float64)
+    hist = np.empty((K, n_iter), dtype=np.float64)
+    tr = np.empty((K, n_iter + 1, nx), dtype=np.float64) if trace else None
+    check(call(ctypes.byref(descent), res, x_last.ctypes.data, x_best.ctypes.data, hist.ctypes.data, tr.ctypes.data if trace else None))
+    return [DescentResult(x_best[z], x_last[z], res[z].best_loss, res[z].best_iter, res[z].n_done, res[z].last_lr, hist[z], tr[z] if trace else None)
+            for z in range(K)]
 
 
 def require_gpu():

@@ -524,6 +524,26 @@ class CMaxHandle:
         with torch.cuda.device(self.device):
             return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(h, dref, theta0.ctypes.data, o, res, xl, xb, hist, tr, stream), 2, descent, trace)
 
+    def descend_batch(self, desc: CmaxObjective, theta0s, descent: "_lib.CmaxDescent", trace: bool = False) -> list:
+        """K independent trajectories of `descend` from the starts `theta0s` [K, 2] (host): cmax_objective_descend_batch, at most
+        _lib.DESCENT_MAX_STARTS = 64 starts per call (more are cut into several calls).  For the plain variance without a blur on an
+        unweighted default handle the K candidates share the launches of one, every iteration; everything else runs start by start
+        inside the call.  Blocks; returns a list of K _lib.DescentResult."""
+        theta0s = np.ascontiguousarray(np.asarray(theta0s.detach().cpu() if isinstance(theta0s, torch.Tensor) else theta0s, dtype=np.float64))
+        if theta0s.ndim != 2 or theta0s.shape[1] != 2:
+            raise ValueError(f"theta0s has shape {tuple(theta0s.shape)}, the starts of a 2-DoF descent are [K, 2]")
+        if desc.motion_dtype != _lib.F64:  # the iterates are fp64 in device memory
+            desc = CmaxObjective.from_buffer_copy(desc)
+            desc.motion_dtype = _lib.F64
+        fn, h, dref, stream = self._lib.cmax_objective_descend_batch, self._h, ctypes.byref(desc), F._stream()
+        out = []
+        with torch.cuda.device(self.device):
+            for b in range(0, theta0s.shape[0], _lib.DESCENT_MAX_STARTS):
+                part = np.ascontiguousarray(theta0s[b:b + _lib.DESCENT_MAX_STARTS])
+                k = int(part.shape[0])
+                out += _lib.run_descent_batch(lambda o, res, xl, xb, hist, tr: fn(h, dref, part.ctypes.data, k, o, res, xl, xb, hist, tr, stream), k, 2, descent, trace)
+        return out
+
     def has_raw(self, desc: CmaxObjective) -> bool:
         """Whether `desc` on the current batch has a raw form (cmax_objective_has_raw): every 2-DoF objective in the default
         (non-deterministic) mode on a non-empty batch, except a normalised plain variance."""
@@ -1212,6 +1232,11 @@ class ContrastObjective:
         (CMaxHandle.descend; the reference's run_torch with its constants as defaults, src/solver/base.py:857-862; lr_step None: n_iter).
         2-DoF models with exactly one fused term of weight 1: a hybrid of several terms (or an "inv" weight, a total_variation member, a
         cost without a fused kernel) has no single fused objective whose gradient the device-side step could read -- refused."""
+        desc = self._descent_term()
+        return self.handle.descend(desc, theta0, _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps), trace=trace)
+
+    def _descent_term(self) -> CmaxObjective:
+        """The one fused term a device-resident descent steps on, or NotImplementedError with what is refused."""
         if F.MODEL_CODES[self.motion_model] != _lib.MODEL_2DOF:
             raise NotImplementedError(f"descend: 2-DoF motion models only, not {self.motion_model!r} (a patch grid descends through PatchFlowObjective.descend)")
         if len(self.terms) != 1 or self.terms[0][2] is None or isinstance(self.terms[0][2], _CustomTerm):
@@ -1220,7 +1245,17 @@ class ContrastObjective:
         name, weight, desc = self.terms[0]
         if weight == "inv" or float(weight) != 1.0:
             raise NotImplementedError(f"descend: the term's weight must be 1 (got {weight!r}): the step reads the fused term's own gradient")
-        return self.handle.descend(desc, theta0, _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps), trace=trace)
+        return desc
+
+    def descend_batch(self, theta0s, method: str = "Adam", n_iter: int = 100, lr: float = 0.05, lr_step: Optional[int] = None, lr_decay: float = 0.1,
+                      momentum: float = 0.0, betas=(0.9, 0.999), eps: float = 1e-8, trace: bool = False) -> list:
+        """`descend` from K starts `theta0s` [K, 2] as K independent trajectories in ONE library call per 64 starts (CMaxHandle.descend_batch;
+        multi-start for a non-convex objective: the reference's "global-best" grid is correct only to its spacing, src/solver/
+        patch_contrast_base.py:164-187).  Same arguments and refusals as `descend`; returns a list of K _lib.DescentResult.  Like `descend` it
+        leaves the batch's time-slab order as the caller set it: no host stands between the iterations, so whoever wants slabs decides them
+        once, for all starts, before the call (solver.translation_search.refine_translation: from max |theta0| + lr * n_iter)."""
+        desc = self._descent_term()
+        return self.handle.descend_batch(desc, theta0s, _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps), trace=trace)
 
     def evaluate_candidates(self, motions, coarse_flows=None) -> torch.Tensor:
         """Loss of K candidate motions `motions` [K, ...] -> float64 [K] on the device: one cmax_objective_batch call per fused term

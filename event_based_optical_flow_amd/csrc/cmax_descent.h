@@ -1,6 +1,7 @@
-// Device-resident SGD / Adam (cmax_patch_plan_descend, cmax_objective_descend; the rules are pinned in include/cmax_hip.h): the update
-// of one iteration as the two kernels that apply it share it -- k_descent_step (cmax_solver.hip: one workgroup, any nx) and
-// k_finish_raw_step (cmax_fused.hip: lane 63 of the one-wave finishing kernel, nx = 2) -- and the host-side descriptor checks.
+// Device-resident SGD / Adam (cmax_patch_plan_descend, cmax_objective_descend, cmax_objective_descend_batch; the rules are pinned in
+// include/cmax_hip.h): the update of one iteration as the kernels that apply it share it -- k_descent_step (cmax_solver.hip: one workgroup,
+// any nx), k_finish_raw_step (cmax_fused.hip: lane 63 of the one-wave finishing kernel, nx = 2) and its sibling k_finish_raw_step_batch
+// (one such wave per candidate, every candidate its own state) -- and the host-side descriptor checks.
 // SolverBase.run_torch, src/solver/base.py:840-881.
 #pragma once
 #include <cmath>

@@ -1061,9 +1061,9 @@ k_finish_raw(const double *__restrict__ raw, int n_ref, ObjParams op, const doub
 // k_finish_raw for an iteration of the device-resident descent (cmax_objective_descend, src/solver/base.py:840-881): the same wave, the
 // same three 16-byte loads per lane in flight, the same DPP sums and finalize_deferred -- and lane 63 then applies the optimiser's step to
 // theta in place (cmax_descent.h, nx = 2), so that an iteration stays at K1 -> K3 -> ONE finishing launch.  result / gtheta: device memory.
-__global__ void __launch_bounds__(64)
-k_finish_raw_step(const double *__restrict__ raw, int n_ref, ObjParams op, const double *__restrict__ stat, double *__restrict__ result, double *__restrict__ gtheta,
-                  DescentArgs step) {
+// (one body for the single-start launch and its batched sibling below: the wave of one candidate)
+__device__ __forceinline__ void finish_raw_step_wave(const double *__restrict__ raw, int n_ref, const ObjParams &op, const double *__restrict__ stat,
+                                                     double *__restrict__ result, double *__restrict__ gtheta, const DescentArgs &step) {
     const int lane = threadIdx.x;
     double v[4][6];
     typedef double double2_v __attribute__((ext_vector_type(2)));
@@ -1122,6 +1122,25 @@ k_finish_raw_step(const double *__restrict__ raw, int n_ref, ObjParams op, const
             *step.flag = step.seq;
         }
     }
+}
+
+__global__ void __launch_bounds__(64)
+k_finish_raw_step(const double *__restrict__ raw, int n_ref, ObjParams op, const double *__restrict__ stat, double *__restrict__ result, double *__restrict__ gtheta,
+                  DescentArgs step) {
+    finish_raw_step_wave(raw, n_ref, op, stat, result, gtheta, step);
+}
+
+// The same for the K candidates of cmax_objective_descend_batch: blockIdx.x = candidate, one wave each, on that candidate's raw lines (as
+// k_finish_raw indexes them), result block, gradient, theta (the double[K][2] the batched K1 / K3 read through RefArgs::z_motion) and
+// descent state (st_stride doubles apart).  Every candidate decides, steps and stops on its own control block; nothing is published to
+// the host from here (step.res_pinned and step.flag are null: the call copies the states out behind the last launch).
+__global__ void __launch_bounds__(64)
+k_finish_raw_step_batch(const double *__restrict__ raw, int n_ref, ObjParams op, const double *__restrict__ stat, double *__restrict__ result,
+                        double *__restrict__ gtheta, DescentArgs step, int64_t st_stride) {
+    const int64_t z = blockIdx.x;
+    step.x += 2 * z;
+    step.st += z * st_stride;
+    finish_raw_step_wave(raw + z * n_ref * kRawStride, n_ref, op, stat, result + 8 * z, gtheta + 2 * z, step);
 }
 
 // ---------------------------------------------------------------------------------------------
@@ -3125,33 +3144,18 @@ int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *
     return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, h->comm);
 }
 
-// K candidate motions in ONE launch pair.  The reference's gradient-free paths evaluate the objective for batches of sampled motions
-// (src/solver/base.py:738-758 run_optuna; src/solver/patch_contrast_pyramid.py:363-415), and a line search asks for several steps
-// along one direction: each evaluation of such a batch alone is two dependent launches and a finishing one, and at cfg2's size those
-// launches' floor is 40 % of it (roofline.launch_floor_us).  Here blockIdx.z of K1 / K3 is the candidate -- every candidate its own
-// vote image, raw-sum lines and windows -- and the finishing kernel runs one wave per candidate.
-// Fast path: 2-DoF, plain image variance (sigma 0, not normalised), default mode, one GPU -- the headline objective.  Everything
-// else is evaluated candidate by candidate inside this call (same results, no speed-up).
-int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void *motions_v, int K, double *results, void *grads,
-                         cmax_stream_t stream) {
-    const float *motions = static_cast<const float *>(motions_v);
-    int rc = check_objective_args(h, d, motions);
-    if (rc) return rc;
-    CMAX_REQUIRE(results != nullptr && K >= 1 && K <= 64, "objective_batch: results / 1 <= K <= 64");
-    hipStream_t s = (hipStream_t)stream;
-    const bool two_dof = d->model == CMAX_MODEL_2DOF;
-    const GradExtent g = grad_extent(h, d);
-    const int64_t mfloats = (two_dof ? 2 : g.count) * (d->motion_dtype == CMAX_F64 ? 2 : 1);  // floats per candidate motion
-    const bool fast = K > 1 && grads && deferred_applies(h, d, grads) && !d->normalized && !h->comm && !h->profiling;
-    if (!fast) {
-        for (int z = 0; z < K; ++z) {
-            const float *motion = nullptr;  // (an fp64 flow: every candidate is split in front of its evaluation, stream-ordered in the one scratch)
-            rc = kernel_motion(h, d, motions + z * mfloats, s, &motion);
-            if (!rc) rc = objective_eval(h, d, motion, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
-            if (rc) return rc;
-        }
-        return 0;
-    }
+// when K candidates share the launches of one (cmax_objective_batch, cmax_objective_descend_batch): the headline objective on one GPU
+static bool batch_fast_applies(const cmax_handle_s *h, const cmax_objective_t *d, int K, const void *grads) {
+    return K > 1 && grads && deferred_applies(h, d, grads) && !d->normalized && !h->comm && !h->profiling;
+}
+
+// The fast path of cmax_objective_batch, enqueued: K1 and K3 with blockIdx.z = candidate on the batch workspace (grown here), then ONE
+// finishing launch of K waves -- k_finish_raw into results / grads (step == nullptr), or k_finish_raw_step_batch, which also applies
+// iteration step->it of cmax_objective_descend_batch to every candidate (step->x = motions as double[K][2], step->st the first
+// candidate's state, st_stride doubles between candidates) -- and the double-buffer bookkeeping of one evaluation.
+static int batch_enqueue(cmax_handle_t h, const cmax_objective_t *d, const float *motions, int K, int64_t mfloats, double *results, double *grads,
+                         const DescentArgs *step, int64_t st_stride, hipStream_t s) {
+    int rc = 0;
     const int64_t npix = (int64_t)h->Hp * h->Wp;
     const int nr = d->n_ref;
     if (K > h->batch_cap || h->nseg > h->batch_seg_cap) {
@@ -3193,13 +3197,45 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
     CMAX_CHECK_LAUNCH();
     launch_grad<CMAX_MODEL_2DOF>(h, ev, wp, ra, nr, kFoldDeferred, op, h->braw, nullptr, nullptr, false, s, 0, -1, K);
     CMAX_CHECK_LAUNCH();
-    hipLaunchKernelGGL(k_finish_raw, dim3(K), dim3(64), 0, s, (const double *)h->braw, nr, op, h->d_stat, results, (double *)grads,
-                       (volatile unsigned long long *)nullptr, 0ull);
+    if (step)
+        hipLaunchKernelGGL(k_finish_raw_step_batch, dim3(K), dim3(64), 0, s, (const double *)h->braw, nr, op, h->d_stat, results, grads, *step, st_stride);
+    else
+        hipLaunchKernelGGL(k_finish_raw, dim3(K), dim3(64), 0, s, (const double *)h->braw, nr, op, h->d_stat, results, grads,
+                           (volatile unsigned long long *)nullptr, 0ull);
     CMAX_CHECK_LAUNCH();
     h->batch_zero[h->batch_cur] = 0;           // holds votes now
     h->batch_zero[h->batch_cur ^ 1] = K * nr;  // K3 cleared the first K * nr images of the other buffer (a larger batch clears it itself)
     h->batch_cur ^= 1;
     return 0;
+}
+
+// K candidate motions in ONE launch pair.  The reference's gradient-free paths evaluate the objective for batches of sampled motions
+// (src/solver/base.py:738-758 run_optuna; src/solver/patch_contrast_pyramid.py:363-415), and a line search asks for several steps
+// along one direction: each evaluation of such a batch alone is two dependent launches and a finishing one, and at cfg2's size those
+// launches' floor is 40 % of it (roofline.launch_floor_us).  Here blockIdx.z of K1 / K3 is the candidate -- every candidate its own
+// vote image, raw-sum lines and windows -- and the finishing kernel runs one wave per candidate.
+// Fast path: 2-DoF, plain image variance (sigma 0, not normalised), default mode, one GPU -- the headline objective.  Everything
+// else is evaluated candidate by candidate inside this call (same results, no speed-up).
+int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void *motions_v, int K, double *results, void *grads,
+                         cmax_stream_t stream) {
+    const float *motions = static_cast<const float *>(motions_v);
+    int rc = check_objective_args(h, d, motions);
+    if (rc) return rc;
+    CMAX_REQUIRE(results != nullptr && K >= 1 && K <= 64, "objective_batch: results / 1 <= K <= 64");
+    hipStream_t s = (hipStream_t)stream;
+    const bool two_dof = d->model == CMAX_MODEL_2DOF;
+    const GradExtent g = grad_extent(h, d);
+    const int64_t mfloats = (two_dof ? 2 : g.count) * (d->motion_dtype == CMAX_F64 ? 2 : 1);  // floats per candidate motion
+    if (!batch_fast_applies(h, d, K, grads)) {
+        for (int z = 0; z < K; ++z) {
+            const float *motion = nullptr;  // (an fp64 flow: every candidate is split in front of its evaluation, stream-ordered in the one scratch)
+            rc = kernel_motion(h, d, motions + z * mfloats, s, &motion);
+            if (!rc) rc = objective_eval(h, d, motion, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
+            if (rc) return rc;
+        }
+        return 0;
+    }
+    return batch_enqueue(h, d, motions, K, mfloats, results, (double *)grads, nullptr, 0, s);
 }
 
 int cmax_objective_has_raw(cmax_handle_t h, const cmax_objective_t *d) {
@@ -3331,11 +3367,31 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
     return 0;
 }
 
+// The n_iter iterations of ONE trajectory, enqueued: what cmax_objective runs from the device-resident theta, the step riding on the deferred
+// path's finishing launch or launched behind the evaluation.  hp_dev (may be null): the device view of the pinned block that receives the
+// result and, behind it, the run counter `seq` from the last iteration.
+static int descend_one(cmax_handle_t h, const cmax_objective_t *d, const cmax_descent_t *o, double *theta, double *grad, double *result, double *st, bool trace,
+                       double *hp_dev, unsigned long long seq, hipStream_t s) {
+    static const bool no_fused_step = getenv("CMAX_DESCENT_NO_FUSED_STEP") != nullptr;  // (tools/probe_descent.py: the separate finish + step)
+    for (int it = 0; it < o->n_iter; ++it) {
+        DescentArgs a = descent_args(*o, it, 2, trace, theta, st);
+        if (it == o->n_iter - 1 && hp_dev) {
+            a.res_pinned = hp_dev;
+            a.flag = reinterpret_cast<volatile unsigned long long *>(hp_dev + 16);
+            a.seq = seq;
+        }
+        bool stepped = false;
+        int rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, nullptr, nullptr, nullptr, 0, false, no_fused_step ? nullptr : &a, &stepped);
+        if (!rc && !stepped) rc = launch_descent_step(a, result, grad, s);
+        if (rc) return rc;
+    }
+    return 0;
+}
+
 // SolverBase.run_torch (src/solver/base.py:840-881) on a 2-DoF fused objective: theta0 once, n_iter x (what cmax_objective runs from the
 // device-resident theta -> the step) eagerly on the caller's stream, ONE wait behind the last iteration's run counter, the copies out.
 int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, const cmax_descent_t *o, cmax_descent_result_t *res_host,
                            double *x_last_host, double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream) {
-    static const bool no_fused_step = getenv("CMAX_DESCENT_NO_FUSED_STEP") != nullptr;  // (tools/probe_descent.py: the separate finish + step)
     int rc = descent_check(o, "objective_descend");
     if (rc) return rc;
     CMAX_REQUIRE(h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, "objective_descend: null pointer");
@@ -3365,18 +3421,8 @@ int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const dou
     h->hp_out[8] = theta0_host[0];  // (pinned staging of theta0; doubles 0..3 receive the result block, 16 the run counter)
     h->hp_out[9] = theta0_host[1];
     CMAX_CHECK_HIP(hipMemcpyAsync(theta, h->hp_out + 8, 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    for (int it = 0; it < n_iter; ++it) {
-        DescentArgs a = descent_args(*o, it, nx, trace, theta, st);
-        if (it == n_iter - 1) {
-            a.res_pinned = hp_dev;
-            a.flag = reinterpret_cast<volatile unsigned long long *>(hp_dev + 16);
-            a.seq = seq;
-        }
-        bool stepped = false;
-        rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, nullptr, nullptr, nullptr, 0, false, no_fused_step ? nullptr : &a, &stepped);
-        if (!rc && !stepped) rc = launch_descent_step(a, result, grad, s);
-        if (rc) return rc;
-    }
+    rc = descend_one(h, d, o, theta, grad, result, st, trace, hp_dev, seq, s);
+    if (rc) return rc;
     bool seen = false;
     for (long spin = 0; spin < 20000000L; ++spin) {  // tens of ms at most, then ask the runtime
         if (*flag == seq) {
@@ -3399,6 +3445,68 @@ int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const dou
     CMAX_CHECK_HIP(hipMemcpyAsync(loss_history_host, st + kDcCtrl + 4 * nx, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, s));
     if (trace) CMAX_CHECK_HIP(hipMemcpyAsync(x_trace_host, st + kDcCtrl + 4 * nx + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, s));
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// K independent trajectories of cmax_objective_descend in one call (multi-start: the 2-DoF objective is not convex, and the reference's
+// "global-best" grid, src/solver/patch_contrast_base.py:164-187, is correct only to its spacing).  Where cmax_objective_batch's fast path
+// applies, an iteration of ALL K candidates is K1 -> K3 (blockIdx.z = candidate) -> one finishing launch of K waves that also steps every
+// candidate on its own state; everything else, and K = 1, runs candidate by candidate as cmax_objective_descend does.  ONE wait: the copy of
+// all states to pinned memory behind the last launch.
+// h->descent_batch: theta[K][2] | grad[K][2] | pad[K][4] | result[K][8] | K descent states (cmax_descent.h, nx = 2).
+int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, int K, const cmax_descent_t *o,
+                                 cmax_descent_result_t *res_host, double *x_last_host, double *x_best_host, double *loss_history_host,
+                                 double *x_trace_host, cmax_stream_t stream) {
+    int rc = descent_check(o, "objective_descend_batch");
+    if (rc) return rc;
+    CMAX_REQUIRE(K >= 1 && K <= CMAX_DESCENT_MAX_STARTS, "objective_descend_batch: 1 <= K <= 64 starts per call");
+    CMAX_REQUIRE(h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, "objective_descend_batch: null pointer");
+    CMAX_REQUIRE(d->model == CMAX_MODEL_2DOF, "objective_descend_batch: 2-DoF descriptors only (a dense flow / voxel descends through a patch plan: cmax_patch_plan_descend)");
+    CMAX_REQUIRE(d->motion_dtype == CMAX_F64, "objective_descend_batch: the iterates are fp64 in device memory: desc->motion_dtype must be CMAX_F64");
+    if (h->comm) {
+        set_error("objective_descend_batch: not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const int nx = 2, n_iter = o->n_iter;
+    const bool trace = x_trace_host != nullptr;
+    constexpr int kHead = 16;  // per candidate: theta[2], grad[2], pad[4], result[8]
+    const int64_t S = descent_state_doubles(nx, n_iter, trace);
+    rc = h->descent_batch.reserve(&h->bytes, (int64_t)K * (kHead + S), s);
+    if (!rc) rc = h->hp_out.reserve(std::max((int64_t)4 * kRawStride, (int64_t)K * S));
+    if (rc) return rc;
+    double *theta = h->descent_batch, *grad = theta + 2 * K, *result = theta + 8 * K, *st = theta + (int64_t)kHead * K;
+    rc = check_objective_args(h, d, reinterpret_cast<const float *>(theta));
+    if (rc) return rc;
+    std::memcpy(h->hp_out, theta0_host, (size_t)K * 2 * sizeof(double));  // (pinned staging; the states come back into the same block)
+    CMAX_CHECK_HIP(hipMemcpyAsync(theta, h->hp_out, (size_t)K * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    if (batch_fast_applies(h, d, K, grad)) {
+        for (int it = 0; it < n_iter; ++it) {
+            const DescentArgs a = descent_args(*o, it, nx, trace, theta, st);
+            rc = batch_enqueue(h, d, reinterpret_cast<const float *>(theta), K, 4, result, grad, &a, S, s);
+            if (rc) return rc;
+        }
+    } else {
+        for (int z = 0; z < K; ++z) {
+            rc = descend_one(h, d, o, theta + 2 * z, grad + 2 * z, result + 8 * z, st + z * S, trace, nullptr, 0, s);
+            if (rc) return rc;
+        }
+    }
+    CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out, st, (size_t)(K * S) * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    for (int z = 0; z < K; ++z) {
+        const double *c = h->hp_out + z * S, *xb = c + kDcCtrl, *hist = xb + 4 * nx;
+        res_host[z].best_loss = c[kDcBest];
+        res_host[z].best_iter = (int32_t)c[kDcBestIter];
+        res_host[z].n_done = (int32_t)c[kDcDone];
+        res_host[z].last_lr = c[kDcLastLr];
+        std::memcpy(x_best_host + (int64_t)z * nx, xb, nx * sizeof(double));
+        std::memcpy(x_last_host + (int64_t)z * nx, xb + nx, nx * sizeof(double));
+        std::memcpy(loss_history_host + (int64_t)z * n_iter, hist, (size_t)n_iter * sizeof(double));
+        if (trace) std::memcpy(x_trace_host + (int64_t)z * (n_iter + 1) * nx, hist + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double));
+    }
+    // (the block is also where cmax_objective_host / cmax_objective_descend poll their run counter: leave the word at the last value seen)
+    *reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16) = h->host_seq;
     return 0;
 }
 

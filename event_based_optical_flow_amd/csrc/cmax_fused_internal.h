@@ -214,6 +214,8 @@ struct cmax_handle_s {
     cmax::PinnedBuf<double> hp_out;
     unsigned long long host_seq = 0;  // run counter of the finishing kernel that writes into hp_out (polled by cmax_objective_host)
     cmax::DevBuf<double> descent;     // cmax_objective_descend (on first use): theta[2] | grad[2] | pad[4] | result[8] | the descent state (cmax_descent.h)
+    // cmax_objective_descend_batch (on first use): theta[K][2] | grad[K][2] | pad[K][4] | result[K][8] | K descent states
+    cmax::DevBuf<double> descent_batch;
     cmax::DevBuf<int> d_ticket;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches
     cmax::DevBuf<double> d_musum;  // [2 buffers][4 reference times][kMuStride] K1's sums for the blurred variance (RefArgs::musum)
     int mu_buf = 0;             // buffer the next evaluation adds into (the other one is being cleared / is clear); flipped by the launch that reads the sums

@@ -39,12 +39,33 @@ def _check_key_and_bool(config: dict, key: str) -> bool:
     return key in config.keys() and bool(config[key])
 
 
-def whole_image_guess(handle: CMaxHandle, t_scale: float, **search_cost):
+REFINE_KEYS = ("top_k", "n_iter", "method", "lr")  # patch.global_best_refine
+
+
+def global_best_refine(slv_config: dict) -> Optional[dict]:
+    """The optional solver key patch.global_best_refine: {top_k, n_iter, method, lr} (not in the reference): None when absent."""
+    refine = slv_config.get("patch", {}).get("global_best_refine")
+    if refine is None:
+        return None
+    unknown = sorted(set(refine) - set(REFINE_KEYS))
+    if unknown:
+        raise KeyError(f"patch.global_best_refine: unknown keys {unknown} (known: {list(REFINE_KEYS)})")
+    return dict(refine)
+
+
+def whole_image_guess(handle: CMaxHandle, t_scale: float, refine: Optional[dict] = None, **search_cost):
     """patch.initialize: "global-best" (src/solver/patch_contrast_base.py:164-187): the best of the 30 x 30 translations
     np.arange(-150, 150, 10)^2 for the WHOLE batch under the solver's own cost, warped as one 2-DoF motion (`motion * t_scale`,
     objective_scipy_for_patch 244-271).  900 objective evaluations in the reference, 900 / 32 cmax_objective_batch calls here,
-    the batch in time slabs while the candidates are large (CMaxHandle.auto_time_slabs).  -> (guess [2], losses [30, 30])"""
-    return grid_search_translation(handle, t_scale, WHOLE_IMAGE_FIELD, **search_cost)
+    the batch in time slabs while the candidates are large (CMaxHandle.auto_time_slabs).  -> (guess [2], losses [30, 30])
+    refine = {top_k (4), n_iter, method, lr} (patch.global_best_refine; None: exactly the calls above, nothing more): the top_k best grid
+    points are the starts of a multi-start descent (translation_search.refine_translation), start 0 being the grid's pick -- so the
+    refined guess is never worse than it.  -> (guess [2], losses [30, 30], per-start DescentResults)"""
+    if refine is None:
+        return grid_search_translation(handle, t_scale, WHOLE_IMAGE_FIELD, **search_cost)
+    refine = dict(refine)
+    top_k = int(refine.pop("top_k", 4))
+    return grid_search_translation(handle, t_scale, WHOLE_IMAGE_FIELD, refine_top=top_k, refine=refine, **search_cost)
 
 
 def one_patch_guess(events: np.ndarray, box, image_shape, padding: int, normalize_t: bool = True, **search_cost):

@@ -19,8 +19,8 @@ import numpy as np
 
 from ..cmax import CMaxHandle
 from . import scipy_autograd
-from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, one_patch_guess, run_descent,
-                     whole_image_guess)
+from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, global_best_refine, one_patch_guess,
+                     run_descent, whole_image_guess)
 from .patch_objective import PatchFlowObjective, patch_pad
 
 logger = logging.getLogger(__name__)
@@ -135,9 +135,11 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         return self._search_handle.set_events(events, on_dropped="raise")
 
     def initialize_guess_from_whole_image(self, events: np.ndarray) -> np.ndarray:
-        """patch.initialize "global-best": common.whole_image_guess over the whole batch."""
-        guess, loss = whole_image_guess(self._translation_handle(events), self._batch_t_scale(events), **self._search_cost())
-        self.search_history.append(("global-best", loss, guess))
+        """patch.initialize "global-best": common.whole_image_guess over the whole batch; with the optional key patch.global_best_refine
+        its best grid points are refined by a multi-start descent (the per-start results are then recorded behind the guess)."""
+        guess, loss, *refined = whole_image_guess(self._translation_handle(events), self._batch_t_scale(events),
+                                                  refine=global_best_refine(self.slv_config), **self._search_cost())
+        self.search_history.append(("global-best", loss, guess) + tuple(refined))
         logger.info(f"Initial value: best_guess = {guess}")
         return guess
 

@@ -30,7 +30,7 @@ from ..cmax import CMaxHandle
 from . import scipy_autograd
 from .patch_objective import PatchFlowObjective
 from .common import (DESCENT_OPTIMIZERS, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, calculate_flow_error_numpy,  # noqa: F401
-                     check_opt_method, one_patch_guess, run_descent, whole_image_guess)
+                     check_opt_method, global_best_refine, one_patch_guess, run_descent, whole_image_guess)
 
 logger = logging.getLogger(__name__)
 
@@ -196,8 +196,9 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
         if self.is_time_aware:
             raise NotImplementedError("global-best initialisation on a time-binned handle is not built (the 2-DoF search wants slabs)")
         # a 2-DoF warp would keep events from off the sensor; this handle dropped them on request (and raised if there were any)
-        guess, loss = whole_image_guess(handle, t_scale, **self._search_cost())
-        self.search_history.append((self.coarest_scale, "global-best", loss, guess))
+        # (optional key patch.global_best_refine: the best grid points refined by a multi-start descent, the per-start results recorded)
+        guess, loss, *refined = whole_image_guess(handle, t_scale, refine=global_best_refine(self.slv_config), **self._search_cost())
+        self.search_history.append((self.coarest_scale, "global-best", loss, guess) + tuple(refined))
         logger.info(f"Initial value: best_guess = {guess}")
         return guess
 

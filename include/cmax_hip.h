@@ -738,6 +738,29 @@ int cmax_patch_plan_descend(cmax_patch_plan_t plan, const double *x0_host, int w
 int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *desc_host, const double *theta0_host,
                            const cmax_descent_t *descent, cmax_descent_result_t *res_host, double *x_last_host,
                            double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
+/* Multi-start: K independent trajectories of cmax_objective_descend in ONE call (src/solver/base.py:840-881 from K starting points; the
+ * 2-DoF objective is not convex and the grid of patch.initialize "global-best", src/solver/patch_contrast_base.py:164-187, is correct
+ * only to its spacing).  theta0_host [K][2]; res_host [K], x_last_host [K][2], x_best_host [K][2], loss_history_host [K][n_iter]:
+ * filled; x_trace_host [K][n_iter + 1][2] or NULL.  The rules above hold PER CANDIDATE: every candidate has its own control block,
+ * optimiser state, history and trace, and a candidate that stops freezes alone -- the others go on.
+ * Where cmax_objective_batch shares its launches (K > 1; plain variance without a blur, not normalised, on an unweighted,
+ * non-deterministic handle without profiling), an iteration of all K candidates is three launches: the vote and the gather with one
+ * grid layer per candidate, and a finishing launch of K waves, each of which folds its candidate's sums and applies its step
+ * (k_finish_raw_step_batch).  Every other objective, weighted and deterministic handles, and K = 1 run candidate by candidate
+ * inside the call exactly as cmax_objective_descend runs (same results, no speed-up).
+ * Checked in this order, before any launch: the descent descriptor (CMAX_EINVAL as above, needs neither handle nor device); null
+ * pointers and 1 <= K <= CMAX_DESCENT_MAX_STARTS (CMAX_EINVAL); desc->model / desc->motion_dtype as for cmax_objective_descend
+ * (CMAX_EINVAL with the reason); a handle with a communicator (CMAX_EUNSUPPORTED).
+ * State: one handle-owned device buffer of 8 * K * (32 + n_iter + (x_trace_host ? 2 * (n_iter + 1) : 0)) bytes, counted in
+ * cmax_handle_info, kept while it is large enough (a later call with a smaller K or n_iter allocates nothing); on the shared-launch
+ * path also the workspace of cmax_objective_batch for K candidates.  Iteration 0 reads none of the state: a call never sees what
+ * an earlier call left, whatever K was.  The handle's evaluation state advances as n_iter cmax_objective_batch calls (or K * n_iter
+ * cmax_objective calls) would advance it.  One wait: the states are copied to pinned memory behind the last launch and the stream
+ * is synchronised once.  Never replayed from a graph.  Blocks until the results are on the host.                         */
+#define CMAX_DESCENT_MAX_STARTS 64
+int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *desc_host, const double *theta0_host, int K,
+                                 const cmax_descent_t *descent, cmax_descent_result_t *res_host, double *x_last_host,
+                                 double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
 
 /* The reduction of the scale_later map as a leaf operator (the autograd-chained path chains it with cmax_patch_to_dense and
  * cmax_voxel_construct).  x: device fp32 / fp64 [n].  out: device double[4] -- out[0] = max x (signed), out[1] = number of
