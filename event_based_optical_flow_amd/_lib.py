@@ -315,23 +315,9 @@ class DescentResult:
         return f"DescentResult(best_loss={self.best_loss!r}, best_iter={self.best_iter}, n_done={self.n_done}, nx={self.x_best.size})"
 
 
-def run_descent(call, nx: int, descent: CmaxDescent, trace: bool) -> DescentResult:
-    """Allocates the host outputs of a descend entry point, runs `call(descent*, result*, x_last, x_best, history, trace)`."""
-    import numpy as np
-
-    n_iter = max(int(descent.n_iter), 1)
-    res = CmaxDescentResult()
-    x_last, x_best = np.empty(nx, dtype=np.float64), np.empty(nx, dtype=np.float64)
-    hist = np.empty(n_iter, dtype=np.float64)
-    tr = np.empty((n_iter + 1, nx), dtype=np.float64) if trace else None
-    check(call(ctypes.byref(descent), ctypes.byref(res), x_last.ctypes.data, x_best.ctypes.data, hist.ctypes.data,
-               tr.ctypes.data if trace else None))
-    return DescentResult(x_best, x_last, res.best_loss, res.best_iter, res.n_done, res.last_lr, hist, tr)
-
-
-def run_descent_batch(call, K: int, nx: int, descent: CmaxDescent, trace: bool) -> list:
-    """The same for the K trajectories of cmax_objective_descend_batch: `call(descent*, results[K], x_last, x_best, history, trace)`
-    -> K DescentResults (views of the [K, ...] host arrays)."""
+def _run_descents(call, K: int, nx: int, descent: CmaxDescent, trace: bool) -> list:
+    """Allocates the host outputs of K trajectories, runs `call(descent*, results[K], x_last, x_best, history, trace)` -> K DescentResults
+    (views of the [K, ...] host arrays)."""
     import numpy as np
 
     n_iter = max(int(descent.n_iter), 1)
@@ -342,6 +328,16 @@ def run_descent_batch(call, K: int, nx: int, descent: CmaxDescent, trace: bool) 
     check(call(ctypes.byref(descent), res, x_last.ctypes.data, x_best.ctypes.data, hist.ctypes.data, tr.ctypes.data if trace else None))
     return [DescentResult(x_best[z], x_last[z], res[z].best_loss, res[z].best_iter, res[z].n_done, res[z].last_lr, hist[z], tr[z] if trace else None)
             for z in range(K)]
+
+
+def run_descent(call, nx: int, descent: CmaxDescent, trace: bool) -> DescentResult:
+    """The host outputs of a single-start descend entry point (cmax_patch_plan_descend, cmax_objective_descend): one trajectory."""
+    return _run_descents(call, 1, nx, descent, trace)[0]
+
+
+def run_descent_batch(call, K: int, nx: int, descent: CmaxDescent, trace: bool) -> list:
+    """... and of the K trajectories of cmax_objective_descend_batch."""
+    return _run_descents(call, K, nx, descent, trace)
 
 
 def require_gpu():

@@ -140,6 +140,32 @@ def compose_events_grad(grad_events: torch.Tensor, csum: torch.Tensor, t: torch.
     return out
 
 
+def _with_motion_dtype(desc: CmaxObjective, want: int) -> CmaxObjective:
+    """`desc` itself when its motion_dtype is `want`, otherwise a copy that says so (the caller's descriptor is never written)."""
+    if desc.motion_dtype == want:
+        return desc
+    desc = CmaxObjective.from_buffer_copy(desc)
+    desc.motion_dtype = want
+    return desc
+
+
+def _unit_tangent(tangent, shape=None):
+    """(tangent / max|tangent| as contiguous fp32, max|tangent| as a 0-dim fp64 tensor): the derivative votes are fixed point, so a
+    tangent crosses in unit max-norm and the caller scales the result back.  (None, 0) for a zero or empty tangent."""
+    u = to_device_tensor(tangent, "tangent").detach().to(torch.float64)
+    if shape is not None:
+        u = u.reshape(shape)
+    umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
+    if float(umax) == 0.0:
+        return None, umax
+    return (u / umax).to(torch.float32).contiguous(), umax
+
+
+def _ptr(a):
+    """Address of a device tensor or a host array as ctypes takes it; None stays None."""
+    return None if a is None else a.data_ptr() if isinstance(a, torch.Tensor) else a.ctypes.data
+
+
 class CMaxHandle:
     """One GPU workspace for one event batch (cmax_create / cmax_set_events / cmax_objective)."""
 
@@ -362,10 +388,43 @@ class CMaxHandle:
         m = to_device_tensor(motion, "motion").detach()
         want = _lib.F64 if (m.dtype == torch.float64 and (desc.model == _lib.MODEL_2DOF or exact_flow)) else _lib.F32
         m = m.contiguous() if want == _lib.F64 else m.to(torch.float32).contiguous()
-        if desc.motion_dtype != want:
-            desc = CmaxObjective.from_buffer_copy(desc)
-            desc.motion_dtype = want
-        return m, desc
+        return m, _with_motion_dtype(desc, want)
+
+    def _grad_out(self, desc, m, host: bool = False):
+        """An uninitialised buffer of the motion gradient's form (also a Hessian-vector product's): float64 [2] for the 2-DoF model,
+        else float32 of the motion's shape; `desc`: a CmaxObjective or a CmaxIwes; a device tensor, or a numpy array with `host`."""
+        two_dof = desc.model == _lib.MODEL_2DOF
+        if host:
+            return np.empty(2, dtype=np.float64) if two_dof else np.empty(tuple(m.shape), dtype=np.float32)
+        if two_dof:
+            return torch.empty(2, dtype=torch.float64, device=self.device)
+        return torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+
+    def _outputs(self, desc, m, want_grad: bool = True, host: bool = False):
+        """(result double[8], grad or None): the outputs of one objective call, on the device or (host) as numpy arrays."""
+        result = np.empty(8, dtype=np.float64) if host else torch.empty(8, dtype=torch.float64, device=self.device)
+        return result, (self._grad_out(desc, m, host) if want_grad else None)
+
+    def _per_event_out(self, cols: Tuple[int, ...] = (), want: bool = True):
+        """(n, buffer): float32 [max(n, 1), *cols] on the device for one entry per event handed to set_events (None unless `want`);
+        callers return buffer[:n] (an empty batch still hands over a valid pointer: a tensor without elements has none)."""
+        n = int(getattr(self, "_n_in", 0))
+        return n, (torch.empty((max(n, 1),) + cols, dtype=torch.float32, device=self.device) if want else None)
+
+    def _prepared(self, fn, desc, m, outs, k: Optional[int] = None):
+        """A prepared call `fn(handle, desc, motion[, k], *outs, stream)`: function and pointers resolved once; `call()` enqueues it on
+        the current stream.  call.keepalive holds what the pointers point into, call.motion is the tensor the call reads."""
+        args = (self._h, ctypes.byref(desc), m.data_ptr()) + (() if k is None else (k,)) + tuple(_ptr(o) for o in outs)
+        stream = F._stream
+
+        def call():
+            rc = fn(*args, stream())
+            if rc:
+                check(rc)
+
+        call.keepalive = (m, desc) + tuple(outs)
+        call.motion = m
+        return call
 
     def iwe(self, motion, motion_model: Optional[str], direction: Union[str, float] = "first",
             normalize_t: bool = True, sigma: float = 0.0) -> torch.Tensor:
@@ -386,13 +445,7 @@ class CMaxHandle:
         """One cmax_objective call.  Returns (result double[8] on device, grad or None).
         result[0] = loss, result[1..n_ref] = raw contrasts, result[5] = contrast of orig_iwe."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            if desc.model == _lib.MODEL_2DOF:
-                grad = torch.empty(2, dtype=torch.float64, device=self.device)
-            else:
-                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+        result, grad = self._outputs(desc, m, want_grad)
         check(self._lib.cmax_objective(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
                                        grad.data_ptr() if grad is not None else None, F._stream()))
         return result, grad
@@ -404,19 +457,11 @@ class CMaxHandle:
         by w (an event of weight 0 has a derivative), an unweighted handle means w = 1, and events that were not packed get 0.
         Deterministic handles and handles with a communicator raise NotImplementedError with the library's text."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            if desc.model == _lib.MODEL_2DOF:
-                grad = torch.empty(2, dtype=torch.float64, device=self.device)
-            else:
-                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
-        n = int(getattr(self, "_n_in", 0))
-        buf = torch.empty(max(n, 1), dtype=torch.float32, device=self.device)  # (an empty batch still hands over a valid pointer: a
-        grad_w = buf[:n]                                                        # tensor without elements has none)
+        result, grad = self._outputs(desc, m, want_grad)
+        n, buf = self._per_event_out()
         check(self._lib.cmax_objective_weight_grad(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
                                                    grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, F._stream()))
-        return result, grad, grad_w
+        return result, grad, buf[:n]
 
     def evaluate_event_grad(self, desc: CmaxObjective, motion, want_grad: bool = True, exact_flow: bool = False):
         """One cmax_objective_event_grad call: (result, grad or None, grad_events, csum).  result and grad as `evaluate` returns them;
@@ -427,15 +472,8 @@ class CMaxHandle:
         packed keep a row of zeros.  Deterministic handles and handles with a communicator raise NotImplementedError with the
         library's text."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            if desc.model == _lib.MODEL_2DOF:
-                grad = torch.empty(2, dtype=torch.float64, device=self.device)
-            else:
-                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
-        n = int(getattr(self, "_n_in", 0))
-        buf = torch.empty((max(n, 1), 3), dtype=torch.float32, device=self.device)  # (an empty batch still hands over a valid pointer)
+        result, grad = self._outputs(desc, m, want_grad)
+        n, buf = self._per_event_out((3,))
         csum = torch.empty(4, dtype=torch.float64, device=self.device)
         check(self._lib.cmax_objective_event_grad(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
                                                   grad.data_ptr() if grad is not None else None, buf.data_ptr(), n, csum.data_ptr(), F._stream()))
@@ -457,21 +495,8 @@ class CMaxHandle:
         optimiser that updates its own tensor in place must write into `call.motion` instead (call.motion_is_callers tells).  `evaluate` spends ~6 us per call in Python (two allocations, tensor checks) -- as
         much as the three launches of a 1M-event 2-DoF evaluation leave the host to spare (profiles/r02_ablation.txt)."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            grad = (torch.empty(2, dtype=torch.float64, device=self.device) if desc.model == _lib.MODEL_2DOF
-                    else torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device))
-        fn = self._lib.cmax_objective_dist if dist else self._lib.cmax_objective
-        h, dref, mp, rp, gp, stream = self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(), grad.data_ptr() if grad is not None else None, F._stream
-
-        def call():
-            rc = fn(h, dref, mp, rp, gp, stream())
-            if rc:
-                check(rc)
-
-        call.keepalive = (m, desc, result, grad)  # the pointers above stay valid as long as the callable lives
-        call.motion = m
+        result, grad = self._outputs(desc, m, want_grad)
+        call = self._prepared(self._lib.cmax_objective_dist if dist else self._lib.cmax_objective, desc, m, (result, grad))
         call.motion_is_callers = isinstance(motion, torch.Tensor) and motion.is_cuda and motion.data_ptr() == m.data_ptr()
         return call, result, grad
 
@@ -482,10 +507,7 @@ class CMaxHandle:
         blocks.  For the 2-DoF image-variance objective the finishing kernel writes into pinned host memory and the call polls a
         run counter behind the results: no copy engine, no driver call on the way back."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = np.empty(8, dtype=np.float64)
-        grad = None
-        if want_grad:
-            grad = np.empty(2, dtype=np.float64) if desc.model == _lib.MODEL_2DOF else np.empty(tuple(m.shape), dtype=np.float32)
+        result, grad = self._outputs(desc, m, want_grad, host=True)
         check(self._lib.cmax_objective_host(self._h, ctypes.byref(desc), m.data_ptr(), result.ctypes.data,
                                             grad.ctypes.data if grad is not None else None, F._stream()))
         return result, grad
@@ -494,21 +516,8 @@ class CMaxHandle:
         """Prepared cmax_objective_host call: (call, result, grad) with `result` / `grad` numpy arrays that every `call()`
         overwrites (it returns when they are filled)."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = np.empty(8, dtype=np.float64)
-        grad = None
-        if want_grad:
-            grad = np.empty(2, dtype=np.float64) if desc.model == _lib.MODEL_2DOF else np.empty(tuple(m.shape), dtype=np.float32)
-        fn = self._lib.cmax_objective_host
-        h, dref, mp, rp, gp, stream = self._h, ctypes.byref(desc), m.data_ptr(), result.ctypes.data, grad.ctypes.data if grad is not None else None, F._stream
-
-        def call():
-            rc = fn(h, dref, mp, rp, gp, stream())
-            if rc:
-                check(rc)
-
-        call.keepalive = (m, desc, result, grad)
-        call.motion = m
-        return call, result, grad
+        result, grad = self._outputs(desc, m, want_grad, host=True)
+        return self._prepared(self._lib.cmax_objective_host, desc, m, (result, grad)), result, grad
 
     def descend(self, desc: CmaxObjective, theta0, descent: "_lib.CmaxDescent", trace: bool = False) -> "_lib.DescentResult":
         """One cmax_objective_descend call: descent.n_iter iterations of SGD / Adam on a 2-DoF objective (the reference's run_torch,
@@ -517,9 +526,7 @@ class CMaxHandle:
         theta0 = np.ascontiguousarray(np.asarray(theta0.detach().cpu() if isinstance(theta0, torch.Tensor) else theta0, dtype=np.float64).reshape(-1))
         if theta0.size != 2:
             raise ValueError(f"theta0 has {theta0.size} elements, a 2-DoF descent needs 2")
-        if desc.motion_dtype != _lib.F64:  # the iterate is fp64 in device memory
-            desc = CmaxObjective.from_buffer_copy(desc)
-            desc.motion_dtype = _lib.F64
+        desc = _with_motion_dtype(desc, _lib.F64)  # the iterate is fp64 in device memory
         fn, h, dref, stream = self._lib.cmax_objective_descend, self._h, ctypes.byref(desc), F._stream()
         with torch.cuda.device(self.device):
             return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(h, dref, theta0.ctypes.data, o, res, xl, xb, hist, tr, stream), 2, descent, trace)
@@ -532,9 +539,7 @@ class CMaxHandle:
         theta0s = np.ascontiguousarray(np.asarray(theta0s.detach().cpu() if isinstance(theta0s, torch.Tensor) else theta0s, dtype=np.float64))
         if theta0s.ndim != 2 or theta0s.shape[1] != 2:
             raise ValueError(f"theta0s has shape {tuple(theta0s.shape)}, the starts of a 2-DoF descent are [K, 2]")
-        if desc.motion_dtype != _lib.F64:  # the iterates are fp64 in device memory
-            desc = CmaxObjective.from_buffer_copy(desc)
-            desc.motion_dtype = _lib.F64
+        desc = _with_motion_dtype(desc, _lib.F64)  # the iterates are fp64 in device memory
         fn, h, dref, stream = self._lib.cmax_objective_descend_batch, self._h, ctypes.byref(desc), F._stream()
         out = []
         with torch.cuda.device(self.device):
@@ -562,23 +567,17 @@ class CMaxHandle:
             raise _lib.CmaxError(-1, "this objective has no raw form (2-DoF, default mode, non-empty batch; not a normalised plain variance)")
         raw = torch.empty((desc.n_ref, _lib.RAW_DOUBLES), dtype=torch.float64, device=self.device)
         host = torch.empty((desc.n_ref, _lib.RAW_DOUBLES), dtype=torch.float64).pin_memory()
-        fn, fin = self._lib.cmax_objective_raw, self._lib.cmax_finalize_raw_host
-        h, dref, mp, rp, stream = self._h, ctypes.byref(desc), m.data_ptr(), raw.data_ptr(), F._stream
-
-        def call():
-            rc = fn(h, dref, mp, rp, stream())
-            if rc:
-                check(rc)
+        call = self._prepared(self._lib.cmax_objective_raw, desc, m, (raw,))
+        fin, h, dref = self._lib.cmax_finalize_raw_host, self._h, ctypes.byref(desc)
 
         def finalize():
             host.copy_(raw, non_blocking=True)
             torch.cuda.current_stream().synchronize()
-            result, grad = np.empty(8, dtype=np.float64), np.empty(2, dtype=np.float64)
+            result, grad = self._outputs(desc, m, host=True)
             check(fin(h, dref, host.data_ptr(), result.ctypes.data, grad.ctypes.data))
             return result, grad
 
-        call.keepalive = (m, desc, raw, host)
-        call.motion = m
+        call.keepalive += (host,)
         return call, raw, finalize
 
     def prepare_batch(self, desc: CmaxObjective, motions, exact_flow: bool = False):
@@ -588,27 +587,13 @@ class CMaxHandle:
         image-variance objective the K evaluations share one launch of each kernel (blockIdx.z = candidate)."""
         mt = to_device_tensor(motions, "motions").detach()
         K = int(mt.shape[0])
-        desc = CmaxObjective.from_buffer_copy(desc)
-        if mt.dtype == torch.float64 and (desc.model == _lib.MODEL_2DOF or exact_flow):
-            desc.motion_dtype = _lib.F64
-            m = mt.contiguous()
-        else:
-            desc.motion_dtype = _lib.F32
-            m = mt.to(torch.float32).contiguous()
+        m, desc = self._motion_arg(desc, mt, exact_flow)
         results = torch.empty((K, 8), dtype=torch.float64, device=self.device)
         if desc.model == _lib.MODEL_2DOF:
             grads = torch.empty((K, 2), dtype=torch.float64, device=self.device)
         else:
             grads = torch.empty((K,) + tuple(m.shape[1:]), dtype=torch.float32, device=self.device)
-        fn, h, dref, mp, rp, gp, stream = self._lib.cmax_objective_batch, self._h, ctypes.byref(desc), m.data_ptr(), results.data_ptr(), grads.data_ptr(), F._stream
-
-        def call():
-            rc = fn(h, dref, mp, K, rp, gp, stream())
-            if rc:
-                check(rc)
-
-        call.keepalive = (m, desc, results, grads)
-        return call, results, grads
+        return self._prepared(self._lib.cmax_objective_batch, desc, m, (results, grads), k=K), results, grads
 
     def evaluate_batch(self, desc: CmaxObjective, motions, exact_flow: bool = False):
         """(results [K, 8], grads [K, ...]) of K candidate motions: one cmax_objective_batch call."""
@@ -624,19 +609,11 @@ class CMaxHandle:
         if exact_flow:
             m, desc = self._motion_arg(desc, motion, True)
         else:
-            m = self._motion32(motion)
-            if desc.motion_dtype != _lib.F32:
-                desc = CmaxObjective.from_buffer_copy(desc)
-                desc.motion_dtype = _lib.F32
-        u = to_device_tensor(tangent, "tangent").detach().to(torch.float64)
-        umax = u.abs().max()
-        if float(umax) == 0.0:
-            return torch.zeros(2, dtype=torch.float64, device=self.device) if desc.model == _lib.MODEL_2DOF else torch.zeros_like(m, dtype=torch.float32)
-        un = (u / umax).to(torch.float32).contiguous()  # unit max-norm: the derivative votes are fixed point
-        if desc.model == _lib.MODEL_2DOF:
-            hv = torch.empty(2, dtype=torch.float64, device=self.device)
-        else:
-            hv = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+            m, desc = self._motion32(motion), _with_motion_dtype(desc, _lib.F32)
+        un, umax = _unit_tangent(tangent)
+        hv = self._grad_out(desc, m)
+        if un is None:
+            return hv.zero_()
         check(self._lib.cmax_objective_hvp(self._h, ctypes.byref(desc), m.data_ptr(), un.data_ptr(), hv.data_ptr(), F._stream()))
         return hv * umax.to(hv.dtype)
 
@@ -668,11 +645,6 @@ class CMaxHandle:
             raise ValueError(f"{what} must be [{n_planes}, {self.padded_size[0]}, {self.padded_size[1]}], got {tuple(t.shape)}")
         return t
 
-    def _iwes_grad_like(self, d: CmaxIwes, m: torch.Tensor) -> torch.Tensor:
-        if d.model == _lib.MODEL_2DOF:
-            return torch.empty(2, dtype=torch.float64, device=self.device)
-        return torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
-
     def iwes(self, motion, motion_model: str, directions=("first",), sigma: float = 0.0, normalize_t: bool = True,
              with_orig: bool = False, exact_flow: bool = False) -> torch.Tensor:
         """The images of warped events at every reference time in `directions` in one call (cmax_iwes): fp32 [K, Hp, Wp], K =
@@ -691,9 +663,8 @@ class CMaxHandle:
         `iwes`' result, the caller's dL/dI.  The result is that of the handle's state (order, weights) at the time of THIS call."""
         m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, with_orig, exact_flow)
         g = self._iwes_planes(gimages, d.n_ref + d.with_orig, "gimages")
-        grad = self._iwes_grad_like(d, m)
-        n = int(getattr(self, "_n_in", 0))
-        buf = torch.empty(max(n, 1), dtype=torch.float32, device=self.device) if want_grad_w else None
+        grad = self._grad_out(d, m)
+        n, buf = self._per_event_out(want=want_grad_w)
         check(self._lib.cmax_iwes_vjp(self._h, ctypes.byref(d), m.data_ptr(), g.data_ptr(), grad.data_ptr(),
                                       buf.data_ptr() if want_grad_w else None, n, F._stream()))
         return grad, (buf[:n] if want_grad_w else None)
@@ -704,11 +675,9 @@ class CMaxHandle:
         for the fixed-point derivative votes and the result scaled back, as `hvp` does."""
         m, d = self._iwes_args(motion, motion_model, directions, sigma, normalize_t, False, exact_flow)
         out = torch.zeros((d.n_ref,) + self.padded_size, dtype=torch.float32, device=self.device)
-        u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
-        umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
-        if float(umax) == 0.0:
+        un, umax = _unit_tangent(tangent, m.shape)
+        if un is None:
             return out
-        un = (u / umax).to(torch.float32).contiguous()
         check(self._lib.cmax_iwes_jvp(self._h, ctypes.byref(d), m.data_ptr(), un.data_ptr(), out.data_ptr(), F._stream()))
         return out * umax.to(torch.float32)
 
@@ -721,13 +690,11 @@ class CMaxHandle:
         n_planes = d.n_ref + d.with_orig
         g = self._iwes_planes(gimages, n_planes, "gimages")
         gt = torch.zeros_like(g) if gimages_tan is None else self._iwes_planes(gimages_tan, n_planes, "gimages_tan")
-        u = to_device_tensor(tangent, "tangent").detach().to(torch.float64).reshape(m.shape)
-        umax = u.abs().max() if u.numel() else torch.zeros((), dtype=torch.float64)
-        if float(umax) == 0.0:  # what is left is J^T gimages_tan
+        un, umax = _unit_tangent(tangent, m.shape)
+        if un is None:  # what is left is J^T gimages_tan
             return self.iwes_vjp(motion, motion_model, gt, directions, sigma, normalize_t, with_orig, exact_flow=exact_flow)[0]
-        un = (u / umax).to(torch.float32).contiguous()
         gt = (gt / umax.to(torch.float32)).contiguous()  # linear in (tangent, gimages_tan) jointly
-        out = self._iwes_grad_like(d, m)
+        out = self._grad_out(d, m)
         check(self._lib.cmax_iwes_vjp_tan(self._h, ctypes.byref(d), m.data_ptr(), un.data_ptr(), g.data_ptr(), gt.data_ptr(),
                                           out.data_ptr(), F._stream()))
         return out * umax.to(out.dtype)
@@ -749,13 +716,7 @@ class CMaxHandle:
         tensor's memory, so keep the tensor alive (and unchanged) until then -- a freed one gives stale values with no error."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
         images = images.contiguous()
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            if desc.model == _lib.MODEL_2DOF:
-                grad = torch.empty(2, dtype=torch.float64, device=self.device)
-            else:
-                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+        result, grad = self._outputs(desc, m, want_grad)
         check(self._lib.cmax_objective_finish(self._h, ctypes.byref(desc), m.data_ptr(), images.data_ptr(),
                                               int(images.shape[0]), result.data_ptr(),
                                               grad.data_ptr() if grad is not None else None, F._stream()))
@@ -889,13 +850,7 @@ class CMaxHandle:
         """One cmax_objective_dist call: the evaluation of the whole time-sliced batch, both all-reduces enqueued
         by the library between its kernels.  Same returns as `evaluate`, the same on every rank."""
         m, desc = self._motion_arg(desc, motion, exact_flow)
-        result = torch.empty(8, dtype=torch.float64, device=self.device)
-        grad = None
-        if want_grad:
-            if desc.model == _lib.MODEL_2DOF:
-                grad = torch.empty(2, dtype=torch.float64, device=self.device)
-            else:
-                grad = torch.empty(tuple(m.shape), dtype=torch.float32, device=self.device)
+        result, grad = self._outputs(desc, m, want_grad)
         check(self._lib.cmax_objective_dist(self._h, ctypes.byref(desc), m.data_ptr(), result.data_ptr(),
                                             grad.data_ptr() if grad is not None else None, F._stream()))
         return result, grad
@@ -943,6 +898,12 @@ class CMaxHandle:
         return out
 
 
+def _chain(g: Optional[torch.Tensor], gout: torch.Tensor, dtype, device) -> Optional[torch.Tensor]:
+    """The chain rule of a fused loss for one input: its stored derivative g (None: not asked for) times dL/dloss, in the input's dtype
+    on the input's device."""
+    return None if g is None else (g.to(dtype) * gout.to(g.device).to(dtype)).to(device)
+
+
 class _FusedFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, motion, handle, desc, exact_flow=False):
@@ -955,11 +916,7 @@ class _FusedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        g = ctx.grad
-        if g is None:
-            return None, None, None, None
-        g = g.to(ctx.mdtype) * gout.to(g.device).to(ctx.mdtype)
-        return g.to(ctx.mdevice), None, None, None
+        return _chain(ctx.grad, gout, ctx.mdtype, ctx.mdevice), None, None, None
 
 
 class _FusedWeightedFn(torch.autograd.Function):
@@ -977,11 +934,8 @@ class _FusedWeightedFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        gm = gw = None
-        if ctx.grad is not None:
-            gm = (ctx.grad.to(ctx.mdtype) * gout.to(ctx.grad.device).to(ctx.mdtype)).to(ctx.mdevice)
-        if ctx.grad_w is not None:
-            gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
+        gm = _chain(ctx.grad, gout, ctx.mdtype, ctx.mdevice)
+        gw = _chain(ctx.grad_w, gout, ctx.wdtype, ctx.wdevice)
         return gm, gw, None, None, None
 
 
@@ -996,7 +950,7 @@ class _FusedEventsFn(torch.autograd.Function):
         ctx.grad_ev = None
         if events.requires_grad:
             ctx.grad_ev = compose_events_grad(ge, csum, handle._batch_t, ref_fractions(desc), bool(desc.normalize_t), handle._batch_t_range)
-        ctx.grad_w = None
+        ctx.grad_w = ctx.wdtype = ctx.wdevice = None
         if weights is not None and weights.requires_grad:
             ctx.grad_w = handle.evaluate_weight_grad(desc, motion, want_grad=False, exact_flow=exact_flow)[2]
             ctx.wdtype, ctx.wdevice = weights.dtype, weights.device
@@ -1006,14 +960,10 @@ class _FusedEventsFn(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gout):
-        gm = ge = gw = None
-        if ctx.grad is not None:
-            gm = (ctx.grad.to(ctx.mdtype) * gout.to(ctx.grad.device).to(ctx.mdtype)).to(ctx.mdevice)
-        if ctx.grad_ev is not None:
-            ge = (ctx.grad_ev * gout.to(ctx.grad_ev.device).to(torch.float64)).to(ctx.edtype).to(ctx.edevice)
-        if ctx.grad_w is not None:
-            gw = (ctx.grad_w.to(ctx.wdtype) * gout.to(ctx.grad_w.device).to(ctx.wdtype)).to(ctx.wdevice)
-        return gm, ge, gw, None, None, None
+        gm = _chain(ctx.grad, gout, ctx.mdtype, ctx.mdevice)
+        ge = _chain(ctx.grad_ev, gout, torch.float64, ctx.edevice)  # (the product in the fp64 of compose_events_grad, rounded once)
+        gw = _chain(ctx.grad_w, gout, ctx.wdtype, ctx.wdevice)
+        return gm, (None if ge is None else ge.to(ctx.edtype)), gw, None, None, None
 
 
 class _IwesVjpFn(torch.autograd.Function):

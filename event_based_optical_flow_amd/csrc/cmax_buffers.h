@@ -1,4 +1,5 @@
-// Owning buffers of the library's host code: device memory (DevBuf) and pinned host staging (PinnedBuf), grown on demand.
+// Owning buffers of the library's host code: device memory (DevBuf) and pinned host staging (PinnedBuf), grown on demand, and the wait
+// on a run counter that a kernel writes into such staging (wait_run_counter).
 // Needs the HIP runtime and cmax_common.h only (tests/buffers_check.hip compiles it without the handle).
 //
 // The synchronisation rule, for every buffer: the stream is synchronised before memory that may be in use by work queued on it is
@@ -6,6 +7,7 @@
 // of it orders nothing anew, it names the stream whose work the memory belongs to.)
 #pragma once
 
+#include <atomic>
 #include <cstring>
 #include <utility>
 
@@ -83,6 +85,7 @@ static int release_all(hipStream_t stream, B &...b) {
 // Coherent + mapped: kernels write results and run counters straight into these buffers and the host polls them (cmax_objective_host,
 // the patch plan's tail) -- visibility must not hang on HIP_HOST_COHERENT; zeroed: a flag word is polled before anything ever wrote it.
 // Nothing waits before the old memory is freed: its users wait for the last copy out of it themselves (an event, or the stream).
+// dev(): the address a kernel writes the block through, taken where the memory is obtained -- null whenever get() is.
 template <typename T>
 class __attribute__((visibility("hidden"))) PinnedBuf {
    public:
@@ -93,11 +96,12 @@ class __attribute__((visibility("hidden"))) PinnedBuf {
 
     T *get() const { return p_; }
     operator T *() const { return p_; }
+    T *dev() const { return dev_; }
     int64_t capacity() const { return cap_; }
 
     void release() {
         if (p_) (void)hipHostFree(p_);
-        p_ = nullptr;
+        p_ = dev_ = nullptr;
         cap_ = 0;
     }
 
@@ -112,12 +116,35 @@ class __attribute__((visibility("hidden"))) PinnedBuf {
         }
         std::memset((void *)p_, 0, (size_t)want * sizeof(T));
         cap_ = want;
+        if (hipHostGetDevicePointer((void **)&dev_, p_, 0) != hipSuccess) {
+            (void)hipGetLastError();
+            dev_ = p_;  // unified addressing: pinned host memory is addressable from the device as it is
+        }
         return 0;
     }
 
    private:
-    T *p_ = nullptr;
+    T *p_ = nullptr, *dev_ = nullptr;
     int64_t cap_ = 0;
 };
+
+// The one wait on a run counter: a kernel stores `expected` into *flag (pinned memory) behind a system-wide fence once its results are
+// visible.  Polling that word returns as soon as the last kernel has written, without the sleep / wake-up of hipStreamSynchronize (~10 us
+// late, profiles/r02_solver_objective.txt); when `spins` polls have not seen it -- none are made with spins == 0 -- the stream is waited
+// for like everybody else does.  *seen = the counter's value at return: what a value other than `expected` means is the caller's to say.
+static inline int wait_run_counter(volatile unsigned long long *flag, unsigned long long expected, long spins, hipStream_t stream,
+                                   unsigned long long *seen) {
+    for (long spin = 0; spin < spins && *flag != expected; ++spin) {
+#if defined(__x86_64__) || defined(__i386__)
+        __builtin_ia32_pause();
+#elif defined(__aarch64__)
+        asm volatile("yield" ::: "memory");
+#endif
+    }
+    if (*flag != expected) CMAX_CHECK_HIP(hipStreamSynchronize(stream));
+    *seen = *flag;
+    std::atomic_thread_fence(std::memory_order_acquire);
+    return 0;
+}
 
 }  // namespace cmax

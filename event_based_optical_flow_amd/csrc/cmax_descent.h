@@ -1,10 +1,14 @@
 // Device-resident SGD / Adam (cmax_patch_plan_descend, cmax_objective_descend, cmax_objective_descend_batch; the rules are pinned in
 // include/cmax_hip.h): the update of one iteration as the kernels that apply it share it -- k_descent_step (cmax_solver.hip: one workgroup,
 // any nx), k_finish_raw_step (cmax_fused.hip: lane 63 of the one-wave finishing kernel, nx = 2) and its sibling k_finish_raw_step_batch
-// (one such wave per candidate, every candidate its own state) -- and the host-side descriptor checks.
+// (one such wave per candidate, every candidate its own state) -- and what the three entries share on the host: the checks of descriptor
+// and arguments (descent_check, descent_entry_check), the view of a final state's regions (descent_view) and the one routine that hands
+// them to the caller (descent_copy_out), from device memory or from a host copy of the state.  The state's layout is written in this file
+// only: the device functions below and descent_view.
 // SolverBase.run_torch, src/solver/base.py:840-881.
 #pragma once
 #include <cmath>
+#include <cstring>
 
 #include "cmax_common.h"
 
@@ -70,12 +74,66 @@ static inline int descent_check(const cmax_descent_t *o, const char *who) {
     return CMAX_EINVAL;
 }
 
+// What the three entries ask of their caller before anything is reserved or enqueued.  pointers: none of the entry's required pointers is
+// null; d: the objective's descriptor (null for a patch plan, whose terms were checked when it was made); comm: the handle holds a communicator.
+static inline int descent_entry_check(const char *who, const cmax_descent_t *o, bool pointers, const cmax_objective_t *d, bool comm) {
+    const int rc = descent_check(o, who);
+    if (rc) return rc;
+    const char *why = nullptr;
+    if (!pointers) why = "null pointer";
+    else if (d && d->model != CMAX_MODEL_2DOF) why = "2-DoF descriptors only (a dense flow / voxel descends through a patch plan: cmax_patch_plan_descend)";
+    else if (d && d->motion_dtype != CMAX_F64) why = "the iterate is fp64 in device memory: desc->motion_dtype must be CMAX_F64";
+    if (why) {
+        set_error("bad argument: %s: %s", who, why);
+        return CMAX_EINVAL;
+    }
+    if (comm) {
+        set_error("%s: not built for time-sliced batches (the handle holds a communicator)", who);
+        return CMAX_EUNSUPPORTED;
+    }
+    return 0;
+}
+
 // pinned result block -> the caller's struct
 static inline void descent_result(const double *res_pinned, cmax_descent_result_t *out) {
     out->best_loss = res_pinned[0];
     out->best_iter = (int32_t)res_pinned[1];
     out->n_done = (int32_t)res_pinned[2];
     out->last_lr = res_pinned[3];
+}
+
+// The regions of one state that a caller receives, from the layout above (host code's only reading of it; m and v stay the kernels')
+struct DescentView {
+    const double *ctrl, *x_best, *x_last, *history, *trace;
+};
+static inline DescentView descent_view(const double *st, int nx, int n_iter) {
+    const double *xb = st + kDcCtrl, *hist = xb + 4 * (int64_t)nx;
+    return {st, xb, xb + nx, hist, hist + n_iter};
+}
+
+// x_best, x_last, the history and (x_trace_host non-null) the trace of the FINAL state `st` to the caller.  on_device: st is device memory
+// -- one copy per region queued on s, the caller waits for the stream; otherwise st is host memory that holds the state already.
+static inline int descent_copy_out(const double *st, bool on_device, int nx, int n_iter, double *x_best_host, double *x_last_host,
+                                   double *loss_history_host, double *x_trace_host, hipStream_t s) {
+    const DescentView v = descent_view(st, nx, n_iter);
+    const struct {
+        double *dst;
+        const double *src;
+        int64_t n;
+    } part[4] = {{x_best_host, v.x_best, nx}, {x_last_host, v.x_last, nx}, {loss_history_host, v.history, n_iter}, {x_trace_host, v.trace, ((int64_t)n_iter + 1) * nx}};
+    for (const auto &c : part) {
+        if (!c.dst) continue;
+        if (on_device) CMAX_CHECK_HIP(hipMemcpyAsync(c.dst, c.src, (size_t)c.n * sizeof(double), hipMemcpyDeviceToHost, s));
+        else std::memcpy(c.dst, c.src, (size_t)c.n * sizeof(double));
+    }
+    return 0;
+}
+// the control block of a final state in host memory -> the caller's struct
+static inline void descent_result_of_state(const double *ctrl, cmax_descent_result_t *out) {
+    out->best_loss = ctrl[kDcBest];
+    out->best_iter = (int32_t)ctrl[kDcBestIter];
+    out->n_done = (int32_t)ctrl[kDcDone];
+    out->last_lr = ctrl[kDcLastLr];
 }
 
 // cmax_solver.hip: one k_descent_step launch; loss[1] and grad[nx] where the evaluation left them in device memory

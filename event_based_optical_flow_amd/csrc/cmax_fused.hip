@@ -2333,8 +2333,22 @@ struct EvalPlan {
     VoteJobs vote;      // what K1 does for the launches behind it
 };
 
-static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool whole, cmax::Comm *comm = nullptr, bool skip_c2 = false,
-                          double *raw_out = nullptr, volatile unsigned long long *host_flag = nullptr, unsigned long long host_seq = 0) {
+// The form of an evaluation as its entry asks for it; an entry names the fields it sets, eval_plan alone reads them.
+struct EvalForm {
+    cmax::Comm *comm = nullptr;  // time-sliced batch: the images are all-reduced, and (not skip_c2) the gradient or result[8] behind them
+    bool skip_c2 = false;        // ... the gradient stays this rank's share (objective_dist_local_grad)
+    double *raw_out = nullptr;   // stop at the raw sums of the 2-DoF K3, written here (cmax_objective_raw; `grad` is then only a non-null marker)
+    volatile unsigned long long *host_flag = nullptr;  // `result` and `grad` are pinned host memory: the finishing kernel writes the run
+    unsigned long long host_seq = 0;                   // counter host_seq behind them (cmax_objective_host)
+    const DescentArgs *step = nullptr;  // a descent's step, to ride on the finishing launch where the path has one that can apply it
+    bool *stepped = nullptr;            // ... out: it does (otherwise the caller launches the step behind the evaluation)
+};
+
+static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, const void *grad, bool whole, const EvalForm &form = {}) {
+    cmax::Comm *const comm = form.comm;
+    const bool skip_c2 = form.skip_c2;
+    double *const raw_out = form.raw_out;
+    volatile unsigned long long *const host_flag = form.host_flag;
     static const int tan2_env = getenv("CMAX_TAN2") ? atoi(getenv("CMAX_TAN2")) : -1;
     static const bool no_fused_bv = getenv("CMAX_NO_FUSED_BLURVAR") != nullptr;
     static const bool no_stats_inside = getenv("CMAX_NO_STATS_INSIDE") != nullptr;
@@ -2351,13 +2365,16 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.result_alone = dist && !grad && !raw_out && !skip_c2;
     p.raw_only = raw_out != nullptr;
     p.host_flag = host_flag;
-    p.host_seq = host_seq;
+    p.host_seq = form.host_seq;
     p.g = grad_extent(h, d);
     const bool det = h->deterministic, two_dof = d->model == CMAX_MODEL_2DOF;
     const bool fold_var = d->cost == CMAX_COST_VARIANCE && !(d->sigma > 0);
     // (the deferred K3 takes sum I and sum I^2 from its own events' gather: the image must be what THIS handle's events voted in this
     // call -- an image the caller hands to cmax_objective_finish, or one that was all-reduced, keeps its statistics launch)
     p.deferred = deferred_applies(h, d, grad) && whole && !dist;
+    // (a descent's step rides on the deferred path's finishing launch; on every other path the caller launches it behind the evaluation)
+    p.step = (p.deferred && !p.tan2 && !p.empty) ? form.step : nullptr;
+    if (form.stepped) *form.stepped = p.step != nullptr;
     p.lines = two_dof_lines(h, d, grad);
     p.raw = p.lines ? (raw_out ? raw_out : h->d_raw) : nullptr;
     p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
@@ -2791,16 +2808,12 @@ static int objective_eval_tan2(cmax_handle_t h, const cmax_objective_t *d, const
 }
 
 // vote -> [all-reduce of the images] -> finish -> [all-reduce of the gradient], all on the handle's double-buffered images
-// raw_out: non-null = stop at the raw sums of the 2-DoF K3 (cmax_objective_raw; `grad` is then only a non-null marker)
 static int objective_eval(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s,
-                          cmax::Comm *comm, double *raw_out = nullptr, volatile unsigned long long *host_flag = nullptr,
-                          unsigned long long host_seq = 0, bool skip_c2 = false, const DescentArgs *step = nullptr, bool *stepped = nullptr) {
-    EvalPlan p = eval_plan(h, d, grad, true, comm, skip_c2, raw_out, host_flag, host_seq);
-    // (a descent's step rides on the deferred path's finishing launch; on every other path the caller launches it behind the evaluation)
-    p.step = (step && p.deferred && !p.tan2 && !p.empty) ? step : nullptr;
-    if (stepped) *stepped = p.step != nullptr;
+                          const EvalForm &form = {}) {
+    const EvalPlan p = eval_plan(h, d, grad, true, form);
+    cmax::Comm *const comm = form.comm;
     if (p.tan2) return objective_eval_tan2(h, d, motion, result, grad, s, comm);
-    if (raw_out && !p.lines) {
+    if (p.raw_only && !p.lines) {
         set_error("objective_raw: this objective has no raw form (2-DoF, a non-empty batch, not deterministic)");
         return CMAX_EINVAL;
     }
@@ -2852,7 +2865,7 @@ int cmax_objective(cmax_handle_t h, const cmax_objective_t *d, const void *motio
     CMAX_REQUIRE(result, "objective: result");
     rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
     if (rc) return rc;
-    return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, nullptr);
+    return objective_eval(h, d, motion, result, grad, (hipStream_t)stream);
 }
 
 }  // extern "C"
@@ -3094,7 +3107,7 @@ static int per_event_eval(cmax_handle_t h, const cmax_objective_t *d, const floa
     *orig_raw = h->imgs + (int64_t)h->cur_buf * 5 * npix + (int64_t)d->n_ref * npix;
     h->general_only = true;
     if (d->normalized) h->orig_valid = false;
-    const int rc = objective_eval(h, d, motion, result, grad, s, nullptr);
+    const int rc = objective_eval(h, d, motion, result, grad, s);
     h->general_only = false;
     return rc;
 }
@@ -3141,7 +3154,9 @@ int cmax_objective_dist(cmax_handle_t h, const cmax_objective_t *d, const void *
     CMAX_REQUIRE(result, "objective_dist: result");
     rc = kernel_motion(h, d, motion_v, (hipStream_t)stream, &motion);
     if (rc) return rc;
-    return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, h->comm);
+    EvalForm form;
+    form.comm = h->comm;
+    return objective_eval(h, d, motion, result, grad, (hipStream_t)stream, form);
 }
 
 // when K candidates share the launches of one (cmax_objective_batch, cmax_objective_descend_batch): the headline objective on one GPU
@@ -3230,7 +3245,7 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
         for (int z = 0; z < K; ++z) {
             const float *motion = nullptr;  // (an fp64 flow: every candidate is split in front of its evaluation, stream-ordered in the one scratch)
             rc = kernel_motion(h, d, motions + z * mfloats, s, &motion);
-            if (!rc) rc = objective_eval(h, d, motion, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s, nullptr);
+            if (!rc) rc = objective_eval(h, d, motion, results + 8 * z, grads ? (char *)grads + (size_t)z * g.bytes : nullptr, s);
             if (rc) return rc;
         }
         return 0;
@@ -3252,7 +3267,9 @@ int cmax_objective_raw(cmax_handle_t h, const cmax_objective_t *d, const void *m
     if (rc) return rc;
     CMAX_REQUIRE(raw, "objective_raw: raw");
     CMAX_REQUIRE(cmax_objective_has_raw(h, d), "objective_raw: this objective has no raw form (see cmax_objective_has_raw)");
-    return objective_eval(h, d, motion, nullptr, (void *)raw, (hipStream_t)stream, nullptr, raw);
+    EvalForm form;
+    form.raw_out = raw;
+    return objective_eval(h, d, motion, nullptr, (void *)raw, (hipStream_t)stream, form);
 }
 
 int cmax_finalize_raw_host(cmax_handle_t h, const cmax_objective_t *d, const double *raw_host, double *result_host, double *grad_host) {
@@ -3300,14 +3317,16 @@ static int spin_until_done(hipStream_t s) {
     return 0;
 }
 
-static inline void cpu_relax() {
-#if defined(__x86_64__) || defined(__i386__)
-    __builtin_ia32_pause();
-#elif defined(__aarch64__)
-    asm volatile("yield" ::: "memory");
-#else
-    std::atomic_signal_fence(std::memory_order_seq_cst);
-#endif
+// The wait of the entries whose last kernel stores run counter `seq` into the head of h->hp_out: polled for tens of ms at most, then the
+// runtime is asked.  who: the entry and the kernel that should have reported.
+static int wait_host_seq(cmax_handle_t h, unsigned long long seq, hipStream_t s, const char *who) {
+    unsigned long long seen = 0;
+    const int rc = wait_run_counter(cmax_handle_s::hp_counter(h->hp_out), seq, 20000000L, s, &seen);
+    if (!rc && seen != seq) {
+        set_error("%s did not report (stream finished without its run counter)", who);
+        return CMAX_ESTATE;
+    }
+    return rc;
 }
 
 int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *motion_v, double *result_host, void *grad_host,
@@ -3324,46 +3343,33 @@ int cmax_objective_host(cmax_handle_t h, const cmax_objective_t *d, const void *
         // MEMORY and then a run counter behind them; the host polls that word.  No copy engine and no driver call between the
         // last kernel and the caller (a 4 KB device-to-host copy of the raw sums + hipStreamQuery polling was 5-6 us slower per
         // evaluation, profiles/r03_ablation.txt 10).
-        rc = h->hp_out.reserve((int64_t)4 * kRawStride);
+        rc = h->hp_out.reserve(cmax_handle_s::kHpPayload);
         if (rc) return rc;
-        volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16);
-        const unsigned long long seq = ++h->host_seq;
-        for (int k = 0; k < 8; ++k) h->hp_out[k] = 0.0;  // (the kernel writes the entries the descriptor uses)
-        rc = objective_eval(h, d, motion, h->hp_out, h->hp_out + 8, s, nullptr, nullptr, flag, seq);
+        double *const hp = h->hp_out, *const hp_dev = h->hp_out.dev();
+        EvalForm form;
+        form.host_flag = cmax_handle_s::hp_counter(hp_dev);
+        form.host_seq = ++h->host_seq;
+        for (int k = 0; k < 8; ++k) hp[cmax_handle_s::kHpResult + k] = 0.0;  // (the kernel writes the entries the descriptor uses)
+        rc = objective_eval(h, d, motion, hp_dev + cmax_handle_s::kHpResult, hp_dev + cmax_handle_s::kHpStaged, s, form);
+        if (!rc) rc = wait_host_seq(h, form.host_seq, s, "objective_host: the finishing kernel");
         if (rc) return rc;
-        bool seen = false;
-        for (long spin = 0; spin < 20000000L; ++spin) {  // tens of ms at most, then ask the runtime
-            if (*flag == seq) {
-                seen = true;
-                break;
-            }
-            cpu_relax();
-        }
-        if (!seen) {
-            rc = spin_until_done(s);
-            if (rc) return rc;
-            if (*flag != seq) {
-                set_error("objective_host: the finishing kernel did not report (stream finished without its run counter)");
-                return CMAX_ESTATE;
-            }
-        }
-        std::atomic_thread_fence(std::memory_order_acquire);
-        std::memcpy(result_host, h->hp_out, 8 * sizeof(double));
-        std::memcpy(grad_host, h->hp_out + 8, 2 * sizeof(double));
+        std::memcpy(result_host, hp + cmax_handle_s::kHpResult, 8 * sizeof(double));
+        std::memcpy(grad_host, hp + cmax_handle_s::kHpStaged, 2 * sizeof(double));
         return 0;
     }
     const int64_t gbytes = grad_host ? (int64_t)grad_extent(h, d).bytes : 0;
     rc = h->d_host_grad.reserve(&h->bytes, gbytes, s);
-    if (!rc) rc = h->hp_out.reserve(8 + (gbytes + 7) / 8);
+    if (!rc) rc = h->hp_out.reserve(cmax_handle_s::kHpPayload + (gbytes + 7) / 8);
     if (rc) return rc;
-    rc = objective_eval(h, d, motion, h->d_host_result, grad_host ? h->d_host_grad.get() : nullptr, s, nullptr);
+    rc = objective_eval(h, d, motion, h->d_host_result, grad_host ? h->d_host_grad.get() : nullptr, s);
     if (rc) return rc;
-    CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out, h->d_host_result, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (grad_host) CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out + 8, h->d_host_grad, (size_t)gbytes, hipMemcpyDeviceToHost, s));
+    double *const hp_result = h->hp_out + cmax_handle_s::kHpResult, *const hp_grad = h->hp_out + cmax_handle_s::kHpPayload;
+    CMAX_CHECK_HIP(hipMemcpyAsync(hp_result, h->d_host_result, 8 * sizeof(double), hipMemcpyDeviceToHost, s));
+    if (grad_host) CMAX_CHECK_HIP(hipMemcpyAsync(hp_grad, h->d_host_grad, (size_t)gbytes, hipMemcpyDeviceToHost, s));
     rc = spin_until_done(s);
     if (rc) return rc;
-    std::memcpy(result_host, h->hp_out, 8 * sizeof(double));
-    if (grad_host) std::memcpy(grad_host, h->hp_out + 8, (size_t)gbytes);
+    std::memcpy(result_host, hp_result, 8 * sizeof(double));
+    if (grad_host) std::memcpy(grad_host, hp_grad, (size_t)gbytes);
     return 0;
 }
 
@@ -3376,12 +3382,15 @@ static int descend_one(cmax_handle_t h, const cmax_objective_t *d, const cmax_de
     for (int it = 0; it < o->n_iter; ++it) {
         DescentArgs a = descent_args(*o, it, 2, trace, theta, st);
         if (it == o->n_iter - 1 && hp_dev) {
-            a.res_pinned = hp_dev;
-            a.flag = reinterpret_cast<volatile unsigned long long *>(hp_dev + 16);
+            a.res_pinned = hp_dev + cmax_handle_s::kHpResult;
+            a.flag = cmax_handle_s::hp_counter(hp_dev);
             a.seq = seq;
         }
         bool stepped = false;
-        int rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, nullptr, nullptr, nullptr, 0, false, no_fused_step ? nullptr : &a, &stepped);
+        EvalForm form;
+        form.step = no_fused_step ? nullptr : &a;
+        form.stepped = &stepped;
+        int rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, form);
         if (!rc && !stepped) rc = launch_descent_step(a, result, grad, s);
         if (rc) return rc;
     }
@@ -3392,58 +3401,29 @@ static int descend_one(cmax_handle_t h, const cmax_objective_t *d, const cmax_de
 // device-resident theta -> the step) eagerly on the caller's stream, ONE wait behind the last iteration's run counter, the copies out.
 int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, const cmax_descent_t *o, cmax_descent_result_t *res_host,
                            double *x_last_host, double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream) {
-    int rc = descent_check(o, "objective_descend");
+    int rc = descent_entry_check("objective_descend", o, h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, d, h && h->comm);
     if (rc) return rc;
-    CMAX_REQUIRE(h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, "objective_descend: null pointer");
-    CMAX_REQUIRE(d->model == CMAX_MODEL_2DOF, "objective_descend: 2-DoF descriptors only (a dense flow / voxel descends through a patch plan: cmax_patch_plan_descend)");
-    CMAX_REQUIRE(d->motion_dtype == CMAX_F64, "objective_descend: the iterate is fp64 in device memory: desc->motion_dtype must be CMAX_F64");
-    if (h->comm) {
-        set_error("objective_descend: not built for time-sliced batches (the handle holds a communicator)");
-        return CMAX_EUNSUPPORTED;
-    }
     hipStream_t s = (hipStream_t)stream;
     const int nx = 2, n_iter = o->n_iter;
     const bool trace = x_trace_host != nullptr;
     constexpr int kHead = 16;  // theta[2] | grad[2] | pad[4] | result[8]
     rc = h->descent.reserve(&h->bytes, kHead + descent_state_doubles(nx, n_iter, trace), s);
-    if (!rc) rc = h->hp_out.reserve((int64_t)4 * kRawStride);
+    if (!rc) rc = h->hp_out.reserve(cmax_handle_s::kHpPayload);
     if (rc) return rc;
     double *theta = h->descent, *grad = theta + 2, *result = theta + 8, *st = theta + kHead;
     rc = check_objective_args(h, d, reinterpret_cast<const float *>(theta));
     if (rc) return rc;
-    double *hp_dev = nullptr;
-    if (hipHostGetDevicePointer((void **)&hp_dev, h->hp_out, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        hp_dev = h->hp_out;  // unified addressing
-    }
-    volatile unsigned long long *flag = reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16);
     const unsigned long long seq = ++h->host_seq;
-    h->hp_out[8] = theta0_host[0];  // (pinned staging of theta0; doubles 0..3 receive the result block, 16 the run counter)
-    h->hp_out[9] = theta0_host[1];
-    CMAX_CHECK_HIP(hipMemcpyAsync(theta, h->hp_out + 8, 2 * sizeof(double), hipMemcpyHostToDevice, s));
-    rc = descend_one(h, d, o, theta, grad, result, st, trace, hp_dev, seq, s);
+    double *const theta0_pinned = h->hp_out + cmax_handle_s::kHpStaged;
+    theta0_pinned[0] = theta0_host[0];
+    theta0_pinned[1] = theta0_host[1];
+    CMAX_CHECK_HIP(hipMemcpyAsync(theta, theta0_pinned, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    rc = descend_one(h, d, o, theta, grad, result, st, trace, h->hp_out.dev(), seq, s);
+    if (!rc) rc = wait_host_seq(h, seq, s, "objective_descend: the last step");
     if (rc) return rc;
-    bool seen = false;
-    for (long spin = 0; spin < 20000000L; ++spin) {  // tens of ms at most, then ask the runtime
-        if (*flag == seq) {
-            seen = true;
-            break;
-        }
-        cpu_relax();
-    }
-    if (!seen) {
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        if (*flag != seq) {
-            set_error("objective_descend: the last step did not report (stream finished without its run counter)");
-            return CMAX_ESTATE;
-        }
-    }
-    std::atomic_thread_fence(std::memory_order_acquire);
-    descent_result(h->hp_out, res_host);
-    CMAX_CHECK_HIP(hipMemcpyAsync(x_best_host, st + kDcCtrl, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    CMAX_CHECK_HIP(hipMemcpyAsync(x_last_host, st + kDcCtrl + nx, 2 * sizeof(double), hipMemcpyDeviceToHost, s));
-    CMAX_CHECK_HIP(hipMemcpyAsync(loss_history_host, st + kDcCtrl + 4 * nx, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (trace) CMAX_CHECK_HIP(hipMemcpyAsync(x_trace_host, st + kDcCtrl + 4 * nx + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    descent_result(h->hp_out + cmax_handle_s::kHpResult, res_host);
+    rc = descent_copy_out(st, true, nx, n_iter, x_best_host, x_last_host, loss_history_host, x_trace_host, s);
+    if (rc) return rc;
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
 }
@@ -3457,29 +3437,23 @@ int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const dou
 int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, int K, const cmax_descent_t *o,
                                  cmax_descent_result_t *res_host, double *x_last_host, double *x_best_host, double *loss_history_host,
                                  double *x_trace_host, cmax_stream_t stream) {
-    int rc = descent_check(o, "objective_descend_batch");
-    if (rc) return rc;
     CMAX_REQUIRE(K >= 1 && K <= CMAX_DESCENT_MAX_STARTS, "objective_descend_batch: 1 <= K <= 64 starts per call");
-    CMAX_REQUIRE(h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, "objective_descend_batch: null pointer");
-    CMAX_REQUIRE(d->model == CMAX_MODEL_2DOF, "objective_descend_batch: 2-DoF descriptors only (a dense flow / voxel descends through a patch plan: cmax_patch_plan_descend)");
-    CMAX_REQUIRE(d->motion_dtype == CMAX_F64, "objective_descend_batch: the iterates are fp64 in device memory: desc->motion_dtype must be CMAX_F64");
-    if (h->comm) {
-        set_error("objective_descend_batch: not built for time-sliced batches (the handle holds a communicator)");
-        return CMAX_EUNSUPPORTED;
-    }
+    int rc = descent_entry_check("objective_descend_batch", o, h && d && theta0_host && res_host && x_last_host && x_best_host && loss_history_host, d, h && h->comm);
+    if (rc) return rc;
     hipStream_t s = (hipStream_t)stream;
     const int nx = 2, n_iter = o->n_iter;
     const bool trace = x_trace_host != nullptr;
     constexpr int kHead = 16;  // per candidate: theta[2], grad[2], pad[4], result[8]
     const int64_t S = descent_state_doubles(nx, n_iter, trace);
     rc = h->descent_batch.reserve(&h->bytes, (int64_t)K * (kHead + S), s);
-    if (!rc) rc = h->hp_out.reserve(std::max((int64_t)4 * kRawStride, (int64_t)K * S));
+    if (!rc) rc = h->hp_out.reserve(cmax_handle_s::kHpPayload + (int64_t)K * S);
     if (rc) return rc;
     double *theta = h->descent_batch, *grad = theta + 2 * K, *result = theta + 8 * K, *st = theta + (int64_t)kHead * K;
     rc = check_objective_args(h, d, reinterpret_cast<const float *>(theta));
     if (rc) return rc;
-    std::memcpy(h->hp_out, theta0_host, (size_t)K * 2 * sizeof(double));  // (pinned staging; the states come back into the same block)
-    CMAX_CHECK_HIP(hipMemcpyAsync(theta, h->hp_out, (size_t)K * 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    double *const staged = h->hp_out + cmax_handle_s::kHpPayload;  // (theta0[K] goes out of it, the K states come back into it)
+    std::memcpy(staged, theta0_host, (size_t)K * 2 * sizeof(double));
+    CMAX_CHECK_HIP(hipMemcpyAsync(theta, staged, (size_t)K * 2 * sizeof(double), hipMemcpyHostToDevice, s));
     if (batch_fast_applies(h, d, K, grad)) {
         for (int it = 0; it < n_iter; ++it) {
             const DescentArgs a = descent_args(*o, it, nx, trace, theta, st);
@@ -3492,21 +3466,13 @@ int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *d, con
             if (rc) return rc;
         }
     }
-    CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_out, st, (size_t)(K * S) * sizeof(double), hipMemcpyDeviceToHost, s));
+    CMAX_CHECK_HIP(hipMemcpyAsync(staged, st, (size_t)(K * S) * sizeof(double), hipMemcpyDeviceToHost, s));
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
     for (int z = 0; z < K; ++z) {
-        const double *c = h->hp_out + z * S, *xb = c + kDcCtrl, *hist = xb + 4 * nx;
-        res_host[z].best_loss = c[kDcBest];
-        res_host[z].best_iter = (int32_t)c[kDcBestIter];
-        res_host[z].n_done = (int32_t)c[kDcDone];
-        res_host[z].last_lr = c[kDcLastLr];
-        std::memcpy(x_best_host + (int64_t)z * nx, xb, nx * sizeof(double));
-        std::memcpy(x_last_host + (int64_t)z * nx, xb + nx, nx * sizeof(double));
-        std::memcpy(loss_history_host + (int64_t)z * n_iter, hist, (size_t)n_iter * sizeof(double));
-        if (trace) std::memcpy(x_trace_host + (int64_t)z * (n_iter + 1) * nx, hist + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double));
+        descent_result_of_state(staged + z * S, &res_host[z]);
+        (void)descent_copy_out(staged + z * S, false, nx, n_iter, x_best_host + (int64_t)z * nx, x_last_host + (int64_t)z * nx, loss_history_host + (int64_t)z * n_iter,
+                               trace ? x_trace_host + (int64_t)z * (n_iter + 1) * nx : nullptr, s);
     }
-    // (the block is also where cmax_objective_host / cmax_objective_descend poll their run counter: leave the word at the last value seen)
-    *reinterpret_cast<volatile unsigned long long *>(h->hp_out + 16) = h->host_seq;
     return 0;
 }
 
@@ -4044,7 +4010,10 @@ int objective_dist_local_grad(cmax_handle_t h, const cmax_objective_t *d, const 
     CMAX_REFUSE_WEIGHTED(h, "patch plan evaluation");
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
-    return objective_eval(h, d, motion, result, grad, s, h->comm, nullptr, nullptr, 0, true);
+    EvalForm form;
+    form.comm = h->comm;
+    form.skip_c2 = true;
+    return objective_eval(h, d, motion, result, grad, s, form);
 }
 int objective_hvp_dist_local(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *tangent, void *hv, hipStream_t s) {
     CMAX_REFUSE_WEIGHTED(h, "patch plan product");
@@ -4055,7 +4024,7 @@ int objective_hvp_dist_local(cmax_handle_t h, const cmax_objective_t *d, const f
 int objective_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, double *result, void *grad, hipStream_t s) {
     int rc = check_objective_args(h, d, motion);
     if (rc) return rc;
-    return objective_eval(h, d, motion, result, grad, s, nullptr);
+    return objective_eval(h, d, motion, result, grad, s);
 }
 int objective_hvp_presplit(cmax_handle_t h, const cmax_objective_t *d, const float *motion, const float *tangent, void *hv, hipStream_t s) {
     CMAX_REFUSE_WEIGHTED(h, "patch plan product");

@@ -211,8 +211,15 @@ struct cmax_handle_s {
     // cmax_objective_host: device outputs + pinned staging of one evaluation whose results go straight to the host
     cmax::DevBuf<double> d_host_result;  // [8]
     cmax::DevBuf<char> d_host_grad;
+    // The one pinned block of the calls that hand results to the host (cmax_objective_host, cmax_objective_descend[_batch]), in doubles.
+    // A fixed head: the result block a finishing kernel or a descent's last step writes, two staged doubles (the polled 2-DoF gradient
+    // coming back, theta0 going out) and the run counter those kernels store behind their results.  Everything of variable size -- the
+    // gradient of cmax_objective_host's copy path, theta0[K] and the K states of a batch descent -- starts at kHpPayload: no payload
+    // reaches the counter.  Kernels are given hp_out.dev() + these offsets.
+    static constexpr int kHpResult = 0, kHpStaged = 8, kHpCounter = 16, kHpPayload = 24;
     cmax::PinnedBuf<double> hp_out;
-    unsigned long long host_seq = 0;  // run counter of the finishing kernel that writes into hp_out (polled by cmax_objective_host)
+    static volatile unsigned long long *hp_counter(double *block) { return reinterpret_cast<volatile unsigned long long *>(block + kHpCounter); }
+    unsigned long long host_seq = 0;  // the last value a polled call had its kernel store there
     cmax::DevBuf<double> descent;     // cmax_objective_descend (on first use): theta[2] | grad[2] | pad[4] | result[8] | the descent state (cmax_descent.h)
     // cmax_objective_descend_batch (on first use): theta[K][2] | grad[K][2] | pad[K][4] | result[K][8] | K descent states
     cmax::DevBuf<double> descent_batch;

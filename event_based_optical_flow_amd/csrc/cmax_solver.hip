@@ -404,14 +404,12 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     bool exact = false;
     // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
     cmax::DevBuf<double> dense64, sl, sl_partial;
-    double *h_out_dev = nullptr;  // device view of the pinned output: the tail kernel writes the result there
-    cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter
+    cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter (the tail kernel writes h_out through its dev())
     cmax::DevBuf<unsigned long long> seq_dev;  // device-side run counter of the tail kernel
     unsigned long long seq_seen = 0;           // its value after the last completed call
     // cmax_patch_plan_descend (reserved on first use): the tail's output in device memory (loss | grad | counter slot), the descent state
     cmax::DevBuf<double> d_out, descent;
     cmax::PinnedBuf<double> h_res;  // ... and the result block the last step writes (the run counter goes to h_out's slot, like every tail's)
-    double *h_res_dev = nullptr;
     // Captured launch sequences (hipGraph), replayed on the plan's own stream: an evaluation is ~25 small launches,
     // host-bound when issued one by one.  Keyed by everything that changes the sequence: the kind of call and the
     // handle's host-side state (which vote buffer is current, which images are already zero, whether the
@@ -691,7 +689,7 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     for (int i = 0; i < 4; ++i) fp.weight[i] = 0.0;
     fp.tv_weight = 0.0;
     fp.gscale = d.t_scale;  // the outer t P^T; times |v|_inf from device memory
-    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, vmax, p->h_out_dev, p->seq_dev);
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, vmax, p->h_out.dev(), p->seq_dev);
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -760,7 +758,7 @@ int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
     for (int i = 0; i < 4; ++i) fp.weight[i] = 0.0;
     fp.tv_weight = 0.0;
     fp.gscale = 1.0;  // t is in gd_D; times |v|_inf from device memory
-    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, vmax, p->h_out_dev, p->seq_dev,
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, vmax, p->h_out.dev(), p->seq_dev,
                        (const double *)(p->sl + 1));
     CMAX_CHECK_LAUNCH();
     return 0;
@@ -805,7 +803,7 @@ int enqueue_hvp(cmax_patch_plan_s *p, hipStream_t s) {
     for (int i = 0; i < 4; ++i) fp.weight[i] = 0.0;
     fp.tv_weight = 0.0;
     fp.gscale = d.t_scale * d.t_scale * wscale;  // H_x = t^2 P^T H_flow P (times |v|_inf, from device memory)
-    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, vmax, p->h_out_dev, p->seq_dev);
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, vmax, p->h_out.dev(), p->seq_dev);
     CMAX_CHECK_LAUNCH();
     return 0;
 }
@@ -817,32 +815,16 @@ void drop_graphs(cmax_patch_plan_s *p) {
     p->graphs.clear();
 }
 
-// The tail kernel bumps a run counter in the pinned output after its results are visible.  Polling it returns as
-// soon as the graph's last kernel has written, without the sleep / wake-up of hipStreamSynchronize.
-static volatile unsigned long long *plan_flag(cmax_patch_plan_s *p) {
-    return reinterpret_cast<volatile unsigned long long *>(p->h_out + 1 + p->nx);
+// The tail kernel bumps a run counter in the pinned output after its results are visible: the slot behind loss | grad, in the host's
+// view of h_out or the device's.
+static volatile unsigned long long *plan_flag(const cmax_patch_plan_s *p, double *h_out) {
+    return reinterpret_cast<volatile unsigned long long *>(h_out + 1 + p->nx);
 }
 
+// poll: a few ms at most, then sleep like everybody else.  Whatever the counter says once the stream is done is adopted.
 static int wait_for_tail(cmax_patch_plan_s *p, hipStream_t s, bool poll, unsigned long long n_tails = 1ull) {
     const unsigned long long expected = p->seq_seen + n_tails;  // (a descent: one tail per iteration, the last step publishes the counter)
-    if (poll) {
-        volatile unsigned long long *flag = plan_flag(p);
-        for (long spin = 0; spin < 4000000L; ++spin) {  // a few ms at most, then sleep like everybody else
-            if (*flag == expected) {
-                std::atomic_thread_fence(std::memory_order_acquire);
-                p->seq_seen = expected;
-                return 0;
-            }
-#if defined(__x86_64__) || defined(__i386__)
-            __builtin_ia32_pause();
-#elif defined(__aarch64__)
-            asm volatile("yield" ::: "memory");
-#endif
-        }
-    }
-    CMAX_CHECK_HIP(hipStreamSynchronize(s));
-    p->seq_seen = *plan_flag(p);
-    return 0;
+    return wait_run_counter(plan_flag(p, p->h_out), expected, poll ? 4000000L : 0L, s, &p->seq_seen);
 }
 
 // Runs `enqueue(stream)` and waits for its result.  Default: eager launches on the caller's stream -- the first kernel
@@ -966,14 +948,9 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     if (!rc) rc = p->h_in.reserve(2 * (int64_t)p->nx + 2);
     if (!rc && hipStreamCreateWithFlags(&p->own_stream, hipStreamNonBlocking) != hipSuccess) rc = CMAX_ENOMEM;
     if (!rc && hipEventCreateWithFlags(&p->ev_caller, hipEventDisableTiming) != hipSuccess) rc = CMAX_ENOMEM;
-    if (!rc) rc = p->h_out.reserve(2 + (int64_t)p->nx);
-    if (!rc && hipHostGetDevicePointer((void **)&p->h_out_dev, p->h_out, 0) != hipSuccess) {
-        (void)hipGetLastError();
-        p->h_out_dev = p->h_out;  // unified addressing: pinned host memory is addressable from the device as it is
-    }
+    if (!rc) rc = p->h_out.reserve(2 + (int64_t)p->nx);  // (zero-filled: the run counter starts where seq_dev and seq_seen do)
     if (!rc) rc = p->seq_dev.reserve(nullptr, 1, nullptr);
     if (!rc && hipMemset(p->seq_dev, 0, sizeof(unsigned long long)) != hipSuccess) rc = CMAX_ENOMEM;
-    if (!rc) reinterpret_cast<unsigned long long *>(p->h_out + 1 + p->nx)[0] = 0ull;
     if (rc) {
         if (rc == CMAX_ENOMEM) set_error("patch_plan_create: allocation failed");
         cmax_patch_plan_destroy(p);
@@ -1019,7 +996,7 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t p, const double *x_host, int with
     const bool tv = with_tv && p->d.tv_weight != 0.0;
     std::memcpy(p->h_in, x_host, (size_t)p->nx * sizeof(double));
     const int kind = (tv ? 1 : 0) | (grad_host ? 2 : 0);
-    int rc = run_sequence(p, kind, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_evaluate(p, tv, grad_host != nullptr, s, p->h_in, p->h_out_dev); });
+    int rc = run_sequence(p, kind, (hipStream_t)stream, [&](hipStream_t s) { return enqueue_evaluate(p, tv, grad_host != nullptr, s, p->h_in, p->h_out.dev()); });
     if (rc) return rc;
     *loss_host = p->h_out[0];
     if (grad_host) std::memcpy(grad_host, p->h_out + 1, (size_t)p->nx * sizeof(double));
@@ -1032,13 +1009,9 @@ int cmax_sizeof_descent(void) { return (int)sizeof(cmax_descent_t); }
 // into a device buffer -> k_descent_step) eagerly on the caller's stream, ONE wait, the copies out.
 int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with_tv, const cmax_descent_t *o, cmax_descent_result_t *res_host,
                             double *x_last_host, double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream) {
-    int rc = descent_check(o, "patch_plan_descend");
+    int rc = descent_entry_check("patch_plan_descend", o, p && x0_host && res_host && x_last_host && x_best_host && loss_history_host, nullptr,
+                                 p && handle_has_comm(p->handle));
     if (rc) return rc;
-    CMAX_REQUIRE(p && x0_host && res_host && x_last_host && x_best_host && loss_history_host, "patch_plan_descend: null pointer");
-    if (handle_has_comm(p->handle)) {
-        set_error("patch_plan_descend: not built for time-sliced batches (the handle holds a communicator)");
-        return CMAX_EUNSUPPORTED;
-    }
     if (handle_is_weighted(p->handle)) {
         set_error("patch_plan_descend: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
         return CMAX_EUNSUPPORTED;
@@ -1049,13 +1022,7 @@ int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with
     const int64_t n_state = descent_state_doubles(nx, n_iter, trace);
     rc = p->d_out.reserve(nullptr, 2 + (int64_t)nx, s);
     if (!rc) rc = p->descent.reserve(nullptr, n_state, s);
-    if (!rc && !p->h_res.get()) {
-        rc = p->h_res.reserve(4);
-        if (!rc && hipHostGetDevicePointer((void **)&p->h_res_dev, p->h_res, 0) != hipSuccess) {
-            (void)hipGetLastError();
-            p->h_res_dev = p->h_res;  // unified addressing
-        }
-    }
+    if (!rc) rc = p->h_res.reserve(4);
     if (rc) return rc;
     std::memcpy(p->h_in, x0_host, (size_t)nx * sizeof(double));
     CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, s));
@@ -1064,8 +1031,8 @@ int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with
         if (rc) return rc;
         DescentArgs a = descent_args(*o, it, nx, trace, p->x64, p->descent);
         if (it == n_iter - 1) {
-            a.res_pinned = p->h_res_dev;
-            a.flag = reinterpret_cast<volatile unsigned long long *>(p->h_out_dev + 1 + nx);
+            a.res_pinned = p->h_res.dev();
+            a.flag = plan_flag(p, p->h_out.dev());
             a.seq_src = p->seq_dev;
         }
         rc = launch_descent_step(a, p->d_out, p->d_out + 1, s);
@@ -1075,13 +1042,8 @@ int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with
     rc = wait_for_tail(p, s, p->eager_calls > 1, (unsigned long long)n_iter);
     if (rc) return rc;
     descent_result(p->h_res, res_host);
-    // (behind the wait: the state is final; x_best | x_last lead it, history and trace close it)
-    const double *st = p->descent;
-    CMAX_CHECK_HIP(hipMemcpyAsync(x_best_host, st + kDcCtrl, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    CMAX_CHECK_HIP(hipMemcpyAsync(x_last_host, st + kDcCtrl + nx, (size_t)nx * sizeof(double), hipMemcpyDeviceToHost, s));
-    CMAX_CHECK_HIP(hipMemcpyAsync(loss_history_host, st + kDcCtrl + 4 * (int64_t)nx, (size_t)n_iter * sizeof(double), hipMemcpyDeviceToHost, s));
-    if (trace)
-        CMAX_CHECK_HIP(hipMemcpyAsync(x_trace_host, st + kDcCtrl + 4 * (int64_t)nx + n_iter, (size_t)(n_iter + 1) * nx * sizeof(double), hipMemcpyDeviceToHost, s));
+    rc = descent_copy_out(p->descent, true, nx, n_iter, x_best_host, x_last_host, loss_history_host, x_trace_host, s);  // (behind the wait: the state is final)
+    if (rc) return rc;
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;
 }

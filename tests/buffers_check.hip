@@ -46,9 +46,11 @@ static void check_without_device() {
         CHECK(cmax::release_all(nullptr, a, b) == 0);
         PinnedBuf<int> p;
         CHECK(p.reserve(100) == CMAX_ENOMEM);
-        CHECK(p.get() == nullptr && p.capacity() == 0);
+        CHECK(p.get() == nullptr && p.dev() == nullptr && p.capacity() == 0);  // the device view fails with the pointer
         CHECK(p.reserve(10) == CMAX_ENOMEM);
+        CHECK(p.get() == nullptr && p.dev() == nullptr);
         p.release();
+        CHECK(p.dev() == nullptr);
     }  // (the destructors of empty buffers)
     CHECK(bytes == 0);
 }
@@ -89,9 +91,19 @@ static void check_with_device() {
         int sum = 0;
         for (int64_t i = 0; i < p.capacity(); ++i) sum |= p[i];
         CHECK(sum == 0);  // zero-filled
-        int *pp = p.get();
-        CHECK(p.reserve(200) == 0 && p.get() == pp);
+        // the device view: there with the memory, kept by a reserve that fits, the new block's after one that grows, gone with release
+        auto views_block = [](const PinnedBuf<int> &buf) {
+            hipPointerAttribute_t at;
+            return buf.dev() != nullptr && hipPointerGetAttributes(&at, buf.dev()) == hipSuccess && at.hostPointer == (void *)buf.get() &&
+                   at.devicePointer == (void *)buf.dev();
+        };
+        CHECK(views_block(p));
+        int *pp = p.get(), *pd = p.dev();
+        CHECK(p.reserve(200) == 0 && p.get() == pp && p.dev() == pd);
         CHECK(p.reserve(1000) == 0 && p.capacity() == 1000 + 500 + 64);
+        CHECK(views_block(p));
+        p.release();
+        CHECK(p.get() == nullptr && p.dev() == nullptr && p.capacity() == 0);
     }  // b's destructor takes its bytes off
     CHECK(bytes == 0);
     CHECK(hipDeviceSynchronize() == hipSuccess);

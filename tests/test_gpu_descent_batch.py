@@ -216,8 +216,10 @@ def rel_max(a, b):
 def test_state_hygiene():
     """cmax_objective_batch shares its double-buffered workspace with the multi-start descent: evaluations of 8 fixed candidates before,
     between and after three descents (K 5 x 6 iterations; K 3 x 5, whose odd count flips the buffer parity; K 16) agree with the fp64 reference
-    and with each other at run-to-run accuracy, and so do a single-start `descend` and an `evaluate`.  The state buffer grows by exactly what
-    the header documents, and only when a call needs more than is there."""
+    and with each other at run-to-run accuracy, and so do a single-start `descend` and an `evaluate`.  Every observation also takes the two
+    host paths, which share one pinned block with the descents: an `evaluate_host` whose results are copied (a dense flow's gradient) and,
+    directly behind it, one whose results are polled (the 2-DoF objective), each against `evaluate` of the same motion at the same run-to-run
+    bounds.  The state buffer grows by exactly what the header documents, and only when a call needs more than is there."""
     h, obj = setup()
     desc = obj.terms[0][2]
     fixed = torch.tensor(B.sgd_starts(64)[3::8].copy(), dtype=torch.float64, device="cuda")  # 8 of the 8 x 8 grid
@@ -225,9 +227,25 @@ def test_state_hygiene():
     refs = [B.reference(t) for t in fixed.cpu().numpy()]
     ref_loss, ref_grad = np.array([r[0] for r in refs]), np.stack([r[1] for r in refs])
 
+    dense = E.ContrastObjective(h, "dense-flow", cost="image_variance").terms[0][2]
+    rows, cols = torch.meshgrid(torch.arange(SIZE[0], dtype=torch.float32), torch.arange(SIZE[1], dtype=torch.float32), indexing="ij")
+    flow = torch.stack([3.0 + 0.02 * rows - 0.01 * cols, -2.0 + 0.015 * cols]).cuda()  # [2, H, W], a few pixels over the batch
+
     def observe():
         results, grads = h.evaluate_batch(desc, fixed)
         r1, g1 = h.evaluate(desc, theta1)
+        rd, gd = h.evaluate(dense, flow)
+        # the host paths share the handle's pinned block with both descents: a copied result whose payload (the flow gradient, 17920
+        # bytes) is far longer than the block's head, and IMMEDIATELY behind it a polled one, which waits on the run counter in that head
+        hd, hgd = h.evaluate_host(dense, flow)
+        hp, hgp = h.evaluate_host(desc, theta1)
+        e_copy = abs(hd[0] - rd[0].item()) / abs(rd[0].item()), rel_max(hgd, gd.cpu().numpy())
+        e_poll = abs(hp[0] - r1[0].item()) / abs(r1[0].item()), rel_max(hgp, g1.cpu().numpy())
+        print(f"[descent-batch] hygiene, evaluate_host vs evaluate: copied (dense flow) loss {e_copy[0]:.2e} grad {e_copy[1]:.2e}; "
+              f"polled (2-DoF) behind it loss {e_poll[0]:.2e} grad {e_poll[1]:.2e}")
+        assert hgd.shape == (2,) + SIZE and hgd.dtype == np.float32 and hgp.shape == (2,) and hgp.dtype == np.float64
+        assert e_copy[0] <= 1e-6 and e_copy[1] <= 1e-5
+        assert e_poll[0] <= 1e-6 and e_poll[1] <= 1e-5
         one = obj.descend(B.ADAM_STARTS[0], trace=True, **B.SCHEDULE, **B.METHODS["sgd"])
         return results[:, 0].cpu().numpy(), grads.cpu().numpy(), float(r1[0].item()), g1.cpu().numpy(), one
 
