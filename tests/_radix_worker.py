@@ -1,9 +1,13 @@
-"""Child program of tests/test_gpu_radix_sort.py.
+"""Child program of tests/test_gpu_radix_sort.py and tests/test_gpu_counting_sort.py.
 
-CMAX_SORT and CMAX_RS_BITS are read once per process, so the radix pipeline on small batches, and a digit width of its own, need a
-process of their own.  usage: _radix_worker.py <out.npz>, with CMAX_SORT=radix (and optionally CMAX_RS_BITS) in the environment.  For
-every case of tests/_sort_cases.py it builds the handle, applies the case's steps, and writes after every step the packed events with
-their group starts, batch_info, work_list_info and the evaluations the case asks for; the parent does all the comparing."""
+CMAX_SORT, CMAX_RS_BITS and CMAX_NO_RUN_SORT are read once per process, so the radix pipeline on small batches, a digit width of its
+own, and the counting sort without its run sort each need a process of their own.
+usage: _radix_worker.py <out.npz> [<table module> [NAME=VALUE | NAME= ...]]
+The table module (default _sort_cases) gives CASES, batch, weights and motion; NAME=VALUE is what the environment must hold, NAME= what
+it must NOT hold (default CMAX_SORT=radix, with CMAX_RS_BITS as the parent chose).  For every case of the table it builds the handle,
+applies the case's steps, and writes after every step the packed events with their group starts, batch_info, work_list_info and the
+evaluations the case asks for; the parent does all the comparing."""
+import importlib
 import os
 import sys
 
@@ -14,7 +18,8 @@ sys.path.insert(0, ROOT)
 
 import event_based_optical_flow_amd as E  # noqa: E402
 
-import _sort_cases as C  # noqa: E402
+C = importlib.import_module(sys.argv[2] if len(sys.argv) > 2 else "_sort_cases")
+EXPECTED_ENV = [a.split("=", 1) for a in sys.argv[3:]] if len(sys.argv) > 3 else [["CMAX_SORT", "radix"]]
 
 
 def record(out, key, h, c, evals):
@@ -40,7 +45,8 @@ def record(out, key, h, c, evals):
 
 
 def main(out_path):
-    assert os.environ.get("CMAX_SORT") == "radix"
+    for name, value in EXPECTED_ENV:
+        assert os.environ.get(name) == (value if value else None), (name, os.environ.get(name), value)
     out = {}
     for c in C.CASES:
         ev = C.batch(c)

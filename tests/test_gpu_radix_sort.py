@@ -147,7 +147,8 @@ def check_exact_order(tag, c, x, packed, gs, info):
     if x["T"] > 0:
         np.testing.assert_array_equal(packed[:, 0] >> 24, R.voxel_bin(x["tau64"], x["T"]), err_msg=f"{tag}: top byte against voxel_bin")
         np.testing.assert_array_equal(packed[:, 0], x["word0"], err_msg=f"{tag}: word 0")
-    else:
+    else:  # un-binned: the top byte is the residual of tau64 beyond fp32 (tau_residual8), computed from the same tau64 by both pipelines
+        np.testing.assert_array_equal(packed[:, 0] >> 24, R.tau_residual8(x["tau64"]), err_msg=f"{tag}: top byte against tau_residual8")
         np.testing.assert_array_equal(packed[:, 0] & 0xFFFFFF, x["word0"], err_msg=f"{tag}: word 0")
     np.testing.assert_array_equal(gs, x["group_start"], err_msg=f"{tag}: group starts")
 
