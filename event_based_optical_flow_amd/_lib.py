@@ -87,6 +87,26 @@ class CmaxPatchObjective(ctypes.Structure):
     ]
 
 
+class CmaxBasisObjective(ctypes.Structure):
+    """Mirror of cmax_basis_objective_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("n_terms", ctypes.c_int32),
+        ("time_aware", ctypes.c_int32),
+        ("T", ctypes.c_int32),
+        ("scheme", ctypes.c_int32),
+        ("t0", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("K", ctypes.c_int32),
+        ("basis_dtype", ctypes.c_int32),
+        ("scale_later", ctypes.c_int32),  # must be 0
+        ("t_scale", ctypes.c_double),
+        ("weight", ctypes.c_double * 4),
+        ("term", CmaxObjective * 4),
+    ]
+
+
 class CmaxDescent(ctypes.Structure):
     """Mirror of cmax_descent_t (include/cmax_hip.h): every value explicit, torch's defaults are filled by `descent_descriptor`."""
 
@@ -125,6 +145,8 @@ OPT_SGD, OPT_ADAM = 0, 1
 OPT_CODES = {"SGD": OPT_SGD, "Adam": OPT_ADAM}
 DESCENT_MAX_ITER = 4096
 DESCENT_MAX_STARTS = 64  # CMAX_DESCENT_MAX_STARTS: trajectories per cmax_objective_descend_batch call
+BASIS_MAX_K = 64  # CMAX_BASIS_MAX_K: fields of a flow basis
+BASIS_ADJ_CHUNK = 2048  # CMAX_BASIS_ADJ_CHUNK: elements of [2,H,W] per workgroup of the basis adjoint
 EINVAL = -1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
@@ -219,6 +241,9 @@ SIGNATURES = {
     "cmax_objective_descend": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult),
                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_descend_batch": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_int, ctypes.POINTER(CmaxDescent), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_basis_to_dense": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
+    "cmax_sizeof_basis_objective": (c_int, []),
+    "cmax_basis_plan_create": (c_int, [c_vp, ctypes.POINTER(CmaxBasisObjective), c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "cmax_patch_search": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_vp]),
@@ -264,6 +289,8 @@ def load():
             raise RuntimeError("cmax_iwes_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_patch_objective() != ctypes.sizeof(CmaxPatchObjective):
             raise RuntimeError("cmax_patch_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_basis_objective() != ctypes.sizeof(CmaxBasisObjective):
+            raise RuntimeError("cmax_basis_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_descent() != ctypes.sizeof(CmaxDescent):
             raise RuntimeError("cmax_descent_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_abi_version() != ABI_VERSION:

@@ -13,11 +13,15 @@
 // (measured on the cfg1-shaped objective: 0.40 ms -> 0.09 ms per value + gradient).
 // Pre/post stages run in fp64 like the reference's solver (patch_contrast_pyramid.py:186); the event
 // path is fp32 per event with fp64 reductions as everywhere in cmax_fused.hip.
+// A plan made by cmax_basis_plan_create is the same plan with the patch interpolation exchanged for a flow basis, D = sum_k x_k B_k
+// (cmax_basis_kernels.h): a motion model linear in its parameters.  The reference has no counterpart for that map; D is warped by its
+// dense-flow rule x' = x - dt * D[src] (src/warp.py:263-313).
 #include <cstring>
 #include <new>
 #include <atomic>
 #include <vector>
 
+#include "cmax_basis_kernels.h"
 #include "cmax_buffers.h"
 #include "cmax_common.h"
 #include "cmax_descent.h"
@@ -260,6 +264,8 @@ k_field_max_adj(const T *__restrict__ x, int64_t n, const double *__restrict__ o
     if (i < n) gx[i] = (double)x[i] == out[0] ? (T)(gout[0] / out[1]) : (T)0;
 }
 
+enum { kMapPatch = 0, kMapBasis = 1 };  // cmax_patch_plan_s::map_kind
+
 struct FinalParams {
     int n_terms, with_tv, nx;  // nx = 0: value only
     int flag_slot;             // index (in doubles) of the run counter in the output: 1 + the plan's nx, whatever this call's nx is
@@ -391,7 +397,7 @@ int launch_descent_step(const DescentArgs &a, const double *loss, const double *
 struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: its implicit destructor is no export)
     cmax_handle_t handle = nullptr;
     cmax_patch_objective_t d;
-    int nx = 0;            // 2 * ph * pw
+    int nx = 0;            // 2 * ph * pw (basis plan: K)
     int64_t nflow = 0;     // 2 * H * W
     int64_t nmotion = 0;   // nflow or T * nflow
     cmax::DevBuf<double> x64, flow64, vox64, gacc64, gflow64, gx64, results;
@@ -402,6 +408,13 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     // the terms carry motion_dtype == CMAX_F64: motion32 is [2][nmotion], the high plane (the fp32 motion of every other plan) and the low
     // plane of the fp64 flow / voxel the plan holds anyway, written by the same conversion launches and read by K1's fp64 cell decisions
     bool exact = false;
+    // What maps x to the dense flow: the patch interpolation P (d.filter_type), or a flow basis B [K][2][H][W] (cmax_basis_plan_create: nx = K,
+    // the plan's own copy of the basis in the caller's dtype, max |B_k| per field on the host, the chunk sums of the adjoint)
+    int map_kind = cmax::kMapPatch;
+    int basis_dtype = CMAX_F32;
+    cmax::DevBuf<float> basis32;
+    cmax::DevBuf<double> basis64, basis_partial;
+    std::vector<double> bmax;
     // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
     cmax::DevBuf<double> dense64, sl, sl_partial;
     cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter (the tail kernel writes h_out through its dev())
@@ -473,6 +486,61 @@ void launch_patch_to_dense_max(cmax_patch_plan_s *p, const double *src64, hipStr
                            p->dense64, p->sl_partial);
 }
 
+const void *plan_basis(const cmax_patch_plan_s *p) { return p->basis_dtype == CMAX_F64 ? (const void *)p->basis64.get() : (const void *)p->basis32.get(); }
+
+// Basis plan: dst = scale [* *scale_dev] * B src64, as fp32 (both planes when `lo32`) or fp64
+int basis_forward(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, float *lo32, double *dst64, hipStream_t s) {
+    const bool b64 = p->basis_dtype == CMAX_F64;
+    const void *B = plan_basis(p);
+    if (dst64) {
+        if (b64) launch_basis_to_dense<double, double>(src64, B, p->nx, p->nflow, scale, scale_dev, dst64, s);
+        else launch_basis_to_dense<float, double>(src64, B, p->nx, p->nflow, scale, scale_dev, dst64, s);
+    } else if (lo32) {
+        if (b64) launch_basis_to_dense_split<double>(src64, B, p->nx, p->nflow, scale, scale_dev, dst32, lo32, s);
+        else launch_basis_to_dense_split<float>(src64, B, p->nx, p->nflow, scale, scale_dev, dst32, lo32, s);
+    } else {
+        if (b64) launch_basis_to_dense<double, float>(src64, B, p->nx, p->nflow, scale, scale_dev, dst32, s);
+        else launch_basis_to_dense<float, float>(src64, B, p->nx, p->nflow, scale, scale_dev, dst32, s);
+    }
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+// The plan's map x -> dense flow, unscaled, in fp64 (the patch interpolation with the plan's filter, or the basis)
+int map_forward64(cmax_patch_plan_s *p, const double *src64, double *dst64, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    if (p->map_kind == kMapBasis) return basis_forward(p, src64, 1.0, nullptr, nullptr, nullptr, dst64, s);
+    return cmax_patch_to_dense_filter(src64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, dst64, s);
+}
+
+// ... and its adjoint on a flow gradient in fp32 or fp64: the result is returned through the pointer of its dtype (the patch adjoint
+// answers in the dtype of its input, the basis adjoint always in fp64)
+int map_adjoint(cmax_patch_plan_s *p, const float *g32, const double *g64, const double **gx64, const float **gx32, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    if (p->map_kind == kMapBasis) {
+        const bool b64 = p->basis_dtype == CMAX_F64;
+        const void *B = plan_basis(p);
+        if (g32) {
+            if (b64) launch_basis_adj<double, float>(g32, B, p->nx, p->nflow, p->basis_partial, p->gx64, s);
+            else launch_basis_adj<float, float>(g32, B, p->nx, p->nflow, p->basis_partial, p->gx64, s);
+        } else {
+            if (b64) launch_basis_adj<double, double>(g64, B, p->nx, p->nflow, p->basis_partial, p->gx64, s);
+            else launch_basis_adj<float, double>(g64, B, p->nx, p->nflow, p->basis_partial, p->gx64, s);
+        }
+        CMAX_CHECK_LAUNCH();
+        *gx64 = p->gx64;
+        return 0;
+    }
+    if (g32) {
+        int rc = cmax_patch_to_dense_filter(g32, CMAX_F32, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx32, s);
+        if (!rc) *gx32 = p->gx32;
+        return rc;
+    }
+    int rc = cmax_patch_to_dense_filter(g64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
+    if (!rc) *gx64 = p->gx64;
+    return rc;
+}
+
 // x (host) -> fp32 motion of the fused objective: flow [2,H,W] or voxel [T,2,H,W] in pixel per normalised time.
 // Leaves the fp64 flow (scaled) in flow64 and, when time-aware, the fp64 voxel in vox64.
 int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, hipStream_t s) {
@@ -481,6 +549,18 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
     const bool split = p->exact && dst32 == p->motion32;  // the motion of an exact plan (not its tangent): both planes, in the launches below
     const bool nearest = d.filter_type == CMAX_FILTER_NEAREST;
     float *lo32 = dst32 + p->nmotion;
+    if (p->map_kind == kMapBasis) {  // the basis kernels scale (scale_dev included) and round in the launch that sums
+        if (!d.time_aware) return basis_forward(p, src64, scale, scale_dev, dst32, split ? lo32 : nullptr, nullptr, s);
+        int rc = basis_forward(p, src64, scale, scale_dev, nullptr, nullptr, p->flow64, s);
+        if (rc) return rc;
+        bool wrote32 = false;  // the voxel on the displacement field, as the patch plan's time-aware branch below
+        rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, split ? nullptr : dst32, split ? nullptr : &wrote32, s);
+        if (rc) return rc;
+        if (split) hipLaunchKernelGGL(k_convert_split, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32, lo32);
+        else if (!wrote32) hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, dst32);
+        CMAX_CHECK_LAUNCH();
+        return 0;
+    }
     if (!d.time_aware && !scale_dev && split) {
         if (nearest) hipLaunchKernelGGL(k_patch_to_dense_split<CMAX_FILTER_NEAREST>, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
         else hipLaunchKernelGGL(k_patch_to_dense_split<CMAX_FILTER_BILINEAR>, dim3(grid), dim3(256), 0, s, src64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, dst32, lo32, scale);
@@ -556,9 +636,8 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
     if (d.n_terms == 1 && !d.time_aware) {
         // one term on the dense flow: the adjoint of the interpolation reads the fp32 flow gradient as it is
         // (fp64 accumulation inside), the term's weight is applied by the tail
-        int rc = cmax_patch_to_dense_filter(p->grad32, CMAX_F32, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx32, s);
+        int rc = map_adjoint(p, p->grad32, nullptr, gx64, gx32, s);
         if (rc) return rc;
-        *gx32 = p->gx32;
         *weight_scale = d.weight[0];
         return 0;
     }
@@ -583,10 +662,7 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
         if (rc) return rc;
         gflow = p->gacc64 + (int64_t)d.t0 * p->nflow;
     }
-    int rc = cmax_patch_to_dense_filter(gflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
-    if (rc) return rc;
-    *gx64 = p->gx64;
-    return 0;
+    return map_adjoint(p, nullptr, gflow, gx64, gx32, s);
 }
 
 // Everything between the input and the output of one evaluation, enqueued on `s` (no synchronisation).  x_src: pinned host memory the
@@ -644,9 +720,9 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     const double *inv_vmax = p->x64 + 2 * p->nx, *vmax = inv_vmax + 1;
     const int fgrid = div_up(p->nflow, 256), mgrid = div_up(p->nmotion, 256);
     // F = t P x,  dF = t P v / |v|_inf
-    int rc = cmax_patch_to_dense_filter(p->x64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->flow64, s);
+    int rc = map_forward64(p, p->x64, p->flow64, s);
     if (rc) return rc;
-    rc = cmax_patch_to_dense_filter(p->v64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, p->dflow64, s);
+    rc = map_forward64(p, p->v64, p->dflow64, s);
     if (rc) return rc;
     hipLaunchKernelGGL((k_convert_scale<double, double>), dim3(fgrid), dim3(256), 0, s, p->flow64, p->nflow, d.t_scale, (const double *)nullptr, p->flow64);
     hipLaunchKernelGGL((k_convert_scale<double, double>), dim3(fgrid), dim3(256), 0, s, p->dflow64, p->nflow, d.t_scale, inv_vmax, p->dflow64);
@@ -675,7 +751,9 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     // the sweep leaves d(dL/dF) in bin t0 of the tangent gradient voxel: the interpolation adjoint reads it there
     rc = voxel_construct_adj_tan_f64(p->vox64, p->dvox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, p->dgacc64, s, handle_is_deterministic(p->handle));
     if (rc) return rc;
-    rc = cmax_patch_to_dense_filter(p->dgacc64 + (int64_t)d.t0 * p->nflow, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 1, p->gx64, s);
+    const double *gx64 = nullptr;
+    const float *gx32 = nullptr;
+    rc = map_adjoint(p, nullptr, p->dgacc64 + (int64_t)d.t0 * p->nflow, &gx64, &gx32, s);
     if (!rc) rc = plan_reduce_gx(p, p->gx64, nullptr, s);
     if (rc) return rc;
     FinalParams fp;
@@ -895,6 +973,8 @@ extern "C" {
 
 int cmax_sizeof_patch_objective(void) { return (int)sizeof(cmax_patch_objective_t); }
 
+static int plan_allocate(cmax_handle_t h, const cmax_patch_objective_t &d, int nx, const char *who, cmax_patch_plan_t *out);
+
 int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, cmax_patch_plan_t *out) {
     CMAX_REQUIRE(h && desc && out, "patch_plan_create: null pointer");
     if (handle_is_weighted(h)) {
@@ -915,14 +995,19 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
         set_error("patch_plan_create: scale_later is not built for time-sliced batches (the handle holds a communicator)");
         return CMAX_EINVAL;
     }
+    return plan_allocate(h, d, 2 * d.ph * d.pw, "patch_plan_create", out);
+}
+
+// The plan's buffers for a checked descriptor and nx unknowns (`who` names the entry point in messages)
+static int plan_allocate(cmax_handle_t h, const cmax_patch_objective_t &d, int nx, const char *who, cmax_patch_plan_t *out) {
     cmax_patch_plan_s *p = new (std::nothrow) cmax_patch_plan_s();
     if (!p) {
-        set_error("patch_plan_create: out of host memory");
+        set_error("%s: out of host memory", who);
         return CMAX_ENOMEM;
     }
     p->handle = h;
     p->d = d;
-    p->nx = 2 * d.ph * d.pw;
+    p->nx = nx;
     if (const char *e = getenv("CMAX_PLAN_GRAPHS")) p->graphs_ok = atoi(e) != 0;
     p->nflow = 2 * (int64_t)d.H * d.W;
     p->nmotion = d.time_aware ? (int64_t)d.T * p->nflow : p->nflow;
@@ -952,11 +1037,113 @@ int cmax_patch_plan_create(cmax_handle_t h, const cmax_patch_objective_t *desc, 
     if (!rc) rc = p->seq_dev.reserve(nullptr, 1, nullptr);
     if (!rc && hipMemset(p->seq_dev, 0, sizeof(unsigned long long)) != hipSuccess) rc = CMAX_ENOMEM;
     if (rc) {
-        if (rc == CMAX_ENOMEM) set_error("patch_plan_create: allocation failed");
+        if (rc == CMAX_ENOMEM) set_error("%s: allocation failed", who);
         cmax_patch_plan_destroy(p);
         return rc;
     }
     *out = p;
+    return 0;
+}
+
+int cmax_sizeof_basis_objective(void) { return (int)sizeof(cmax_basis_objective_t); }
+
+// A patch plan whose map x -> dense flow is D = sum_k x_k B_k (cmax_basis_kernels.h; no counterpart in the reference, whose dense-flow
+// warp rule src/warp.py:263-313 the model composes with).  The descriptor becomes a cmax_patch_objective_t with a 1 x K "grid" that
+// nothing interpolates (map_kind picks the basis wherever the filter is picked) and no total variation.
+int cmax_basis_plan_create(cmax_handle_t h, const cmax_basis_objective_t *desc, const void *basis_dev, cmax_stream_t stream, cmax_patch_plan_t *out) {
+    CMAX_REQUIRE(h && desc && basis_dev && out, "basis_plan_create: null pointer");
+    if (handle_is_weighted(h)) {
+        set_error("basis_plan_create: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (handle_has_comm(h)) {
+        set_error("basis_plan_create: not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EUNSUPPORTED;
+    }
+    const cmax_basis_objective_t &b = *desc;
+    CMAX_REQUIRE(b.K >= 1 && b.K <= CMAX_BASIS_MAX_K, "basis_plan_create: K (1 .. CMAX_BASIS_MAX_K)");
+    CMAX_REQUIRE(b.basis_dtype == CMAX_F32 || b.basis_dtype == CMAX_F64, "basis_plan_create: basis_dtype (CMAX_F32 or CMAX_F64)");
+    CMAX_REQUIRE(b.scale_later == 0, "basis_plan_create: scale_later is not built for a flow basis");
+    CMAX_REQUIRE(b.n_terms >= 1 && b.n_terms <= 4, "basis_plan_create: n_terms");
+    CMAX_REQUIRE(b.H > 0 && b.W > 0, "basis_plan_create: sizes");
+    CMAX_REQUIRE(!b.time_aware || (b.T > 0 && b.t0 >= 0 && b.t0 < b.T), "basis_plan_create: time bins");
+    for (int i = 0; i < b.n_terms; ++i) {
+        CMAX_REQUIRE(b.term[i].model == (b.time_aware ? CMAX_MODEL_VOXEL : CMAX_MODEL_DENSE), "basis_plan_create: term model must match time_aware");
+        CMAX_REQUIRE(!b.time_aware || b.term[i].T == b.T, "basis_plan_create: term T");
+        CMAX_REQUIRE(b.term[i].motion_dtype == b.term[0].motion_dtype, "basis_plan_create: the terms must agree on motion_dtype");
+    }
+    cmax_patch_objective_t d;
+    std::memset(&d, 0, sizeof(d));
+    d.n_terms = b.n_terms;
+    d.time_aware = b.time_aware;
+    d.T = b.T;
+    d.scheme = b.scheme;
+    d.t0 = b.t0;
+    d.H = b.H;
+    d.W = b.W;
+    d.ph = 1;
+    d.pw = b.K;
+    d.sw_h = d.sw_w = 1;
+    d.filter_type = CMAX_FILTER_BILINEAR;
+    d.t_scale = b.t_scale;
+    for (int i = 0; i < 4; ++i) d.weight[i] = b.weight[i];
+    for (int i = 0; i < b.n_terms; ++i) d.term[i] = b.term[i];
+    cmax_patch_plan_t p = nullptr;
+    int rc = plan_allocate(h, d, b.K, "basis_plan_create", &p);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nb = (int64_t)b.K * p->nflow;
+    p->map_kind = kMapBasis;
+    p->basis_dtype = b.basis_dtype;
+    const bool b64 = b.basis_dtype == CMAX_F64;
+    rc = b64 ? p->basis64.reserve(nullptr, nb, nullptr) : p->basis32.reserve(nullptr, nb, nullptr);
+    if (!rc) rc = p->basis_partial.reserve(nullptr, (int64_t)basis_adj_chunks(p->nflow) * b.K, nullptr);
+    double bmax[CMAX_BASIS_MAX_K];
+    if (!rc) {
+        // the plan's copy, max |B_k| per field (into the chunk sums' buffer: K doubles fit and nothing else uses it yet), the read-back
+        hipError_t e = hipMemcpyAsync(const_cast<void *>(plan_basis(p)), basis_dev, (size_t)nb * (b64 ? sizeof(double) : sizeof(float)), hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) {
+            if (b64) hipLaunchKernelGGL(k_basis_absmax<double>, dim3(b.K), dim3(256), 0, s, (const double *)p->basis64, p->nflow, (double *)p->basis_partial);
+            else hipLaunchKernelGGL(k_basis_absmax<float>, dim3(b.K), dim3(256), 0, s, (const float *)p->basis32, p->nflow, (double *)p->basis_partial);
+            e = hipGetLastError();
+        }
+        if (e == hipSuccess) e = hipMemcpyAsync(bmax, p->basis_partial, (size_t)b.K * sizeof(double), hipMemcpyDeviceToHost, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("basis_plan_create: copying the basis failed: %s", hipGetErrorString(e));
+            rc = (int)e;
+        }
+    }
+    if (rc) {
+        if (rc == CMAX_ENOMEM) set_error("basis_plan_create: allocation failed");
+        cmax_patch_plan_destroy(p);
+        return rc;
+    }
+    p->bmax.assign(bmax, bmax + b.K);
+    *out = p;
+    return 0;
+}
+
+int cmax_basis_to_dense(const void *theta_dev, const void *basis_dev, int dtype, int K, int H, int W, int adjoint, void *out, cmax_stream_t stream) {
+    CMAX_REQUIRE(theta_dev && basis_dev && out && H > 0 && W > 0, "basis_to_dense");
+    CMAX_REQUIRE(K >= 1 && K <= CMAX_BASIS_MAX_K, "basis_to_dense: K (1 .. CMAX_BASIS_MAX_K)");
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "basis_to_dense: dtype");
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t n = 2 * (int64_t)H * W;
+    if (!adjoint) {
+        if (dtype == CMAX_F32) launch_basis_to_dense<float, float>((const double *)theta_dev, basis_dev, K, n, 1.0, nullptr, (float *)out, s);
+        else launch_basis_to_dense<double, double>((const double *)theta_dev, basis_dev, K, n, 1.0, nullptr, (double *)out, s);
+        CMAX_CHECK_LAUNCH();
+        return 0;
+    }
+    // the chunk sums: a stream-ordered temporary keeps the operator stateless (as the accumulators of cmax_warp_events_bwd)
+    double *partial = nullptr;
+    CMAX_CHECK_HIP(hipMallocAsync((void **)&partial, (size_t)basis_adj_chunks(n) * K * sizeof(double), s));
+    if (dtype == CMAX_F32) launch_basis_adj<float, float>((const float *)theta_dev, basis_dev, K, n, partial, (double *)out, s);
+    else launch_basis_adj<double, double>((const double *)theta_dev, basis_dev, K, n, partial, (double *)out, s);
+    const hipError_t e = hipGetLastError();
+    CMAX_CHECK_HIP(hipFreeAsync(partial, s));
+    CMAX_CHECK_HIP(e);
     return 0;
 }
 
@@ -1064,8 +1251,12 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
         if (!rc) rc = p->scal.reserve(nullptr, 4, s);
         if (rc) return rc;
     }
+    // |v|_inf bounds |P v|_inf (a negated convex combination); a basis can amplify: sum_k |v_k| max|B_k| bounds |B v|_inf
     double vmax = 0.0;
-    for (int j = 0; j < p->nx; ++j) vmax = fabs(v_host[j]) > vmax ? fabs(v_host[j]) : vmax;
+    if (p->map_kind == kMapBasis)
+        for (int j = 0; j < p->nx; ++j) vmax += fabs(v_host[j]) * p->bmax[j];
+    else
+        for (int j = 0; j < p->nx; ++j) vmax = fabs(v_host[j]) > vmax ? fabs(v_host[j]) : vmax;
     if (!(vmax > 0.0)) {
         std::memset(hv_host, 0, (size_t)p->nx * sizeof(double));
         return 0;

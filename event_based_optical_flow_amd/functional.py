@@ -384,6 +384,45 @@ def patch_to_dense(motion, image_size, sliding_window, pad, filter_type="bilinea
                                  (int(sliding_window[0]), int(sliding_window[1])), (int(pad[0]), int(pad[1])), FILTER_CODES[filter_type])
 
 
+class _BasisToDenseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, theta, basis):
+        K, _, H, W = basis.shape
+        theta64 = theta.detach().to(torch.float64).contiguous()
+        flow = torch.empty((2, H, W), dtype=basis.dtype, device=basis.device)
+        check(_lib.load().cmax_basis_to_dense(_ptr(theta64), _ptr(basis), _code(basis), K, H, W, 0, _ptr(flow), _stream()))
+        ctx.save_for_backward(basis)
+        ctx.theta_dtype = theta.dtype
+        return flow
+
+    @staticmethod
+    def backward(ctx, gflow):
+        (basis,) = ctx.saved_tensors
+        K, _, H, W = basis.shape
+        gflow = gflow.to(basis.dtype).contiguous()
+        gtheta = torch.empty(K, dtype=torch.float64, device=basis.device)
+        check(_lib.load().cmax_basis_to_dense(_ptr(gflow), _ptr(basis), _code(basis), K, H, W, 1, _ptr(gtheta), _stream()))
+        return gtheta.to(ctx.theta_dtype), None
+
+
+def basis_to_dense(theta, basis):
+    """Dense flow of a motion model that is linear in its parameters: D = sum_k theta_k B_k for theta [K] and a basis [K,2,H,W]
+    (float32 or float64, K <= 64; utils.flow_utils.flow_basis builds the usual ones) -> [2,H,W] in the basis' dtype, accumulated in
+    float64 in the order of k and rounded once.  The reference has no counterpart: D goes where any dense flow goes, the warp rule
+    x' = x - dt * D[src] (src/warp.py:263-313).  The backward is the adjoint B^T g in float64 without atomics (bit-repeatable);
+    the basis itself is a constant, it receives no gradient."""
+    _lib.require_gpu()
+    basis = _cuda(basis, "basis")
+    theta = _cuda(theta, "theta").reshape(-1)
+    if basis.dim() != 4 or basis.shape[1] != 2:
+        raise ValueError(f"basis must be [K, 2, H, W], got {tuple(basis.shape)}")
+    if not 1 <= basis.shape[0] <= _lib.BASIS_MAX_K:
+        raise ValueError(f"a flow basis has 1 .. {_lib.BASIS_MAX_K} fields, got {basis.shape[0]}")
+    if theta.numel() != basis.shape[0]:
+        raise ValueError(f"theta has {theta.numel()} elements, the basis has {basis.shape[0]} fields")
+    return _BasisToDenseFn.apply(theta, basis)
+
+
 class _FieldMaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

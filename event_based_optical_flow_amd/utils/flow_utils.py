@@ -32,6 +32,43 @@ def generate_smooth_flow(image_size: tuple, max_val: float = 20, grid: int = 16,
     return (1 - fr) * (1 - fc) * g00 + fr * (1 - fc) * g10 + (1 - fr) * fc * g01 + fr * fc * g11
 
 
+FLOW_BASIS_MODELS = {"translation": 2, "similarity": 4, "affine": 6, "rotation": 3}
+
+
+def flow_basis(model: str, image_size: tuple, calib=None) -> np.ndarray:
+    """[K,2,H,W] float64 basis of a motion model that is linear in its parameters: the dense flow is D = sum_k theta_k B_k
+    (functional.basis_to_dense, solver.FlowBasisObjective).  The reference has no such models; D is warped by its dense-flow rule
+    x' = x - dt * D[src] (src/warp.py:263-313), so with u(x) = sum_k theta_k u_k(x) the velocity an event at x is moved with,
+    x' = x + dt u(x), every field is B_k = -u_k.  Rows first, like every flow here: component 0 acts on the row coordinate.
+    r = i - (H - 1) / 2 and c = j - (W - 1) / 2 are the coordinates of pixel (i, j) from the sensor's centre.
+      "translation" (2)  u = (theta_0, theta_1): theta is the theta of the "2d-translation" warp, x' = x + dt theta, hence B = -1
+      "similarity"  (4)  u = (theta_0, theta_1) + theta_2 (r, c) + theta_3 (-c, r): translation, zoom, in-plane rotation
+      "affine"      (6)  u = (theta_0 + theta_2 r + theta_3 c,  theta_1 + theta_4 r + theta_5 c)
+      "rotation"    (3)  calib = (fx, fy, cx, cy) in pixels, fx / cx along the columns, fy / cy along the rows.  The motion field of a
+                         static scene under the camera's angular velocity theta = (w_x, w_y, w_z) (x along the columns, y along the
+                         rows, z the optical axis), with x = (j - cx) / fx, y = (i - cy) / fy:
+                           u_col = fx (x y w_x - (1 + x^2) w_y + y w_z),   u_row = fy ((1 + y^2) w_x - x y w_y - x w_z)"""
+    if model not in FLOW_BASIS_MODELS:
+        raise ValueError(f"flow_basis model {model!r}: one of {sorted(FLOW_BASIS_MODELS)}")
+    H, W = int(image_size[0]), int(image_size[1])
+    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    r, c = i - (H - 1) / 2.0, j - (W - 1) / 2.0
+    one, zero = np.ones((H, W)), np.zeros((H, W))
+    if model == "rotation":
+        if calib is None or len(calib) != 4:
+            raise ValueError("flow_basis('rotation') needs calib = (fx, fy, cx, cy)")
+        fx, fy, cx, cy = (float(v) for v in calib)
+        x, y = (j - cx) / fx, (i - cy) / fy
+        u = [(fy * (1.0 + y * y), fx * x * y), (-fy * x * y, -fx * (1.0 + x * x)), (-fy * x, fx * y)]  # (u_row, u_col) per w_x, w_y, w_z
+    else:
+        u = [(one, zero), (zero, one)]
+        if model == "similarity":
+            u += [(r, c), (-c, r)]
+        elif model == "affine":
+            u += [(r, zero), (c, zero), (zero, r), (zero, c)]
+    return np.ascontiguousarray(0.0 - np.stack([np.stack(f) for f in u]))  # (0.0 - x: no negative zeros)
+
+
 def construct_dense_flow_voxel_torch(dense_flow: torch.Tensor, time_bin: int, scheme: str = "upwind",
                                      t0_location: str = "middle", clamp: Optional[int] = None) -> torch.Tensor:
     """[(b,) 2,H,W] flow at t0 -> [(b,) time_bin, 2, H, W] voxel, differentiable.

@@ -185,6 +185,22 @@ int cmax_patch_to_dense(const void *motion, int dtype, int ph, int pw, int pad_h
 int cmax_patch_to_dense_filter(const void *motion, int dtype, int ph, int pw, int pad_h, int pad_w, int sw_h,
                                int sw_w, int H, int W, int filter, int adjoint, void *out, cmax_stream_t stream);
 
+/* Flow basis -> dense flow: D = sum_k theta_k B_k, the map of every motion model that is linear in its parameters (similarity,
+ * affine, the rotational motion field of a calibrated camera, a polynomial / PCA / learned basis).  The reference has no
+ * counterpart; D is warped by its dense-flow rule x' = x - dt * D[src] (src/warp.py:263-313).
+ *   basis_dev  device [K][2][H][W], fp32 or fp64 (`dtype`), 1 <= K <= CMAX_BASIS_MAX_K
+ *   adjoint == 0: theta_dev = device DOUBLE [K] whatever `dtype` is; out = D [2][H][W] in `dtype`.  Accumulated in fp64 in the
+ *                 order k = 0 .. K-1 and rounded once.
+ *   adjoint != 0: theta_dev = dL/dD [2][H][W] in `dtype`; out = device DOUBLE [K], out[k] = sum_e B_k[e] g[e].  Workgroups own
+ *                 chunks of CMAX_BASIS_ADJ_CHUNK consecutive elements of [2][H][W], reduce them in fp64 in a fixed tree and a
+ *                 second launch adds the chunks in index order: no atomics, bit-identical from run to run.  The chunk sums use a
+ *                 stream-ordered temporary of ceil(2 H W / CMAX_BASIS_ADJ_CHUNK) * K doubles (hipMallocAsync).
+ * Asynchronous on `stream`.                                                                                              */
+#define CMAX_BASIS_MAX_K 64
+#define CMAX_BASIS_ADJ_CHUNK 2048
+int cmax_basis_to_dense(const void *theta_dev, const void *basis_dev, int dtype, int K, int H, int W, int adjoint, void *out,
+                        cmax_stream_t stream);
+
 /* =============================================================================================
  * Fused objective (the hot path): events are packed + sorted once per batch, then every
  * evaluation runs  warp+vote -> contrast -> gather-gradient  without materialising warped events.
@@ -761,6 +777,41 @@ int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *desc_host, c
 int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *desc_host, const double *theta0_host, int K,
                                  const cmax_descent_t *descent, cmax_descent_result_t *res_host, double *x_last_host,
                                  double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
+
+/* =============================================================================================
+ * Flow-basis plan: the optimiser's objective for a motion model that is LINEAR in its parameters, in one call.
+ *   theta [K] (host fp64)  ->  dense flow D = sum_k theta_k B_k (cmax_basis_to_dense) * t_scale
+ *     [-> voxel (cmax_voxel_construct)] -> fp32 -> loss = sum_i weight_i * cmax_objective(term_i)
+ * and back: the gradient B^T dL/dD, the exact product H_theta = t^2 B^T H_flow B (time-aware plans add the voxel chain's
+ * second-order adjoint), and the device-resident descent.  The reference has no counterpart (its models: 2-DoF translation,
+ * per-pixel flow, patch grid); D is warped by its dense-flow rule x' = x - dt * D[src] (src/warp.py:263-313).  The map
+ * theta -> D is linear exactly as the patch interpolation is, and the plan IS a patch plan with that map exchanged:
+ * cmax_basis_plan_create returns a cmax_patch_plan_t with nx = K on which cmax_patch_plan_evaluate / _hvp / _descend /
+ * _set_t_scale / _info / _destroy work unchanged (with_tv is ignored: there is no patch grid).
+ * cmax_basis_objective_t is a new struct: the ABI version is unchanged.
+ * ============================================================================================= */
+typedef struct {
+    int32_t n_terms;          /* 1..4 fused contrast terms */
+    int32_t time_aware;       /* 0: terms use CMAX_MODEL_DENSE; 1: CMAX_MODEL_VOXEL on the propagated flow */
+    int32_t T, scheme, t0;    /* as cmax_patch_objective_t */
+    int32_t H, W;             /* sensor size of the handle */
+    int32_t K;                /* 1 .. CMAX_BASIS_MAX_K basis fields */
+    int32_t basis_dtype;      /* CMAX_F32 or CMAX_F64: what basis_dev points to, and what the plan keeps */
+    int32_t scale_later;      /* must be 0: the rescaled propagation is not built for these plans (CMAX_EINVAL) */
+    double t_scale;           /* pixel per time unit -> pixel per normalised batch period */
+    double weight[4];
+    cmax_objective_t term[4]; /* motion_dtype == CMAX_F64 on all of them or on none (an exact plan, as for the patch plan) */
+} cmax_basis_objective_t;
+int cmax_sizeof_basis_objective(void);
+/* basis_dev: device [K][2][H][W] in desc->basis_dtype; the plan keeps ITS OWN COPY in that dtype (copied on `stream`).  The call
+ * reduces max |B_k| per field on the device and reads the K numbers back: it synchronises `stream`.  A product's tangent v is
+ * handed to cmax_objective_hvp as B v / sum_k |v_k| max|B_k| (max-norm <= 1; unlike the patch interpolation a basis can amplify)
+ * and the product is scaled back; time-aware plans keep their device-side maximum behind the voxel chain.
+ * Refused: K outside 1 .. CMAX_BASIS_MAX_K, an unknown basis_dtype, scale_later != 0 and everything cmax_patch_plan_create
+ * checks about the terms (CMAX_EINVAL); a handle that holds a communicator and a handle that holds per-event weights
+ * (CMAX_EUNSUPPORTED).  A plan on a deterministic handle is bit-repeatable: the basis kernels use no atomics.            */
+int cmax_basis_plan_create(cmax_handle_t h, const cmax_basis_objective_t *desc_host, const void *basis_dev, cmax_stream_t stream,
+                           cmax_patch_plan_t *out);
 
 /* The reduction of the scale_later map as a leaf operator (the autograd-chained path chains it with cmax_patch_to_dense and
  * cmax_voxel_construct).  x: device fp32 / fp64 [n].  out: device double[4] -- out[0] = max x (signed), out[1] = number of
