@@ -139,6 +139,7 @@ F32, F64 = 0, 1
 MODEL_2DOF, MODEL_DENSE, MODEL_VOXEL = 0, 1, 2
 REF_FIRST, REF_LAST, REF_FRAC = 0, 1, 2
 COST_VARIANCE, COST_GRADMAG = 0, 1
+COST_MEAN_SQUARE, COST_LAPLACIAN, COST_HESSIAN = 2, 3, 4  # the focus losses (include/cmax_hip.h)
 SCHEME_BURGERS, SCHEME_UPWIND = 0, 1
 FILTER_BILINEAR, FILTER_NEAREST = 0, 1
 OPT_SGD, OPT_ADAM = 0, 1

@@ -34,6 +34,16 @@ _COST_TABLE = {
 }
 FUSED_COSTS = tuple(_COST_TABLE)
 
+# the focus losses (costs/focus.py, costs.focus_functions): fused like the gradient-magnitude trio, never routed to fused_iwes
+_FOCUS_TABLE = {
+    prefix + kind: (code, normalized, refs)
+    for kind, code in (("mean_square", _lib.COST_MEAN_SQUARE), ("laplacian_magnitude", _lib.COST_LAPLACIAN),
+                       ("hessian_magnitude", _lib.COST_HESSIAN))
+    for prefix, normalized, refs in (("", 0, (("first", 1.0),)), ("normalized_", 1, (("first", 1.0),)),
+                                     ("multi_focal_normalized_", 1, (("last", 1.0), ("first", 1.0), ("middle", 2.0))))
+}
+FOCUS_COSTS = tuple(_FOCUS_TABLE)
+
 
 def _cost_registry():
     from . import costs  # (lazy: the costs package is imported after this module)
@@ -45,13 +55,13 @@ def make_descriptor(cost: str, motion_model: str, direction: str = "minimize", s
                     omit_boundary: bool = True, normalize_t: bool = True, time_bin: int = 0,
                     warp_direction: Union[str, float] = "first") -> CmaxObjective:
     """Build the cmax_objective_t for one named cost (include/cmax_hip.h)."""
-    if cost not in _COST_TABLE:
-        raise KeyError(f"cost {cost!r} has no fused kernel; fused costs: {FUSED_COSTS}")
+    if cost not in _COST_TABLE and cost not in _FOCUS_TABLE:
+        raise KeyError(f"cost {cost!r} has no fused kernel; fused costs: {FUSED_COSTS + FOCUS_COSTS}")
     if motion_model not in F.MODEL_CODES:
         raise KeyError(motion_model)
     if direction not in ("minimize", "maximize", "natural"):
         raise ValueError(f"direction should be minimize, maximize, and natural. Got {direction}.")
-    code, normalized, refs = _COST_TABLE[cost]
+    code, normalized, refs = _COST_TABLE[cost] if cost in _COST_TABLE else _FOCUS_TABLE[cost]
     d = CmaxObjective()
     d.model = F.MODEL_CODES[motion_model]
     d.cost = code
@@ -1098,7 +1108,8 @@ class _CustomTerm:
 class ContrastObjective:
     """loss = objective(motion[, coarse_flow]) with the reference's cost names.
 
-    cost: any key of costs.functions, or "hybrid" with cost_with_weight={name: weight | "inv"}
+    cost: any key of costs.functions or costs.focus_functions (FOCUS_COSTS: the mean-square, Laplacian and Hessian focus losses, fused
+    like the gradient-magnitude trio), or "hybrid" with cost_with_weight={name: weight | "inv"}
     (src/costs/hybrid.py).  Event-based costs run as fused kernels on `handle`; total_variation runs
     on the patch flow handed in as `coarse_flow` (patch_contrast_base.py:349-350).
     A cost WITHOUT a fused kernel -- a CostBase instance, a callable arg_dict -> 0-dim tensor, or a name registered in

@@ -22,4 +22,6 @@ def inheritors(klass):
 
 functions = {k.name: k for k in inheritors(CostBase)}
 
+# the focus losses beyond the reference's names: a registry of their own, imported only now so that the walk above does not see them
+from .focus import focus_functions  # noqa: E402
 from .hybrid import HybridCost  # noqa: E402

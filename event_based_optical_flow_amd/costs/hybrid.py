@@ -8,7 +8,7 @@ import logging
 from dataclasses import dataclass
 from typing import Dict, Union
 
-from . import CostBase, functions
+from . import CostBase, focus_functions, functions
 
 logger = logging.getLogger(__name__)
 
@@ -43,7 +43,9 @@ class HybridCost(CostBase):
         logger.info(f"Log functions are mix of {cost_with_weight}")
         self._members: Dict[str, _Member] = {}
         for cost_name, weight in cost_with_weight.items():
-            member_cost = functions[cost_name](direction=direction, store_history=store_history, *args, **kwargs)
+            # the reference's names first, then the focus losses (costs/focus.py); anything else is a KeyError
+            cost_class = functions[cost_name] if cost_name in functions or cost_name not in focus_functions else focus_functions[cost_name]
+            member_cost = cost_class(direction=direction, store_history=store_history, *args, **kwargs)
             self._members[cost_name] = _Member(member_cost, weight)
         super().__init__(direction=direction, store_history=store_history)
         self.required_keys = [key for m in self._members.values() for key in m.cost.required_keys]

@@ -1188,7 +1188,9 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             const double coef = fabs(chain_coef<true>(op, stat, kk, &mud));
             const double imx = (double)__uint_as_float(ra.imax[kk]);
             const double npx = region_pixels(op.H, op.W, op.omit);
-            const double gb = op.cost == CMAX_COST_VARIANCE ? coef * 2.0 / (npx - 1.0) * (imx + fabs(mud)) : coef * 2.0 * imx / npx;
+            // (a focus loss: coef (2/n) A max|I|, A = sum_s c_s |S_s|_1^2 of its stencils -- 1 mean square, 64 Laplacian, 34 Hessian)
+            const double gb = op.cost == CMAX_COST_VARIANCE ? coef * 2.0 / (npx - 1.0) * (imx + fabs(mud))
+                                                            : coef * 2.0 * (op.cost == CMAX_COST_LAPLACIAN ? 64.0 : (op.cost == CMAX_COST_HESSIAN ? 34.0 : 1.0)) * imx / npx;
             const double dk = (double)ra.d[kk - ra.k0];
             return 4.0 * fmax(fabs(dk), fabs(1.0 - dk)) * (double)time_scale(wp) * 2.0 * gb;  // x4: fp32 rounding of G and of the term
         };

@@ -17,7 +17,8 @@
 //                   k_blur_stats_adj_var (variance with blur and a gradient: ONE kernel, the mean comes from K1's vote sums;
 //                   value-only / multi-GPU: k_blur_stats_var + k_gimage_blur_adj_var),
 //                   k_stats_gimage_gm / k_blur_stats_gimage_gm (gradient magnitude: statistics + the
-//                   G = dL/dIWE, blurs included).  They also clear the OTHER vote buffer for
+//                   G = dL/dIWE, blurs included), k_stats_gimage_st<COST> (the focus losses: statistics + G over
+//                   FocusStencil, between k_blur3 and k_blur3_adj when the cost blurs).  They also clear the OTHER vote buffer for
 //                   the next evaluation (double buffering: no memset in the steady state) and the
 //                   flow-gradient buffer, with write-through stores.  Plain variance needs no G image:
 //                   K3 gathers the raw image (the mean cancels in the gather's differences except at the
@@ -52,6 +53,7 @@
 //   CMAX_NO_STATS_INSIDE=1   plain variance on owned groups: k_stats as a launch of its own instead of inside K3's
 //   CMAX_STAT_SWEEPS=n       statistics inside K3's launch: 4-pixel sweeps per statistics workgroup (fewer, longer workgroups)
 //   CMAX_NO_FUSED_BLURVAR=1  blurred variance: k_blur_stats_var + k_gimage_blur_adj_var instead of k_blur_stats_adj_var
+//   CMAX_NO_FUSED_FOCUS=1    focus losses: k_stats + k_gimage as launches of their own instead of k_stats_gimage_st
 //   CMAX_NSUB=n          statistics sub-accumulators (cache lines) per image
 //   CMAX_TAN2=0 | 1      2-DoF tangent-image path: never / also without a communicator
 //   CMAX_PLAN_GRAPHS=1   replay the patch plan from captured hipGraphs (cmax_solver.hip)
@@ -277,9 +279,15 @@ k_stats(const float *__restrict__ img, int H, int W, int omit, int nsub, double 
             } else if (in[u]) {
                 const unsigned p = base + (unsigned)u * stride;
                 const int r = (int)(p / (unsigned)W), c = (int)(p - (unsigned)r * (unsigned)W);
-                float gx, gy;
-                sobel8_f32(img, H, W, r, c, gx, gy);
-                v[0] += (double)(gx * gx + gy * gy);
+                if constexpr (COST == CMAX_COST_GRADMAG) {
+                    float gx, gy;
+                    sobel8_f32(img, H, W, r, c, gx, gy);
+                    v[0] += (double)(gx * gx + gy * gy);
+                } else if constexpr (COST != CMAX_COST_VARIANCE) {  // a focus loss: the energy of its responses (FocusStencil, cmax_image_kernels.h)
+                    float n[3][3];
+                    focus_load<1, float>(img, H, W, r, c, n);
+                    v[0] += (double)focus_energy<COST, float>(n);
+                }
             }
         }
     }
@@ -417,6 +425,76 @@ k_stats_gimage_gm(const float *__restrict__ in0, int64_t in_stride, int H, int W
     CMAX_STAMP(2, 6);
     if (threadIdx.x == 0) atomic_add(&stat_slot[kSubStride * (blockIdx.x % nsub)], v[0]);
     CMAX_STAMP(2, 7);
+}
+
+// K2 + K2b in one pass for a focus loss (FocusStencil<COST>, cmax_image_kernels.h), after the border form of k_stats_gimage_gm: the
+// image tile with a halo of 2 in LDS; the responses of the tile's pixels and a ring of one around them, ZERO outside Omega, once
+// per pixel; the transpose as a plain 3 x 3 correlation on those (no tests of Omega); the energy of the thread's own pixel in fp64
+// into the `nsub` accumulators.  G' = (2 / n) sum_s c_s S_s^T (r_s 1_Omega) leaves with the constant chain factor of a plain cost
+// (ia.chain) and without one for the normalised forms (kFoldScale: K3 applies it).
+// LDS pitch: every access is a ds_read_b32 / ds_write_b32 (bank = dword address mod 32, conflicts within a 32-lane half only).  A
+// half-wave reads 32 consecutive floats of one row -- conflict-free at any pitch -- and the staging loops write consecutive q, which
+// is conflict-free exactly when a row's pitch equals its width: the response tiles carry no padding.  (The image tile keeps the pitch
+// of stage_tile's other user.)
+template <int COST>
+__global__ void __launch_bounds__(256)
+k_stats_gimage_st(const float *__restrict__ in0, int64_t in_stride, int H, int W, ImgArgs ia, int omit, int nsub, double *__restrict__ stat_base, float4 *__restrict__ zero_extra,
+                  int64_t n_extra4) {
+    using S = FocusStencil<COST>;
+    constexpr int kRH = kGmTileH + 2, kRW = kGmTileW + 2;  // responses: the tile and a ring of one
+    __shared__ double smem[2 * 4];
+    __shared__ float tile[kGmTileH + 4][kGmTileW + 4 + 1];  // image tile with a halo of 2 (zero outside the image)
+    __shared__ float t_r[S::kResp][kRH][kRW];
+    const float *__restrict__ img = in0 + blockIdx.y * in_stride;  // (leading, preloaded arguments: the tile loads leave without waiting for the argument block)
+    float *__restrict__ zero_img = ia.zero[blockIdx.y];
+    float *__restrict__ G = ia.G[blockIdx.y];
+    double *__restrict__ stat_slot = stat_base + blockIdx.y * kStatStride;
+    const int64_t gtid = (int64_t)blockIdx.x * 256 + threadIdx.x, gthreads = (int64_t)gridDim.x * 256;
+    const int tiles_w = (W + kGmTileW - 1) / kGmTileW;
+    const int tr = blockIdx.x / tiles_w, tc = blockIdx.x - tr * tiles_w;
+    const int r0 = tr * kGmTileH - 2, c0 = tc * kGmTileW - 2;
+    stage_tile<kGmTileH + 4, kGmTileW + 4>(tile, img, r0, c0, H, W);
+    __syncthreads();
+    if (blockIdx.y == 0) zero_fill_sc1((float *)zero_extra, 4 * n_extra4, gtid, gthreads);  // behind the loads (see k_stats)
+    zero_fill_sc1(zero_img, (int64_t)H * W, gtid, gthreads);
+    const int i0 = omit ? 1 : 0;
+    const float gscale = (float)(2.0 / region_pixels(H, W, omit)) * ia.chain[blockIdx.y];
+    for (int q = threadIdx.x; q < kRH * kRW; q += 256) {
+        const int y = q / kRW, x = q - y * kRW;  // response of pixel (r0 + 1 + y, c0 + 1 + x): 3 x 3 window with top-left tile[y][x]
+        const int qi = r0 + 1 + y, qj = c0 + 1 + x;
+        const bool in_om = qi >= i0 && qi < H - i0 && qj >= i0 && qj < W - i0;
+        float n[3][3], r[S::kResp];
+#pragma unroll
+        for (int a = 0; a < 3; ++a)
+#pragma unroll
+            for (int b = 0; b < 3; ++b) n[a][b] = tile[y + a][x + b];
+        S::resp(n, r);
+#pragma unroll
+        for (int s = 0; s < S::kResp; ++s) t_r[s][y][x] = in_om ? r[s] : 0.f;
+    }
+    __syncthreads();
+    const int la = threadIdx.x / kGmTileW, lb = threadIdx.x - la * kGmTileW;  // pixel of this thread inside the tile
+    const int i = r0 + 2 + la, j = c0 + 2 + lb;
+    // transpose: output pixel q = (i - a, j - b) reads this pixel with tap (a, b); q outside Omega holds zeros
+    float g = 0.f, e = 0.f;
+#pragma unroll
+    for (int a = -1; a <= 1; ++a)
+#pragma unroll
+        for (int b = -1; b <= 1; ++b) {
+            float r[S::kResp];
+#pragma unroll
+            for (int s = 0; s < S::kResp; ++s) r[s] = S::tap(s, a, b) != 0.f ? t_r[s][la + 1 - a][lb + 1 - b] : 0.f;
+            g += focus_tap_sum<COST, float>(r, a, b);
+        }
+#pragma unroll
+    for (int s = 0; s < S::kResp; ++s) {
+        const float rc = t_r[s][la + 1][lb + 1];  // (zero outside Omega, the image included)
+        e += S::weight(s) * rc * rc;
+    }
+    if (i < H && j < W) G[(int64_t)i * W + j] = gscale * g;
+    double v[2] = {(double)e, 0.0};
+    block_sum<2>(v, smem);
+    if (threadIdx.x == 0) atomic_add(&stat_slot[kSubStride * (blockIdx.x % nsub)], v[0]);
 }
 
 // Blurred gradient-magnitude cost (the shipped YAML cost), whole image side of one reference time in ONE kernel:
@@ -721,8 +799,12 @@ k_gimage(const float *__restrict__ img, ObjParams op, int k, const double *__res
     if (COST == CMAX_COST_VARIANCE) {
         const bool in = (i >= i0) && (i < H - i0) && (j >= i0) && (j < W - i0);
         G[p] = in ? (float)(coef * 2.0 * ((double)img[p] - mu) / (npix - 1.0)) : 0.f;
-    } else {
+    } else if constexpr (COST == CMAX_COST_GRADMAG) {
         G[p] = (float)(coef * (2.0 / npix) / 8.0) * sobel8_adj_f32(img, H, W, i0, i, j);
+    } else if constexpr (COST != CMAX_COST_VARIANCE) {  // a focus loss (FocusStencil, cmax_image_kernels.h)
+        float v5[5][5];
+        focus_load<2, float>(img, H, W, i, j, v5);
+        G[p] = (float)(coef * (2.0 / npix)) * focus_adj<COST, float>(v5, H, W, i0, i, j);
     }
 }
 
@@ -764,11 +846,16 @@ k_stats_tan(const float *__restrict__ img, const float *__restrict__ dimg, int H
             const double d = (double)dimg[p];
             v[0] += d;
             v[1] += d * (double)img[p];
-        } else {
+        } else if constexpr (COST == CMAX_COST_GRADMAG) {
             float gx, gy, hx, hy;
             sobel8_f32(img, H, W, r, c, gx, gy);
             sobel8_f32(dimg, H, W, r, c, hx, hy);
             v[0] += (double)(gx * hx + gy * hy);
+        } else if constexpr (COST != CMAX_COST_VARIANCE) {  // a focus loss: sum_s c_s r_s(I) r_s(dI)
+            float n[3][3], m[3][3];
+            focus_load<1, float>(img, H, W, r, c, n);
+            focus_load<1, float>(dimg, H, W, r, c, m);
+            v[0] += (double)focus_dot<COST, float>(n, m);
         }
     }
     block_sum<2>(v, smem);
@@ -821,10 +908,21 @@ k_gimage_tan(const float *__restrict__ img, const float *__restrict__ dimg, ObjP
         const double dv = 2.0 / (npix - 1.0) * (tacc[1] - mu * tacc[0]);  // <G0, dI>
         const bool in = (i >= i0) && (i < H - i0) && (j >= i0) && (j < W - i0);
         Gp[p] = in ? (float)((p1 * 2.0 * ((double)dimg[p] - dmean) + p2 * dv * 2.0 * ((double)img[p] - mu)) / (npix - 1.0)) : 0.f;
-    } else {
+    } else if constexpr (COST == CMAX_COST_GRADMAG) {
         const double dv = 2.0 / npix * tacc[0];
         const double c = (2.0 / npix) / 8.0;
         Gp[p] = (float)(p1 * c) * sobel8_adj_f32(dimg, H, W, i0, i, j) + (float)(p2 * dv * c) * sobel8_adj_f32(img, H, W, i0, i, j);
+    } else if constexpr (COST != CMAX_COST_VARIANCE) {  // a focus loss is quadratic: the same operator on the tangent image, plus the p2 term of the normalised forms
+        const double dv = 2.0 / npix * tacc[0];
+        const double c = 2.0 / npix;
+        float v5[5][5];
+        focus_load<2, float>(dimg, H, W, i, j, v5);
+        float g = (float)(p1 * c) * focus_adj<COST, float>(v5, H, W, i0, i, j);
+        if (p2 != 0.0) {
+            focus_load<2, float>(img, H, W, i, j, v5);
+            g += (float)(p2 * dv * c) * focus_adj<COST, float>(v5, H, W, i0, i, j);
+        }
+        Gp[p] = g;
     }
 }
 
@@ -1187,11 +1285,26 @@ static void with_model(int model, F &&f) {
     else if (model == CMAX_MODEL_DENSE) f(int_c<CMAX_MODEL_DENSE>{});
     else f(int_c<CMAX_MODEL_VOXEL>{});
 }
-// f(int_c<COST>{}) for the contrast of an objective (check_objective_args: one of the two)
+// f(int_c<COST>{}) for the contrast of an objective (check_objective_args: one of the five)
 template <class F>
 static void with_cost(int cost, F &&f) {
-    if (cost == CMAX_COST_VARIANCE) f(int_c<CMAX_COST_VARIANCE>{});
-    else f(int_c<CMAX_COST_GRADMAG>{});
+    switch (cost) {
+    case CMAX_COST_VARIANCE: f(int_c<CMAX_COST_VARIANCE>{}); break;
+    case CMAX_COST_GRADMAG: f(int_c<CMAX_COST_GRADMAG>{}); break;
+    case CMAX_COST_MEAN_SQUARE: f(int_c<CMAX_COST_MEAN_SQUARE>{}); break;
+    case CMAX_COST_LAPLACIAN: f(int_c<CMAX_COST_LAPLACIAN>{}); break;
+    case CMAX_COST_HESSIAN: f(int_c<CMAX_COST_HESSIAN>{}); break;
+    default: break;  // (refused by cost_known at every entry)
+    }
+}
+// the focus losses (FocusStencil, cmax_image_kernels.h): the general path K1 -> image kernel(s) -> K3, none of the variance shortcuts
+static bool cost_is_focus(int cost) { return cost == CMAX_COST_MEAN_SQUARE || cost == CMAX_COST_LAPLACIAN || cost == CMAX_COST_HESSIAN; }
+static bool cost_known(int cost) { return cost == CMAX_COST_VARIANCE || cost == CMAX_COST_GRADMAG || cost_is_focus(cost); }
+template <class F>
+static void with_focus_cost(int cost, F &&f) {
+    if (cost == CMAX_COST_MEAN_SQUARE) f(int_c<CMAX_COST_MEAN_SQUARE>{});
+    else if (cost == CMAX_COST_LAPLACIAN) f(int_c<CMAX_COST_LAPLACIAN>{});
+    else if (cost == CMAX_COST_HESSIAN) f(int_c<CMAX_COST_HESSIAN>{});
 }
 
 static EvView ev_view(const cmax_handle_s *h) {
@@ -2132,7 +2245,7 @@ static ObjParams obj_params(const cmax_handle_s *h, const cmax_objective_t *d) {
 static int check_objective_args(cmax_handle_t h, const cmax_objective_t *d, const float *motion) {
     CMAX_REQUIRE(h && d && motion, "objective: null pointer");
     CMAX_REQUIRE(d->model >= CMAX_MODEL_2DOF && d->model <= CMAX_MODEL_VOXEL, "objective: model");
-    CMAX_REQUIRE(d->cost == CMAX_COST_VARIANCE || d->cost == CMAX_COST_GRADMAG, "objective: cost");
+    CMAX_REQUIRE(cost_known(d->cost), "objective: cost");
     CMAX_REQUIRE(d->n_ref >= 1 && d->n_ref <= 4, "objective: n_ref");
     CMAX_REQUIRE(d->motion_dtype == CMAX_F32 || d->motion_dtype == CMAX_F64, "objective: motion_dtype must be CMAX_F32 or CMAX_F64");
     CMAX_REQUIRE(d->model != CMAX_MODEL_VOXEL || (d->T > 0 && d->T == h->n_time_bin), "objective: voxel T must match the handle's time bins");
@@ -2315,6 +2428,8 @@ struct EvalPlan {
     bool deferred;  // deferred_applies: no K2, K3 gathers the statistics, k_finish_raw applies the chain factors
     bool lines;     // two_dof_lines (includes the deferred case)
     bool fused_gm;  // gradient magnitude with a gradient: K2 and K2b (and the blurs) are one kernel: statistics + G image without its chain factor
+    bool fused_st;  // a focus loss with a gradient: [k_blur3 ->] k_stats_gimage_st (statistics + G image, chain factor as for fused_gm) [-> k_blur3_adj]
+    bool plain_st;  // ... with CMAX_NO_FUSED_FOCUS=1: k_stats in front, k_gimage with the full chain factor behind it (kFoldNone)
     bool blur_var;  // blurred variance: blur + statistics in one kernel
     bool fused_bv;  // ... with a gradient on one GPU: K1 also sums the votes against blur^T 1_Omega, so that ONE image kernel can blur, sum and
                     // write the un-centred, unscaled A' = 2 / (n - 1) blur^T [Ib 1_Omega] (k_blur_stats_adj_var); K3 applies the chain factor
@@ -2352,6 +2467,7 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     static const int tan2_env = getenv("CMAX_TAN2") ? atoi(getenv("CMAX_TAN2")) : -1;
     static const bool no_fused_bv = getenv("CMAX_NO_FUSED_BLURVAR") != nullptr;
     static const bool no_stats_inside = getenv("CMAX_NO_STATS_INSIDE") != nullptr;
+    static const bool no_fused_focus = getenv("CMAX_NO_FUSED_FOCUS") != nullptr;
     static const int sweeps_env = getenv("CMAX_STAT_SWEEPS") ? std::max(1, atoi(getenv("CMAX_STAT_SWEEPS"))) : 0;
     EvalPlan p = {};
     const bool dist = comm != nullptr;  // also a 1-rank communicator: the same enqueue sequence, RCCL included
@@ -2378,6 +2494,8 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.lines = two_dof_lines(h, d, grad);
     p.raw = p.lines ? (raw_out ? raw_out : h->d_raw) : nullptr;
     p.fused_gm = !det && grad && d->cost == CMAX_COST_GRADMAG && h->n > 0;
+    p.fused_st = !det && grad && cost_is_focus(d->cost) && h->n > 0 && !no_fused_focus;
+    p.plain_st = !det && grad && cost_is_focus(d->cost) && h->n > 0 && no_fused_focus;
     p.blur_var = !det && d->cost == CMAX_COST_VARIANCE && d->sigma > 0;
     // K1 can sum its votes for the kernels behind it (not on a weighted handle: the sum counts events)
     const bool k1_sums_ok = whole && !dist && !h->weighted && !h->general_only && h->Hp >= 4 && h->Wp >= 4;
@@ -2403,7 +2521,7 @@ static EvalPlan eval_plan(const cmax_handle_s *h, const cmax_objective_t *d, con
     p.memset_grad = grad && !two_dof && !p.owned && !det && !clearable;
     p.fold = p.deferred ? kFoldDeferred
                         : (p.stats_inside ? kFoldStatsInside
-                                          : (fold_var ? kFoldStats : (((p.fused_gm || p.fused_bv) && d->normalized) ? kFoldScale : kFoldNone)));
+                                          : (fold_var ? kFoldStats : (((p.fused_gm || p.fused_st || p.fused_bv) && d->normalized) ? kFoldScale : kFoldNone)));
     if (p.stats_inside) {
         // Sweeps of 4 pixels per thread and statistics workgroup: two (round 3, standard segments: K3 of cfg5 with 1 / 2 / 4 / 8 sweeps 18.8 /
         // 17.9 / 18.3 / 18.3 us) -- unless the gathering workgroups fit the chip in ONE round and the statistics workgroups are what
@@ -2518,7 +2636,7 @@ static int finish_contrast_stats(cmax_handle_s *h, const cmax_objective_t *d, co
             hipLaunchKernelGGL(k_blur_stats_var, dim3(stat_blocks(h), d->n_ref), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, p.tap0, p.tap1, d->omit_boundary,
                                op.nsub, h->d_stat, p.stats_clear4, p.n_stats_clear4);
         CMAX_CHECK_LAUNCH();
-    } else if (!(p.deferred || p.fused_gm || p.stats_inside)) {  // those get their statistics from K3 / from the fused image kernel
+    } else if (!(p.deferred || p.fused_gm || p.fused_st || p.stats_inside)) {  // those get their statistics from K3 / from the fused image kernel
         for (int k = 0; k < d->n_ref; ++k) {
             const float *img = nullptr;
             int rc = blur_image(h, d->sigma, ia.in[k], h->iweb[k], &img, s);
@@ -2562,6 +2680,27 @@ static int launch_finish_det(cmax_handle_s *h, const cmax_objective_t *d, void *
     return 0;
 }
 
+// dL/dIWE with its chain factor from the finished statistics: k_gimage on the (blurred) image, then the blur transpose (the unfused image
+// path: deterministic mode, and the focus losses under CMAX_NO_FUSED_FOCUS)
+static int launch_gimage_unfused(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, hipStream_t s) {
+    const int Hp = h->Hp, Wp = h->Wp;
+    const int64_t npix = (int64_t)Hp * Wp;
+    if (d->sigma > 0) {
+        int rc = h->Gt_det.reserve(&h->bytes, 4 * npix, s);
+        if (rc) return rc;
+    }
+    float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
+    const dim3 igrid(div_up(npix, 256), d->n_ref);
+    // the n_ref images are not contiguous (last_iwe[k] = blurred copies or the caller's buffer): one launch each
+    with_cost(d->cost, [&](auto c) {
+        for (int k = 0; k < d->n_ref; ++k)
+            hipLaunchKernelGGL(k_gimage<c.value>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
+    });
+    if (d->sigma > 0) hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt_det, Hp, Wp, p.tap0, p.tap1, h->G, npix);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 // backward, image space: the clearing memset of the flow gradient where no launch does it, then dL/dIWE as a G image per reference time
 // (folded into K3 for the plain variance) -- deterministic: absmax pre-pass + the unfused k_gimage [+ blur transpose]
 static int finish_gimage(cmax_handle_s *h, const cmax_objective_t *d, const EvalPlan &p, const ObjParams &op, const ImgArgs &ia, void *grad, hipStream_t s) {
@@ -2575,22 +2714,47 @@ static int finish_gimage(cmax_handle_s *h, const cmax_objective_t *d, const Eval
         for (int k = 0; k < d->n_ref; ++k) im.in[k] = h->last_iwe[k];
         hipLaunchKernelGGL(k_image_absmax, dim3(std::min(stream_grid(npix, 1024), 256), d->n_ref), dim3(256), 0, s, im, npix, 0, h->d_imax);
         CMAX_CHECK_LAUNCH();
-        if (p.fold == kFoldNone) {  // dL/dIWE with its chain factor: k_gimage on the (blurred) image, then the blur transpose
-            if (d->sigma > 0) {
-                int rc = h->Gt_det.reserve(&h->bytes, 4 * npix, s);
-                if (rc) return rc;
-            }
-            float *gdst = d->sigma > 0 ? h->Gt_det : h->G;
-            const dim3 igrid(div_up(npix, 256), d->n_ref);
-            // the n_ref images are not contiguous (last_iwe[k] = blurred copies or the caller's buffer): one launch each
-            with_cost(d->cost, [&](auto c) {
-                for (int k = 0; k < d->n_ref; ++k)
-                    hipLaunchKernelGGL(k_gimage<c.value>, dim3(igrid.x), dim3(256), 0, s, h->last_iwe[k], op, k, h->d_stat, gdst + k * npix, (int64_t)0);
-            });
-            if (d->sigma > 0) hipLaunchKernelGGL(k_blur3_adj<float>, igrid, dim3(256), 0, s, h->Gt_det, Hp, Wp, p.tap0, p.tap1, h->G, npix);
-            CMAX_CHECK_LAUNCH();
+        if (p.fold == kFoldNone) {
+            int rc = launch_gimage_unfused(h, d, p, op, s);
+            if (rc) return rc;
         }
         return d->model == CMAX_MODEL_2DOF ? 0 : reserve_g64(h, p.g.count, s);
+    }
+    if (p.plain_st) {  // CMAX_NO_FUSED_FOCUS: the statistics are finished (finish_contrast_stats), G with its chain factor by k_gimage
+        ProfScope prof(h, kProfGimage, s);
+        return launch_gimage_unfused(h, d, p, op, s);
+    }
+    if (p.fused_st) {
+        ProfScope prof(h, kProfStats, s);
+        for (int rep = 0; rep < h->prof_repeat; ++rep) {
+            if (!(d->sigma > 0)) {  // the votes are contiguous: every reference time in one launch
+                with_focus_cost(d->cost, [&](auto c) {
+                    hipLaunchKernelGGL(k_stats_gimage_st<c.value>, gm_grid(h, d), dim3(256), 0, s, ia.in[0], npix, Hp, Wp, ia, d->omit_boundary, op.nsub, h->d_stat,
+                                       p.stats_clear4, p.n_stats_clear4);
+                });
+                continue;
+            }
+            // sigma > 0: k_blur3 -> the fused kernel on the blurred copy, G' into the scratch -> k_blur3_adj (the copies are buffers of
+            // their own: one launch per reference time)
+            int rc = h->Gt_det.reserve(&h->bytes, 4 * npix, s);
+            if (rc) return rc;
+            for (int k = 0; k < d->n_ref; ++k) {
+                const float *img = nullptr;
+                rc = blur_image(h, d->sigma, ia.in[k], h->iweb[k], &img, s);
+                if (rc) return rc;
+                ImgArgs ik = {};
+                ik.zero[0] = ia.zero[k];
+                ik.G[0] = h->Gt_det + k * npix;
+                ik.chain[0] = ia.chain[k];
+                with_focus_cost(d->cost, [&](auto c) {
+                    hipLaunchKernelGGL(k_stats_gimage_st<c.value>, dim3(gm_grid(h, d).x), dim3(256), 0, s, img, (int64_t)0, Hp, Wp, ik, d->omit_boundary, op.nsub,
+                                       h->d_stat + k * kStatStride, k == 0 ? p.stats_clear4 : nullptr, k == 0 ? p.n_stats_clear4 : (int64_t)0);
+                });
+            }
+            hipLaunchKernelGGL(k_blur3_adj<float>, dim3(div_up(npix, 256), d->n_ref), dim3(256), 0, s, h->Gt_det, Hp, Wp, p.tap0, p.tap1, h->G, npix);
+        }
+        CMAX_CHECK_LAUNCH();
+        return 0;
     }
     if (p.fused_bv) {
         // dL/dIWE was written (without mean and chain factor) by the statistics kernel
@@ -2898,8 +3062,12 @@ __global__ void __launch_bounds__(256) k_gimage_orig(const float *__restrict__ i
     if (COST == CMAX_COST_VARIANCE) {
         const bool in = (i >= i0) && (i < H - i0) && (j >= i0) && (j < W - i0);
         G[p] = in ? (float)(coef * 2.0 * ((double)img[p] - mu) / (npix - 1.0)) : 0.f;
-    } else {
+    } else if constexpr (COST == CMAX_COST_GRADMAG) {
         G[p] = (float)(coef * (2.0 / npix) / 8.0) * sobel8_adj_f32(img, H, W, i0, i, j);
+    } else if constexpr (COST != CMAX_COST_VARIANCE) {  // a focus loss (FocusStencil, cmax_image_kernels.h)
+        float v5[5][5];
+        focus_load<2, float>(img, H, W, i, j, v5);
+        G[p] = (float)(coef * (2.0 / npix)) * focus_adj<COST, float>(v5, H, W, i0, i, j);
     }
 }
 
@@ -3255,6 +3423,7 @@ int cmax_objective_batch(cmax_handle_t h, const cmax_objective_t *d, const void 
 
 int cmax_objective_has_raw(cmax_handle_t h, const cmax_objective_t *d) {
     if (!h || !d || h->weighted) return 0;  // (the raw form is not carried for per-event weights)
+    if (cost_is_focus(d->cost)) return 0;   // (nor offered for the focus losses)
     if (!two_dof_lines(h, d, (const void *)h)) return 0;
     // (a NORMALISED plain variance runs the deferred K3, whose fold needs the un-warped image's statistics from the device)
     return deferred_applies(h, d, (const void *)h) && d->normalized ? 0 : 1;

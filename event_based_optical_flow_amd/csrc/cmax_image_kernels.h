@@ -140,4 +140,114 @@ __device__ __forceinline__ float sobel8_adj_f32(const float *__restrict__ img, i
     return s;
 }
 
+// ---------------------------------------------------------------------------------------------
+// Focus losses (CMAX_COST_MEAN_SQUARE / _LAPLACIAN / _HESSIAN): v = (1/n) sum_{q in Omega} sum_s c_s r_s(q)^2, every response
+// r_s = S_s * I a 3 x 3 stencil on the image read as zero outside it.  One trait per cost:
+//   kResp         number of responses
+//   resp(n, r)    the responses at a pixel from its neighbourhood n[a + 1][b + 1] = I(r + a, c + b)
+//   tap(s, a, b)  S_s[a][b]: what response s of pixel q reads of pixel q + (a, b) -- the transpose taps
+//   weight(s)     c_s
+// dv/dI[p] = (2/n) sum_{(a, b)} 1_Omega(p - (a, b)) sum_s c_s r_s(p - (a, b)) tap(s, a, b).  The kernels are written once over the
+// trait; A is the arithmetic type (float on the fused path, double in the leaf operator).
+// sum_s c_s |S_s|_1^2 (the deterministic K3's bound): 1, 64, 34.
+// ---------------------------------------------------------------------------------------------
+template <int COST>
+struct FocusStencil;
+
+template <>
+struct FocusStencil<CMAX_COST_MEAN_SQUARE> {
+    static constexpr int kResp = 1;
+    template <typename A>
+    __device__ __forceinline__ static void resp(const A (&n)[3][3], A (&r)[1]) { r[0] = n[1][1]; }
+    __host__ __device__ static constexpr float tap(int, int a, int b) { return (a == 0 && b == 0) ? 1.f : 0.f; }
+    __host__ __device__ static constexpr float weight(int) { return 1.f; }
+};
+
+template <>
+struct FocusStencil<CMAX_COST_LAPLACIAN> {
+    static constexpr int kResp = 1;
+    template <typename A>
+    __device__ __forceinline__ static void resp(const A (&n)[3][3], A (&r)[1]) { r[0] = ((n[0][1] + n[2][1]) + (n[1][0] + n[1][2])) - (A)4 * n[1][1]; }
+    __host__ __device__ static constexpr float tap(int, int a, int b) { return (a == 0 && b == 0) ? -4.f : ((a == 0 || b == 0) ? 1.f : 0.f); }
+    __host__ __device__ static constexpr float weight(int) { return 1.f; }
+};
+
+template <>
+struct FocusStencil<CMAX_COST_HESSIAN> {
+    static constexpr int kResp = 3;  // h_rr, h_cc, h_rc
+    template <typename A>
+    __device__ __forceinline__ static void resp(const A (&n)[3][3], A (&r)[3]) {
+        r[0] = (n[0][1] + n[2][1]) - (A)2 * n[1][1];
+        r[1] = (n[1][0] + n[1][2]) - (A)2 * n[1][1];
+        r[2] = (A)0.25 * ((n[2][2] - n[2][0]) - (n[0][2] - n[0][0]));
+    }
+    __host__ __device__ static constexpr float tap(int s, int a, int b) {
+        return s == 0 ? (b != 0 ? 0.f : (a == 0 ? -2.f : 1.f)) : (s == 1 ? (a != 0 ? 0.f : (b == 0 ? -2.f : 1.f)) : 0.25f * (float)(a * b));
+    }
+    __host__ __device__ static constexpr float weight(int s) { return s == 2 ? 2.f : 1.f; }
+};
+
+// sum_s c_s r_s(n) r_s(m): the energy of a pixel with m = n, the tangent statistic with m = the tangent image's neighbourhood
+template <int COST, typename A>
+__device__ __forceinline__ A focus_dot(const A (&n)[3][3], const A (&m)[3][3]) {
+    using S = FocusStencil<COST>;
+    A rn[S::kResp], rm[S::kResp], e = (A)0;
+    S::resp(n, rn);
+    S::resp(m, rm);
+#pragma unroll
+    for (int s = 0; s < S::kResp; ++s) e += (A)S::weight(s) * rn[s] * rm[s];
+    return e;
+}
+template <int COST, typename A>
+__device__ __forceinline__ A focus_energy(const A (&n)[3][3]) { return focus_dot<COST, A>(n, n); }
+
+// what output pixel q = p - (a, b) hands back to p: sum_s c_s r_s(q) tap(s, a, b) (the zero taps fold away)
+template <int COST, typename A>
+__device__ __forceinline__ A focus_tap_sum(const A (&r)[FocusStencil<COST>::kResp], int a, int b) {
+    using S = FocusStencil<COST>;
+    A t = (A)0;
+#pragma unroll
+    for (int s = 0; s < S::kResp; ++s)
+        if (S::tap(s, a, b) != 0.f) t += (A)(S::weight(s) * S::tap(s, a, b)) * r[s];
+    return t;
+}
+
+// the (2R + 1)^2 neighbourhood of (i, j), zero outside the image
+template <int R, typename A, typename T>
+__device__ __forceinline__ void focus_load(const T *__restrict__ img, int H, int W, int i, int j, A (&v)[2 * R + 1][2 * R + 1]) {
+#pragma unroll
+    for (int a = 0; a < 2 * R + 1; ++a)
+#pragma unroll
+        for (int b = 0; b < 2 * R + 1; ++b) {
+            const int r = i + a - R, c = j + b - R;
+            v[a][b] = (r < 0 || r >= H || c < 0 || c >= W) ? (A)0 : (A)img[(int64_t)r * W + c];
+        }
+}
+
+// dv/dI[p] * n / 2 at p = (i, j) from its 5 x 5 neighbourhood v (v[2][2] = I(p)): the sum over the output pixels q in Omega that read p
+template <int COST, typename A>
+__device__ __forceinline__ A focus_adj(const A (&v)[5][5], int H, int W, int i0, int i, int j) {
+    using S = FocusStencil<COST>;
+    A s = (A)0;
+#pragma unroll
+    for (int a = -1; a <= 1; ++a)
+#pragma unroll
+        for (int b = -1; b <= 1; ++b) {
+            bool any = false;
+#pragma unroll
+            for (int t = 0; t < S::kResp; ++t) any = any || S::tap(t, a, b) != 0.f;
+            if (!any) continue;
+            const int qi = i - a, qj = j - b;
+            if (qi < i0 || qi >= H - i0 || qj < i0 || qj >= W - i0) continue;
+            A n[3][3], r[S::kResp];
+#pragma unroll
+            for (int x = 0; x < 3; ++x)
+#pragma unroll
+                for (int y = 0; y < 3; ++y) n[x][y] = v[1 - a + x][1 - b + y];
+            S::resp(n, r);
+            s += focus_tap_sum<COST, A>(r, a, b);
+        }
+    return s;
+}
+
 }  // namespace cmax

@@ -351,6 +351,39 @@ k_gm_final(const T *__restrict__ img, int H, int W, int omit, double *acc, T *__
     G[p] = (T)(gs * (2.0 / n) * s / 8.0);
 }
 
+// focus losses (FocusStencil<COST>, cmax_image_kernels.h) in fp64 arithmetic: acc[1] += sum_Omega sum_s c_s r_s^2
+template <typename T, int COST>
+__global__ void __launch_bounds__(256) k_focus_sums(const T *__restrict__ img, int H, int W, int omit, double *acc) {
+    __shared__ double smem[1 * 4];
+    const int i0 = omit ? 1 : 0, h = H - 2 * i0, w = W - 2 * i0;
+    const int64_t n = (int64_t)(h > 0 ? h : 0) * (w > 0 ? w : 0);
+    double v[1] = {0.0};
+    for (int64_t q = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; q < n; q += (int64_t)gridDim.x * blockDim.x) {
+        int i = (int)(q / w) + i0, j = (int)(q % w) + i0;
+        double nb[3][3];
+        focus_load<1, double>(img, H, W, i, j, nb);
+        v[0] += focus_energy<COST, double>(nb);
+    }
+    block_sum<1>(v, smem);
+    if (threadIdx.x == 0) atomic_add(&acc[1], v[0]);
+}
+
+// G[p] = (2/n) * sum over q in Omega, q = p - (a,b), of sum_s c_s r_s(q) S_s[a][b]
+template <typename T, int COST>
+__global__ void __launch_bounds__(256)
+k_focus_final(const T *__restrict__ img, int H, int W, int omit, double *acc, T *__restrict__ G, const double *__restrict__ gscale) {
+    const int i0 = omit ? 1 : 0, h = H - 2 * i0, w = W - 2 * i0;
+    const double n = (double)(h > 0 ? h : 0) * (double)(w > 0 ? w : 0);
+    int64_t p = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    if (p == 0) acc[0] = acc[1] / n;
+    if (!G || p >= (int64_t)H * W) return;
+    int i = (int)(p / W), j = (int)(p % W);
+    double v5[5][5];
+    focus_load<2, double>(img, H, W, i, j, v5);
+    double gs = gscale ? *gscale : 1.0;
+    G[p] = (T)(gs * (2.0 / n) * focus_adj<COST, double>(v5, H, W, i0, i, j));
+}
+
 // total variation of a [2,h,w] flow  (src/costs/total_variation.py:60-75,110-126)
 template <typename T>
 __global__ void __launch_bounds__(256) k_tv_sums(const T *__restrict__ flow, int h, int w, int crop, double *acc) {
@@ -441,6 +474,13 @@ using namespace cmax;
         else if ((dtype) == CMAX_F64) { using T = double; CALL; } \
         else { set_error("unknown dtype %d", (int)(dtype)); return CMAX_EINVAL; } \
     } while (0)
+
+template <int COST>
+static int launch_focus_contrast(const void *img, int dtype, int H, int W, int omit, double *value, void *G, const double *gscale, int rgrid, int fgrid, hipStream_t s) {
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((k_focus_sums<T, COST>), dim3(rgrid), dim3(256), 0, s, (const T *)img, H, W, omit, value));
+    DISPATCH_DTYPE(dtype, hipLaunchKernelGGL((k_focus_final<T, COST>), dim3(G ? fgrid : 1), dim3(256), 0, s, (const T *)img, H, W, omit, value, (T *)G, gscale));
+    return 0;
+}
 
 extern "C" {
 
@@ -538,7 +578,7 @@ int cmax_blur3(const void *in, int dtype, int H, int W, double sigma, int adjoin
 int cmax_contrast(const void *img, int dtype, int H, int W, int cost, int omit_boundary, int ddof, double *value,
                   void *G, const double *gscale, cmax_stream_t stream) {
     CMAX_REQUIRE(img && value && H > 0 && W > 0, "contrast");
-    CMAX_REQUIRE(cost == CMAX_COST_VARIANCE || cost == CMAX_COST_GRADMAG, "contrast: cost");
+    CMAX_REQUIRE(cost >= CMAX_COST_VARIANCE && cost <= CMAX_COST_HESSIAN, "contrast: cost");
     CMAX_REQUIRE(!omit_boundary || (H > 2 && W > 2), "contrast: image too small for omit_boundary");
     hipStream_t s = (hipStream_t)stream;
     CMAX_CHECK_HIP(hipMemsetAsync(value, 0, 4 * sizeof(double), s));
@@ -547,6 +587,11 @@ int cmax_contrast(const void *img, int dtype, int H, int W, int cost, int omit_b
     if (cost == CMAX_COST_VARIANCE) {
         DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_var_sums<T>, dim3(rgrid), dim3(256), 0, s, (const T *)img, H, W, omit_boundary, value));
         DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_var_final<T>, dim3(G ? fgrid : 1), dim3(256), 0, s, (const T *)img, H, W, omit_boundary, ddof, value, (T *)G, gscale));
+    } else if (cost != CMAX_COST_GRADMAG) {  // a focus loss (`ddof` is ignored, as for the gradient magnitude)
+        int rc = cost == CMAX_COST_MEAN_SQUARE ? launch_focus_contrast<CMAX_COST_MEAN_SQUARE>(img, dtype, H, W, omit_boundary, value, G, gscale, rgrid, fgrid, s)
+                 : cost == CMAX_COST_LAPLACIAN ? launch_focus_contrast<CMAX_COST_LAPLACIAN>(img, dtype, H, W, omit_boundary, value, G, gscale, rgrid, fgrid, s)
+                                               : launch_focus_contrast<CMAX_COST_HESSIAN>(img, dtype, H, W, omit_boundary, value, G, gscale, rgrid, fgrid, s);
+        if (rc) return rc;
     } else {
         DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_gm_sums<T>, dim3(rgrid), dim3(256), 0, s, (const T *)img, H, W, omit_boundary, value));
         DISPATCH_DTYPE(dtype, hipLaunchKernelGGL(k_gm_final<T>, dim3(G ? fgrid : 1), dim3(256), 0, s, (const T *)img, H, W, omit_boundary, value, (T *)G, gscale));

@@ -190,7 +190,7 @@ def gaussian_blur3(img, sigma):
 
 # ------------------------------------------------------------------------------------------------
 class _ContrastFn(torch.autograd.Function):
-    """RAW contrast (variance or gradient magnitude) of one [H,W] image."""
+    """RAW contrast (variance, gradient magnitude or a focus loss: _lib.COST_*) of one [H,W] image."""
 
     @staticmethod
     def forward(ctx, img, cost, omit, ddof):

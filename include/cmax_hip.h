@@ -48,6 +48,13 @@ extern "C" {
 /* contrast functions */
 #define CMAX_COST_VARIANCE 0 /* ImageVariance      src/costs/image_variance.py:27-71 */
 #define CMAX_COST_GRADMAG 1  /* GradientMagnitude  src/costs/gradient_magnitude.py:60-76 */
+/* Focus losses (Gallego, Gehrig, Scaramuzza, "Focus is all you need", CVPR 2019): quadratic forms of the image I with 3 x 3
+ * support, I read as zero outside the image; Omega = the image, without its one-pixel border when omit_boundary; n = |Omega|.
+ * No further scale factors; `ddof` of cmax_contrast is ignored, as for the gradient magnitude. */
+#define CMAX_COST_MEAN_SQUARE 2 /* (1/n) sum_Omega I^2 */
+#define CMAX_COST_LAPLACIAN 3   /* (1/n) sum_Omega l^2,  l = I(r-1,c) + I(r+1,c) + I(r,c-1) + I(r,c+1) - 4 I(r,c) */
+#define CMAX_COST_HESSIAN 4     /* (1/n) sum_Omega (h_rr^2 + 2 h_rc^2 + h_cc^2),  h_rr = I(r-1,c) - 2 I(r,c) + I(r+1,c), h_cc likewise
+                                 * along columns, h_rc = (I(r+1,c+1) - I(r+1,c-1) - I(r-1,c+1) + I(r-1,c-1)) / 4 */
 
 /* flow propagation schemes -- src/utils/flow_utils.py */
 #define CMAX_SCHEME_BURGERS 0 /* inviscid_burger_flow_to_voxel_torch  567-639 */
@@ -275,10 +282,13 @@ int cmax_iwe(cmax_handle_t h, int model, const float *motion, int T, int ref_mod
  *   normalized == 1 : term = v_orig / v_k  ("minimize")       (normalized_*.py, multi_focal_*.py)
  *                     or v_k / v_orig      (otherwise)
  * v = raw contrast (cost, omit_boundary) of the (blurred) IWE; v_orig of the un-warped IWE
- * (NOT boundary-cropped for the variance, normalized_image_variance.py:40-41).                */
+ * (NOT boundary-cropped for the variance, normalized_image_variance.py:40-41; cropped like the
+ * warped one for every other cost).  The focus losses CMAX_COST_MEAN_SQUARE / _LAPLACIAN /
+ * _HESSIAN take the place of the gradient magnitude in every form above; they have no raw form
+ * (cmax_objective_has_raw = 0) and are evaluated candidate by candidate by the batched entries. */
 typedef struct {
     int32_t model;        /* CMAX_MODEL_* */
-    int32_t cost;         /* CMAX_COST_* */
+    int32_t cost;         /* CMAX_COST_*: 0 .. 4, anything else is CMAX_EINVAL */
     int32_t normalized;   /* 0 / 1 */
     int32_t minimize;     /* 1 = direction "minimize", 0 = "natural"/"maximize" value */
     int32_t negate;       /* 1 = return -loss (multi_focal_* with direction "maximize") */
