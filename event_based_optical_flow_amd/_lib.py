@@ -134,6 +134,18 @@ class CmaxDescentResult(ctypes.Structure):
     ]
 
 
+class CmaxFlowRegularizer(ctypes.Structure):
+    """Mirror of cmax_flow_regularizer_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("kind", ctypes.c_int32),
+        ("reserved", ctypes.c_int32),
+        ("weight", ctypes.c_double),
+        ("eps", ctypes.c_double),
+        ("s", ctypes.c_double),
+    ]
+
+
 # constants (include/cmax_hip.h)
 F32, F64 = 0, 1
 MODEL_2DOF, MODEL_DENSE, MODEL_VOXEL = 0, 1, 2
@@ -148,6 +160,8 @@ DESCENT_MAX_ITER = 4096
 DESCENT_MAX_STARTS = 64  # CMAX_DESCENT_MAX_STARTS: trajectories per cmax_objective_descend_batch call
 BASIS_MAX_K = 64  # CMAX_BASIS_MAX_K: fields of a flow basis
 BASIS_ADJ_CHUNK = 2048  # CMAX_BASIS_ADJ_CHUNK: elements of [2,H,W] per workgroup of the basis adjoint
+FLOWREG_NONE, FLOWREG_DIVERGENCE, FLOWREG_AREA = 0, 1, 2
+FLOWREG_CODES = {"divergence": FLOWREG_DIVERGENCE, "area": FLOWREG_AREA}
 EINVAL = -1
 ABI_VERSION = 4
 COMM_ID_BYTES = 128
@@ -247,6 +261,10 @@ SIGNATURES = {
     "cmax_basis_plan_create": (c_int, [c_vp, ctypes.POINTER(CmaxBasisObjective), c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_sizeof_flow_regularizer": (c_int, []),
+    "cmax_flow_regularizer": (c_int, [c_vp, c_int, c_int, c_int, ctypes.POINTER(CmaxFlowRegularizer), c_vp, c_vp, c_vp]),
+    "cmax_flow_regularizer_tan": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.POINTER(CmaxFlowRegularizer), c_vp, c_vp]),
+    "cmax_patch_plan_set_flow_regularizer": (c_int, [c_vp, ctypes.POINTER(CmaxFlowRegularizer)]),
     "cmax_patch_search": (c_int, [c_vp, c_int, c_vp, c_int, c_int, c_int, c_vp, c_dbl, c_vp, c_vp, c_vp]),
 }
 
@@ -294,6 +312,8 @@ def load():
             raise RuntimeError("cmax_basis_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_descent() != ctypes.sizeof(CmaxDescent):
             raise RuntimeError("cmax_descent_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_flow_regularizer() != ctypes.sizeof(CmaxFlowRegularizer):
+            raise RuntimeError("cmax_flow_regularizer_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_abi_version() != ABI_VERSION:
             raise RuntimeError(f"libcmax_hip ABI {lib.cmax_abi_version()} != binding ABI {ABI_VERSION}")
         _lib = lib
@@ -319,6 +339,41 @@ def descent_descriptor(method: str = "Adam", n_iter: int = 100, lr: float = 0.05
     d.lr_step = int(n_iter if lr_step is None else lr_step)
     d.lr_decay, d.momentum, d.beta1, d.beta2, d.eps = float(lr_decay), float(momentum), float(betas[0]), float(betas[1]), float(eps)
     return d
+
+
+def flow_regularizer_descriptor(kind, weight: float = 1.0, eps: float = 0.0, s: float = 1.0) -> CmaxFlowRegularizer:
+    """cmax_flow_regularizer_t from a kind name ("divergence" | "area") or code; checked here as the library checks it, so that a bad
+    parameter is refused without a device: eps >= 0, s > 0, everything finite."""
+    import math
+
+    if isinstance(kind, str):
+        if kind not in FLOWREG_CODES:
+            raise ValueError(f"flow regulariser kind {kind!r}: one of {sorted(FLOWREG_CODES)}")
+        code = FLOWREG_CODES[kind]
+    else:
+        code = int(kind)
+        if code not in FLOWREG_CODES.values():
+            raise ValueError(f"flow regulariser kind {kind!r}: {FLOWREG_DIVERGENCE} (divergence) or {FLOWREG_AREA} (area)")
+    weight, eps, s = float(weight), float(eps), float(s)
+    if not (math.isfinite(weight) and math.isfinite(eps) and math.isfinite(s)):
+        raise ValueError(f"flow regulariser: weight, eps and s must be finite (got {weight}, {eps}, {s})")
+    if eps < 0.0:
+        raise ValueError(f"flow regulariser: eps must be >= 0 (got {eps})")
+    if s <= 0.0:
+        raise ValueError(f"flow regulariser: s must be > 0 (got {s})")
+    d = CmaxFlowRegularizer()
+    d.kind, d.reserved, d.weight, d.eps, d.s = code, 0, weight, eps, s
+    return d
+
+
+def flow_regularizer_from_config(cfg) -> CmaxFlowRegularizer:
+    """... from the dictionary the objectives and the solver key `solver.flow_regularizer` take: {"kind", "weight", "eps", "s"}."""
+    if isinstance(cfg, CmaxFlowRegularizer):
+        return cfg
+    unknown = set(cfg) - {"kind", "weight", "eps", "s"}
+    if unknown or "kind" not in cfg:
+        raise ValueError(f"flow_regularizer: a dictionary with 'kind' and optionally 'weight', 'eps', 's' (got keys {sorted(cfg)})")
+    return flow_regularizer_descriptor(cfg["kind"], cfg.get("weight", 1.0), cfg.get("eps", 0.0), cfg.get("s", 1.0))
 
 
 class DescentResult:

@@ -25,6 +25,7 @@
 #include "cmax_buffers.h"
 #include "cmax_common.h"
 #include "cmax_descent.h"
+#include "cmax_flowreg_kernels.h"
 #include "cmax_image_kernels.h"
 #include "cmax_patch_kernels.h"
 
@@ -271,13 +272,14 @@ struct FinalParams {
     int flag_slot;             // index (in doubles) of the run counter in the output: 1 + the plan's nx, whatever this call's nx is
     int ph, pw, tv_crop;       // patch grid of the total-variation term
     double weight[4], tv_weight, gscale;
+    double reg_weight = 0.0;  // flow regulariser (cmax_flowreg_kernels.h): its value is results[8 * 4]; 0 = no such term
 };
 
 // Tail of an evaluation in ONE workgroup (every dependent launch costs ~4.5 us on this chip and the operands are a
 // few hundred numbers): total variation of the patch motion x [2,ph,pw] -- mean |Sobel/8| over 4 channels,
 // TotalVariation.calculate_torch, src/costs/total_variation.py:60-75, 110-126 -- and its sub-gradient, the weighted
 // sum of the contrast terms, and the chain through t_scale:
-//   out[0] = sum_i w_i result_i + w_tv TV(x),   out[1 + j] = gscale * gx[j] + w_tv dTV/dx[j]
+//   out[0] = sum_i w_i result_i + w_tv TV(x) [+ w_reg R(F), the flow regulariser's value in the fifth result slot],   out[1 + j] = gscale * gx[j] + w_tv dTV/dx[j]
 // gx comes as fp64 (gx64) or fp32 (gx32); gscale_dev multiplies gscale (Hessian-vector products).  `out` may be
 // pinned host memory.  ok_dev (scale_later plans): *ok_dev == 0 -> loss and gradient are NaN.
 constexpr int kTailLds = 4096;  // patch-grid values staged in LDS by k_patch_tail (2 x 45 x 45 patches)
@@ -327,6 +329,7 @@ k_patch_tail(FinalParams fp, const double *__restrict__ results, const double *_
         double loss = 0.0;
         for (int i = 0; i < fp.n_terms; ++i) loss += fp.weight[i] * results[8 * i];
         if (fp.with_tv) loss += fp.tv_weight * s_tv;
+        if (fp.reg_weight != 0.0) loss += fp.reg_weight * results[8 * 4];
         out[0] = undefined ? (double)NAN : loss;
     }
     for (int p = threadIdx.x; p < fp.nx; p += blockDim.x) {
@@ -415,6 +418,9 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     cmax::DevBuf<float> basis32;
     cmax::DevBuf<double> basis64, basis_partial;
     std::vector<double> bmax;
+    // cmax_patch_plan_set_flow_regularizer: one more term on F = t (map x), kind CMAX_FLOWREG_NONE = none; the tiles' energies
+    cmax_flow_regularizer_t reg = {};
+    cmax::DevBuf<double> reg_partial;
     // scale_later: D = P x (flow64 then holds u = t D / s), the scalars and the partial sums of the reductions
     cmax::DevBuf<double> dense64, sl, sl_partial;
     cmax::PinnedBuf<double> h_in, h_out;       // pinned staging: x | v | 2 scalars, loss | grad | run counter (the tail kernel writes h_out through its dev())
@@ -541,6 +547,29 @@ int map_adjoint(cmax_patch_plan_s *p, const float *g32, const double *g64, const
     return rc;
 }
 
+bool plan_has_reg(const cmax_patch_plan_s *p) { return p->reg.kind != CMAX_FLOWREG_NONE; }
+int plan_refuse_reg_comm(const cmax_patch_plan_s *p, const char *who) {
+    if (!plan_has_reg(p) || !handle_has_comm(p->handle)) return 0;
+    set_error("%s: the plan's flow regulariser is not built for time-sliced batches (the handle holds a communicator): the term would be counted once per rank", who);
+    return CMAX_EUNSUPPORTED;
+}
+
+// The flow regulariser on F = t (map x) in fp64, before any rounding: its value into the fifth result slot and, with `acc`, weight * dR/dF
+// added into that fp64 [2,H,W] accumulator.  A time-aware plan holds F in flow64 already; any other plan maps x once more, unscaled, and
+// the kernel scales as it stages.
+int plan_flowreg(cmax_patch_plan_s *p, double *acc, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    double scale = 1.0;
+    if (!d.time_aware) {
+        int rc = map_forward64(p, p->x64, p->flow64, s);
+        if (rc) return rc;
+        scale = d.t_scale;
+    }
+    launch_flowreg<double>(p->reg, p->flow64, scale, d.H, d.W, p->reg_partial, p->results + 8 * 4, acc, 1, p->reg.weight, s);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 // x (host) -> fp32 motion of the fused objective: flow [2,H,W] or voxel [T,2,H,W] in pixel per normalised time.
 // Leaves the fp64 flow (scaled) in flow64 and, when time-aware, the fp64 voxel in vox64.
 int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, hipStream_t s) {
@@ -633,7 +662,7 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
     *gx64 = nullptr;
     *gx32 = nullptr;
     *weight_scale = 1.0;
-    if (d.n_terms == 1 && !d.time_aware) {
+    if (d.n_terms == 1 && !d.time_aware && !plan_has_reg(p)) {
         // one term on the dense flow: the adjoint of the interpolation reads the fp32 flow gradient as it is
         // (fp64 accumulation inside), the term's weight is applied by the tail
         int rc = map_adjoint(p, p->grad32, nullptr, gx64, gx32, s);
@@ -660,6 +689,10 @@ int backward_motion(cmax_patch_plan_s *p, const double **gx64, const float **gx3
     } else if (d.time_aware) {  // the sweep leaves dL/dF in bin t0 of the gradient voxel: read it there
         int rc = voxel_construct_adj_f64(p->vox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, s, handle_is_deterministic(p->handle));
         if (rc) return rc;
+        if (plan_has_reg(p)) {  // one more term on F: where the map's adjoint reads
+            rc = plan_flowreg(p, p->gacc64 + (int64_t)d.t0 * p->nflow, s);
+            if (rc) return rc;
+        }
         gflow = p->gacc64 + (int64_t)d.t0 * p->nflow;
     }
     return map_adjoint(p, nullptr, gflow, gx64, gx32, s);
@@ -673,7 +706,8 @@ int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t 
     if (x_src) CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, x_src, (size_t)p->nx * sizeof(double), hipMemcpyHostToDevice, s));
     int rc = forward_motion(p, p->x64, d.t_scale, nullptr, p->motion32, s);
     if (rc) return rc;
-    const bool accumulate = want_grad && !(d.n_terms == 1 && !d.time_aware);
+    const bool reg = plan_has_reg(p);
+    const bool accumulate = want_grad && (reg || !(d.n_terms == 1 && !d.time_aware));  // (the regulariser adds into gacc64)
     for (int i = 0; i < d.n_terms; ++i) {
         rc = plan_objective(p, &d.term[i], p->results + 8 * i, want_grad ? p->grad32 : nullptr, s);
         if (rc) return rc;
@@ -681,6 +715,10 @@ int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t 
             hipLaunchKernelGGL(k_accumulate, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->gacc64);
             CMAX_CHECK_LAUNCH();
         }
+    }
+    if (reg && !(d.time_aware && want_grad)) {  // (a time-aware gradient: behind the adjoint sweep, in backward_motion)
+        rc = plan_flowreg(p, want_grad ? (double *)p->gacc64 : nullptr, s);
+        if (rc) return rc;
     }
     const double *gx64 = nullptr;
     const float *gx32 = nullptr;
@@ -700,6 +738,7 @@ int enqueue_evaluate(cmax_patch_plan_s *p, bool tv, bool want_grad, hipStream_t 
     for (int i = 0; i < 4; ++i) fp.weight[i] = d.weight[i];
     fp.tv_weight = d.tv_weight;
     fp.gscale = d.t_scale * wscale;  // d(flow * t_scale) / d flow
+    fp.reg_weight = reg ? p->reg.weight : 0.0;
     if (d.time_aware && d.scale_later) fp.gscale = 1.0;
     const double *ok_dev = d.time_aware && d.scale_later ? p->sl + 1 : nullptr;
     hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, gx64, gx32, (const double *)nullptr, out, p->seq_dev, ok_dev);
@@ -751,6 +790,10 @@ int enqueue_hvp_time_aware(cmax_patch_plan_s *p, hipStream_t s) {
     // the sweep leaves d(dL/dF) in bin t0 of the tangent gradient voxel: the interpolation adjoint reads it there
     rc = voxel_construct_adj_tan_f64(p->vox64, p->dvox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, p->dgacc64, s, handle_is_deterministic(p->handle));
     if (rc) return rc;
+    if (plan_has_reg(p)) {  // w (grad^2_F R)[dF] for the same tangent, where the map's adjoint reads
+        launch_flowreg_tan<double>(p->reg, p->flow64, p->dflow64, 1.0, 1.0, nullptr, d.H, d.W, p->dgacc64 + (int64_t)d.t0 * p->nflow, 1, p->reg.weight, s);
+        CMAX_CHECK_LAUNCH();
+    }
     const double *gx64 = nullptr;
     const float *gx32 = nullptr;
     rc = map_adjoint(p, nullptr, p->dgacc64 + (int64_t)d.t0 * p->nflow, &gx64, &gx32, s);
@@ -855,7 +898,8 @@ int enqueue_hvp(cmax_patch_plan_s *p, hipStream_t s) {
     // |P v|_inf <= |v|_inf): u = (t_scale * |v|_inf) * tan32, and H is linear in u
     rc = forward_motion(p, p->v64, 1.0, inv_vmax, p->tan32, s);
     if (rc) return rc;
-    const bool accumulate = !(d.n_terms == 1 && !d.time_aware);
+    const bool reg = plan_has_reg(p);
+    const bool accumulate = reg || !(d.n_terms == 1 && !d.time_aware);
     for (int i = 0; i < d.n_terms; ++i) {
         rc = plan_objective_hvp(p, &d.term[i], p->grad32, s);
         if (rc) return rc;
@@ -863,6 +907,13 @@ int enqueue_hvp(cmax_patch_plan_s *p, hipStream_t s) {
             hipLaunchKernelGGL(k_accumulate, dim3(div_up(p->nmotion, 256)), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->gacc64);
             CMAX_CHECK_LAUNCH();
         }
+    }
+    if (reg) {  // w (grad^2_F R)[P v / |v|_inf] at F = t P x, in fp64: scaled by t^2 |v|_inf with the rest
+        rc = map_forward64(p, p->x64, p->flow64, s);
+        if (!rc) rc = map_forward64(p, p->v64, p->dflow64, s);
+        if (rc) return rc;
+        launch_flowreg_tan<double>(p->reg, p->flow64, p->dflow64, d.t_scale, 1.0, inv_vmax, d.H, d.W, p->gacc64, 1, p->reg.weight, s);
+        CMAX_CHECK_LAUNCH();
     }
     const double *gx64 = nullptr;
     const float *gx32 = nullptr;
@@ -1025,7 +1076,7 @@ static int plan_allocate(cmax_handle_t h, const cmax_patch_objective_t &d, int n
         if (!rc) rc = p->sl_partial.reserve(nullptr, kSlSlots * kSlBlocks, nullptr);
     }
     if (!rc) rc = p->gx64.reserve(nullptr, p->nx, nullptr);
-    if (!rc) rc = p->results.reserve(nullptr, 8 * 4, nullptr);
+    if (!rc) rc = p->results.reserve(nullptr, 8 * 5, nullptr);  // four terms and the flow regulariser's value
     if (!rc) rc = p->motion32.reserve(nullptr, (p->exact ? 2 : 1) * p->nmotion, nullptr);
     if (!rc) rc = p->grad32.reserve(nullptr, p->nmotion, nullptr);
     if (!rc) rc = p->tan32.reserve(nullptr, p->nmotion, nullptr);
@@ -1157,6 +1208,66 @@ int cmax_patch_plan_set_t_scale(cmax_patch_plan_t p, double t_scale) {
     return 0;
 }
 
+int cmax_sizeof_flow_regularizer(void) { return (int)sizeof(cmax_flow_regularizer_t); }
+
+int cmax_patch_plan_set_flow_regularizer(cmax_patch_plan_t p, const cmax_flow_regularizer_t *desc) {
+    CMAX_REQUIRE(p != nullptr, "patch_plan_set_flow_regularizer: null plan");
+    cmax_flow_regularizer_t r = {};
+    if (desc && desc->kind != CMAX_FLOWREG_NONE) {
+        r = *desc;
+        CMAX_REQUIRE(flowreg_desc_ok(r), "patch_plan_set_flow_regularizer: kind (CMAX_FLOWREG_DIVERGENCE or _AREA), eps >= 0 and s > 0, all finite");
+        CMAX_REQUIRE(r.weight >= -1.7e308 && r.weight <= 1.7e308, "patch_plan_set_flow_regularizer: weight must be finite");
+        CMAX_REQUIRE(p->d.H >= 3 && p->d.W >= 3, "patch_plan_set_flow_regularizer: the sensor must be at least 3 x 3");
+        if (p->d.time_aware && p->d.scale_later) {
+            set_error("patch_plan_set_flow_regularizer: not built for a scale_later plan (its map is rescaled by a maximum: F is not t_scale * map x)");
+            return CMAX_EINVAL;
+        }
+        if (handle_has_comm(p->handle)) {
+            set_error("patch_plan_set_flow_regularizer: not built for time-sliced batches (the handle holds a communicator): the term would be counted once per rank");
+            return CMAX_EUNSUPPORTED;
+        }
+        r.reserved = 0;
+        int rc = p->reg_partial.reserve(nullptr, flowreg_tiles(p->d.H, p->d.W), nullptr);
+        if (rc) {
+            set_error("patch_plan_set_flow_regularizer: allocation failed");
+            return rc;
+        }
+    }
+    p->reg = r;
+    drop_graphs(p);  // the term's launches and its parameters are baked into captured sequences
+    p->eager_calls = 0;
+    return 0;
+}
+
+int cmax_flow_regularizer(const void *F, int dtype, int H, int W, const cmax_flow_regularizer_t *desc, double *value_dev, void *grad, cmax_stream_t stream) {
+    CMAX_REQUIRE(F && desc && value_dev, "flow_regularizer: null pointer");
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "flow_regularizer: dtype");
+    CMAX_REQUIRE(H >= 3 && W >= 3, "flow_regularizer: H and W must be at least 3");
+    CMAX_REQUIRE(flowreg_desc_ok(*desc), "flow_regularizer: kind (CMAX_FLOWREG_DIVERGENCE or _AREA), eps >= 0 and s > 0, all finite");
+    hipStream_t s = (hipStream_t)stream;
+    // the tiles' energies: a stream-ordered temporary keeps the operator stateless (as the chunk sums of cmax_basis_to_dense)
+    double *partial = nullptr;
+    CMAX_CHECK_HIP(hipMallocAsync((void **)&partial, (size_t)flowreg_tiles(H, W) * sizeof(double), s));
+    if (dtype == CMAX_F32) launch_flowreg<float>(*desc, (const float *)F, 1.0, H, W, partial, value_dev, grad, 0, 1.0, s);
+    else launch_flowreg<double>(*desc, (const double *)F, 1.0, H, W, partial, value_dev, grad, 0, 1.0, s);
+    const hipError_t e = hipGetLastError();
+    CMAX_CHECK_HIP(hipFreeAsync(partial, s));
+    CMAX_CHECK_HIP(e);
+    return 0;
+}
+
+int cmax_flow_regularizer_tan(const void *F, const void *dF, int dtype, int H, int W, const cmax_flow_regularizer_t *desc, void *hv, cmax_stream_t stream) {
+    CMAX_REQUIRE(F && dF && desc && hv, "flow_regularizer_tan: null pointer");
+    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "flow_regularizer_tan: dtype");
+    CMAX_REQUIRE(H >= 3 && W >= 3, "flow_regularizer_tan: H and W must be at least 3");
+    CMAX_REQUIRE(flowreg_desc_ok(*desc), "flow_regularizer_tan: kind (CMAX_FLOWREG_DIVERGENCE or _AREA), eps >= 0 and s > 0, all finite");
+    hipStream_t s = (hipStream_t)stream;
+    if (dtype == CMAX_F32) launch_flowreg_tan<float>(*desc, (const float *)F, (const float *)dF, 1.0, 1.0, nullptr, H, W, hv, 0, 1.0, s);
+    else launch_flowreg_tan<double>(*desc, (const double *)F, (const double *)dF, 1.0, 1.0, nullptr, H, W, hv, 0, 1.0, s);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 int cmax_patch_plan_info(cmax_patch_plan_t p, int *n_graphs, int *graph_replay_enabled) {
     CMAX_REQUIRE(p && n_graphs && graph_replay_enabled, "patch_plan_info");
     *n_graphs = (int)p->graphs.size();
@@ -1180,6 +1291,7 @@ int cmax_patch_plan_evaluate(cmax_patch_plan_t p, const double *x_host, int with
         set_error("patch_plan_evaluate: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
         return CMAX_EUNSUPPORTED;
     }
+    if (int rc = plan_refuse_reg_comm(p, "patch_plan_evaluate")) return rc;
     const bool tv = with_tv && p->d.tv_weight != 0.0;
     std::memcpy(p->h_in, x_host, (size_t)p->nx * sizeof(double));
     const int kind = (tv ? 1 : 0) | (grad_host ? 2 : 0);
@@ -1241,7 +1353,12 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
         set_error("patch_plan_hvp: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
         return CMAX_EUNSUPPORTED;
     }
+    if (int rc = plan_refuse_reg_comm(p, "patch_plan_hvp")) return rc;
     const cmax_patch_objective_t &d = p->d;
+    if (plan_has_reg(p) && !d.time_aware) {  // the regulariser's fp64 tangent field, on first use
+        int rc = p->dflow64.reserve(nullptr, p->nflow, (hipStream_t)stream);
+        if (rc) return rc;
+    }
     if (d.time_aware) {  // second-order buffers of the voxel chain, on first use
         hipStream_t s = (hipStream_t)stream;
         int rc = p->dflow64.reserve(nullptr, p->nflow, s);

@@ -6,6 +6,7 @@ torch's current stream and wraps forward/backward in a torch.autograd.Function s
 (src/solver/scipy_autograd/torch_wrapper.py:40) -- flows through the HIP kernels.
 PyTorch is used for device memory, streams and the autograd tape only.
 """
+import ctypes
 from typing import Optional, Tuple, Union
 
 import torch
@@ -445,6 +446,63 @@ def field_max(x):
     gradient evenly over the elements equal to it (`scale = dense_flow.max()`, src/solver/patch_contrast_pyramid.py:489-490)."""
     _lib.require_gpu()
     return _FieldMaxFn.apply(_cuda(x, "x"))
+
+
+class _FlowRegGradFn(torch.autograd.Function):
+    """flow -> dR/dflow (handed over by the launch that took the value); its backward is the exact product (grad^2 R)[v] -- the
+    Hessian is symmetric -- from cmax_flow_regularizer_tan."""
+
+    @staticmethod
+    def forward(ctx, flow, grad, desc):
+        ctx.save_for_backward(flow)
+        ctx.desc = desc
+        return grad.clone()
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, v):
+        (flow,) = ctx.saved_tensors
+        _, H, W = flow.shape
+        v = v.to(flow.dtype).contiguous()
+        hv = torch.empty_like(flow)
+        check(_lib.load().cmax_flow_regularizer_tan(_ptr(flow), _ptr(v), _code(flow), H, W, ctypes.byref(ctx.desc), _ptr(hv), _stream()))
+        return hv, None, None
+
+
+class _FlowRegFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, flow, desc):
+        _, H, W = flow.shape
+        value = torch.empty(1, dtype=torch.float64, device=flow.device)
+        grad = torch.empty_like(flow)
+        check(_lib.load().cmax_flow_regularizer(_ptr(flow), _code(flow), H, W, ctypes.byref(desc), _ptr(value), _ptr(grad), _stream()))
+        ctx.save_for_backward(flow, grad)
+        ctx.desc = desc
+        return value[0].to(flow.dtype)
+
+    @staticmethod
+    def backward(ctx, gout):
+        flow, grad = ctx.saved_tensors
+        return gout * _FlowRegGradFn.apply(flow, grad, ctx.desc), None
+
+
+def flow_regularizer(flow, kind, eps: float = 0.0, s: float = 1.0):
+    """Event-collapse regulariser of a displacement field `flow` [2,H,W] (float32 or float64; flow[0] along rows, flow[1] along
+    columns; pixel over the batch), as a 0-dim tensor: kind "divergence", mean over the interior of psi(dF0/dr + dF1/dc), or "area",
+    mean of [psi(A(+s) - 1) + psi(A(-s) - 1)] / 2 with A(sigma) = det(I - sigma grad F) the area ratio of a pixel cell under the warp
+    x' = x - sigma F; central differences, psi(u) = sqrt(u^2 + eps^2) - eps (include/cmax_hip.h has the full statement).  All
+    arithmetic is float64 on the device, the value a fixed-order sum (bit-repeatable).  Differentiable twice: the backward is the
+    hand-written gradient, and ITS backward the exact second-order product, so torch.autograd.grad(..., create_graph=True) and
+    torch.autograd.functional.vhp work through it.  The reference has no counterpart."""
+    desc = _lib.flow_regularizer_descriptor(kind, 1.0, eps, s)
+    if not isinstance(flow, torch.Tensor) or flow.dim() != 3 or flow.shape[0] != 2:
+        raise ValueError(f"flow must be a [2, H, W] tensor, got {tuple(getattr(flow, 'shape', ()))}")
+    if flow.shape[1] < 3 or flow.shape[2] < 3:
+        raise ValueError(f"flow regulariser: H and W must be at least 3 (the interior is empty), got {tuple(flow.shape[1:])}")
+    if flow.dtype not in (torch.float32, torch.float64):
+        raise TypeError(f"libcmax_hip supports float32/float64 tensors, got {flow.dtype}")
+    _lib.require_gpu()
+    return _FlowRegFn.apply(_cuda(flow, "flow"), desc)
 
 
 def gaussian_filter(img, sigma):

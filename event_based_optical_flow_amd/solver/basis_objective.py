@@ -26,13 +26,14 @@ class FlowBasisObjective:
     def __init__(self, handle: CMaxHandle, t_scale: float, basis_or_model, cost="hybrid",
                  cost_with_weight: Optional[Dict[str, Union[float, str]]] = None, blur_sigma: float = 1.0, time_aware: bool = False,
                  time_bin: int = 10, flow_interpolation: str = "burgers", t0_flow_location: str = "middle", omit_boundary: bool = True,
-                 exact_flow: bool = False, calib=None):
+                 exact_flow: bool = False, calib=None, flow_regularizer=None):
         """basis_or_model: a model name of utils.flow_utils.flow_basis ("translation", "similarity", "affine", "rotation" -- the
         last with calib = (fx, fy, cx, cy)), or a basis [K,2,H,W] (numpy array or tensor, float32 or float64, 1 <= K <= 64) on the
         handle's sensor; it is kept on the device in its dtype (model names: float64).
         The other arguments are PatchFlowObjective's.  There is no patch grid, hence no total_variation term and no `scale_later`.
         Numeric hybrid weights of fused costs run on the native plan; "inv" weights and costs without a fused kernel keep the
-        autograd-chained path of `__call__` (no exact product there: TorchWrapper takes a difference quotient of the gradient)."""
+        autograd-chained path of `__call__` (no exact product there: TorchWrapper takes a difference quotient of the gradient).
+        flow_regularizer: {"kind": "divergence" | "area", "weight", "eps", "s"} or None -- `set_flow_regularizer`."""
         self.handle = handle
         self.t_scale = float(t_scale)
         if isinstance(basis_or_model, str):
@@ -64,6 +65,9 @@ class FlowBasisObjective:
         self.auto_slabs = True
         self._plan = None
         self._build_native_plan()
+        self.flow_reg = None
+        if flow_regularizer is not None:
+            self.set_flow_regularizer(flow_regularizer)
 
     # -- one-call native path (cmax_basis_plan_create + cmax_patch_plan_*, csrc/cmax_solver.hip) ----------------------
     def _descriptor(self):
@@ -114,6 +118,22 @@ class FlowBasisObjective:
         self.t_scale = float(t_scale)
         if self._plan is not None:
             _lib.check(_lib.load().cmax_patch_plan_set_t_scale(self._plan, self.t_scale))
+
+    def set_flow_regularizer(self, flow_regularizer):
+        """One more term, weight * functional.flow_regularizer(F), on the displacement field F = t_scale * basis_to_dense(theta): a model
+        with a zoom (similarity, affine, a free basis) has a contrast optimum that is not the motion -- every event shrunk onto a point
+        -- and this penalty on the divergence of the flow or on the change of area under the warp is the remedy (include/cmax_hip.h).
+        A dictionary {"kind": "divergence" | "area", "weight", "eps", "s"}; None removes the term.  `weight` carries the sign of the
+        cost direction (a minimised loss: positive).  As PatchFlowObjective.set_flow_regularizer."""
+        desc = None if flow_regularizer is None else _lib.flow_regularizer_from_config(flow_regularizer)
+        if self._plan is not None:
+            _lib.check(_lib.load().cmax_patch_plan_set_flow_regularizer(self._plan, None if desc is None else ctypes.byref(desc)))
+        self.flow_reg = desc
+
+    def flow_field(self, theta: torch.Tensor) -> torch.Tensor:
+        """[K] parameters -> the displacement field [2,H,W] over the batch, t_scale * basis_to_dense(theta): what the flow regulariser
+        acts on."""
+        return F.basis_to_dense(theta.reshape(-1), self.basis) * self.t_scale
 
     def native_plan_info(self):
         """(number of captured hipGraphs, graph replay enabled) of the native plan."""
@@ -204,4 +224,8 @@ class FlowBasisObjective:
         """The autograd-chained path: basis_to_dense -> ContrastObjective, one Python-level call per stage."""
         theta = theta.to(self.handle.device)
         self.ensure_time_slabs(theta)
-        return self.contrast(self.dense_flow(theta))
+        loss = self.contrast(self.dense_flow(theta))
+        if self.flow_reg is not None:
+            r = self.flow_reg
+            loss = loss + r.weight * F.flow_regularizer(self.flow_field(theta), r.kind, r.eps, r.s)
+        return loss

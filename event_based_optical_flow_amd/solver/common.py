@@ -53,6 +53,22 @@ def global_best_refine(slv_config: dict) -> Optional[dict]:
     return dict(refine)
 
 
+def flow_regularizer_config(slv_config: dict, scale_later: bool = False) -> Optional[dict]:
+    """The optional solver key solver.flow_regularizer: {kind: divergence | area, weight, eps, s} (not in the reference; the remedy
+    for event collapse, PatchFlowObjective.set_flow_regularizer): None when absent -- the solver then makes not one call more.
+    Checked here, at construction: the parameters, and `scale_later`, whose flow is rescaled by its maximum."""
+    cfg = slv_config.get("flow_regularizer")
+    if cfg is None:
+        return None
+    from .. import _lib
+
+    _lib.flow_regularizer_from_config(cfg)  # raises on unknown keys / kinds and bad parameters
+    if scale_later:
+        raise NotImplementedError("solver.flow_regularizer is not built with solver.scale_later: that flow is divided by its maximum before "
+                                  "the propagation and multiplied by it afterwards, so the regularised field would not be the one the events are warped by")
+    return dict(cfg)
+
+
 def whole_image_guess(handle: CMaxHandle, t_scale: float, refine: Optional[dict] = None, **search_cost):
     """patch.initialize: "global-best" (src/solver/patch_contrast_base.py:164-187): the best of the 30 x 30 translations
     np.arange(-150, 150, 10)^2 for the WHOLE batch under the solver's own cost, warped as one 2-DoF motion (`motion * t_scale`,

@@ -19,7 +19,7 @@ import numpy as np
 
 from ..cmax import CMaxHandle
 from . import scipy_autograd
-from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, global_best_refine, one_patch_guess,
+from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, flow_regularizer_config, global_best_refine, one_patch_guess,
                      run_descent, whole_image_guess)
 from .patch_objective import PatchFlowObjective, patch_pad
 
@@ -71,6 +71,7 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
             self.time_bin, self.flow_interpolation, self.t0_flow_location = 0, "burgers", "middle"
         self.scale_later = False
         self.exact_flow = _check_key_and_bool(solver_config, "exact_flow")  # optional, as in the pyramid solver
+        self.flow_regularizer = flow_regularizer_config(solver_config)  # optional, as in the pyramid solver
         # one grid at one scale (patch_contrast_base.py:36-49, patch_contrast_mixed.py:45-54)
         patch = solver_config["patch"]
         if patch.get("initialize") == "optuna-sampling":
@@ -180,7 +181,8 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
                 handle, t_scale, self.patch_image_size, self.patch_size, self.sliding_window, self.patch_shift,
                 cost=self.cost_name, cost_with_weight=self.cost_weight, blur_sigma=self.iwe_config["blur_sigma"],
                 time_aware=self.is_time_aware, time_bin=self.time_bin, flow_interpolation=self.flow_interpolation,
-                t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=False, exact_flow=self.exact_flow)
+                t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=False, exact_flow=self.exact_flow,
+                flow_regularizer=self.flow_regularizer)
         else:
             self._objective.set_t_scale(t_scale)
         return self._objective

@@ -52,7 +52,7 @@ class PatchFlowObjective:
                  patch_shift=(0, 0), cost="hybrid", cost_with_weight: Optional[Dict[str, Union[float, str]]] = None,
                  blur_sigma: float = 1.0, time_aware: bool = False, time_bin: int = 10,
                  flow_interpolation: str = "burgers", t0_flow_location: str = "middle", filter_type: str = "bilinear", sliced=None,
-                 scale_later: bool = False, omit_boundary: bool = True, exact_flow: bool = False):
+                 scale_later: bool = False, omit_boundary: bool = True, exact_flow: bool = False, flow_regularizer=None):
         """omit_boundary: the reference's `arg["omit_boundary"]`, for the contrast terms and the total variation alike.
         sliced: a distributed.TimeSlicedObjective around `handle` when the batch is time-sliced over ranks.  With the library's own
         communicator on the handle (RCCL) the native plan evaluates the whole batch (cmax_patch_plan_* exchange images + 2 n_patch
@@ -66,7 +66,8 @@ class PatchFlowObjective:
         plan (cmax_patch_objective_t::filter_type) and the autograd-chained path (functional.patch_to_dense) alike.
         exact_flow: the fused terms receive the float64 dense flow / voxel this objective computes from x instead of its fp32 rounding
         (ContrastObjective(exact_flow=True); the native plan's terms carry motion_dtype = CMAX_F64 and the plan hands over the
-        fp64 field it holds): the cells of events on a cell border are then the ones the reference's float64 solver takes."""
+        fp64 field it holds): the cells of events on a cell border are then the ones the reference's float64 solver takes.
+        flow_regularizer: {"kind": "divergence" | "area", "weight", "eps", "s"} or None -- `set_flow_regularizer`."""
         if filter_type not in F.FILTER_CODES:
             raise ValueError(f"patch filter_type {filter_type!r}: 'bilinear' or 'nearest' (patch_contrast_base.py:492-495)")
         self.filter_type = filter_type
@@ -94,6 +95,9 @@ class PatchFlowObjective:
         self.sliced = sliced if (sliced is not None and sliced.world_size > 1 and not sliced.collectives.startswith("in-library")) else None
         if self.sliced is None:
             self._build_native_plan()
+        self.flow_reg = None
+        if flow_regularizer is not None:
+            self.set_flow_regularizer(flow_regularizer)
 
     # -- one-call native path (cmax_patch_plan_*, csrc/cmax_solver.hip) ---------------------------------
     def _build_native_plan(self):
@@ -147,6 +151,33 @@ class PatchFlowObjective:
         self.t_scale = float(t_scale)
         if self._plan is not None:
             _lib.check(_lib.load().cmax_patch_plan_set_t_scale(self._plan, self.t_scale))
+
+    def set_flow_regularizer(self, flow_regularizer):
+        """One more term, weight * functional.flow_regularizer(F), on the displacement field F = t_scale * patch_to_dense(x) the fused
+        terms warp by (the t0 field of a time-aware objective): the remedy for event collapse, a penalty on the divergence of the flow
+        or on the change of area under the warp (include/cmax_hip.h).  A dictionary {"kind": "divergence" | "area", "weight", "eps",
+        "s"}; None removes the term.  `weight` carries the sign of the cost direction (a minimised loss: positive).  The native plan
+        carries it through value, gradient, exact product and descent (cmax_patch_plan_set_flow_regularizer); `__call__` adds the same
+        number on the autograd tape.  Not built for `scale_later` (that map is rescaled by a maximum) nor for time-sliced batches."""
+        desc = None if flow_regularizer is None else _lib.flow_regularizer_from_config(flow_regularizer)
+        if desc is not None and self.scale_later:
+            raise ValueError("flow_regularizer is not built for scale_later: that flow is rescaled by its maximum before the propagation, "
+                             "F is not t_scale * patch_to_dense(x)")
+        if desc is not None and self.sliced is not None:
+            raise NotImplementedError("flow_regularizer is not built for time-sliced batches")
+        if self._plan is not None:
+            _lib.check(_lib.load().cmax_patch_plan_set_flow_regularizer(self._plan, None if desc is None else ctypes.byref(desc)))
+        self.flow_reg = desc
+
+    def flow_field(self, x: torch.Tensor) -> torch.Tensor:
+        """[2*ph*pw] patch motion -> the displacement field [2,H,W] over the batch, t_scale * patch_to_dense(x): what the flow
+        regulariser acts on."""
+        motion = x.reshape((2,) + self.patch_image_size)
+        return F.patch_to_dense(motion, self.handle.image_size, self.sliding_window, self.pad, self.filter_type) * self.t_scale
+
+    def _flow_reg_value(self, x: torch.Tensor):
+        r = self.flow_reg
+        return r.weight * F.flow_regularizer(self.flow_field(x), r.kind, r.eps, r.s)
 
     def native_plan_info(self):
         """(number of captured hipGraphs, graph replay enabled) of the native plan."""
@@ -265,6 +296,8 @@ class PatchFlowObjective:
             else:
                 value = _FusedFn.apply(self.dense_flow(xt), self.handle, desc, self.exact_flow)
             loss = loss + combine(weight, value)
+        if self.flow_reg is not None:
+            loss = loss + self._flow_reg_value(xt)
         (g,) = torch.autograd.grad(loss, xt)
         return g
 
@@ -303,6 +336,10 @@ class PatchFlowObjective:
         dense = F.patch_to_dense(x.detach().reshape(shape), size, sw, pad, self.filter_type) * self.t_scale
         vdense = F.patch_to_dense(v.detach().reshape(shape).to(x.dtype), size, sw, pad, self.filter_type) * self.t_scale
         hflow = self.contrast.hvp(dense, vdense).to(x.dtype)  # [2,H,W]
+        if self.flow_reg is not None:  # its exact product on the same field and tangent (functional.flow_regularizer is differentiable twice)
+            r, field = self.flow_reg, dense.detach().clone().requires_grad_()
+            (g,) = torch.autograd.grad(F.flow_regularizer(field, r.kind, r.eps, r.s), field, create_graph=True)
+            hflow = hflow + r.weight * torch.autograd.grad(g, field, grad_outputs=vdense.to(field.dtype).contiguous())[0]
         # adjoint of the (linear) interpolation: the backward of patch_to_dense applied to hflow
         probe = x.detach().reshape(shape).clone().requires_grad_()
         out = F.patch_to_dense(probe, size, sw, pad, self.filter_type)
@@ -314,7 +351,10 @@ class PatchFlowObjective:
         self.ensure_time_slabs(x)
         if self.sliced is not None:
             return self._call_sliced(x)
-        return self.contrast(self.dense_flow(x), x.reshape((2,) + self.patch_image_size))
+        loss = self.contrast(self.dense_flow(x), x.reshape((2,) + self.patch_image_size))
+        if self.flow_reg is not None:
+            loss = loss + self._flow_reg_value(x)
+        return loss
 
     def _call_sliced(self, x: torch.Tensor) -> torch.Tensor:
         """The objective on a time-sliced batch with torch.distributed collectives: identical loss and gradient on every rank."""

@@ -29,7 +29,7 @@ import scipy.ndimage as ndi
 from ..cmax import CMaxHandle
 from . import scipy_autograd
 from .patch_objective import PatchFlowObjective
-from .common import (DESCENT_OPTIMIZERS, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, calculate_flow_error_numpy,  # noqa: F401
+from .common import (DESCENT_OPTIMIZERS, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, flow_regularizer_config, calculate_flow_error_numpy,  # noqa: F401
                      check_opt_method, global_best_refine, one_patch_guess, run_descent, whole_image_guess)
 
 logger = logging.getLogger(__name__)
@@ -93,6 +93,7 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
         # optional, absent = False: the fused terms see the float64 flow / voxel this solver optimises in, not its fp32 rounding
         # (PatchFlowObjective(exact_flow=True): the border cells of the reference's float64 arithmetic)
         self.exact_flow = _check_key_and_bool(solver_config, "exact_flow")
+        self.flow_regularizer = flow_regularizer_config(solver_config, self.scale_later)  # optional, absent = None: no such term
         # pyramid (patch_contrast_pyramid.py:50-61)
         patch = solver_config["patch"]
         self.filter_type = patch["filter_type"]
@@ -152,7 +153,7 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
                     cost=self.cost_name, cost_with_weight=self.cost_weight, blur_sigma=self.iwe_config["blur_sigma"],
                     time_aware=self.is_time_aware, time_bin=self.time_bin, flow_interpolation=self.flow_interpolation,
                     t0_flow_location=self.t0_flow_location, filter_type=self.filter_type, scale_later=self.scale_later,
-                    exact_flow=self.exact_flow)
+                    exact_flow=self.exact_flow, flow_regularizer=self.flow_regularizer)
             else:
                 objective.set_t_scale(t_scale)
             if self.previous_frame_best_estimation is not None and s == self.coarest_scale:

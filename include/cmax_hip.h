@@ -832,6 +832,56 @@ int cmax_field_max(const void *x, int dtype, int64_t n, double *out, cmax_stream
 int cmax_field_max_adj(const void *x, int dtype, int64_t n, const double *out, const double *gout, void *gx, cmax_stream_t stream);
 
 /* =============================================================================================
+ * Event-collapse regularisers on the dense flow.  A contrast objective on a motion model that contains a zoom (similarity, affine,
+ * a free basis, a patch grid) has a global optimum that is not the motion: shrinking every event onto a line or a point maximises
+ * every focus measure (Shiba, Aoki, Gallego, "Event Collapse in Contrast Maximization Frameworks", Sensors 2022).  Their remedy is a
+ * penalty on the deformation of the warp; this is its form on the flow FIELD (the per-event, IWE-weighted form is not built).  The
+ * reference has no counterpart: these formulas are the contract.
+ *   F [2,H,W]: displacement field in pixel over the batch, F[0] along rows, F[1] along columns.  The warp is x' = x - dt F[src]; its
+ *   Jacobian for a time offset s is I - s grad F.
+ *   Omega: 1 <= r <= H-2, 1 <= c <= W-2;  n = (H-2)(W-2);  H, W >= 3 (CMAX_EINVAL otherwise).
+ *   On Omega, central differences:  a = (F0(r+1,c) - F0(r-1,c))/2   b = (F0(r,c+1) - F0(r,c-1))/2
+ *                                   c = (F1(r+1,c) - F1(r-1,c))/2   d = (F1(r,c+1) - F1(r,c-1))/2
+ *   psi_eps(u) = sqrt(u^2 + eps^2) - eps, eps >= 0.  eps = 0: |u| with psi'(0) = 0 and psi'' = 0; otherwise
+ *   psi' = u / sqrt(u^2 + eps^2), psi'' = eps^2 / (u^2 + eps^2)^(3/2).
+ *   CMAX_FLOWREG_DIVERGENCE  R = (1/n)  sum_Omega psi(a + d)
+ *   CMAX_FLOWREG_AREA        R = (1/2n) sum_Omega [psi(A(+s) - 1) + psi(A(-s) - 1)],
+ *                            A(sigma) = det(I - sigma grad F) = 1 - sigma (a + d) + sigma^2 (a d - b c);  s > 0 is the caller's (1: the
+ *                            area ratio of a pixel cell warped across the whole batch, in both directions)
+ *   Gradient w.r.t. F: the transposed central difference of dR/d(a,b,c,d), which are zero outside Omega -- non-zero on the whole image.
+ *   Product (grad^2 R)[dF]: psi'' acts on the directional derivative of u, psi' on the constant Hessian of A (d2A/da dd = sigma^2,
+ *   d2A/db dc = -sigma^2): the area product is non-zero even at eps = 0, the divergence product at eps = 0 is exactly zero.
+ * All arithmetic is fp64 whatever the field's dtype is; the value is a fixed-order sum without atomics (the same field gives the same
+ * bits).  cmax_flow_regularizer_t is a new struct: the ABI version is unchanged.
+ * ============================================================================================= */
+#define CMAX_FLOWREG_NONE 0
+#define CMAX_FLOWREG_DIVERGENCE 1
+#define CMAX_FLOWREG_AREA 2
+typedef struct {
+    int32_t kind;      /* CMAX_FLOWREG_* */
+    int32_t reserved;  /* 0 */
+    double weight;     /* the plan's weight of the term (sign of the cost direction included); ignored by the leaf operators */
+    double eps;        /* >= 0 */
+    double s;          /* > 0 (area; checked for both kinds) */
+} cmax_flow_regularizer_t;
+int cmax_sizeof_flow_regularizer(void);
+/* Leaf operators.  F, dF: device fp32 / fp64 [2,H,W] (`dtype`); value_dev: device double[1]; grad / hv: device [2,H,W] in `dtype`
+ * (grad may be NULL: value only).  CMAX_EINVAL for H or W < 3, eps < 0, s <= 0, a non-finite parameter or an unknown kind.
+ * Asynchronous on `stream`.                                                                                                    */
+int cmax_flow_regularizer(const void *F, int dtype, int H, int W, const cmax_flow_regularizer_t *desc_host, double *value_dev,
+                          void *grad_or_null, cmax_stream_t stream);
+int cmax_flow_regularizer_tan(const void *F, const void *dF, int dtype, int H, int W, const cmax_flow_regularizer_t *desc_host, void *hv,
+                              cmax_stream_t stream);
+/* One more term of a patch plan or a basis plan: loss += weight * R(F) with F = t_scale * (map x), the field the fused terms warp by
+ * (the t0 field of a time-aware plan), evaluated in fp64 on the plan's fp64 field before it is rounded for the event kernels.
+ * cmax_patch_plan_evaluate, _hvp (the exact second-order term) and _descend carry it.  desc_host NULL or kind CMAX_FLOWREG_NONE removes
+ * the term: such a plan enqueues exactly the launches of a plan on which this was never called.  Captured launch sequences are dropped.
+ * Refused: bad parameters as above, a non-finite weight, a sensor smaller than 3 x 3, a scale_later plan -- its map is rescaled by a
+ * maximum -- (CMAX_EINVAL); a handle that holds a communicator, where the term would be counted once per rank (CMAX_EUNSUPPORTED;
+ * evaluate, hvp and descend refuse likewise if the communicator arrives later).                                                  */
+int cmax_patch_plan_set_flow_regularizer(cmax_patch_plan_t plan, const cmax_flow_regularizer_t *desc_host_or_null);
+
+/* =============================================================================================
  * Per-patch translation search: the re-initialisation the pyramid solver runs at every scale above
  * the coarsest.  Replaces the trial loop of initialize_guess_from_optuna_sampling / objective_initial /
  * calculate_cost_for_small_patch (src/solver/patch_contrast_pyramid.py:320-414): per patch, the events
