@@ -134,6 +134,35 @@ class CmaxDescentResult(ctypes.Structure):
     ]
 
 
+class CmaxLbfgs(ctypes.Structure):
+    """Mirror of cmax_lbfgs_t (include/cmax_hip.h): every value explicit, the defaults are filled by `lbfgs_descriptor`."""
+
+    _fields_ = [
+        ("n_eval", ctypes.c_int32),
+        ("history", ctypes.c_int32),
+        ("max_ls", ctypes.c_int32),
+        ("c1", ctypes.c_double),
+        ("shrink", ctypes.c_double),
+        ("curv_eps", ctypes.c_double),
+        ("gtol", ctypes.c_double),
+        ("step0", ctypes.c_double),
+        ("max_move", ctypes.c_double),
+    ]
+
+
+class CmaxLbfgsResult(ctypes.Structure):
+    """Mirror of cmax_lbfgs_result_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("final_loss", ctypes.c_double),
+        ("gnorm_inf", ctypes.c_double),
+        ("last_alpha", ctypes.c_double),
+        ("n_iter", ctypes.c_int32),
+        ("n_eval_used", ctypes.c_int32),
+        ("status", ctypes.c_int32),
+    ]
+
+
 class CmaxFlowRegularizer(ctypes.Structure):
     """Mirror of cmax_flow_regularizer_t (include/cmax_hip.h)."""
 
@@ -158,6 +187,10 @@ OPT_SGD, OPT_ADAM = 0, 1
 OPT_CODES = {"SGD": OPT_SGD, "Adam": OPT_ADAM}
 DESCENT_MAX_ITER = 4096
 DESCENT_MAX_STARTS = 64  # CMAX_DESCENT_MAX_STARTS: trajectories per cmax_objective_descend_batch call
+LBFGS_MAX_HISTORY = 16  # CMAX_LBFGS_MAX_HISTORY
+LBFGS_STATUS = {0: "BUDGET", 1: "CONVERGED", 2: "LINESEARCH", 3: "BOX", 4: "NONFINITE_START"}  # CMAX_LBFGS_*
+LBFGS_CODES = {0: "start", 1: "accepted", 2: "rejected", 3: "reset", 4: "idle"}  # CMAX_LBFGS_CODE_*
+LBFGS_FIXED_DOUBLES = 1112  # control block and Gram matrix at the head of the state (csrc/cmax_lbfgs.h)
 BASIS_MAX_K = 64  # CMAX_BASIS_MAX_K: fields of a flow basis
 BASIS_ADJ_CHUNK = 2048  # CMAX_BASIS_ADJ_CHUNK: elements of [2,H,W] per workgroup of the basis adjoint
 FLOWREG_NONE, FLOWREG_DIVERGENCE, FLOWREG_AREA = 0, 1, 2
@@ -256,6 +289,10 @@ SIGNATURES = {
     "cmax_objective_descend": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, ctypes.POINTER(CmaxDescent), ctypes.POINTER(CmaxDescentResult),
                                        c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_objective_descend_batch": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, c_int, ctypes.POINTER(CmaxDescent), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_sizeof_lbfgs": (c_int, []),
+    "cmax_patch_plan_lbfgs": (c_int, [c_vp, c_vp, c_int, ctypes.POINTER(CmaxLbfgs), ctypes.POINTER(CmaxLbfgsResult), c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "cmax_objective_lbfgs": (c_int, [c_vp, ctypes.POINTER(CmaxObjective), c_vp, ctypes.POINTER(CmaxLbfgs), ctypes.POINTER(CmaxLbfgsResult),
+                                     c_vp, c_vp, c_vp, c_vp, c_vp, c_vp]),
     "cmax_basis_to_dense": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "cmax_sizeof_basis_objective": (c_int, []),
     "cmax_basis_plan_create": (c_int, [c_vp, ctypes.POINTER(CmaxBasisObjective), c_vp, c_vp, ctypes.POINTER(c_vp)]),
@@ -312,6 +349,8 @@ def load():
             raise RuntimeError("cmax_basis_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_descent() != ctypes.sizeof(CmaxDescent):
             raise RuntimeError("cmax_descent_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_lbfgs() != ctypes.sizeof(CmaxLbfgs):
+            raise RuntimeError("cmax_lbfgs_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_flow_regularizer() != ctypes.sizeof(CmaxFlowRegularizer):
             raise RuntimeError("cmax_flow_regularizer_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_abi_version() != ABI_VERSION:
@@ -421,6 +460,56 @@ def run_descent(call, nx: int, descent: CmaxDescent, trace: bool) -> DescentResu
 def run_descent_batch(call, K: int, nx: int, descent: CmaxDescent, trace: bool) -> list:
     """... and of the K trajectories of cmax_objective_descend_batch."""
     return _run_descents(call, K, nx, descent, trace)
+
+
+LBFGS_DEFAULTS = dict(history=8, max_ls=10, c1=1e-4, shrink=0.5, curv_eps=1e-10, gtol=1e-5, step0=1.0, max_move=10.0)
+
+
+def lbfgs_descriptor(n_eval: int = 32, history: int = 8, max_ls: int = 10, c1: float = 1e-4, shrink: float = 0.5, curv_eps: float = 1e-10,
+                     gtol: float = 1e-5, step0: float = 1.0, max_move: float = 10.0) -> CmaxLbfgs:
+    """cmax_lbfgs_t (the rules: include/cmax_hip.h).  The library checks the values and names the field it refuses."""
+    d = CmaxLbfgs()
+    d.n_eval, d.history, d.max_ls = int(n_eval), int(history), int(max_ls)
+    d.c1, d.shrink, d.curv_eps, d.gtol, d.step0, d.max_move = float(c1), float(shrink), float(curv_eps), float(gtol), float(step0), float(max_move)
+    return d
+
+
+def lbfgs_state_bytes(nx: int, history: int, n_eval: int, trace: bool) -> int:
+    """The size of the L-BFGS state as include/cmax_hip.h documents it (a 2-DoF handle holds 16 doubles more in front of it)."""
+    return 8 * (LBFGS_FIXED_DOUBLES + (4 + 2 * history) * nx + 2 * n_eval + (n_eval + 1) // 2 + ((n_eval + 1) * nx if trace else 0))
+
+
+class LbfgsResult:
+    """What a device-resident L-BFGS solve returns (cmax_patch_plan_lbfgs / cmax_objective_lbfgs), named the way SciPy's result is: x
+    the accepted point, fun its loss, status a word of LBFGS_STATUS (status_code the number), nit accepted steps, nfev evaluations up to
+    the terminating one, success = CONVERGED; loss_history / alpha / code [n_eval] per evaluation (codes: LBFGS_CODES), trace
+    [n_eval + 1, nx] or None, gnorm_inf, last_alpha."""
+
+    def __init__(self, x, res, loss_history, alpha, code, trace):
+        self.x, self.fun, self.gnorm_inf, self.last_alpha = x, float(res.final_loss), float(res.gnorm_inf), float(res.last_alpha)
+        self.status_code, self.status = int(res.status), LBFGS_STATUS[int(res.status)]
+        self.nit, self.nfev, self.success = int(res.n_iter), int(res.n_eval_used), int(res.status) == 1
+        self.loss_history, self.alpha, self.code, self.trace = loss_history, alpha, code, trace
+
+    @property
+    def accepted_losses(self):
+        """The losses of the accepted points in order (start included): non-increasing by construction."""
+        return self.loss_history[(self.code == 0) | (self.code == 1)]
+
+    def __repr__(self):
+        return f"LbfgsResult(fun={self.fun!r}, status={self.status!r}, nit={self.nit}, nfev={self.nfev}, nx={self.x.size})"
+
+
+def run_lbfgs(call, nx: int, lbfgs: CmaxLbfgs, trace: bool) -> LbfgsResult:
+    """Allocates the host outputs, runs `call(lbfgs*, result*, x, loss_history, alpha, code, trace)` -> LbfgsResult."""
+    import numpy as np
+
+    n = max(int(lbfgs.n_eval), 1)
+    res, x = CmaxLbfgsResult(), np.empty(nx, dtype=np.float64)
+    hist, alpha, code = np.empty(n, dtype=np.float64), np.empty(n, dtype=np.float64), np.empty(n, dtype=np.int32)
+    tr = np.empty((n + 1, nx), dtype=np.float64) if trace else None
+    check(call(ctypes.byref(lbfgs), ctypes.byref(res), x.ctypes.data, hist.ctypes.data, alpha.ctypes.data, code.ctypes.data, tr.ctypes.data if trace else None))
+    return LbfgsResult(x, res, hist, alpha, code, tr)
 
 
 def require_gpu():

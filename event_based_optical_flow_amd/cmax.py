@@ -541,6 +541,21 @@ class CMaxHandle:
         with torch.cuda.device(self.device):
             return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(h, dref, theta0.ctypes.data, o, res, xl, xb, hist, tr, stream), 2, descent, trace)
 
+    def minimize_lbfgs(self, desc: CmaxObjective, theta0, lbfgs: "_lib.CmaxLbfgs", trace: bool = False) -> "_lib.LbfgsResult":
+        """One cmax_objective_lbfgs call: lbfgs.n_eval evaluations of a device-resident L-BFGS with a backtracking line search on a 2-DoF
+        objective (the rules: include/cmax_hip.h), theta and the optimiser's state resident in device memory.  theta0: two numbers
+        (host, pixel over the batch); `lbfgs`: _lib.lbfgs_descriptor(...).  theta stays within lbfgs.max_move of theta0, so the batch's
+        time slabs are decided here, ONCE, from max|theta0| + max_move (auto_time_slabs).  Blocks; returns a _lib.LbfgsResult of host arrays."""
+        theta0 = np.ascontiguousarray(np.asarray(theta0.detach().cpu() if isinstance(theta0, torch.Tensor) else theta0, dtype=np.float64).reshape(-1))
+        if theta0.size != 2:
+            raise ValueError(f"theta0 has {theta0.size} elements, a 2-DoF solve needs 2")
+        if np.isfinite(theta0).all() and np.isfinite(lbfgs.max_move):
+            self.auto_time_slabs(float(np.abs(theta0).max()) + abs(float(lbfgs.max_move)))
+        desc = _with_motion_dtype(desc, _lib.F64)  # the iterate is fp64 in device memory
+        fn, h, dref, stream = self._lib.cmax_objective_lbfgs, self._h, ctypes.byref(desc), F._stream()
+        with torch.cuda.device(self.device):
+            return _lib.run_lbfgs(lambda o, res, x, hist, al, code, tr: fn(h, dref, theta0.ctypes.data, o, res, x, hist, al, code, tr, stream), 2, lbfgs, trace)
+
     def descend_batch(self, desc: CmaxObjective, theta0s, descent: "_lib.CmaxDescent", trace: bool = False) -> list:
         """K independent trajectories of `descend` from the starts `theta0s` [K, 2] (host): cmax_objective_descend_batch, at most
         _lib.DESCENT_MAX_STARTS = 64 starts per call (more are cut into several calls).  For the plain variance without a blur on an
@@ -1195,6 +1210,14 @@ class ContrastObjective:
         cost without a fused kernel) has no single fused objective whose gradient the device-side step could read -- refused."""
         desc = self._descent_term()
         return self.handle.descend(desc, theta0, _lib.descent_descriptor(method, n_iter, lr, lr_step, lr_decay, momentum, betas, eps), trace=trace)
+
+    def minimize_lbfgs(self, theta0, n_eval: int = 32, history: int = 8, gtol: float = 1e-5, max_move: float = 10.0, max_ls: int = 10,
+                       c1: float = 1e-4, shrink: float = 0.5, curv_eps: float = 1e-10, step0: float = 1.0, trace: bool = False):
+        """L-BFGS with a backtracking line search on this objective in ONE library call (CMaxHandle.minimize_lbfgs; the rules:
+        include/cmax_hip.h).  2-DoF models with exactly one fused term of weight 1, as `descend`.  theta stays within max_move of theta0:
+        the batch's time slabs are decided ONCE, from max|theta0| + max_move (by CMaxHandle.minimize_lbfgs).  Returns a _lib.LbfgsResult."""
+        desc = self._descent_term()
+        return self.handle.minimize_lbfgs(desc, theta0, _lib.lbfgs_descriptor(n_eval, history, max_ls, c1, shrink, curv_eps, gtol, step0, max_move), trace=trace)
 
     def _descent_term(self) -> CmaxObjective:
         """The one fused term a device-resident descent steps on, or NotImplementedError with what is refused."""

@@ -40,6 +40,7 @@
 #include <atomic>
 
 #include "cmax_descent.h"
+#include "cmax_lbfgs.h"
 #include "cmax_fused_device.h"
 #include "cmax_image_kernels.h"
 #include "cmax_search_kernels.h"
@@ -3592,6 +3593,48 @@ int cmax_objective_descend(cmax_handle_t h, const cmax_objective_t *d, const dou
     if (rc) return rc;
     descent_result(h->hp_out + cmax_handle_s::kHpResult, res_host);
     rc = descent_copy_out(st, true, nx, n_iter, x_best_host, x_last_host, loss_history_host, x_trace_host, s);
+    if (rc) return rc;
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+// L-BFGS on a 2-DoF fused objective (the rules: include/cmax_hip.h): theta0 once, n_eval x (what cmax_objective runs from the device-resident
+// theta, the general sequence -> k_lbfgs_step) eagerly on the caller's stream, ONE wait behind the last step's run counter, the copies out.
+// h->lbfgs: theta[2] | grad[2] | pad[4] | result[8] | the L-BFGS state (cmax_lbfgs.h, nx = 2).
+int cmax_objective_lbfgs(cmax_handle_t h, const cmax_objective_t *d, const double *theta0_host, const cmax_lbfgs_t *o, cmax_lbfgs_result_t *res_host,
+                         double *x_host, double *loss_history_host, double *alpha_host, int32_t *code_host, double *x_trace_host, cmax_stream_t stream) {
+    int rc = lbfgs_entry_check("objective_lbfgs", o, h && d && theta0_host && res_host && x_host && loss_history_host && alpha_host && code_host, d, h && h->comm);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const int nx = 2, n_eval = o->n_eval, m = o->history;
+    const bool trace = x_trace_host != nullptr;
+    constexpr int kHead = 16;  // theta[2] | grad[2] | pad[4] | result[8]
+    rc = h->lbfgs.reserve(&h->bytes, kHead + lbfgs_state_doubles(nx, m, n_eval, trace), s);
+    if (!rc) rc = h->hp_out.reserve(cmax_handle_s::kHpPayload);
+    if (rc) return rc;
+    double *theta = h->lbfgs, *grad = theta + 2, *result = theta + 8, *st = theta + kHead;
+    rc = check_objective_args(h, d, reinterpret_cast<const float *>(theta));
+    if (rc) return rc;
+    const unsigned long long seq = ++h->host_seq;
+    double *const theta0_pinned = h->hp_out + cmax_handle_s::kHpStaged;
+    theta0_pinned[0] = theta0_host[0];
+    theta0_pinned[1] = theta0_host[1];
+    CMAX_CHECK_HIP(hipMemcpyAsync(theta, theta0_pinned, 2 * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int e = 0; e < n_eval; ++e) {
+        LbfgsArgs a = lbfgs_args(*o, e, nx, trace, theta, st);
+        if (e == n_eval - 1) {
+            a.res_pinned = h->hp_out.dev() + cmax_handle_s::kHpResult;
+            a.flag = cmax_handle_s::hp_counter(h->hp_out.dev());
+            a.seq = seq;
+        }
+        rc = objective_eval(h, d, reinterpret_cast<const float *>(theta), result, grad, s, EvalForm());
+        if (!rc) rc = launch_lbfgs_step(a, result, grad, s);
+        if (rc) return rc;
+    }
+    rc = wait_host_seq(h, seq, s, "objective_lbfgs: the last step");
+    if (rc) return rc;
+    lbfgs_result(h->hp_out + cmax_handle_s::kHpResult, res_host);
+    rc = lbfgs_copy_out(st, nx, m, n_eval, x_host, loss_history_host, alpha_host, code_host, x_trace_host, s);
     if (rc) return rc;
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;

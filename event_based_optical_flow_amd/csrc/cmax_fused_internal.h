@@ -221,6 +221,7 @@ struct cmax_handle_s {
     static volatile unsigned long long *hp_counter(double *block) { return reinterpret_cast<volatile unsigned long long *>(block + kHpCounter); }
     unsigned long long host_seq = 0;  // the last value a polled call had its kernel store there
     cmax::DevBuf<double> descent;     // cmax_objective_descend (on first use): theta[2] | grad[2] | pad[4] | result[8] | the descent state (cmax_descent.h)
+    cmax::DevBuf<double> lbfgs;       // cmax_objective_lbfgs (on first use): theta[2] | grad[2] | pad[4] | result[8] | the L-BFGS state (cmax_lbfgs.h)
     // cmax_objective_descend_batch (on first use): theta[K][2] | grad[K][2] | pad[K][4] | result[K][8] | K descent states
     cmax::DevBuf<double> descent_batch;
     cmax::DevBuf<int> d_ticket;    // arrival counters of the statistics workgroups inside K3 (kFoldStatsInside): zero between launches

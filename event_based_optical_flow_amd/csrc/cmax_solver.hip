@@ -25,6 +25,7 @@
 #include "cmax_buffers.h"
 #include "cmax_common.h"
 #include "cmax_descent.h"
+#include "cmax_lbfgs.h"
 #include "cmax_flowreg_kernels.h"
 #include "cmax_image_kernels.h"
 #include "cmax_patch_kernels.h"
@@ -395,6 +396,429 @@ int launch_descent_step(const DescentArgs &a, const double *loss, const double *
     return 0;
 }
 
+// ---- device-resident L-BFGS (cmax_lbfgs.h; the rules: include/cmax_hip.h) ----------------------------------------------------------------
+// exact in any order; every lane receives the result
+__device__ __forceinline__ double wave_max_all(double v) {
+    for (int o = kWave / 2; o; o >>= 1) v = fmax(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ double wave_min_all(double v) {
+    for (int o = kWave / 2; o; o >>= 1) v = fmin(v, __shfl_xor(v, o));
+    return v;
+}
+__device__ __forceinline__ bool lbfgs_held(int slot, int head, int k, int m) { return slot < m && (slot - head + m) % m < k; }
+__device__ __forceinline__ double lbfgs_trial(double xa, double alpha, double d, double x0, double max_move) {
+    return fmin(fmax(xa + alpha * d, x0 - max_move), x0 + max_move);
+}
+
+// The textbook two-loop recursion on the vectors themselves (LbfgsArgs::two_loop; x_a, g_a and the pairs are stored): q lives in v.d, every
+// inner product is a block reduction that waits for the last.  s^T y of a pair comes from the Gram diagonal.  -> g_a^T d in every thread.
+__device__ double lbfgs_two_loop_direction(const LbfgsView &v, int nx, int m, int k, int head, double *s_red, double *s_a, double *s_bc) {
+    constexpr int M = CMAX_LBFGS_MAX_HISTORY, NB = kLbBasis;
+    const int tid = threadIdx.x;
+    for (int p = tid; p < nx; p += blockDim.x) v.d[p] = v.ga[p];
+    for (int i = k - 1; i >= 0; --i) {
+        const int c = (head + i) % m;
+        const double *S = v.S + (int64_t)c * nx, *Y = v.Y + (int64_t)c * nx;
+        double dot[1] = {0.0};
+        for (int p = tid; p < nx; p += blockDim.x) dot[0] += S[p] * v.d[p];
+        block_sum<1>(dot, s_red);
+        if (tid == 0) s_a[c] = dot[0] / v.gram[c * NB + M + c];
+        __syncthreads();
+        const double ai = s_a[c];
+        for (int p = tid; p < nx; p += blockDim.x) v.d[p] -= ai * Y[p];
+    }
+    const int cn = (head + k - 1) % m;
+    const double gamma = v.gram[cn * NB + M + cn] / v.gram[(M + cn) * NB + M + cn];
+    for (int p = tid; p < nx; p += blockDim.x) v.d[p] *= gamma;
+    for (int i = 0; i < k; ++i) {
+        const int c = (head + i) % m;
+        const double *S = v.S + (int64_t)c * nx, *Y = v.Y + (int64_t)c * nx;
+        double dot[1] = {0.0};
+        for (int p = tid; p < nx; p += blockDim.x) dot[0] += Y[p] * v.d[p];
+        block_sum<1>(dot, s_red);
+        if (tid == 0) s_bc[0] = s_a[c] - dot[0] / v.gram[c * NB + M + c];
+        __syncthreads();
+        const double t = s_bc[0];
+        for (int p = tid; p < nx; p += blockDim.x) v.d[p] += t * S[p];
+    }
+    double dot[1] = {0.0};
+    for (int p = tid; p < nx; p += blockDim.x) {
+        const double dp = -v.d[p];
+        v.d[p] = dp;
+        dot[0] += v.ga[p] * dp;
+    }
+    block_sum<1>(dot, s_red);
+    if (tid == 0) s_bc[1] = dot[0];
+    __syncthreads();
+    return s_bc[1];
+}
+
+// One evaluation's decision of the device-resident L-BFGS: loss and gradient are read where the tail / the 2-DoF objective left them, as in
+// k_descent_step; ONE workgroup (nx is 2 .. 8192, m <= 16, every step depends on the last).  The non-finite test covers ALL of g before
+// any store.  An evaluation that passes the Armijo test costs ONE reduction pass behind one barrier: the threads stride over x for the
+// products among the new s, y and g (wave tree, then the four waves in order), and every wave takes eight rows of {S, Y}, four at a time,
+// for their products with s, y and g.  Wave 0 then brings the Gram matrix (LDS copy and state) up to date and runs the two-loop recursion
+// on the COEFFICIENTS of d in the basis {s_i, y_i, g}: lane j keeps u_j = <current vector, basis_j>, so a step of the recursion is one
+// cross-lane read and one multiply-add, with no reduction.  A last pass forms d as one linear combination, stores the new pair, x_a and
+// g_a, and reduces the box's limit on alpha; the trial point is written in place of x.  No atomics: the result depends on nothing but
+// the inputs.  The last evaluation publishes the result block and, behind a system-wide fence, the run counter, as k_descent_step does.
+__global__ void __launch_bounds__(256) k_lbfgs_step(LbfgsArgs a, const double *__restrict__ loss, const double *__restrict__ grad) {
+    constexpr int M = CMAX_LBFGS_MAX_HISTORY, NB = kLbBasis, G = kLbG;
+    __shared__ double s_gram[NB * NB];
+    __shared__ double s_prod[2 * M][3];  // <row, s>, <row, y>, <row, g>: rows 0 .. 15 the S slots, 16 .. 31 the Y slots
+    __shared__ double s_part[4][8];      // per wave: ss, sy, yy, gs, gy, gg, |g|_1, |g|_inf
+    __shared__ double s_coef[NB];
+    __shared__ double s_gd;
+    __shared__ double s_min[4];
+    __shared__ double s_a[M], s_bc[2];  // (two_loop only)
+    const int tid = threadIdx.x, lane = tid & (kWave - 1), wid = tid / kWave, nx = a.nx, m = a.m;
+    const LbfgsView v = lbfgs_view(a.st, nx, m, a.n_eval);
+    const bool first = a.e == 0, last = a.e == a.n_eval - 1;
+    const double L = loss[0];
+    // the control block (every thread reads it; the writer waits behind a barrier).  Evaluation 0 reads none of the state.
+    const bool done_prev = !first && v.ctrl[kLbDone] != 0.0;
+    int status = first ? CMAX_LBFGS_BUDGET : (int)v.ctrl[kLbStatus];
+    double L_a = first ? 0.0 : v.ctrl[kLbLa];
+    const double alpha_e = first ? 0.0 : v.ctrl[kLbAlpha];  // the alpha of the point evaluated here
+    double alpha = alpha_e, gd = first ? 0.0 : v.ctrl[kLbGd];
+    int n_ls = first ? 0 : (int)v.ctrl[kLbNls], n_iter = first ? 0 : (int)v.ctrl[kLbNiter], used = first ? 0 : (int)v.ctrl[kLbUsed];
+    int k = first ? 0 : (int)v.ctrl[kLbK], head = first ? 0 : (int)v.ctrl[kLbHead];
+    double ginf_a = first ? 0.0 : v.ctrl[kLbGinf], g1_a = first ? 0.0 : v.ctrl[kLbG1], gg_a = first ? 0.0 : v.ctrl[kLbGg];
+    double last_alpha = first ? 0.0 : v.ctrl[kLbLastAlpha];
+    if (a.has_trace)
+        for (int p = tid; p < nx; p += blockDim.x) v.trace[(int64_t)a.e * nx + p] = a.x[p];
+
+    int code = CMAX_LBFGS_CODE_IDLE;
+    bool done = done_prev;
+    if (!done_prev) {
+        const bool armijo = first || (isfinite(L) && L <= L_a + a.c1 * alpha * gd);
+        bool ok = false;
+        double ss = 0.0, sy = 0.0, yy = 0.0, gs = 0.0, gy = 0.0, gg = 0.0, g1 = 0.0, ginf = 0.0;
+        if (armijo) {  // (uniform) the one reduction pass
+            if (k > 0 && !a.two_loop)
+                for (int i = tid; i < NB * NB; i += blockDim.x) s_gram[i] = v.gram[i];
+            int bad = isfinite(L) ? 0 : 1;
+            double acc[7] = {0.0, 0.0, 0.0, 0.0, 0.0, 0.0, 0.0}, mx = 0.0;
+            for (int p = tid; p < nx; p += blockDim.x) {
+                const double g = grad[p];
+                bad |= isfinite(g) ? 0 : 1;
+                const double sp = first ? 0.0 : a.x[p] - v.xa[p], yp = first ? 0.0 : g - v.ga[p];
+                acc[0] += sp * sp;
+                acc[1] += sp * yp;
+                acc[2] += yp * yp;
+                acc[3] += g * sp;
+                acc[4] += g * yp;
+                acc[5] += g * g;
+                acc[6] += fabs(g);
+                mx = fmax(mx, fabs(g));
+            }
+#pragma unroll
+            for (int q = 0; q < 7; ++q) acc[q] = wave_sum_lane63(acc[q]);
+            mx = wave_max_all(mx);
+            if (lane == kWave - 1) {
+#pragma unroll
+                for (int q = 0; q < 7; ++q) s_part[wid][q] = acc[q];
+                s_part[wid][7] = mx;
+            }
+            if (k > 0 && !a.two_loop) {
+                for (int grp = 0; grp < 2; ++grp) {
+                    const double *row[4];
+                    bool held[4], any = false;
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+                        const int r = wid + 4 * (4 * grp + t), slot = r & (M - 1);
+                        held[t] = lbfgs_held(slot, head, k, m);
+                        any |= held[t];
+                        row[t] = held[t] ? (r < M ? v.S : v.Y) + (int64_t)slot * nx : v.d;  // (a row that is not held: any readable line, result unused)
+                    }
+                    if (!any) continue;
+                    double pr[4][3] = {};
+                    for (int p = lane; p < nx; p += kWave) {
+                        const double g = grad[p], sp = a.x[p] - v.xa[p], yp = g - v.ga[p];
+#pragma unroll
+                        for (int t = 0; t < 4; ++t) {
+                            const double b = row[t][p];
+                            pr[t][0] += b * sp;
+                            pr[t][1] += b * yp;
+                            pr[t][2] += b * g;
+                        }
+                    }
+#pragma unroll
+                    for (int t = 0; t < 4; ++t) {
+#pragma unroll
+                        for (int c = 0; c < 3; ++c) pr[t][c] = wave_sum_lane63(pr[t][c]);
+                        if (lane == kWave - 1 && held[t]) {
+                            const int r = wid + 4 * (4 * grp + t);
+                            s_prod[r][0] = pr[t][0];
+                            s_prod[r][1] = pr[t][1];
+                            s_prod[r][2] = pr[t][2];
+                        }
+                    }
+                }
+            }
+            bad = __syncthreads_or(bad);
+            ok = bad == 0;
+            ss = s_part[0][0] + s_part[1][0] + s_part[2][0] + s_part[3][0];
+            sy = s_part[0][1] + s_part[1][1] + s_part[2][1] + s_part[3][1];
+            yy = s_part[0][2] + s_part[1][2] + s_part[2][2] + s_part[3][2];
+            gs = s_part[0][3] + s_part[1][3] + s_part[2][3] + s_part[3][3];
+            gy = s_part[0][4] + s_part[1][4] + s_part[2][4] + s_part[3][4];
+            gg = s_part[0][5] + s_part[1][5] + s_part[2][5] + s_part[3][5];
+            g1 = s_part[0][6] + s_part[1][6] + s_part[2][6] + s_part[3][6];
+            ginf = fmax(fmax(s_part[0][7], s_part[1][7]), fmax(s_part[2][7], s_part[3][7]));
+        }
+
+        // what the next trial is formed from: the accepted point's gradient, whether the new point is stored, the direction's kind
+        bool choose = false, accept = false, push = false, steep = true, stored = false;
+        int nslot = -1;
+        double alpha0 = 0.0;
+        if (ok) {
+            accept = true;
+            code = first ? CMAX_LBFGS_CODE_START : CMAX_LBFGS_CODE_ACCEPTED;
+            push = !first && yy > 0.0 && sy > a.curv_eps * yy;
+            const int k_old = k, head_old = head;
+            if (push) {
+                if (k < m) {
+                    nslot = (head + k) % m;
+                    k += 1;
+                } else {
+                    nslot = head;
+                    head = (head + 1) % m;
+                }
+            }
+            if (!first) {
+                n_iter += 1;
+                last_alpha = alpha;
+            }
+            n_ls = 0;
+            L_a = L;
+            ginf_a = ginf;
+            g1_a = g1;
+            gg_a = gg;
+            if (ginf <= a.gtol) {
+                status = CMAX_LBFGS_CONVERGED;
+                done = true;
+            } else {
+                choose = true;
+                if (k > 0 && a.two_loop) {
+                    for (int p = tid; p < nx; p += blockDim.x) {
+                        const double g = grad[p], xt = a.x[p];
+                        if (push) {
+                            v.S[(int64_t)nslot * nx + p] = xt - v.xa[p];
+                            v.Y[(int64_t)nslot * nx + p] = g - v.ga[p];
+                        }
+                        v.xa[p] = xt;
+                        v.ga[p] = g;
+                    }
+                    if (tid == 0 && push) {
+                        v.gram[nslot * NB + M + nslot] = sy;
+                        v.gram[(M + nslot) * NB + M + nslot] = yy;
+                    }
+                    stored = true;
+                    __syncthreads();
+                    const double gdn = lbfgs_two_loop_direction(v, nx, m, k, head, s_min, s_a, s_bc);
+                    if (gdn < 0.0) {
+                        steep = false;
+                        gd = gdn;
+                        alpha0 = 1.0;
+                    } else {
+                        k = 0;
+                        head = 0;
+                    }
+                } else if (k > 0) {
+                    if (wid == 0 && lane < NB) {  // the Gram matrix: the rows of the new s and y, the row of the new g
+                        const int j = lane;
+                        const bool hj = j < G && lbfgs_held(j & (M - 1), head_old, k_old, m);
+                        double ps = j == G ? gs : (hj ? s_prod[j & (2 * M - 1)][0] : 0.0);
+                        double py = j == G ? gy : (hj ? s_prod[j & (2 * M - 1)][1] : 0.0);
+                        double pg = j == G ? gg : (hj ? s_prod[j & (2 * M - 1)][2] : 0.0);
+                        if (push) {
+                            if (j == nslot) ps = ss, py = sy, pg = gs;
+                            if (j == M + nslot) ps = sy, py = yy, pg = gy;
+                            s_gram[nslot * NB + j] = s_gram[j * NB + nslot] = ps;
+                            s_gram[(M + nslot) * NB + j] = s_gram[j * NB + M + nslot] = py;
+                            v.gram[nslot * NB + j] = v.gram[j * NB + nslot] = ps;
+                            v.gram[(M + nslot) * NB + j] = v.gram[j * NB + M + nslot] = py;
+                        }
+                        s_gram[G * NB + j] = s_gram[j * NB + G] = pg;
+                        v.gram[G * NB + j] = v.gram[j * NB + G] = pg;
+                    }
+                    __syncthreads();
+                    if (wid == 0) {  // the two-loop recursion on coefficients: u = <vector, basis_j> per lane
+                        const int j = lane;
+                        const bool hj = j == G || (j < G && lbfgs_held(j & (M - 1), head, k, m));
+                        double u = j < NB ? s_gram[G * NB + j] : 0.0, coef = j == G ? 1.0 : 0.0, a_mine = 0.0;
+                        for (int i = k - 1; i >= 0; --i) {
+                            const int c = (head + i) % m;
+                            const double ai = __shfl(u, c) / s_gram[c * NB + M + c];
+                            if (j == c) a_mine = ai;
+                            if (j == M + c) coef -= ai;
+                            if (j < NB) u -= ai * s_gram[(M + c) * NB + j];
+                        }
+                        const int cn = (head + k - 1) % m;
+                        const double gamma = s_gram[cn * NB + M + cn] / s_gram[(M + cn) * NB + M + cn];
+                        u *= gamma;
+                        coef *= gamma;
+                        for (int i = 0; i < k; ++i) {
+                            const int c = (head + i) % m;
+                            const double t = __shfl(a_mine, c) - __shfl(u, M + c) / s_gram[c * NB + M + c];
+                            if (j == c) coef += t;
+                            if (j < NB) u += t * s_gram[c * NB + j];
+                        }
+                        const double gdn = -__shfl(u, G);
+                        if (j < NB) s_coef[j] = hj ? coef : 0.0;
+                        if (j == 0) s_gd = gdn;
+                    }
+                    __syncthreads();
+                    const double gdn = s_gd;
+                    if (gdn < 0.0) {
+                        steep = false;
+                        gd = gdn;
+                        alpha0 = 1.0;
+                    } else {  // not a descent direction: the history goes
+                        k = 0;
+                        head = 0;
+                    }
+                }
+            }
+        } else if (first) {
+            status = CMAX_LBFGS_NONFINITE_START;
+            done = true;
+            code = CMAX_LBFGS_CODE_START;
+            L_a = L;
+            ginf_a = (double)NAN;
+            for (int p = tid; p < nx; p += blockDim.x) v.xa[p] = a.x[p];
+        } else {
+            n_ls += 1;
+            code = CMAX_LBFGS_CODE_REJECTED;
+            if (n_ls > a.max_ls && k == 0) {
+                status = CMAX_LBFGS_LINESEARCH;
+                done = true;
+                for (int p = tid; p < nx; p += blockDim.x) a.x[p] = v.xa[p];
+            } else if (n_ls > a.max_ls) {
+                code = CMAX_LBFGS_CODE_RESET;
+                k = 0;
+                head = 0;
+                n_ls = 0;
+                choose = true;
+            } else {
+                alpha *= a.shrink;
+                for (int p = tid; p < nx; p += blockDim.x) a.x[p] = lbfgs_trial(v.xa[p], alpha, v.d[p], v.x0[p], a.max_move);
+            }
+        }
+        if (accept && !choose) {  // converged: the accepted point is stored, nothing else
+            for (int p = tid; p < nx; p += blockDim.x) {
+                v.xa[p] = a.x[p];
+                v.ga[p] = grad[p];
+            }
+        }
+        if (choose) {
+            if (steep) {
+                gd = -gg_a;
+                alpha0 = fmin(1.0, a.step0 / g1_a);
+            }
+            double tmin = (double)INFINITY;
+            for (int p = tid; p < nx; p += blockDim.x) {
+                double g, xa, x0, sp = 0.0, yp = 0.0;
+                if (accept && !stored) {
+                    g = grad[p];
+                    xa = a.x[p];
+                    x0 = first ? xa : v.x0[p];
+                    if (!first) {
+                        sp = xa - v.xa[p];
+                        yp = g - v.ga[p];
+                    }
+                    if (push) {
+                        v.S[(int64_t)nslot * nx + p] = sp;
+                        v.Y[(int64_t)nslot * nx + p] = yp;
+                    }
+                    v.xa[p] = xa;
+                    v.ga[p] = g;
+                    if (first) v.x0[p] = xa;
+                } else {
+                    g = v.ga[p];
+                    xa = v.xa[p];
+                    x0 = v.x0[p];
+                }
+                double dp = -g;
+                if (!steep && a.two_loop) {
+                    dp = v.d[p];
+                } else if (!steep) {
+                    double r = 0.0;
+                    for (int i = 0; i < k; ++i) {  // oldest to newest, then g: one fixed order
+                        const int c = (head + i) % m;
+                        const double sv = c == nslot ? sp : v.S[(int64_t)c * nx + p], yv = c == nslot ? yp : v.Y[(int64_t)c * nx + p];
+                        r += s_coef[c] * sv + s_coef[M + c] * yv;
+                    }
+                    dp = -(r + s_coef[G] * g);
+                }
+                v.d[p] = dp;
+                const double lim = dp > 0.0 ? (x0 + a.max_move - xa) / dp : (dp < 0.0 ? (x0 - a.max_move - xa) / dp : (double)INFINITY);
+                tmin = fmin(tmin, lim);
+            }
+            tmin = wave_min_all(tmin);
+            if (lane == 0) s_min[wid] = tmin;
+            __syncthreads();
+            alpha = fmin(alpha0, fmin(fmin(s_min[0], s_min[1]), fmin(s_min[2], s_min[3])));
+            if (alpha > 0.0) {
+                for (int p = tid; p < nx; p += blockDim.x) a.x[p] = lbfgs_trial(v.xa[p], alpha, v.d[p], v.x0[p], a.max_move);
+            } else {
+                status = CMAX_LBFGS_BOX;
+                done = true;
+                for (int p = tid; p < nx; p += blockDim.x) a.x[p] = v.xa[p];
+            }
+        }
+        if (done) used = a.e + 1;
+    }
+    if (last && a.has_trace)
+        for (int p = tid; p < nx; p += blockDim.x) v.trace[(int64_t)a.n_eval * nx + p] = v.xa[p];
+    __syncthreads();  // (every thread has read the control block)
+    if (tid == 0) {
+        v.loss[a.e] = done_prev ? (double)NAN : L;
+        v.alpha[a.e] = done_prev ? 0.0 : alpha_e;
+        v.code[a.e] = code;
+        if (!done_prev) {
+            v.ctrl[kLbDone] = done ? 1.0 : 0.0;
+            v.ctrl[kLbStatus] = (double)status;
+            v.ctrl[kLbLa] = L_a;
+            v.ctrl[kLbAlpha] = alpha;
+            v.ctrl[kLbGd] = gd;
+            v.ctrl[kLbNls] = (double)n_ls;
+            v.ctrl[kLbNiter] = (double)n_iter;
+            v.ctrl[kLbUsed] = (double)used;
+            v.ctrl[kLbK] = (double)k;
+            v.ctrl[kLbHead] = (double)head;
+            v.ctrl[kLbGinf] = ginf_a;
+            v.ctrl[kLbG1] = g1_a;
+            v.ctrl[kLbGg] = gg_a;
+            v.ctrl[kLbLastAlpha] = last_alpha;
+        }
+        if (last && a.res_pinned) {
+            a.res_pinned[0] = L_a;
+            a.res_pinned[1] = ginf_a;
+            a.res_pinned[2] = last_alpha;
+            a.res_pinned[3] = (double)n_iter;
+            a.res_pinned[4] = (double)(done ? used : a.n_eval);
+            a.res_pinned[5] = (double)status;
+        }
+    }
+    if (last && a.flag) {
+        __threadfence_system();
+        __syncthreads();
+        if (tid == 0) *a.flag = a.seq_src ? a.seq_src[0] : a.seq;
+    }
+}
+
+int launch_lbfgs_step(const LbfgsArgs &a_in, const double *loss, const double *grad, hipStream_t s) {
+    static const bool two_loop = getenv("CMAX_LBFGS_TWO_LOOP") != nullptr;  // (tools/probe_lbfgs.py: the textbook recursion, for its cost)
+    LbfgsArgs a = a_in;
+    a.two_loop = two_loop ? 1 : 0;
+    hipLaunchKernelGGL(k_lbfgs_step, dim3(1), dim3(256), 0, s, a, loss, grad);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 }  // namespace cmax
 
 struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: its implicit destructor is no export)
@@ -429,6 +853,7 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     // cmax_patch_plan_descend (reserved on first use): the tail's output in device memory (loss | grad | counter slot), the descent state
     cmax::DevBuf<double> d_out, descent;
     cmax::PinnedBuf<double> h_res;  // ... and the result block the last step writes (the run counter goes to h_out's slot, like every tail's)
+    cmax::DevBuf<double> lbfgs;     // cmax_patch_plan_lbfgs (reserved on first use): the L-BFGS state (cmax_lbfgs.h); d_out and h_res are shared
     // Captured launch sequences (hipGraph), replayed on the plan's own stream: an evaluation is ~25 small launches,
     // host-bound when issued one by one.  Keyed by everything that changes the sequence: the kind of call and the
     // handle's host-side state (which vote buffer is current, which images are already zero, whether the
@@ -1342,6 +1767,50 @@ int cmax_patch_plan_descend(cmax_patch_plan_t p, const double *x0_host, int with
     if (rc) return rc;
     descent_result(p->h_res, res_host);
     rc = descent_copy_out(p->descent, true, nx, n_iter, x_best_host, x_last_host, loss_history_host, x_trace_host, s);  // (behind the wait: the state is final)
+    if (rc) return rc;
+    CMAX_CHECK_HIP(hipStreamSynchronize(s));
+    return 0;
+}
+
+int cmax_sizeof_lbfgs(void) { return (int)sizeof(cmax_lbfgs_t); }
+
+// L-BFGS on the plan's objective (the rules: include/cmax_hip.h): x0 once, n_eval x (evaluate from the device-resident x -> tail into a
+// device buffer -> k_lbfgs_step, which decides and writes the next point) eagerly on the caller's stream, ONE wait, the copies out.
+int cmax_patch_plan_lbfgs(cmax_patch_plan_t p, const double *x0_host, int with_tv, const cmax_lbfgs_t *o, cmax_lbfgs_result_t *res_host, double *x_host,
+                          double *loss_history_host, double *alpha_host, int32_t *code_host, double *x_trace_host, cmax_stream_t stream) {
+    int rc = lbfgs_entry_check("patch_plan_lbfgs", o, p && x0_host && res_host && x_host && loss_history_host && alpha_host && code_host, nullptr,
+                               p && handle_has_comm(p->handle));
+    if (rc) return rc;
+    if (handle_is_weighted(p->handle)) {
+        set_error("patch_plan_lbfgs: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    const bool tv = with_tv && p->d.tv_weight != 0.0, trace = x_trace_host != nullptr;
+    const int nx = p->nx, n_eval = o->n_eval, m = o->history;
+    rc = p->d_out.reserve(nullptr, 2 + (int64_t)nx, s);
+    if (!rc) rc = p->lbfgs.reserve(nullptr, lbfgs_state_doubles(nx, m, n_eval, trace), s);
+    if (!rc) rc = p->h_res.reserve(8);
+    if (rc) return rc;
+    std::memcpy(p->h_in, x0_host, (size_t)nx * sizeof(double));
+    CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (size_t)nx * sizeof(double), hipMemcpyHostToDevice, s));
+    for (int e = 0; e < n_eval; ++e) {
+        rc = enqueue_evaluate(p, tv, true, s, nullptr, p->d_out);
+        if (rc) return rc;
+        LbfgsArgs a = lbfgs_args(*o, e, nx, trace, p->x64, p->lbfgs);
+        if (e == n_eval - 1) {
+            a.res_pinned = p->h_res.dev();
+            a.flag = plan_flag(p, p->h_out.dev());
+            a.seq_src = p->seq_dev;
+        }
+        rc = launch_lbfgs_step(a, p->d_out, p->d_out + 1, s);
+        if (rc) return rc;
+    }
+    ++p->eager_calls;
+    rc = wait_for_tail(p, s, p->eager_calls > 1, (unsigned long long)n_eval);
+    if (rc) return rc;
+    lbfgs_result(p->h_res, res_host);
+    rc = lbfgs_copy_out(p->lbfgs, nx, m, n_eval, x_host, loss_history_host, alpha_host, code_host, x_trace_host, s);  // (behind the wait: the state is final)
     if (rc) return rc;
     CMAX_CHECK_HIP(hipStreamSynchronize(s));
     return 0;

@@ -211,6 +211,21 @@ class FlowBasisObjective:
             return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(plan, theta0.ctypes.data, 0, o, res, xl, xb, hist, tr, stream),
                                     self._nx, descent, trace)
 
+    def minimize_lbfgs(self, theta0: np.ndarray, n_eval: int = 32, history: int = 8, gtol: float = 1e-5, max_move: float = 10.0, max_ls: int = 10,
+                       c1: float = 1e-4, shrink: float = 0.5, curv_eps: float = 1e-10, step0: float = 1.0, trace: bool = False):
+        """L-BFGS with a backtracking line search from theta0 in ONE cmax_patch_plan_lbfgs call (PatchFlowObjective.minimize_lbfgs; the
+        rules: include/cmax_hip.h).  Every parameter stays within max_move of theta0: time slabs are decided ONCE, from the bound at
+        |theta0| + max_move per entry.  Returns a _lib.LbfgsResult."""
+        if self._plan is None:
+            raise NotImplementedError("minimize_lbfgs needs the native plan (numeric hybrid weights, fused costs)")
+        theta0 = self._theta(theta0, "theta0")
+        lbfgs = _lib.lbfgs_descriptor(n_eval, history, max_ls, c1, shrink, curv_eps, gtol, step0, max_move)
+        self.ensure_time_slabs(np.abs(theta0) + abs(float(max_move)))
+        fn, plan, stream = _lib.load().cmax_patch_plan_lbfgs, self._plan, F._stream()
+        with torch.cuda.device(self.handle.device):
+            return _lib.run_lbfgs(lambda o, res, x, hist, al, code, tr: fn(plan, theta0.ctypes.data, 0, o, res, x, hist, al, code, tr, stream),
+                                  self._nx, lbfgs, trace)
+
     def dense_flow(self, theta: torch.Tensor) -> torch.Tensor:
         """[K] parameters -> [2,H,W] (or [T,2,H,W]) flow in pixel per NORMALISED time, in the basis' dtype."""
         if theta.numel() != self._nx:

@@ -17,6 +17,10 @@ SCIPY_OPTIMIZERS = ["Nelder-Mead", "Powell", "CG", "BFGS", "Newton-CG", "L-BFGS-
 # first-order methods of the reference's TORCH_OPTIMIZERS (src/solver/base.py:38-52) that run as a device-resident loop
 # (PatchFlowObjective.descend: n_iter iterations per library call); the other eleven names are not built
 DESCENT_OPTIMIZERS = ["SGD", "Adam"]
+# quasi-Newton methods that run as a device-resident loop (PatchFlowObjective.minimize_lbfgs: a budget of optimizer.n_iter evaluations per
+# library call; not in the reference, whose "LBFGS" is torch.optim's and is not built)
+DEVICE_QUASI_NEWTON = ["device-L-BFGS"]
+LBFGS_KEYS = ("history", "gtol", "max_move", "c1", "shrink", "max_ls", "step0")  # optimizer.lbfgs
 
 
 def check_opt_method(method: str):
@@ -25,14 +29,30 @@ def check_opt_method(method: str):
     if method == "optuna":
         raise NotImplementedError("opt_method 'optuna' is not built: Optuna is not a dependency of this package "
                                   f"(SciPy methods and the device-resident {DESCENT_OPTIMIZERS})")
-    if method not in SCIPY_OPTIMIZERS and method not in DESCENT_OPTIMIZERS:
-        raise NotImplementedError(f"Optimizer {method} is not supported (SciPy methods, and of torch.optim the device-resident {DESCENT_OPTIMIZERS} only)")
+    if method not in SCIPY_OPTIMIZERS and method not in DESCENT_OPTIMIZERS and method not in DEVICE_QUASI_NEWTON:
+        raise NotImplementedError(f"Optimizer {method} is not supported (SciPy methods, and of torch.optim the device-resident {DESCENT_OPTIMIZERS} only; "
+                                  f"the device-resident quasi-Newton solve is {DEVICE_QUASI_NEWTON})")
 
 
 def run_descent(objective, x0: np.ndarray, method: str, opt_config: dict):
     """SolverBase.run_torch (src/solver/base.py:840-881) with its constants: lr 0.05, StepLR(n_iter, 0.1), optimizer.n_iter iterations,
     torch's defaults for the optimiser itself -- one PatchFlowObjective.descend call.  -> _lib.DescentResult (its x is x_best)."""
     return objective.descend(x0, method=method, n_iter=int(opt_config["n_iter"]), lr=0.05, lr_step=None, lr_decay=0.1)
+
+
+def lbfgs_config(opt_config: dict) -> dict:
+    """The optional key optimizer.lbfgs: {history, gtol, max_move, c1, shrink, max_ls, step0} (not in the reference); {} when absent."""
+    cfg = opt_config.get("lbfgs") or {}
+    unknown = sorted(set(cfg) - set(LBFGS_KEYS))
+    if unknown:
+        raise KeyError(f"optimizer.lbfgs: unknown keys {unknown} (known: {list(LBFGS_KEYS)})")
+    return dict(cfg)
+
+
+def run_lbfgs(objective, x0: np.ndarray, opt_config: dict):
+    """optimizer.method "device-L-BFGS": one PatchFlowObjective.minimize_lbfgs call with a budget of optimizer.n_iter evaluations (the key
+    run_torch reads) and the optional optimizer.lbfgs values.  -> _lib.LbfgsResult (its x is the last accepted point)."""
+    return objective.minimize_lbfgs(x0, n_eval=int(opt_config["n_iter"]), **lbfgs_config(opt_config))
 
 
 def _check_key_and_bool(config: dict, key: str) -> bool:

@@ -19,8 +19,8 @@ import numpy as np
 
 from ..cmax import CMaxHandle
 from . import scipy_autograd
-from .common import (DESCENT_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, check_opt_method, flow_regularizer_config, global_best_refine, one_patch_guess,
-                     run_descent, whole_image_guess)
+from .common import (DESCENT_OPTIMIZERS, DEVICE_QUASI_NEWTON, PatchSolverCommon, _check_key_and_bool, check_opt_method, flow_regularizer_config, global_best_refine, one_patch_guess,
+                     lbfgs_config, run_descent, run_lbfgs, whole_image_guess)
 from .patch_objective import PatchFlowObjective, patch_pad
 
 logger = logging.getLogger(__name__)
@@ -46,6 +46,8 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         self.visualizer = visualize_module
         self.opt_method = optimizer_config["method"]
         check_opt_method(self.opt_method)
+        if self.opt_method in DEVICE_QUASI_NEWTON:
+            lbfgs_config(optimizer_config)  # (unknown keys of optimizer.lbfgs: KeyError, at construction)
         self.padding = solver_config["outer_padding"] if "outer_padding" in solver_config else 0
         self.iwe_config = solver_config["iwe"]
         if self.iwe_config["method"] != "bilinear_vote":
@@ -194,6 +196,8 @@ class MixedPatchContrastMaximization(PatchSolverCommon):
         motion0 = self.initial_motion(events)
         if self.opt_method in DESCENT_OPTIMIZERS:  # run_torch's loop (src/solver/base.py:840-881), device-resident; the motion is x_best
             res = run_descent(objective, motion0, self.opt_method, self.opt_config)
+        elif self.opt_method in DEVICE_QUASI_NEWTON:  # L-BFGS, device-resident; the motion is the last accepted point
+            res = run_lbfgs(objective, motion0, self.opt_config)
         else:
             res = scipy_autograd.minimize(objective, motion0, method=self.opt_method, precision="float64",
                                           torch_device=str(self._handle.device),

@@ -235,6 +235,24 @@ class PatchFlowObjective:
             return _lib.run_descent(lambda o, res, xl, xb, hist, tr: fn(plan, x0.ctypes.data, int(with_tv), o, res, xl, xb, hist, tr, stream),
                                     self._nx, descent, trace)
 
+    def minimize_lbfgs(self, x0: np.ndarray, n_eval: int = 32, history: int = 8, gtol: float = 1e-5, max_move: float = 10.0, max_ls: int = 10,
+                       c1: float = 1e-4, shrink: float = 0.5, curv_eps: float = 1e-10, step0: float = 1.0, with_tv: bool = True, trace: bool = False):
+        """L-BFGS with a backtracking line search from x0 [2*ph*pw] in ONE cmax_patch_plan_lbfgs call (the rules: include/cmax_hip.h): a
+        budget of n_eval evaluations enqueued behind each other, every accept / backtrack / reset decision taken on the device, one wait at
+        the end.  Returns a _lib.LbfgsResult (host arrays; x is the last ACCEPTED point, its losses never increase).  The iterate stays
+        within max_move of x0 in every entry, which is what lets the time slabs be decided ONCE, from max|x0| + max_move."""
+        if self._plan is None:
+            raise NotImplementedError("minimize_lbfgs needs the native plan (numeric hybrid weights, fused costs, no torch.distributed fall-back)")
+        x0 = np.ascontiguousarray(x0, dtype=np.float64).reshape(-1)
+        if x0.size != self._nx:
+            raise ValueError(f"x0 has {x0.size} elements, the patch grid needs {self._nx}")
+        lbfgs = _lib.lbfgs_descriptor(n_eval, history, max_ls, c1, shrink, curv_eps, gtol, step0, max_move)
+        self.ensure_time_slabs(np.array([float(np.abs(x0).max()) + abs(float(max_move))]))
+        fn, plan, stream = _lib.load().cmax_patch_plan_lbfgs, self._plan, F._stream()
+        with torch.cuda.device(self.handle.device):
+            return _lib.run_lbfgs(lambda o, res, x, hist, al, code, tr: fn(plan, x0.ctypes.data, int(with_tv), o, res, x, hist, al, code, tr, stream),
+                                  self._nx, lbfgs, trace)
+
     def hvp_numpy(self, x: np.ndarray, v: np.ndarray, disp_step: float = 0.05, exact: bool = True) -> np.ndarray:
         """Hessian-vector product on host arrays through cmax_patch_plan_hvp: exact, what the reference's
         torch.autograd.functional.vhp returns -- for time-aware objectives including the second-order adjoint of the

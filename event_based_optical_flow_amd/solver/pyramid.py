@@ -29,8 +29,8 @@ import scipy.ndimage as ndi
 from ..cmax import CMaxHandle
 from . import scipy_autograd
 from .patch_objective import PatchFlowObjective
-from .common import (DESCENT_OPTIMIZERS, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, flow_regularizer_config, calculate_flow_error_numpy,  # noqa: F401
-                     check_opt_method, global_best_refine, one_patch_guess, run_descent, whole_image_guess)
+from .common import (DESCENT_OPTIMIZERS, DEVICE_QUASI_NEWTON, SCIPY_OPTIMIZERS, PatchSolverCommon, _check_key_and_bool, flow_regularizer_config, calculate_flow_error_numpy,  # noqa: F401
+                     check_opt_method, global_best_refine, one_patch_guess, lbfgs_config, run_descent, run_lbfgs, whole_image_guess)
 
 logger = logging.getLogger(__name__)
 
@@ -71,6 +71,8 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
         self.visualizer = visualize_module
         self.opt_method = optimizer_config["method"]
         check_opt_method(self.opt_method)
+        if self.opt_method in DEVICE_QUASI_NEWTON:
+            lbfgs_config(optimizer_config)  # (unknown keys of optimizer.lbfgs: KeyError, at construction)
         self.padding = solver_config["outer_padding"] if "outer_padding" in solver_config else 0
         self.iwe_config = solver_config["iwe"]
         if self.iwe_config["method"] != "bilinear_vote":
@@ -175,6 +177,8 @@ class PyramidalPatchContrastMaximization(PatchSolverCommon):
                 x0 = self.initialize_random(self.scaled_n_patch[s]).reshape(-1)
             if self.opt_method in DESCENT_OPTIMIZERS:  # run_torch's loop, device-resident, once per scale; the motion is x_best
                 res = run_descent(objective, x0, self.opt_method, self.opt_config)
+            elif self.opt_method in DEVICE_QUASI_NEWTON:  # L-BFGS, device-resident, once per scale; the motion is the last accepted point
+                res = run_lbfgs(objective, x0, self.opt_config)
             else:
                 res = scipy_autograd.minimize(objective, x0, method=self.opt_method, precision="float64",
                                               torch_device=str(handle.device),

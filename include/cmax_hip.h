@@ -789,6 +789,105 @@ int cmax_objective_descend_batch(cmax_handle_t h, const cmax_objective_t *desc_h
                                  double *x_best_host, double *loss_history_host, double *x_trace_host, cmax_stream_t stream);
 
 /* =============================================================================================
+ * Device-resident L-BFGS with a backtracking (Armijo) line search: a quasi-Newton solve in ONE call.  The reference has no
+ * counterpart (its second-order methods are SciPy's, driven from the host through TorchWrapper): the formulas below ARE the
+ * contract.  A call consumes exactly n_eval evaluations e = 0 .. n_eval-1 of the objective, enqueued eagerly on the caller's
+ * stream (evaluation from the device-resident x -> loss and gradient left in device memory -> one k_lbfgs_step launch, which
+ * takes every decision and writes the next point), and waits ONCE, behind the last step.  All state is fp64 in device memory.
+ * cmax_lbfgs_t / cmax_lbfgs_result_t are new structs: the ABI version is unchanged.
+ *
+ * Notation: (x_a, L_a, g_a) the accepted point, d the direction, alpha the trial step, x_t the trial point, gd = g_a^T d;
+ * lo = x0 - max_move, hi = x0 + max_move (entrywise, rounded once); up to m = history pairs (s_i, y_i) in a ring, newest last.
+ *   trial     x_t[p] = min(max(x_a[p] + alpha * d[p], lo[p]), hi[p])      (the clamp only absorbs the rounding of the clipped alpha)
+ *   e = 0     evaluate at x0.  L or any entry of g not finite: status NONFINITE_START, terminate, x = x0 (final_loss = L as
+ *             evaluated, gnorm_inf = NaN).  Otherwise (x_a, L_a, g_a) <- (x0, L, g) (code start; no pair, n_iter stays 0); if
+ *             |g|inf <= gtol: status CONVERGED, terminate; otherwise CHOOSE.
+ *   e > 0     (not terminated)  ok = finite(L) and all finite(g) and L <= L_a + c1 * alpha * gd  -- ONE boolean.
+ *     not ok  n_ls += 1.  n_ls > max_ls and the history is empty: status LINESEARCH, terminate (code rejected).
+ *             n_ls > max_ls and the history is not empty: clear the history, n_ls = 0, CHOOSE from g_a (code reset).
+ *             Otherwise alpha <- shrink * alpha (code rejected) and the next trial is formed from the same x_a and d.
+ *     ok      (code accepted)  s = x_t - x_a (as actually stepped), y = g - g_a.  If y^T y > 0 and s^T y > curv_eps * y^T y: push
+ *             (s, y), dropping the oldest pair when m are held; otherwise the pair is skipped (Armijo alone does not guarantee
+ *             curvature).  (x_a, L_a, g_a) <- (x_t, L, g), n_iter += 1, n_ls = 0, last_alpha = alpha.  If |g|inf <= gtol: status
+ *             CONVERGED, terminate; otherwise CHOOSE.
+ *   CHOOSE    empty history: d = -g_a, alpha = min(1, step0 / |g_a|_1).  Otherwise d = -H g_a by the L-BFGS two-loop recursion
+ *             over the held pairs, oldest i = 0 .. newest i = k-1, rho_i = 1 / (s_i^T y_i):
+ *                 q = g_a;   for i = k-1 .. 0:  a_i = rho_i s_i^T q,  q -= a_i y_i;
+ *                 r = (s_{k-1}^T y_{k-1} / y_{k-1}^T y_{k-1}) q;   for i = 0 .. k-1:  b = rho_i y_i^T r,  r += (a_i - b) s_i;   d = -r
+ *             and alpha = 1.  If not g_a^T d < 0: clear the history and take the empty-history direction.
+ *             (The shipped kernel is the Gram form: it evaluates this recursion on the coefficients of d in the basis {s_i, y_i, g_a},
+ *             with every inner product taken from the Gram matrix of that basis, which it keeps between steps.  Equal in exact
+ *             arithmetic, not bit for bit: products read from the Gram matrix round differently from products of the vectors, by
+ *             an amount that grows with the conditioning of the pairs.  The tests hold the trial points of both forms to
+ *             1e-9 max(1, |x|inf) of the recursion above.)
+ *   BOX       then alpha <- min(alpha, the largest value with lo <= x_a + alpha * d <= hi): over the entries with d[p] > 0 the
+ *             minimum of (hi[p] - x_a[p]) / d[p], with d[p] < 0 of (lo[p] - x_a[p]) / d[p].  This alpha is the one the Armijo test
+ *             and the trial use.  Not alpha > 0: status BOX, terminate.  The box is what lets a caller decide anything that depends
+ *             on the size of x (time slabs) ONCE, from max|x0| + max_move.
+ *   after     termination: the device-resident x is x_a and stays there; the remaining evaluations still run at that finite point
+ *             (code idle, loss_history NaN, alpha 0) -- the host cannot know: the price of not waiting.  The budget exhausted while
+ *             still running: status BUDGET; the result is x_a -- a trial that was never accepted is never returned.
+ *   outputs   x [nx] = x_a;  loss_history[e] = L evaluated at e (NaN for idle evaluations);  alpha[e] = the alpha of the point evaluated
+ *             at e (0 for e = 0 and idle);  code[e];  x_trace (optional) row e = the point evaluated at e, row n_eval = the final x_a;
+ *             final_loss = L_a, gnorm_inf = |g_a|inf, n_iter = accepted steps, n_eval_used = evaluations up to and including the
+ *             terminating one (n_eval: none terminated), last_alpha = alpha of the last accepted step (0: none).
+ * The accepted losses are non-increasing by construction.  Every reduction runs through one fixed tree, without atomics: on a
+ * deterministic handle a solve is bit-repeatable.
+ * ============================================================================================= */
+#define CMAX_LBFGS_MAX_HISTORY 16
+#define CMAX_LBFGS_BUDGET 0          /* status: the budget ran out (also: still running) */
+#define CMAX_LBFGS_CONVERGED 1
+#define CMAX_LBFGS_LINESEARCH 2
+#define CMAX_LBFGS_BOX 3
+#define CMAX_LBFGS_NONFINITE_START 4
+#define CMAX_LBFGS_CODE_START 0      /* code[e] */
+#define CMAX_LBFGS_CODE_ACCEPTED 1
+#define CMAX_LBFGS_CODE_REJECTED 2
+#define CMAX_LBFGS_CODE_RESET 3
+#define CMAX_LBFGS_CODE_IDLE 4
+typedef struct {
+    int32_t n_eval;   /* 1 .. CMAX_DESCENT_MAX_ITER: evaluations per call */
+    int32_t history;  /* m: 1 .. CMAX_LBFGS_MAX_HISTORY */
+    int32_t max_ls;   /* >= 1: rejected trials in a row before a reset / LINESEARCH (four bytes of padding behind it) */
+    double c1;        /* Armijo constant, in (0, 0.5) */
+    double shrink;    /* backtracking factor, in (0, 1) */
+    double curv_eps;  /* >= 0 */
+    double gtol;      /* >= 0 */
+    double step0;     /* > 0: length (1-norm) of the first trial step along -g */
+    double max_move;  /* > 0: the box |x - x0|inf <= max_move */
+} cmax_lbfgs_t;
+typedef struct {
+    double final_loss;
+    double gnorm_inf;
+    double last_alpha;
+    int32_t n_iter;
+    int32_t n_eval_used;
+    int32_t status;   /* CMAX_LBFGS_* (four bytes of padding behind it) */
+} cmax_lbfgs_result_t;
+int cmax_sizeof_lbfgs(void);
+/* L-BFGS on a patch plan's objective (every plan cmax_patch_plan_descend takes: time-aware, scale_later, basis plans, plans with a
+ * flow regulariser).  x0_host [nx]; res_host, x_host [nx], loss_history_host [n_eval], alpha_host [n_eval], code_host [n_eval]:
+ * filled; x_trace_host [(n_eval + 1) * nx] or NULL.
+ * Checked in this order, before any launch: the descriptor (CMAX_EINVAL naming the field: n_eval, history, max_ls, c1, shrink,
+ * curv_eps, gtol, step0, max_move, all finite; needs neither plan nor device); null pointers (CMAX_EINVAL); a handle with a
+ * communicator (CMAX_EUNSUPPORTED); a weighted handle (CMAX_EUNSUPPORTED, as cmax_patch_plan_descend).  Deterministic handles are
+ * allowed.  State: one plan-owned device buffer of 8 * (1112 + (4 + 2 m) nx + 2 n_eval + ceil(n_eval / 2) + (x_trace_host ? (n_eval + 1) nx : 0))
+ * bytes, kept while it is large enough; evaluation 0 reads none of it: a call never sees what an earlier call left.  The
+ * handle's host-side evaluation state advances as n_eval cmax_patch_plan_evaluate calls would advance it; never replayed from a
+ * graph.  Blocks until the results are on the host.                                                                      */
+int cmax_patch_plan_lbfgs(cmax_patch_plan_t plan, const double *x0_host, int with_tv, const cmax_lbfgs_t *lbfgs,
+                          cmax_lbfgs_result_t *res_host, double *x_host, double *loss_history_host, double *alpha_host,
+                          int32_t *code_host, double *x_trace_host, cmax_stream_t stream);
+/* L-BFGS on a 2-DoF fused objective: what cmax_objective runs per evaluation (the general sequence), theta in fp64 in device
+ * memory -- desc->motion_dtype must be CMAX_F64 and desc->model CMAX_MODEL_2DOF (CMAX_EINVAL with the reason otherwise), then the
+ * step launch.  nx = 2.  Weighted and deterministic handles are allowed; a handle with a communicator is CMAX_EUNSUPPORTED.  The
+ * state is handle-owned (16 doubles of theta | gradient | result in front of it) and counted in cmax_handle_info.  Same
+ * descriptor checks, outputs and blocking as cmax_patch_plan_lbfgs.                                                          */
+int cmax_objective_lbfgs(cmax_handle_t h, const cmax_objective_t *desc_host, const double *theta0_host, const cmax_lbfgs_t *lbfgs,
+                         cmax_lbfgs_result_t *res_host, double *x_host, double *loss_history_host, double *alpha_host,
+                         int32_t *code_host, double *x_trace_host, cmax_stream_t stream);
+
+/* =============================================================================================
  * Flow-basis plan: the optimiser's objective for a motion model that is LINEAR in its parameters, in one call.
  *   theta [K] (host fp64)  ->  dense flow D = sum_k theta_k B_k (cmax_basis_to_dense) * t_scale
  *     [-> voxel (cmax_voxel_construct)] -> fp32 -> loss = sum_i weight_i * cmax_objective(term_i)
