@@ -30,6 +30,12 @@ struct EventLayout {
     static constexpr int kAccSmall = 256 * ACC_SMALL_GROUPS;  // ... owned voxel segments of few, well-filled (tile, bin) groups (kGradOwnedSmall)
     static_assert((double)kSegMaxNS * kFixNS < 2147483648.0, "fixed-point vote accumulation would overflow");
     static constexpr int kBlkShift = kBig ? 6 : 5;  // Window::bmask: one bit per kSlots / 64 consecutive slots (see phase_warp)
+    // The head of K1 / K3 that loads everything at entry, beside the segment descriptor, and whose dead waves load unconditionally
+    // (k_vote, issue_event_loads): the standard segments.  Mid and big segments keep the head they had -- with the new one six dense
+    // b512 and one m512 instantiation of k_grad went from 64 to 66 VGPRs, i.e. lost a wave per SIMD, a weighted b512::k_vote began to
+    // spill, and the multi-round launches of big segments, which are bound by issue slots and not by the latency of their first loads,
+    // lost 9 - 16 % (cfg3 31.8 -> 37.0 us, 64M events 247 -> 277): profiles/head_loads_resources.txt, profiles/head_loads_ab.txt.
+    static constexpr bool kEntryHead = kSlots == 2048;
     static constexpr int kShiftWords = kSlots / 8;  // 32-bit words of cell offsets per (reference time, segment): 8 slots per word
     // compact events (see EventLoads), bytes
     static constexpr int kCompactPix = 4 * kSlots, kCompactHdr = 4 * kSlots + kSlots / 2, kCompactStride = kCompactHdr + 64;
@@ -68,10 +74,10 @@ struct b1024 : EventLayout<1024, 4096, 8192, 6, 3> { static constexpr Layout kId
 // 1/64ths of the segment's slots hold an event whose cell moved) and, in the segment's `shifts` words, a nibble per slot = the cell's
 // offset from the fp32 one (row | col << 2, two-bit two's complement).  `nibbles` returns this thread's own (slot u in bits [4u, 4u + 4)).
 //
-// The event loads of a workgroup, issued FIRST THING in a kernel: they need nothing but the segment and the event pointer, both of
-// which a workgroup holds without having seen the kernel's argument block (kernel parameters, k_vote) -- everything that reads the
-// argument block is then fetched while the events are on their way (a workgroup's first dependent loads are ~3 of the ~6 us it
-// lives: tools/timeline.py).
+// The event loads of a workgroup, issued as soon as its segment has arrived: they need nothing but the segment and the event pointer,
+// which a workgroup holds without having seen the kernel's argument block (kernel parameters, k_vote).  Whatever else the warp needs
+// from memory -- theta, the time extremes, the argument block's words -- is loaded BESIDE the segment and has arrived with it (see
+// k_vote: the compiler does not overlap these with the events of its own accord).
 // Default layout: each thread holds kEPT CONSECUTIVE sorted events (slot u = local index kEPT * thread + u,
 // counted from the segment start rounded down to an even index: the buffer is 16-byte aligned and padded),
 // read with 16-byte loads.  Neighbouring lanes then hold events kEPT apart -- mostly different source
@@ -127,17 +133,26 @@ __device__ __forceinline__ void issue_event_loads(const uint2 *__restrict__ evp,
     // workgroup empty).  Such a wave skips the loads, the warp arithmetic and -- through `wave_live` -- the vote /
     // gather phases of the callers; it still takes part in the barriers, the window initialisation and the flush.
     el.wave_live = __builtin_amdgcn_readfirstlane(local_index(0)) < cnt + odd;
-    // All event loads of a live wave are issued back to back, UNCONDITIONALLY: a pair that lies behind the segment's last event
+    // All event loads are issued back to back, UNCONDITIONALLY, by dead waves too: a pair that lies behind the segment's last event
     // re-reads the segment's last pair (its slots are invalid and masked by `valid` / rc == 0 below; the flow they index is
-    // in bounds).  (With `if (l0 < cnt) raw[j] = load` the compiler put every load into its own exec-masked block and waited for
-    // it there -- s_waitcnt vmcnt(0) behind each global_load_dwordx4: two (512 threads) or four (256) dependent round trips to
-    // memory at the head of K1 and K3.)
-    const int l_last = (cnt + odd - 1) & ~1;  // local index of the segment's last pair
-#pragma unroll
-    for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
-    if (el.wave_live) {  // wave-uniform
+    // in bounds; an empty segment reads the pair at its start, which the buffer's padding holds).  (With `if (l0 < cnt) raw[j] = load`
+    // the compiler put every load into its own exec-masked block and waited for it there -- s_waitcnt vmcnt(0) behind each
+    // global_load_dwordx4: two (512 threads) or four (256) dependent round trips to memory at the head of K1 and K3.  With the
+    // loads inside `if (wave_live)` behind a zero initialisation the same happened once more behind a scalar branch: the merge of
+    // the loaded registers with the zeros is a copy IN that block, and K1 waited for its events there, in front of every other
+    // load of its head -- profiles/head_loads_isa.txt.  A dead wave never looks at what it loaded.)
+    if constexpr (L::kEntryHead) {
+        const int l_last = max((cnt + odd - 1) & ~1, 0);  // local index of the segment's last pair
 #pragma unroll
         for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(seg_ev + min(local_index(2 * j), l_last));
+    } else {  // (mid and big segments: live waves only, see EventLayout::kEntryHead)
+        const int l_last = (cnt + odd - 1) & ~1;
+#pragma unroll
+        for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = make_uint4(0u, 0u, 0u, 0u);
+        if (el.wave_live) {  // wave-uniform
+#pragma unroll
+            for (int j = 0; j < L::kEPT / 2; ++j) el.raw[j] = *reinterpret_cast<const uint4 *>(seg_ev + min(local_index(2 * j), l_last));
+        }
     }
 }
 // word k (0 .. 3) of a 16-byte register quadruple, k a compile-time constant after unrolling
@@ -217,11 +232,60 @@ __global__ void __launch_bounds__(L::kThr) k_pack_compact(const int4 *__restrict
 // F64FLOW (dense / voxel): the motion is the caller's fp64 flow, split -- wp.motion is its high plane, the low plane lies behind the field
 // (k_split_motion); read by the border branch only.  A template argument, not a branch on wp.motion_f64: the kernels of an fp32 call
 // are the ones they were (profiles/flow64_resources.txt).
-template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, bool F64FLOW = false, typename Init>
+//
+// HEAD: what a kernel fetched at its entry, beside its segment descriptor (WarpHead: K1 and K3), or NoHead -- the kernels that read the
+// batch period and theta here, through the argument block's pointers.
+struct NoHead {};
+struct WarpHead {
+    double period;      // the batch period (1 when the times are normalised)
+    double thd0, thd1;  // 2-DoF: theta as the caller holds it
+};
+// The head's loads through the LEADING kernel parameters (the first 14 argument dwords arrive in SGPRs: build.py), all of them
+// uniform, unconditional and independent of the argument block, so that they leave with the segment descriptor's load and come back
+// under its wait: the batch's time extremes and -- 2-DoF -- theta in either dtype (an fp32 theta is read twice rather than behind a
+// branch: a load in a block of its own is waited for in that block).  The words are kept RAW until the caller has pinned them together
+// with its segment (CMAX_HEAD_PIN): the conversions to fp64 are VALU work, and the compiler branches around them on the flags -- taken
+// in front of the pin, those branches cut the loads into groups with a wait each (profiles/head_loads_isa.txt).
+// flags: kHeadNormalize | kHeadMotionF64 (WarpParams::normalize / motion_f64).
+constexpr int kHeadNormalize = 1, kHeadMotionF64 = 2;
+struct HeadWords {
+    int4 t;      // (tmin, tmax) as 32-bit words
+    int2 lo, hi; // theta: fp32 (lo.x, lo.y); fp64 lo, hi
+};
+template <int MODEL>
+__device__ __forceinline__ HeadWords load_head_words(const float *__restrict__ motion, const double *__restrict__ tmm, int flags) {
+    HeadWords w;
+    w.t = *reinterpret_cast<const int4 *>(tmm);  // (the handle's own d_tmm: the base of a device allocation, see warp_params)
+    w.lo = make_int2(0, 0);
+    w.hi = make_int2(0, 0);
+    if (MODEL == CMAX_MODEL_2DOF) {
+        // (dword by dword: an fp32 theta of the caller's -- a slice of a tensor -- is only 4-byte aligned)
+        const int *mw = reinterpret_cast<const int *>(motion);
+        const int o = (flags & kHeadMotionF64) ? 2 : 0;
+        w.lo = make_int2(mw[0], mw[1]);
+        w.hi = make_int2(mw[o], mw[o + 1]);
+    }
+    return w;
+}
+#define CMAX_HEAD_PIN_WORDS(HEADW) "s"((HEADW).t.x), "s"((HEADW).t.y), "s"((HEADW).t.z), "s"((HEADW).t.w), "s"((HEADW).lo.x), "s"((HEADW).lo.y), "s"((HEADW).hi.x), "s"((HEADW).hi.y)
+__device__ __forceinline__ WarpHead decode_head_words(const HeadWords &w, int flags) {
+    WarpHead hd;
+    hd.period = (flags & kHeadNormalize) ? 1.0 : __hiloint2double(w.t.w, w.t.z) - __hiloint2double(w.t.y, w.t.x);
+    if (flags & kHeadMotionF64) {
+        hd.thd0 = __hiloint2double(w.lo.y, w.lo.x);
+        hd.thd1 = __hiloint2double(w.hi.y, w.hi.x);
+    } else {
+        hd.thd0 = (double)__int_as_float(w.lo.x);
+        hd.thd1 = (double)__int_as_float(w.lo.y);
+    }
+    return hd;
+}
+template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, bool F64FLOW = false, typename Init, class HEAD>
 __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams &wp, int4 sg, EventLoads<L> &el, unsigned (&rc)[L::kEPT],
                                               float (&fa)[L::kEPT], float (&fb)[L::kEPT], float (&fdt)[L::kEPT], int (&fsrc)[L::kEPT],
                                               uint4 *s_box, const int4 *known, const unsigned *__restrict__ shifts, Init init, bool &wave_live,
-                                              unsigned &nibbles) {
+                                              unsigned &nibbles, const HEAD &head) {
+    constexpr bool kHead = std::is_same_v<HEAD, WarpHead>;
     constexpr bool kExact = MODEL >= 0;  // cells of events on a cell border are decided in fp64 (warp_exact); the un-warped image has no motion
     constexpr bool kFlow = MODEL == CMAX_MODEL_DENSE || MODEL == CMAX_MODEL_VOXEL;
     static_assert(!(KNOWN && !WANT_DT), "K3 re-uses K1's windows");
@@ -238,13 +302,18 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     float negd = -wp.d;
     if (L::kBig) asm volatile("" : "+v"(negd));  // (one VGPR for the whole loop: as an SGPR it is copied in front of every event's fma, whose other operands are scalar too)
     const uint4 (&raw)[L::kEPT / 2] = el.raw;
-    const double period = wp.normalize ? 1.0 : wp.tmm[1] - wp.tmm[0];
+    double period;
+    if constexpr (kHead) period = head.period;
+    else period = wp.normalize ? 1.0 : wp.tmm[1] - wp.tmm[0];
     const float tscale = (float)period;  // (time_scale)
     const float mcoef = exact_margin_coef(wp.d, tscale);
     float th0 = 0.f, th1 = 0.f, mt = 0.f;
     double thd0 = 0.0, thd1 = 0.0;  // theta as the caller holds it: decides the cells of events on a cell border (warp_exact)
     if (MODEL == CMAX_MODEL_2DOF) {
-        if (wp.motion_f64) {  // (as 32-bit words: scalar loads, like the fp32 branch)
+        if constexpr (kHead) {
+            thd0 = head.thd0;
+            thd1 = head.thd1;
+        } else if (wp.motion_f64) {  // (as 32-bit words: scalar loads, like the fp32 branch)
             const int *mw = reinterpret_cast<const int *>(wp.motion);
             thd0 = __hiloint2double(mw[1], mw[0]);
             thd1 = __hiloint2double(mw[3], mw[2]);
@@ -568,6 +637,15 @@ __device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams 
     return win;
 }
 
+// (the kernels without a WarpHead)
+template <class L, int MODEL, bool FRAC, bool WANT_DT, bool STRIDED = false, bool KNOWN = false, bool F64FLOW = false, typename Init>
+__device__ __forceinline__ Window phase_warp(const EvView &ev, const WarpParams &wp, int4 sg, EventLoads<L> &el, unsigned (&rc)[L::kEPT],
+                                              float (&fa)[L::kEPT], float (&fb)[L::kEPT], float (&fdt)[L::kEPT], int (&fsrc)[L::kEPT],
+                                              uint4 *s_box, const int4 *known, const unsigned *__restrict__ shifts, Init init, bool &wave_live,
+                                              unsigned &nibbles) {
+    return phase_warp<L, MODEL, FRAC, WANT_DT, STRIDED, KNOWN, F64FLOW>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, known, shifts, init, wave_live, nibbles, NoHead{});
+}
+
 // Local word index of an event's top-left corner in the fast window, origin = (r0 + 16384) * stride + c0 + 16384
 // (one v_mad_u32_u24: both factors are below 2^24).
 // An empty slot (rc == 0) gives 0 - origin, a huge unsigned, and is sent to `scratch` = kWinCap + lane: a per-lane
@@ -584,10 +662,14 @@ __device__ __forceinline__ int fast_index(unsigned rc, unsigned neg_origin, int 
 // ---------------------------------------------------------------------------------------------
 // MU: also accumulate RefArgs::musum (blurred variance with a gradient) -- its own instantiation, so that the kernel every
 // other objective runs carries none of it
-// Kernel parameters: the work list first.  A workgroup's first three memory operations depend on each other -- kernel arguments ->
-// its segment -> its events -- and are ~3 of the ~6 us it lives (tools/timeline.py, profiles/r04_timeline.txt); with the list's
-// address among the first 16 argument dwords the command processor hands it over in SGPRs (-amdgpu-kernarg-preload-count, build.py)
-// and the segment is fetched without waiting for the argument block.
+// Kernel parameters: what the head dereferences first.  The first 14 argument dwords arrive in SGPRs (-amdgpu-kernarg-preload-count,
+// build.py: 16 user SGPRs, two of them the argument block's own address), and they hold every pointer the head reads through: the work
+// list, the events, theta and the batch's time extremes (K3: K1's windows as well).  As compiled, the head is then TWO dependent round
+// trips -- { segment, theta, extremes, [window,] the argument block's words } under one scalar wait, then the events under one vector
+// wait in front of the first warp instruction (profiles/head_loads_isa.txt).  Until that listing was taken the head was described
+// as "arguments -> segment -> events"; the compiled kernels had four to five dependent trips: the events were waited for inside
+// issue_event_loads (K1), the argument block was read behind them, and the time extremes and theta -- through pointers out of the
+// argument block -- behind that.
 // (second launch bound = waves per SIMD the register allocation has to leave room for: the 512 x 8 kernel of the big segments sat at 68
 // VGPRs -- seven waves -- once the border tracking joined its warp loop; scheduled for 64 it keeps eight: K1 of 20M events 46.2 -> see
 // profiles/r04_ablation.txt)
@@ -597,19 +679,34 @@ __device__ __forceinline__ int fast_index(unsigned rc, unsigned neg_origin, int 
 // EXACT = called with an ExactFlow behind ra (dense / voxel, cmax_objective_t::motion_dtype == CMAX_F64): phase_warp's F64FLOW -- instantiations
 // of their own, the ones without the argument are untouched.
 template <class L, int MODEL, bool FRAC, bool MU = false, bool WEIGHTED = false, class... EXACT>
-__global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, EvView ev, WarpParams wp, RefArgs ra, EXACT...) {
+__global__ void __launch_bounds__(L::kThr, L::kVoteWaves)
+k_vote(const int4 *__restrict__ segs, int nseg, int z_motion, const uint2 *__restrict__ evp, const char *__restrict__ cev, const float *__restrict__ motion,
+       const double *__restrict__ tmm, int head_flags, EvView ev, WarpParams wp, RefArgs ra, EXACT...) {
     constexpr bool F64FLOW = sizeof...(EXACT) > 0;
     static_assert(sizeof...(EXACT) <= 1 && (std::is_same_v<EXACT, ExactFlow> && ...), "k_vote: an ExactFlow or nothing");
     __shared__ int s_win[L::kWinCap + kScratch];
     __shared__ uint4 s_box[L::kNW];
     CMAX_STAMP(0, 0);
-    // first thing: this workgroup's segment (segs, nseg and evp arrive in SGPRs: the load does not wait for the argument block)
+    // first thing: this workgroup's segment, and with it everything else the head reads from memory -- the batch period and theta
+    // (load_head_words; standard segments).  All leading parameters arrive in SGPRs: none of these loads waits for the argument block.
     const int sidx = segment_of_block(nseg);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
+    motion += (int64_t)blockIdx.z * z_motion;  // blockIdx.z = candidate motion (cmax_objective_batch; one candidate otherwise)
     ev.ev = evp;
+    wp.motion = motion;
+    wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time
+    HeadWords headw = {};
+    if constexpr (L::kEntryHead) {
+        headw = load_head_words<MODEL>(motion, tmm, head_flags);
+        // ... and the words of the argument block the warp needs: ONE batch of scalar loads, issued before the first wait.  (Left to
+        // the compiler they followed the wait for the events, in two dependent groups: profiles/head_loads_isa.txt.)
+        asm volatile("" ::"s"(sg.x), "s"(sg.y), CMAX_HEAD_PIN_WORDS(headw), "s"(wp.d), "s"(wp.H), "s"(wp.W), "s"(wp.ph), "s"(wp.pw));
+    }
     EventLoads<L> el;
     issue_event_loads<L, false>(evp, cev, sidx, sg, el);
+    std::conditional_t<L::kEntryHead, WarpHead, NoHead> head;  // (mid / big segments: phase_warp reads period and theta itself)
+    if constexpr (L::kEntryHead) head = decode_head_words(headw, head_flags);
     static_assert(!(MU && WEIGHTED), "the vote sums of the blurred variance count events: weighted handles take the unfused image path");
     float fw[L::kEPT];
     float wscale = 0.f, inv_fix = L::kInvFixNS;  // K / wmax; 1 / K, weighted: wmax / K
@@ -617,9 +714,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
         wscale = ra.wnorm[0] * L::kFixNS;
         inv_fix = ra.wnorm[1] * L::kInvFixNS;
     }
-    wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time
     wp.d_lo = ra.d_lo[blockIdx.y];  // (read by warp_exact only: the compiler sinks this scalar load into that rare path)
-    wp.motion += (int64_t)blockIdx.z * ra.z_motion;  // blockIdx.z = candidate motion (cmax_objective_batch; one candidate otherwise)
     const int zy = (int)(blockIdx.z * gridDim.y + blockIdx.y);  // (candidate, reference time): index of this launch's windows / offsets
     float *__restrict__ iwe = ra.img[blockIdx.y] + blockIdx.z * ra.z_img;
     long long *__restrict__ iwe64 = ra.img64[blockIdx.y];  // deterministic mode: integer image instead (launch-uniform)
@@ -637,7 +732,7 @@ __global__ void __launch_bounds__(L::kThr, L::kVoteWaves) k_vote(const int4 *__r
     const Window win = phase_warp<L, MODEL, FRAC, false, false, false, F64FLOW>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, s_box, nullptr, nullptr, [&](const Window &w) {
         const int wn = w.h * w.stride;
         for (int i = threadIdx.x; i < wn; i += L::kThr) s_win[i] = 0;
-    }, live, nibbles);
+    }, live, nibbles, head);
     CMAX_STAMP(0, 3);
     // the weights of this thread's slots: loaded HERE, not with the events -- live through the warp they are kEPT more registers at the
     // kernel's peak, and the b512 instantiations (eight events per thread under the 64-VGPR bound of kVoteWaves) spilled them to scratch;
@@ -1073,9 +1168,15 @@ __device__ __forceinline__ void stats_inside_role(const float *__restrict__ img,
 //             WEIGHTED term) all follow
 template <class L, int MODEL, bool FRAC, int FOLD, int VARIANT, bool WEIGHTED = false>
 __global__ void __launch_bounds__(L::kThr)
-k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base, int stat_blocks, EvView ev,
-       WarpParams wp, RefArgs ra, ObjParams op, const double *__restrict__ stat, double *__restrict__ gpart_base, float *__restrict__ gflow,
-       double *__restrict__ result) {
+k_grad(const int4 *__restrict__ segs, int nseg, int head_word, const uint2 *__restrict__ evp, const char *__restrict__ cev, const int4 *__restrict__ win_base,
+       const float *__restrict__ motion, const double *__restrict__ tmm, EvView ev, WarpParams wp, RefArgs ra, ObjParams op,
+       const double *__restrict__ stat, double *__restrict__ gpart_base, float *__restrict__ gflow, double *__restrict__ result) {
+    // head_word (the 14 preloaded dwords hold six pointers, nseg and this): bits 0-1 = the head's flags (load_head_words), bits 2-4 =
+    // the launch's reference times (gridDim.y: read from the argument block it was a dependent load in front of the window's); above
+    // them what else the head of this MODEL needs -- 2-DoF: floats between the candidates' thetas (cmax_objective_batch: blockIdx.z),
+    // flow models (one candidate per launch): RefArgs::stat_blocks, the leading workgroups that run the statistics (kFoldStatsInside)
+    const int head_flags = head_word & 3, n_ref_grid = (head_word >> 2) & 7;
+    const int stat_blocks = MODEL == CMAX_MODEL_2DOF ? 0 : head_word >> 5;
     constexpr bool STRIDED = VARIANT == kGradStrided;
     constexpr bool kOwned = VARIANT == kGradOwned || VARIANT == kGradOwnedSmall;
     constexpr bool kDet = VARIANT == kGradDet;  // deterministic mode: every per-event term is added as a 64-bit integer
@@ -1090,24 +1191,59 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
         return;
     }
     CMAX_STAMP(1, 0);
-    // first thing: this workgroup's segment and the window K1 used for it (all five leading arguments arrive in SGPRs: neither load
-    // waits for the argument block)
+    // first thing: this workgroup's segment, the window K1 used for it, the batch period and theta (load_head_words) -- the fourteen
+    // leading argument dwords arrive in SGPRs, so none of these loads waits for the argument block and all come back under one wait
     const int sidx = segment_of_block(nseg, kInside ? blockIdx.x - (unsigned)stat_blocks : blockIdx.x);
     if (sidx >= nseg) return;
     const int4 sg = segs[sidx];
-    const int zy = (int)(blockIdx.z * gridDim.y + blockIdx.y);  // (candidate of cmax_objective_batch, reference time)
+    // (mid / big segments, which keep the head they had, also keep its statements and their order: the 512 x 8 kernels sit at their
+    // register lines, profiles/head_loads_resources.txt)
+    const int zy = (int)(blockIdx.z * (L::kEntryHead ? (unsigned)n_ref_grid : gridDim.y) + blockIdx.y);  // (candidate of cmax_objective_batch, reference time)
     const int4 *known = win_base + (int64_t)zy * nseg + sidx;
+    int4 known_win = make_int4(0, 0, 0, 0);
     ev.ev = evp;
-    wp.motion += (int64_t)blockIdx.z * ra.z_motion;
     EventLoads<L> el;
-    issue_event_loads<L, VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
-    static_assert(!WEIGHTED || (!kDet && !kInside && FOLD != kFoldDeferred), "weighted handles: the general K1 -> statistics -> K3 path");
+    std::conditional_t<L::kEntryHead, WarpHead, NoHead> head;  // (mid / big segments: phase_warp reads period and theta itself)
     float fw[L::kEPT];
-    if constexpr (WEIGHTED) load_slot_weights<L, VARIANT == kGradStrided>(ra.wgt, sg, fw);
-    wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
-    const int k = ra.k0 + (int)blockIdx.y;
-    const float *__restrict__ img = ra.img[blockIdx.y] + blockIdx.z * ra.z_img;
-    float *__restrict__ zero_img = ra.zero[blockIdx.y] ? ra.zero[blockIdx.y] + blockIdx.z * ra.z_img : nullptr;
+    static_assert(!WEIGHTED || (!kDet && !kInside && FOLD != kFoldDeferred), "weighted handles: the general K1 -> statistics -> K3 path");
+    int k;
+    const float *__restrict__ img;
+    int64_t z_img;
+    if constexpr (L::kEntryHead) {
+        if (MODEL == CMAX_MODEL_2DOF) motion += (int64_t)blockIdx.z * (head_word >> 5);
+        else motion += (int64_t)blockIdx.z * ra.z_motion;  // (a flow is first read behind the events)
+        known_win = *known;
+        known = &known_win;
+        const HeadWords headw = load_head_words<MODEL>(motion, tmm, head_flags);
+        wp.motion = motion;
+        wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
+        // ... and the words of the argument block that the warp, the window's staging and the wave that writes the loss need: ONE batch of
+        // scalar loads, issued before the first wait (as in k_vote) -- the window's pixel loads then follow the segment's wait directly.
+        // Only values AS LOADED are pinned: arithmetic on one of them in front of the pin is a use, and the compiler puts a wait there
+        // and the loads it has not issued yet behind it.
+        const float *const img_y = ra.img[blockIdx.y];
+        z_img = ra.z_img;
+        const int k0 = ra.k0;
+        const int64_t z_raw = ra.z_raw;              // (the address of the raw sums and the image to clear: used in front of the window's
+        float *const zero_y = ra.zero[blockIdx.y];  // pixel loads, where they were a scalar wait of their own)
+        asm volatile("" ::"s"(sg.x), "s"(sg.y), "s"(known_win.x), "s"(known_win.y), "s"(known_win.z), "s"(known_win.w), CMAX_HEAD_PIN_WORDS(headw), "s"(wp.d), "s"(wp.H),
+                     "s"(wp.W), "s"(wp.ph), "s"(wp.pw), "s"(wp.Hp), "s"(wp.Wp), "s"(img_y), "s"(z_img), "s"(op.omit), "s"(k0), "s"(gpart_base), "s"(result), "s"(z_raw),
+                     "s"(zero_y));
+        k = k0 + (int)blockIdx.y;
+        img = img_y + blockIdx.z * z_img;
+        issue_event_loads<L, VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
+        head = decode_head_words(headw, head_flags);
+        if constexpr (WEIGHTED) load_slot_weights<L, VARIANT == kGradStrided>(ra.wgt, sg, fw);
+    } else {
+        wp.motion += (int64_t)blockIdx.z * ra.z_motion;
+        issue_event_loads<L, VARIANT == kGradStrided>(evp, cev, sidx, sg, el);
+        if constexpr (WEIGHTED) load_slot_weights<L, VARIANT == kGradStrided>(ra.wgt, sg, fw);
+        wp.d = ra.d[blockIdx.y];  // blockIdx.y = reference time of this workgroup
+        k = ra.k0 + (int)blockIdx.y;
+        z_img = ra.z_img;
+        img = ra.img[blockIdx.y] + blockIdx.z * ra.z_img;
+    }
+    float *__restrict__ zero_img = ra.zero[blockIdx.y] ? ra.zero[blockIdx.y] + blockIdx.z * z_img : nullptr;
     // 2-DoF: the RAW SUMS of reference time k -- kRawLines accumulators, one 128-byte line each, of two doubles (sum dt g) or, with
     // deferred statistics, six (k_finish_lines / k_finish_raw / cmax_finalize_raw_host fold them)
     double *__restrict__ gpart = gpart_base ? gpart_base + blockIdx.z * ra.z_raw + (int64_t)k * kRawStride : nullptr;
@@ -1259,7 +1395,7 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
     const unsigned *__restrict__ shifts = ra.shifts + ((int64_t)zy * nseg + sidx) * L::kShiftWords;
     bool live;  // this wave holds events (wave-uniform)
     unsigned nib_unused;
-    const Window win = phase_warp<L, MODEL, FRAC, true, STRIDED, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused);
+    const Window win = phase_warp<L, MODEL, FRAC, true, STRIDED, true>(ev, wp, sg, el, rc, fa, fb, fdt, fsrc, nullptr, known, shifts, load_window, live, nib_unused, head);
     CMAX_STAMP_AFTER(1, 1, rc[L::kEPT - 1]);
     if (threadIdx.x < kScratch) s_win[L::kWinCap + threadIdx.x] = 0.f;  // empty slots / masked corners read 0 from here
     __syncthreads();
@@ -1693,11 +1829,11 @@ k_grad(const int4 *__restrict__ segs, int nseg, const uint2 *__restrict__ evp, c
             // getting it out again (K1 in the pipeline 8.2 us vs 6.1 us back to back; with sc1 zeroing 7.6).
             const int npix = wp.Hp * wp.Wp;
             if ((npix & 3) == 0 && (reinterpret_cast<uintptr_t>(zero_img) & 15u) == 0) {
-                const int n4 = npix >> 2, chunk4 = (n4 + nseg - 1) / nseg;
+                const int n4 = npix >> 2, chunk4 = ra.zero_chunk4;  // (from the host: the division was ~80 scalar instructions in every wave)
                 const int q1 = min(n4, (sidx + 1) * chunk4);
                 for (int q = sidx * chunk4 + (int)threadIdx.x; q < q1; q += L::kThr) store_zero4_sc1(zero_img + 4 * (int64_t)q);
             } else {
-                const int chunk = (npix + nseg - 1) / nseg, p1 = min(npix, (sidx + 1) * chunk);
+                const int chunk = ra.zero_chunk, p1 = min(npix, (sidx + 1) * chunk);
                 for (int p = sidx * chunk + (int)threadIdx.x; p < p1; p += L::kThr)
                     __hip_atomic_store(&zero_img[p], 0.f, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
             }

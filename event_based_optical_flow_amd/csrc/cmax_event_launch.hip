@@ -408,6 +408,9 @@ static RefArgs weighted_args(const cmax_handle_s *h, const RefArgs &ra_in) {
     return ra;
 }
 
+// WarpParams::normalize / motion_f64 as K1 and K3 take them among their leading parameters (load_head_words)
+static int head_flags(const WarpParams &wp) { return (wp.normalize ? kHeadNormalize : 0) | (wp.motion_f64 ? kHeadMotionF64 : 0); }
+
 template <int MODEL>
 void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra_in, int n_ref, hipStream_t s, int nz) {
     const dim3 grid(seg_blocks(h->nseg), n_ref, nz);  // z: candidate motions of cmax_objective_batch
@@ -420,13 +423,13 @@ void launch_vote(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const
                 using L = decltype(l);
                 with_bool(h->has_frac, [&](auto frac) {
                     if (ra.wgt) {  // weighted handle (never with the vote sums: eval_plan)
-                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev, wp,
-                                           ra, exact...);
+                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, false, true, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ra.z_motion, ev.ev,
+                                           cev, wp.motion, wp.tmm, head_flags(wp), ev, wp, ra, exact...);
                         return;
                     }
                     with_bool(ra.musum[0] != nullptr, [&](auto mu) {
-                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value, false, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ev.ev, cev, ev,
-                                           wp, ra, exact...);
+                        hipLaunchKernelGGL((k_vote<L, MODEL, frac.value, mu.value, false, decltype(exact)...>), grid, dim3(L::kThr), 0, s, h->d_segs, h->nseg, ra.z_motion,
+                                           ev.ev, cev, wp.motion, wp.tmm, head_flags(wp), ev, wp, ra, exact...);
                     });
                 });
             });
@@ -454,12 +457,21 @@ void launch_grad(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const
     const int nseg = seg_n < 0 ? h->nseg : seg_n;
     const dim3 grid(seg_blocks(nseg) + (fold == kFoldStatsInside ? ra_in.stat_blocks : 0), n_ref, nz);
     ProfScope prof(h, kProfGrad, s);
-    const RefArgs ra = weighted_args(h, ra_in);
+    RefArgs ra = weighted_args(h, ra_in);
+    // deferred statistics: the slice of the next evaluation's vote image each workgroup clears, known here once per launch
+    const int npix = wp.Hp * wp.Wp;
+    ra.zero_chunk = nseg > 0 ? (npix + nseg - 1) / nseg : 0;
+    ra.zero_chunk4 = nseg > 0 ? (npix / 4 + nseg - 1) / nseg : 0;
     const char *cev = compact_events<MODEL>(h, seg0);
+    // k_grad's head word: the head's flags, the grid's reference times, and above them the candidates' stride (2-DoF) or the statistics
+    // workgroups (flow models)
+    const int head_payload = MODEL == CMAX_MODEL_2DOF ? ra.z_motion : (fold == kFoldStatsInside ? ra.stat_blocks : 0);
+    if (n_ref < 1 || n_ref > 4 || head_payload < 0 || head_payload >= (1 << 26)) std::abort();  // (three bits, 26 bits: what the word has room for)
+    const int head_word = head_flags(wp) | n_ref << 2 | head_payload << 5;
     auto launch = [&](auto l, auto frac, auto fold_c, auto variant, auto weighted) {
         using L = decltype(l);
-        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, weighted.value>), grid, dim3(L::kThr), 0, s, segs, nseg, ev.ev,
-                           cev, (const int4 *)ra.win, ra.stat_blocks, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
+        hipLaunchKernelGGL((k_grad<L, MODEL, frac.value, fold_c.value, variant.value, weighted.value>), grid, dim3(L::kThr), 0, s, segs, nseg, head_word, ev.ev, cev,
+                           (const int4 *)ra.win, wp.motion, wp.tmm, ev, wp, ra, op, h->d_stat, gpart, gflow, result);
     };
     if (h->deterministic) {  // one workgroup size, two ways of obtaining dL/dIWE (objective_finish runs the unfused image path)
         with_layout<b512, m512, t256>(plain_layout(h), [&](auto l) {

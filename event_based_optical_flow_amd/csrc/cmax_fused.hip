@@ -1113,34 +1113,34 @@ k_finish_raw(const double *__restrict__ raw, int n_ref, ObjParams op, const doub
     // everything finalize_deferred needs is fetched from the argument block beside them: one round trip less in a one-wave kernel)
     // blockIdx.x = candidate motion of cmax_objective_batch (one workgroup otherwise)
     raw += (int64_t)blockIdx.x * n_ref * kRawStride;
-    result += 8 * blockIdx.x;
-    if (gtheta) gtheta += 2 * blockIdx.x;
     const int lane = threadIdx.x;
     double v[4][6];
     // every lane loads ITS line's six doubles as three 16-byte loads, all issued before the first use (lanes >= kRawLines re-read
     // the last line and are zeroed by a select: `lane < 32 ? raw[..] : 0` put each of the 6 x n_ref loads into an exec-masked
-    // block with its own s_waitcnt -- six dependent round trips in a kernel that has only this one wave)
+    // block with its own s_waitcnt -- six dependent round trips in a kernel that has only this one wave).  Likewise the reference
+    // times: `if (k < n_ref)` around the loads of time k was a scalar branch per k whose block merged the loaded registers with the
+    // zeros and WAITED for them there, in front of the next k's loads and of the fetch of `op` (profiles/head_loads_isa.txt) -- a time
+    // the launch does not have re-reads the last one it has, and is never looked at.
     typedef double double2_v __attribute__((ext_vector_type(2)));
     const int line = lane < kRawLines ? lane : kRawLines - 1;
+    double2_v ld[4][3];
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
+        const int kk = k < n_ref ? k : max(n_ref - 1, 0);
+        const double2_v *src = reinterpret_cast<const double2_v *>(raw + (int64_t)kk * kRawStride + line * kSubStride);
 #pragma unroll
-        for (int q = 0; q < 6; ++q) v[k][q] = 0.0;
-        if (k < n_ref) {  // uniform
-            const double2_v *src = reinterpret_cast<const double2_v *>(raw + (int64_t)k * kRawStride + line * kSubStride);
-            const double2_v a = src[0], b = src[1], c = src[2];
-            v[k][0] = a.x;
-            v[k][1] = a.y;
-            v[k][2] = b.x;
-            v[k][3] = b.y;
-            v[k][4] = c.x;
-            v[k][5] = c.y;
-        }
+        for (int q = 0; q < 3; ++q) ld[k][q] = src[q];
     }
+    // what finalize_deferred reads of the argument block, fetched while the lines are on their way (the barrier keeps the loads above in front)
+    __builtin_amdgcn_sched_barrier(0);
+    // (values as loaded only, and no use of the argument block above the barrier: a use is a wait, and it landed in front of the line loads)
+    asm volatile("" ::"s"(op.n_ref), "s"(op.normalized), "s"(op.minimize), "s"(op.negate), "s"(op.omit), "s"(op.H), "s"(op.W), "s"(result), "s"(gtheta));
+    result += 8 * blockIdx.x;
+    if (gtheta) gtheta += 2 * blockIdx.x;
 #pragma unroll
     for (int k = 0; k < 4; ++k)
 #pragma unroll
-        for (int q = 0; q < 6; ++q) v[k][q] = lane < kRawLines ? v[k][q] : 0.0;
+        for (int q = 0; q < 6; ++q) v[k][q] = lane < kRawLines ? ((q & 1) ? ld[k][q >> 1].y : ld[k][q >> 1].x) : 0.0;
     const double v_orig = op.normalized ? orig_value<true>(op, stat) : 0.0;
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
@@ -1149,7 +1149,25 @@ k_finish_raw(const double *__restrict__ raw, int n_ref, ObjParams op, const doub
         for (int q = 0; q < 6; ++q) v[k][q] = wave_sum_lane63(v[k][q]);
     }
     if (lane == kWave - 1) {
-        finalize_deferred(op, v, v_orig, result, gtheta);
+        // (n_ref as a constant per branch, as in finish_raw_step_wave: finalize_deferred's loop unrolls and v[][] stays in registers --
+        // indexed by a run-time k it was 208 bytes of scratch per lane, written behind the loads and read back here)
+        ObjParams on = op;
+        double res[8], g[2];
+        switch (op.n_ref) {
+            case 1: on.n_ref = 1; finalize_deferred(on, v, v_orig, res, g); break;
+            case 2: on.n_ref = 2; finalize_deferred(on, v, v_orig, res, g); break;
+            case 3: on.n_ref = 3; finalize_deferred(on, v, v_orig, res, g); break;
+            default: on.n_ref = 4; finalize_deferred(on, v, v_orig, res, g); break;
+        }
+        result[0] = res[0];
+        result[5] = res[5];
+#pragma unroll
+        for (int k = 0; k < 4; ++k)
+            if (k < op.n_ref) result[1 + k] = res[1 + k];
+        if (gtheta) {
+            gtheta[0] = g[0];
+            gtheta[1] = g[1];
+        }
         if (flag) {
             __threadfence_system();
             *flag = seq;
@@ -1161,6 +1179,8 @@ k_finish_raw(const double *__restrict__ raw, int n_ref, ObjParams op, const doub
 // same three 16-byte loads per lane in flight, the same DPP sums and finalize_deferred -- and lane 63 then applies the optimiser's step to
 // theta in place (cmax_descent.h, nx = 2), so that an iteration stays at K1 -> K3 -> ONE finishing launch.  result / gtheta: device memory.
 // (one body for the single-start launch and its batched sibling below: the wave of one candidate)
+// (its loads keep the `if (k < n_ref)` form k_finish_raw had: changing them is a change to the descent's kernels, which no listing or
+// measurement of profiles/head_loads_* covers -- left for a change of its own)
 __device__ __forceinline__ void finish_raw_step_wave(const double *__restrict__ raw, int n_ref, const ObjParams &op, const double *__restrict__ stat,
                                                      double *__restrict__ result, double *__restrict__ gtheta, const DescentArgs &step) {
     const int lane = threadIdx.x;
@@ -1333,7 +1353,8 @@ static WarpParams warp_params(const cmax_handle_s *h, const float *motion, int T
     wp.d_lo = ref_fraction_lo(ref_mode, frac);
     wp.normalize = normalize;
     wp.motion_f64 = motion_f64;
-    wp.tmm = h->d_tmm;
+    wp.tmm = h->d_tmm;  // ALWAYS the handle's own pair (the base of its per-batch allocation: 16-byte aligned, never null once events are set):
+                        // K1 / K3 load it unconditionally, as one 16-byte scalar load, whatever normalize_t and the model (load_head_words)
     wp.motion = motion;
     return wp;
 }

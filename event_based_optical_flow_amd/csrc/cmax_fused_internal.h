@@ -76,7 +76,10 @@ struct RefArgs {
     // cmax_objective_batch: blockIdx.z = candidate motion.  Element strides between consecutive candidates (0 for every other launch):
     int64_t z_img;    // floats between their vote images (img[k] / zero[k] are candidate 0's)
     int64_t z_raw;    // doubles between their raw-sum lines (stat[k] of K1, gpart of K3)
-    int z_motion;     // floats between their motions
+    int z_motion;     // floats between their motions.  The ONE source: the launchers copy it into K1's leading z_motion / the 2-DoF K3's
+                      // head word (where the head needs it in an SGPR); every other read, the flow models' K3 included, is of this field
+    // K3, deferred statistics: pixels (zero_chunk) and float4s (zero_chunk4) of zero[k] each workgroup clears = ceil(. / nseg), set by launch_grad
+    int zero_chunk, zero_chunk4;
     // K1, blurred variance with a gradient: sum_p I[p] B[p] (B = blur^T 1_Omega = b(r) b(c)) = the sum of the blurred image over
     // Omega, accumulated while the votes are flushed -- the image kernel then knows the mean before it has blurred anything
     double *musum[4];        // kMuLines accumulators (one 128-byte line each) per reference time, or null
