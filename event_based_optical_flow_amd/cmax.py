@@ -318,9 +318,34 @@ class CMaxHandle:
         check(self._lib.cmax_debug_packed_events(self._h, ev.data_ptr(), gs.data_ptr(), ctypes.byref(ng), F._stream()))
         return (ev[:n].cpu().numpy().astype(np.int64) & 0xFFFFFFFF), gs[: ng.value + 1].cpu().numpy()
 
+    WORK_LIST_FLAGS = ("big", "mid", "owned", "small_accumulators", "slab_major", "compact", "long_runs")  # CMAX_WL_*, bit 0 first
+    COMPACT_STRIDE = 4 * 4096 + 4096 // 2 + 64  # bytes per compact region (b512::kCompactStride)
+
+    def work_list(self):
+        """(segments [n_segments, 4] int64 on the host: first event, count, first group, number of groups; flags {name: bool} over
+        WORK_LIST_FLAGS; seg_max) of the current work list as the handle holds it after the last cut (cmax_debug_work_list) -- for tests
+        of the cut."""
+        n, f, m = ctypes.c_int(0), ctypes.c_uint(0), ctypes.c_int(0)
+        check(self._lib.cmax_debug_work_list(self._h, None, ctypes.byref(n), ctypes.byref(f), ctypes.byref(m), F._stream()))
+        segs = torch.zeros((max(n.value, 1), 4), dtype=torch.int32, device=self.device)
+        check(self._lib.cmax_debug_work_list(self._h, segs.data_ptr(), None, None, None, F._stream()))
+        flags = {name: bool(f.value >> k & 1) for k, name in enumerate(self.WORK_LIST_FLAGS)}
+        return segs[: n.value].cpu().numpy().astype(np.int64), flags, m.value
+
+    def compact_events(self):
+        """(regions [n_segments, COMPACT_STRIDE] uint8 on the host, flag) -- the compact copy of the current work list's events and the
+        flag its packing kernel raises when an event does not fit its segment's strip (cmax_debug_compact_events); the library's
+        CMAX_ESTATE (RuntimeError) on a handle without a compact copy."""
+        n = ctypes.c_int(0)
+        check(self._lib.cmax_debug_work_list(self._h, None, ctypes.byref(n), None, None, F._stream()))
+        reg = torch.zeros((max(n.value, 1), self.COMPACT_STRIDE), dtype=torch.uint8, device=self.device)
+        bad = ctypes.c_int(0)
+        check(self._lib.cmax_debug_compact_events(self._h, reg.data_ptr(), ctypes.byref(bad), F._stream()))
+        return reg[: n.value].cpu().numpy(), bad.value
+
     def work_list_info(self) -> Dict[str, int]:
         """{"segments", "segment_events", "small_accumulators"} of the work list the last set_events / set_time_bins cut
-        (cmax_work_list_info): one workgroup of the event kernels per segment; segment_events is 2040 or 4088 (big segments)."""
+        (cmax_work_list_info): one workgroup of the event kernels per segment; segment_events is 2040, 3064 (mid) or 4088 (big segments)."""
         n, e, a = ctypes.c_int(0), ctypes.c_int(0), ctypes.c_int(0)
         check(self._lib.cmax_work_list_info(self._h, ctypes.byref(n), ctypes.byref(e), ctypes.byref(a)))
         return {"segments": n.value, "segment_events": e.value, "small_accumulators": bool(a.value)}

@@ -643,6 +643,7 @@ int pack_compact_events(cmax_handle_s *h, hipStream_t s) {
     CMAX_CHECK_HIP(hipGetLastError());
     return 0;
 }
+int64_t compact_region_bytes() { return b512::kCompactStride; }
 
 // The models today's call sites use: every launcher for the three motion models, the vote and the per-event gathers for the
 // un-warped image (MODEL = -1) as well.

@@ -59,7 +59,8 @@
 //   CMAX_TAN2=0 | 1      2-DoF tangent-image path: never / also without a communicator
 //   CMAX_PLAN_GRAPHS=1   replay the patch plan from captured hipGraphs (cmax_solver.hip)
 //   CMAX_COMPACT=0       big segments read the plain 8-byte events instead of the 4.5-byte compact copy (fp32 time instead of 24-bit fixed point)
-//   CMAX_DEBUG_COMPACT=1 cmax_set_events synchronises behind k_pack_compact and fails if an event did not fit its region's coordinates
+//   CMAX_DEBUG_COMPACT=1 cmax_set_events synchronises behind k_pack_compact and fails if an event did not fit its region's coordinates (tests read the flag
+//                         with cmax_debug_compact_events instead)
 //   CMAX_SORT=radix | bucket   per-batch order by the stable radix sort (cmax_radix_sort.h) / the two-level counting sort, whatever the size
 namespace cmax {
 
@@ -1742,7 +1743,7 @@ static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchRead
         CMAX_CHECK_HIP(hipMemcpyAsync(h->d_segs, h->hp_segs, segs.size() * sizeof(int4), hipMemcpyHostToDevice, s));
         CMAX_CHECK_HIP(hipEventRecord(h->segs_copied, s));
     }
-    // Big segments of an un-binned handle: the compact copy the hot kernels read (6 B/event, one aligned region per segment).
+    // Big segments of an un-binned handle: the compact copy the hot kernels read (4.5 B/event, one aligned region per segment).
     // CMAX_COMPACT=0 switches it off (A/B runs).
     static const int compact_env = getenv("CMAX_COMPACT") ? atoi(getenv("CMAX_COMPACT")) : 1;
     h->compact = false;
@@ -4430,8 +4431,39 @@ int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start
     const int ngroups = h->ntr * h->ntc * (h->n_time_bin > 0 ? h->n_time_bin : 1);
     if (n_groups_host) *n_groups_host = ngroups;
     if (h->n > 0) CMAX_CHECK_HIP(hipMemcpyAsync(events_out, h->evp, (size_t)h->n * sizeof(uint2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (group_start_out)
+    if (group_start_out && h->n == 0)  // (an empty batch is not sorted: d_tile_start holds whatever the allocation or the last batch left)
+        CMAX_CHECK_HIP(hipMemsetAsync(group_start_out, 0, (size_t)(ngroups + 1) * sizeof(int), (hipStream_t)stream));
+    else if (group_start_out)
         CMAX_CHECK_HIP(hipMemcpyAsync(group_start_out, h->d_tile_start, (size_t)(ngroups + 1) * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+int cmax_debug_work_list(cmax_handle_t h, void *segments_out, int *n_segments_host, unsigned *flags_host, int *seg_max_host, cmax_stream_t stream) {
+    CMAX_REQUIRE(h != nullptr, "debug_work_list");
+    if (n_segments_host) *n_segments_host = h->nseg;
+    if (flags_host)
+        *flags_host = (h->big ? CMAX_WL_BIG : 0u) | (h->mid ? CMAX_WL_MID : 0u) | (h->owned ? CMAX_WL_OWNED : 0u) | (h->small_acc ? CMAX_WL_SMALL_ACC : 0u) |
+                      ((h->slab_major && h->n_time_bin > 0) ? CMAX_WL_SLAB_MAJOR : 0u) | (h->compact ? CMAX_WL_COMPACT : 0u) | (h->long_runs ? CMAX_WL_LONG_RUNS : 0u);
+    if (seg_max_host) *seg_max_host = h->seg_max;
+    if (segments_out && h->nseg > 0)  // the list the kernels read, not the host's staging copy
+        CMAX_CHECK_HIP(hipMemcpyAsync(segments_out, h->d_segs, (size_t)h->nseg * sizeof(int4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
+    return 0;
+}
+
+int cmax_debug_compact_events(cmax_handle_t h, void *regions_out, int *flag_host, cmax_stream_t stream) {
+    CMAX_REQUIRE(h != nullptr && regions_out != nullptr, "debug_compact_events");
+    if (!h->compact || h->nseg <= 0) {
+        set_error("debug_compact_events: the current work list has no compact copy");
+        return CMAX_ESTATE;
+    }
+    hipStream_t s = (hipStream_t)stream;
+    CMAX_CHECK_HIP(hipMemcpyAsync(regions_out, h->cev, (size_t)h->nseg * (size_t)compact_region_bytes(), hipMemcpyDeviceToDevice, s));
+    if (flag_host) {  // what k_pack_compact raised: an event that does not fit its segment's strip
+        // (into the flag's own slot of the pinned read-back, which every cut has sized: build_segments)
+        CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_read + 7, h->d_flags + 3, sizeof(int), hipMemcpyDeviceToHost, s));
+        CMAX_CHECK_HIP(hipStreamSynchronize(s));
+        *flag_host = h->hp_read[7];
+    }
     return 0;
 }
 

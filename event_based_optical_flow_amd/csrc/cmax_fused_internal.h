@@ -418,6 +418,7 @@ CMAX_HIDDEN Layout grad_layout(const cmax_handle_s *h, int model, bool owned);
 CMAX_HIDDEN int layout_threads(Layout id);
 // ... and k_pack_compact behind build_segments (cmax_fused.hip): the compact copy of the current work list's events, grown on demand
 CMAX_HIDDEN int pack_compact_events(cmax_handle_s *h, hipStream_t s);
+CMAX_HIDDEN int64_t compact_region_bytes();  // bytes per region of that copy (the big layout's kCompactStride)
 #ifdef CMAX_TIMELINE
 // cmax_fused.hip: where its image kernels stamp (cmax_debug_timeline; every unit holds its own copy of the pointer)
 CMAX_HIDDEN int image_timeline_set(unsigned long long *buffer);

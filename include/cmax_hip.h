@@ -609,7 +609,7 @@ int cmax_batch_info(cmax_handle_t h, int64_t *n_packed, int64_t *n_dropped, int 
 int cmax_set_keep_outside(cmax_handle_t h, int on);
 int cmax_batch_outside(cmax_handle_t h, int64_t *n_outside);
 /* The work list cmax_set_events / cmax_set_time_bins cut for the event kernels (one workgroup per segment): number of
- * segments; segment_events = the most events a segment holds (2040, or 4088 for BIG segments: batches of >= 8M events, and
+ * segments; segment_events = the most events a segment holds (2040, 3064 for MID, or 4088 for BIG segments: batches of >= 8M events, and
  * smaller ones whose group sizes ask for it -- DESIGN.md section 2); small_accumulators = 1 when a binned list was cut at
  * three (tile, bin) groups per segment for the voxel gradient kernel with the small LDS accumulator array.  Any pointer may
  * be NULL.  (Introspection for tests and tuning: results do not depend on the cut.)                                       */
@@ -627,8 +627,27 @@ int cmax_debug_timeline(void *device_buffer);
 /* Test aid (tests/test_gpu_fused.py::test_packed_order): copies the packed, sorted events of the current batch -- n_events x 2 uint32:
  * [row | col << 12 | (time bin, or the time's residual beyond fp32) << 24,  bits of the fp32 normalised time] -- and the group starts
  * the work list was cut from ([n_groups + 1] int32; NULL skips them; *n_groups_host receives their number: source tiles, x time bins
- * / slabs on binned handles) into device buffers, on `stream`.  The layout is what DESIGN.md section 2 describes, not a stable ABI.  */
+ * / slabs on binned handles; all zero for an empty batch, which is not sorted) into device buffers, on `stream`.  The layout is what
+ * DESIGN.md section 2 describes, not a stable ABI.                                                                                    */
 int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start_out, int *n_groups_host, cmax_stream_t stream);
+/* Test aids (tests/test_gpu_work_list.py), in the style of cmax_debug_packed_events: not a stable ABI, nothing allocated that stays.
+ * cmax_debug_work_list copies the work list of the last cut as the event kernels read it -- n_segments x int4 {first event, count, first
+ * group, number of groups} -- into the device buffer segments_out on `stream` (NULL: the count only), and stores on the host the number
+ * of segments, the CMAX_WL_* flags and the most events a segment may hold (2040 / 3064 / 4088), all as the handle holds them after the
+ * last cut (an empty batch makes no cut: zero segments, the flags of the cut before).  Any host pointer may be NULL.
+ * cmax_debug_compact_events copies the compact regions of that work list (cmax_event_kernels.inc, "COMPACT EVENTS": n_segments x 18496
+ * bytes -- 4096 slot words | 512 words of tile nibbles | 16 header words) into the device buffer regions_out and stores the flag the
+ * packing kernel raises when an event does not fit its segment's strip (0: never raised; the call waits for `stream`).  CMAX_ESTATE
+ * on a handle whose current work list has no compact copy.                                                                         */
+#define CMAX_WL_BIG 1u        /* segments of up to 4088 events                              */
+#define CMAX_WL_MID 2u        /* segments of up to 3064 events                              */
+#define CMAX_WL_OWNED 4u      /* every group belongs to exactly one segment of whole groups */
+#define CMAX_WL_SMALL_ACC 8u  /* binned list cut at three groups per segment (five on mid)  */
+#define CMAX_WL_SLAB_MAJOR 16u /* groups are (tile row, slab, tile column)                  */
+#define CMAX_WL_COMPACT 32u   /* a compact copy of the events exists for this list          */
+#define CMAX_WL_LONG_RUNS 64u /* >= 8 events per active source pixel                        */
+int cmax_debug_work_list(cmax_handle_t h, void *segments_out, int *n_segments_host, unsigned *flags_host, int *seg_max_host, cmax_stream_t stream);
+int cmax_debug_compact_events(cmax_handle_t h, void *regions_out, int *flag_host, cmax_stream_t stream);
 
 /* =============================================================================================
  * The optimiser's objective for patch-based flow in one call: what

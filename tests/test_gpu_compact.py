@@ -176,3 +176,30 @@ def test_short_runs_on_big_segments_take_the_plain_events():
             print(f"[compact] short runs on big segments, {cost} #{rep}: rel err loss {e_loss:.2e} grad {e_grad:.2e}")
             assert e_loss <= TOL and e_grad <= TOL, (cost, e_loss, e_grad)
     h.close()
+
+
+def test_work_list_and_compact_words_on_the_natural_path(batch):
+    """The same batch, exactly: the work list equals the restated cut (tests/_worklist_ref.py: 8.2M events take big segments and, not
+    being group-aligned on this sensor, the free cut every 4088 events), it holds what the kernels require, and every word of the compact
+    regions is the one the layout comment describes -- the packing flag stays 0."""
+    import _worklist_ref as R
+
+    ev, h = batch
+    packed, gs = h.packed_events()
+    segs, flags, seg_max = h.work_list()
+    ntr, ntc = (SIZE[0] + 15) // 16, (SIZE[1] + 15) // 16
+    want_segs, want_flags, want_max, why = R.cut_with_reasons(gs, packed.shape[0], ntr, ntc, 0, False, R.long_runs_of(packed, 0), None)
+    assert why["big_rule"] == "8M" and why["free_cut"] and want_flags["compact"], why
+    assert flags == want_flags and seg_max == want_max == 4088, (flags, want_flags, seg_max)
+    np.testing.assert_array_equal(segs, want_segs)
+    assert (segs[:-1, 1] == 4088).mean() > 0.9 and (segs[:, 3] > 1).any()  # full segments, cut inside source tiles
+    R.check_invariants(segs, flags, packed, gs, dict(ntr=ntr, ntc=ntc, T=0, slab=False, seg_max=seg_max))
+    info = h.work_list_info()
+    assert info["segments"] == segs.shape[0] and info["segment_events"] == seg_max and not h.batch_info()["owned_groups"]
+    regions, bad = h.compact_events()
+    assert bad == 0
+    want = R.compact_expected(packed, segs, ntc)
+    differ = np.argwhere(regions.view(np.uint32) != want.view(np.uint32))
+    assert differ.shape[0] == 0, (differ.shape[0], differ[:4].tolist())
+    stored = regions.view(np.uint32)[:, :R.SLOTS] >> 8
+    assert stored.max() == 2 ** 24 - 1  # the event at tau = 1
