@@ -107,6 +107,35 @@ class CmaxBasisObjective(ctypes.Structure):
     ]
 
 
+class CmaxDepthObjective(ctypes.Structure):
+    """Mirror of cmax_depth_objective_t (include/cmax_hip.h)."""
+
+    _fields_ = [
+        ("n_terms", ctypes.c_int32),
+        ("time_aware", ctypes.c_int32),
+        ("T", ctypes.c_int32),
+        ("scheme", ctypes.c_int32),
+        ("t0", ctypes.c_int32),
+        ("H", ctypes.c_int32),
+        ("W", ctypes.c_int32),
+        ("Ka", ctypes.c_int32),
+        ("Kb", ctypes.c_int32),
+        ("ph", ctypes.c_int32),
+        ("pw", ctypes.c_int32),
+        ("pad_h", ctypes.c_int32),
+        ("pad_w", ctypes.c_int32),
+        ("sw_h", ctypes.c_int32),
+        ("sw_w", ctypes.c_int32),
+        ("basis_dtype", ctypes.c_int32),
+        ("scale_later", ctypes.c_int32),  # must be 0
+        ("filter_type", ctypes.c_int32),  # must be FILTER_BILINEAR
+        ("t_scale", ctypes.c_double),
+        ("weight", ctypes.c_double * 4),
+        ("tv_weight", ctypes.c_double),  # must be 0
+        ("term", CmaxObjective * 4),
+    ]
+
+
 class CmaxDescent(ctypes.Structure):
     """Mirror of cmax_descent_t (include/cmax_hip.h): every value explicit, torch's defaults are filled by `descent_descriptor`."""
 
@@ -193,6 +222,7 @@ LBFGS_CODES = {0: "start", 1: "accepted", 2: "rejected", 3: "reset", 4: "idle"} 
 LBFGS_FIXED_DOUBLES = 1112  # control block and Gram matrix at the head of the state (csrc/cmax_lbfgs.h)
 BASIS_MAX_K = 64  # CMAX_BASIS_MAX_K: fields of a flow basis
 BASIS_ADJ_CHUNK = 2048  # CMAX_BASIS_ADJ_CHUNK: elements of [2,H,W] per workgroup of the basis adjoint
+DEPTH_ADJ_CHUNK = 1024  # CMAX_DEPTH_ADJ_CHUNK: pixels per workgroup of the depth map's adjoint
 FLOWREG_NONE, FLOWREG_DIVERGENCE, FLOWREG_AREA = 0, 1, 2
 FLOWREG_CODES = {"divergence": FLOWREG_DIVERGENCE, "area": FLOWREG_AREA}
 EINVAL = -1
@@ -298,6 +328,12 @@ SIGNATURES = {
     "cmax_basis_to_dense": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp, c_vp]),
     "cmax_sizeof_basis_objective": (c_int, []),
     "cmax_basis_plan_create": (c_int, [c_vp, ctypes.POINTER(CmaxBasisObjective), c_vp, c_vp, ctypes.POINTER(c_vp)]),
+    "cmax_depth_to_dense": (c_int, [c_vp] * 5 + [c_int] * 11 + [c_vp, c_vp]),
+    "cmax_depth_to_dense_tan": (c_int, [c_vp] * 7 + [c_int] * 11 + [c_vp, c_vp]),
+    "cmax_depth_to_dense_adj": (c_int, [c_vp] * 5 + [c_int] * 11 + [c_vp] * 4),
+    "cmax_depth_to_dense_adj2": (c_int, [c_vp] * 8 + [c_int] * 11 + [c_vp] * 4),
+    "cmax_sizeof_depth_objective": (c_int, []),
+    "cmax_depth_plan_create": (c_int, [c_vp, ctypes.POINTER(CmaxDepthObjective), c_vp, c_vp, c_vp, ctypes.POINTER(c_vp)]),
     "cmax_field_max": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp]),
     "cmax_field_max_adj": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp]),
     "cmax_sizeof_flow_regularizer": (c_int, []),
@@ -349,6 +385,8 @@ def load():
             raise RuntimeError("cmax_patch_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_basis_objective() != ctypes.sizeof(CmaxBasisObjective):
             raise RuntimeError("cmax_basis_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
+        if lib.cmax_sizeof_depth_objective() != ctypes.sizeof(CmaxDepthObjective):
+            raise RuntimeError("cmax_depth_objective_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_descent() != ctypes.sizeof(CmaxDescent):
             raise RuntimeError("cmax_descent_t layout mismatch between libcmax_hip.so and the ctypes binding")
         if lib.cmax_sizeof_lbfgs() != ctypes.sizeof(CmaxLbfgs):

@@ -16,6 +16,8 @@
 // A plan made by cmax_basis_plan_create is the same plan with the patch interpolation exchanged for a flow basis, D = sum_k x_k B_k
 // (cmax_basis_kernels.h): a motion model linear in its parameters.  The reference has no counterpart for that map; D is warped by its
 // dense-flow rule x' = x - dt * D[src] (src/warp.py:263-313).
+// A plan made by cmax_depth_plan_create maps x = [a | b | s] to D = (Q s) (sum_k a_k A_k) + sum_j b_j B_j (cmax_depth_kernels.h): the motion
+// field of a static scene over a grid of inverse depth.  That map is NOT linear, so its product has a sequence of its own (enqueue_hvp_depth).
 #include <cstring>
 #include <new>
 #include <atomic>
@@ -24,6 +26,7 @@
 #include "cmax_basis_kernels.h"
 #include "cmax_buffers.h"
 #include "cmax_common.h"
+#include "cmax_depth_kernels.h"
 #include "cmax_descent.h"
 #include "cmax_lbfgs.h"
 #include "cmax_flowreg_kernels.h"
@@ -266,7 +269,7 @@ k_field_max_adj(const T *__restrict__ x, int64_t n, const double *__restrict__ o
     if (i < n) gx[i] = (double)x[i] == out[0] ? (T)(gout[0] / out[1]) : (T)0;
 }
 
-enum { kMapPatch = 0, kMapBasis = 1 };  // cmax_patch_plan_s::map_kind
+enum { kMapPatch = 0, kMapBasis = 1, kMapDepth = 2 };  // cmax_patch_plan_s::map_kind
 
 struct FinalParams {
     int n_terms, with_tv, nx;  // nx = 0: value only
@@ -824,7 +827,7 @@ int launch_lbfgs_step(const LbfgsArgs &a_in, const double *loss, const double *g
 struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: its implicit destructor is no export)
     cmax_handle_t handle = nullptr;
     cmax_patch_objective_t d;
-    int nx = 0;            // 2 * ph * pw (basis plan: K)
+    int nx = 0;            // 2 * ph * pw (basis plan: K; depth plan: Ka + Kb + ph * pw)
     int64_t nflow = 0;     // 2 * H * W
     int64_t nmotion = 0;   // nflow or T * nflow
     cmax::DevBuf<double> x64, flow64, vox64, gacc64, gflow64, gx64, results;
@@ -842,6 +845,10 @@ struct __attribute__((visibility("hidden"))) cmax_patch_plan_s {  // (hidden: it
     cmax::DevBuf<float> basis32;
     cmax::DevBuf<double> basis64, basis_partial;
     std::vector<double> bmax;
+    // ... or the depth map (cmax_depth_plan_create: x = [a | b | s], nx = Ka + Kb + ph pw; the basis buffer holds A then B, basis_partial the
+    // chunk sums of k_depth_adj, depth_q its plane q [H,W])
+    int Ka = 0, Kb = 0;
+    cmax::DevBuf<double> depth_q;
     // cmax_patch_plan_set_flow_regularizer: one more term on F = t (map x), kind CMAX_FLOWREG_NONE = none; the tiles' energies
     cmax_flow_regularizer_t reg = {};
     cmax::DevBuf<double> reg_partial;
@@ -937,17 +944,69 @@ int basis_forward(cmax_patch_plan_s *p, const double *src64, double scale, const
     return 0;
 }
 
-// The plan's map x -> dense flow, unscaled, in fp64 (the patch interpolation with the plan's filter, or the basis)
+DepthGeom plan_depth_geom(const cmax_patch_plan_s *p) {
+    const cmax_patch_objective_t &d = p->d;
+    return DepthGeom{d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W};
+}
+// the plan's copy of A, and of B behind it, as typed by basis_dtype
+const void *plan_depth_B(const cmax_patch_plan_s *p) {
+    const int64_t off = (int64_t)p->Ka * p->nflow;
+    return p->basis_dtype == CMAX_F64 ? (const void *)(p->basis64.get() + off) : (const void *)(p->basis32.get() + off);
+}
+
+// Depth plan: dst = scale [* *scale_dev] * D(src64), src64 = [a | b | s], as fp32 (both planes when `lo32`) or fp64
+int depth_forward(cmax_patch_plan_s *p, const double *src64, double scale, const double *scale_dev, float *dst32, float *lo32, double *dst64, hipStream_t s) {
+    const bool b64 = p->basis_dtype == CMAX_F64;
+    const void *A = plan_basis(p), *B = plan_depth_B(p);
+    const DepthGeom g = plan_depth_geom(p);
+    const int Ka = p->Ka, Kb = p->Kb;
+    const double *a = src64, *b = src64 + Ka, *sg = src64 + Ka + Kb;
+    if (dst64) {
+        if (b64) launch_depth_to_dense<double, double>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst64, s);
+        else launch_depth_to_dense<float, double>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst64, s);
+    } else if (lo32) {
+        if (b64) launch_depth_to_dense_split<double>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst32, lo32, s);
+        else launch_depth_to_dense_split<float>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst32, lo32, s);
+    } else {
+        if (b64) launch_depth_to_dense<double, float>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst32, s);
+        else launch_depth_to_dense<float, float>(a, b, sg, A, B, Ka, Kb, g, scale, scale_dev, dst32, s);
+    }
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+// ... its adjoint at x = x64 into gx64 [a | b | s] (SECOND: the second-order adjoint along v64 for the seeds (g, dg)); always fp64
+template <typename TG, bool SECOND>
+int depth_adjoint(cmax_patch_plan_s *p, const TG *g, const TG *dg, hipStream_t s) {
+    const void *A = plan_basis(p), *B = plan_depth_B(p);
+    const DepthGeom geo = plan_depth_geom(p);
+    const int Ka = p->Ka, Kb = p->Kb;
+    const double *x = p->x64, *v = p->v64;
+    if (p->basis_dtype == CMAX_F64)
+        launch_depth_adj<double, TG, SECOND>(g, dg, x, x + Ka + Kb, v, v + Ka + Kb, A, B, Ka, Kb, geo, p->basis_partial, p->depth_q, p->gx64, p->gx64 + Ka + Kb, s);
+    else
+        launch_depth_adj<float, TG, SECOND>(g, dg, x, x + Ka + Kb, v, v + Ka + Kb, A, B, Ka, Kb, geo, p->basis_partial, p->depth_q, p->gx64, p->gx64 + Ka + Kb, s);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+// The plan's map x -> dense flow, unscaled, in fp64 (the patch interpolation with the plan's filter, the basis, or the depth map)
 int map_forward64(cmax_patch_plan_s *p, const double *src64, double *dst64, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
+    if (p->map_kind == kMapDepth) return depth_forward(p, src64, 1.0, nullptr, nullptr, nullptr, dst64, s);
     if (p->map_kind == kMapBasis) return basis_forward(p, src64, 1.0, nullptr, nullptr, nullptr, dst64, s);
     return cmax_patch_to_dense_filter(src64, CMAX_F64, d.ph, d.pw, d.pad_h, d.pad_w, d.sw_h, d.sw_w, d.H, d.W, d.filter_type, 0, dst64, s);
 }
 
 // ... and its adjoint on a flow gradient in fp32 or fp64: the result is returned through the pointer of its dtype (the patch adjoint
-// answers in the dtype of its input, the basis adjoint always in fp64)
+// answers in the dtype of its input, the basis adjoint and the depth adjoint -- taken at the x the plan holds in x64 -- always in fp64)
 int map_adjoint(cmax_patch_plan_s *p, const float *g32, const double *g64, const double **gx64, const float **gx32, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
+    if (p->map_kind == kMapDepth) {
+        int rc = g32 ? depth_adjoint<float, false>(p, g32, nullptr, s) : depth_adjoint<double, false>(p, g64, nullptr, s);
+        if (!rc) *gx64 = p->gx64;
+        return rc;
+    }
     if (p->map_kind == kMapBasis) {
         const bool b64 = p->basis_dtype == CMAX_F64;
         const void *B = plan_basis(p);
@@ -1003,9 +1062,13 @@ int forward_motion(cmax_patch_plan_s *p, const double *src64, double scale, cons
     const bool split = p->exact && dst32 == p->motion32;  // the motion of an exact plan (not its tangent): both planes, in the launches below
     const bool nearest = d.filter_type == CMAX_FILTER_NEAREST;
     float *lo32 = dst32 + p->nmotion;
-    if (p->map_kind == kMapBasis) {  // the basis kernels scale (scale_dev included) and round in the launch that sums
-        if (!d.time_aware) return basis_forward(p, src64, scale, scale_dev, dst32, split ? lo32 : nullptr, nullptr, s);
-        int rc = basis_forward(p, src64, scale, scale_dev, nullptr, nullptr, p->flow64, s);
+    if (p->map_kind == kMapBasis || p->map_kind == kMapDepth) {  // these kernels scale (scale_dev included) and round in the launch that sums
+        const bool depth = p->map_kind == kMapDepth;
+        if (!d.time_aware)
+            return depth ? depth_forward(p, src64, scale, scale_dev, dst32, split ? lo32 : nullptr, nullptr, s)
+                         : basis_forward(p, src64, scale, scale_dev, dst32, split ? lo32 : nullptr, nullptr, s);
+        int rc = depth ? depth_forward(p, src64, scale, scale_dev, nullptr, nullptr, p->flow64, s)
+                       : basis_forward(p, src64, scale, scale_dev, nullptr, nullptr, p->flow64, s);
         if (rc) return rc;
         bool wrote32 = false;  // the voxel on the displacement field, as the patch plan's time-aware branch below
         rc = voxel_construct_f64_f32(p->flow64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, split ? nullptr : dst32, split ? nullptr : &wrote32, s);
@@ -1310,8 +1373,88 @@ int enqueue_hvp_scale_later(cmax_patch_plan_s *p, hipStream_t s) {
     return 0;
 }
 
+// Depth plan (the map x -> D is a product of unknowns: its derivative J depends on x).  With F = t D(x), g_F = dL/dF and v the tangent:
+//   H_x v = t [ J^T (H_FF t dD) + (dJ[v])^T g_F ],   dD = J v (k_depth_to_dense_tan)
+// -- the second-order adjoint of k_depth_adj on the seeds (g_F, dg_F).  A time-aware plan puts the voxel chain between F and the fused
+// terms exactly as enqueue_hvp_time_aware does.  The tangent handed to cmax_objective_hvp is scaled to unit max-norm from a maximum taken
+// on the device: no host bound holds for the product (Q ds) (A a), and the scalars the host sends with x | v are not used.
+int enqueue_hvp_depth(cmax_patch_plan_s *p, hipStream_t s) {
+    const cmax_patch_objective_t &d = p->d;
+    CMAX_CHECK_HIP(hipMemcpyAsync(p->x64, p->h_in, (2 * (size_t)p->nx + 2) * sizeof(double), hipMemcpyHostToDevice, s));
+    const int mgrid = div_up(p->nmotion, 256);
+    const int Ka = p->Ka, Kb = p->Kb;
+    const int64_t off0 = d.time_aware ? (int64_t)d.t0 * p->nflow : 0;
+    // F = t D(x) -> the fp32 motion (flow64 / vox64 as an evaluation leaves them);  dF = t J v in fp64
+    const double *x = p->x64, *v = p->v64;
+    if (p->basis_dtype == CMAX_F64)
+        launch_depth_to_dense_tan<double, double>(x, x + Ka + Kb, v, v + Ka, v + Ka + Kb, plan_basis(p), plan_depth_B(p), Ka, Kb, plan_depth_geom(p), d.t_scale,
+                                                  (double *)p->dflow64, s);
+    else
+        launch_depth_to_dense_tan<float, double>(x, x + Ka + Kb, v, v + Ka, v + Ka + Kb, plan_basis(p), plan_depth_B(p), Ka, Kb, plan_depth_geom(p), d.t_scale,
+                                                 (double *)p->dflow64, s);
+    CMAX_CHECK_LAUNCH();
+    int rc = 0;
+    const double *tan64 = p->dflow64;
+    if (d.time_aware) {
+        rc = depth_forward(p, p->x64, d.t_scale, nullptr, nullptr, nullptr, p->flow64, s);
+        if (rc) return rc;
+        rc = cmax_voxel_construct_tan(p->flow64, p->dflow64, CMAX_F64, d.T, d.t0, d.H, d.W, d.scheme, p->vox64, p->dvox64, s);
+        if (rc) return rc;
+        if (p->exact) hipLaunchKernelGGL(k_convert_split, dim3(mgrid), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, p->motion32, p->motion32 + p->nmotion);
+        else hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, p->vox64, p->nmotion, 1.0, (const double *)nullptr, p->motion32);
+        CMAX_CHECK_LAUNCH();
+        tan64 = p->dvox64;
+    } else {
+        rc = forward_motion(p, p->x64, d.t_scale, nullptr, p->motion32, s);
+        if (rc) return rc;
+    }
+    unsigned long long *bits = reinterpret_cast<unsigned long long *>(p->scal + 2);
+    CMAX_CHECK_HIP(hipMemsetAsync(bits, 0, sizeof(unsigned long long), s));
+    hipLaunchKernelGGL(k_absmax, dim3(mgrid < 256 ? mgrid : 256), dim3(256), 0, s, tan64, p->nmotion, bits);
+    hipLaunchKernelGGL(k_absmax_finish, dim3(1), dim3(1), 0, s, bits, p->scal);
+    hipLaunchKernelGGL((k_convert_scale<float, double>), dim3(mgrid), dim3(256), 0, s, tan64, p->nmotion, 1.0, p->scal + 1, p->tan32);
+    CMAX_CHECK_LAUNCH();
+    for (int i = 0; i < d.n_terms; ++i) {
+        rc = plan_objective(p, &d.term[i], p->results + 8 * i, p->grad32, s);  // g of the motion
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_accumulate, dim3(mgrid), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->gacc64, (const double *)nullptr);
+        CMAX_CHECK_LAUNCH();
+        rc = plan_objective_hvp(p, &d.term[i], p->grad32, s);  // H (tangent / its max-norm)
+        if (rc) return rc;
+        hipLaunchKernelGGL(k_accumulate, dim3(mgrid), dim3(256), 0, s, p->grad32, p->nmotion, d.weight[i], i == 0 ? 1 : 0, p->dgacc64, (const double *)p->scal);
+        CMAX_CHECK_LAUNCH();
+    }
+    if (d.time_aware) {  // the dual sweep leaves g_F and dg_F in bin t0 of the two gradient voxels
+        rc = voxel_construct_adj_tan_f64(p->vox64, p->dvox64, d.T, d.t0, d.H, d.W, d.scheme, p->gacc64, p->dgacc64, s, handle_is_deterministic(p->handle));
+        if (rc) return rc;
+    }
+    if (plan_has_reg(p)) {  // one more term on F: w dR/dF into g_F, w (grad^2_F R)[dF] into dg_F
+        rc = plan_flowreg(p, p->gacc64 + off0, s);  // (a plan that is not time-aware: flow64 = D(x) unscaled from here on)
+        if (rc) return rc;
+        launch_flowreg_tan<double>(p->reg, p->flow64, p->dflow64, d.time_aware ? 1.0 : d.t_scale, 1.0, nullptr, d.H, d.W, p->dgacc64 + off0, 1, p->reg.weight, s);
+        CMAX_CHECK_LAUNCH();
+    }
+    rc = depth_adjoint<double, true>(p, p->gacc64 + off0, p->dgacc64 + off0, s);
+    if (rc) return rc;
+    FinalParams fp;
+    fp.n_terms = 0;
+    fp.flag_slot = 1 + (int)p->nx;
+    fp.with_tv = 0;
+    fp.nx = p->nx;
+    fp.ph = d.ph;
+    fp.pw = d.pw;
+    fp.tv_crop = 0;
+    for (int i = 0; i < 4; ++i) fp.weight[i] = 0.0;
+    fp.tv_weight = 0.0;
+    fp.gscale = d.t_scale;  // the outer t J^T (the inner t is in dF)
+    hipLaunchKernelGGL(k_patch_tail, dim3(1), dim3(256), 0, s, fp, p->results, p->x64, p->gx64, (const float *)nullptr, (const double *)nullptr, p->h_out.dev(), p->seq_dev);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
 int enqueue_hvp(cmax_patch_plan_s *p, hipStream_t s) {
     const cmax_patch_objective_t &d = p->d;
+    if (p->map_kind == kMapDepth) return enqueue_hvp_depth(p, s);
     if (d.time_aware && d.scale_later) return enqueue_hvp_scale_later(p, s);
     if (d.time_aware) return enqueue_hvp_time_aware(p, s);
     // x64 | v64 | scal64 are one allocation: a single copy brings x, v and the two scalars
@@ -1623,6 +1766,172 @@ int cmax_basis_to_dense(const void *theta_dev, const void *basis_dev, int dtype,
     return 0;
 }
 
+int cmax_sizeof_depth_objective(void) { return (int)sizeof(cmax_depth_objective_t); }
+
+// A patch plan whose map is the depth map of cmax_depth_kernels.h: the descriptor becomes a cmax_patch_objective_t that carries the grid's
+// geometry (the kernels read it there) and no total variation; map_kind picks the map wherever the filter is picked.
+int cmax_depth_plan_create(cmax_handle_t h, const cmax_depth_objective_t *desc, const void *A_dev, const void *B_dev, cmax_stream_t stream,
+                           cmax_patch_plan_t *out) {
+    CMAX_REQUIRE(h && desc && A_dev && out, "depth_plan_create: null pointer");
+    if (handle_is_weighted(h)) {
+        set_error("depth_plan_create: not built for a handle that holds per-event weights (cmax_set_event_weights); pass weights = NULL to clear them");
+        return CMAX_EUNSUPPORTED;
+    }
+    if (handle_has_comm(h)) {
+        set_error("depth_plan_create: not built for time-sliced batches (the handle holds a communicator)");
+        return CMAX_EUNSUPPORTED;
+    }
+    const cmax_depth_objective_t &b = *desc;
+    CMAX_REQUIRE(b.Ka >= 1 && b.Kb >= 0 && b.Ka <= CMAX_BASIS_MAX_K && b.Kb <= CMAX_BASIS_MAX_K && b.Ka + b.Kb <= CMAX_BASIS_MAX_K,
+                 "depth_plan_create: Ka, Kb (1 <= Ka, 0 <= Kb, Ka + Kb <= CMAX_BASIS_MAX_K)");
+    CMAX_REQUIRE(b.Kb == 0 || B_dev, "depth_plan_create: null B with Kb > 0");
+    CMAX_REQUIRE(b.basis_dtype == CMAX_F32 || b.basis_dtype == CMAX_F64, "depth_plan_create: basis_dtype (CMAX_F32 or CMAX_F64)");
+    CMAX_REQUIRE(b.scale_later == 0, "depth_plan_create: scale_later is not built for the depth map");
+    CMAX_REQUIRE(b.filter_type == CMAX_FILTER_BILINEAR, "depth_plan_create: filter_type: only CMAX_FILTER_BILINEAR is built for the depth map (nearest is refused)");
+    CMAX_REQUIRE(b.tv_weight == 0.0, "depth_plan_create: tv_weight: total variation is not built for the depth grid (must be 0)");
+    CMAX_REQUIRE(b.n_terms >= 1 && b.n_terms <= 4, "depth_plan_create: n_terms");
+    CMAX_REQUIRE(b.H > 0 && b.W > 0 && b.ph > 0 && b.pw > 0 && b.sw_h > 0 && b.sw_w > 0 && b.pad_h >= 0 && b.pad_w >= 0, "depth_plan_create: sizes");
+    CMAX_REQUIRE((int64_t)b.ph * b.pw <= (1 << 20), "depth_plan_create: sizes (ph pw)");
+    CMAX_REQUIRE(!b.time_aware || (b.T > 0 && b.t0 >= 0 && b.t0 < b.T), "depth_plan_create: time bins");
+    for (int i = 0; i < b.n_terms; ++i) {
+        CMAX_REQUIRE(b.term[i].model == (b.time_aware ? CMAX_MODEL_VOXEL : CMAX_MODEL_DENSE), "depth_plan_create: term model must match time_aware");
+        CMAX_REQUIRE(!b.time_aware || b.term[i].T == b.T, "depth_plan_create: term T");
+        CMAX_REQUIRE(b.term[i].motion_dtype == b.term[0].motion_dtype, "depth_plan_create: the terms must agree on motion_dtype");
+    }
+    cmax_patch_objective_t d;
+    std::memset(&d, 0, sizeof(d));
+    d.n_terms = b.n_terms;
+    d.time_aware = b.time_aware;
+    d.T = b.T;
+    d.scheme = b.scheme;
+    d.t0 = b.t0;
+    d.H = b.H;
+    d.W = b.W;
+    d.ph = b.ph;
+    d.pw = b.pw;
+    d.sw_h = b.sw_h;
+    d.sw_w = b.sw_w;
+    d.pad_h = b.pad_h;
+    d.pad_w = b.pad_w;
+    d.filter_type = CMAX_FILTER_BILINEAR;
+    d.t_scale = b.t_scale;
+    for (int i = 0; i < 4; ++i) d.weight[i] = b.weight[i];
+    for (int i = 0; i < b.n_terms; ++i) d.term[i] = b.term[i];
+    cmax_patch_plan_t p = nullptr;
+    const int K = b.Ka + b.Kb;
+    int rc = plan_allocate(h, d, K + b.ph * b.pw, "depth_plan_create", &p);
+    if (rc) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    p->map_kind = kMapDepth;
+    p->Ka = b.Ka;
+    p->Kb = b.Kb;
+    p->basis_dtype = b.basis_dtype;
+    const bool b64 = b.basis_dtype == CMAX_F64;
+    const size_t esz = b64 ? sizeof(double) : sizeof(float);
+    rc = b64 ? p->basis64.reserve(nullptr, (int64_t)K * p->nflow, nullptr) : p->basis32.reserve(nullptr, (int64_t)K * p->nflow, nullptr);
+    if (!rc) rc = p->basis_partial.reserve(nullptr, (int64_t)depth_adj_chunks(p->nflow / 2) * K, nullptr);
+    if (!rc) rc = p->depth_q.reserve(nullptr, p->nflow / 2, nullptr);
+    if (!rc) {
+        hipError_t e = hipMemcpyAsync(const_cast<void *>(plan_basis(p)), A_dev, (size_t)b.Ka * p->nflow * esz, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess && b.Kb > 0) e = hipMemcpyAsync(const_cast<void *>(plan_depth_B(p)), B_dev, (size_t)b.Kb * p->nflow * esz, hipMemcpyDeviceToDevice, s);
+        if (e == hipSuccess) e = hipStreamSynchronize(s);
+        if (e != hipSuccess) {
+            set_error("depth_plan_create: copying the bases failed: %s", hipGetErrorString(e));
+            rc = (int)e;
+        }
+    }
+    if (rc) {
+        if (rc == CMAX_ENOMEM) set_error("depth_plan_create: allocation failed");
+        cmax_patch_plan_destroy(p);
+        return rc;
+    }
+    *out = p;
+    return 0;
+}
+
+// what every depth leaf checks before it launches
+static int depth_leaf_check(const char *who, bool pointers, int dtype, int Ka, int Kb, const void *B, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w,
+                            int H, int W) {
+    const bool ok = pointers && (Kb == 0 || B) && (dtype == CMAX_F32 || dtype == CMAX_F64) && Ka >= 1 && Kb >= 0 && Ka <= CMAX_BASIS_MAX_K &&
+                    Kb <= CMAX_BASIS_MAX_K && Ka + Kb <= CMAX_BASIS_MAX_K && H > 0 && W > 0 && ph > 0 && pw > 0 && sw_h > 0 && sw_w > 0 && pad_h >= 0 &&
+                    pad_w >= 0 && (int64_t)ph * pw <= (1 << 20);
+    if (!ok) {
+        set_error("%s: bad argument: null pointer, dtype, Ka / Kb (1 <= Ka, 0 <= Kb, Ka + Kb <= CMAX_BASIS_MAX_K) or sizes", who);
+        return CMAX_EINVAL;
+    }
+    return 0;
+}
+
+int cmax_depth_to_dense(const void *a, const void *b, const void *s_, const void *A, const void *B, int dtype, int Ka, int Kb, int ph, int pw, int pad_h,
+                        int pad_w, int sw_h, int sw_w, int H, int W, void *out, cmax_stream_t stream) {
+    if (int rc = depth_leaf_check("depth_to_dense", a && s_ && A && out && (Kb == 0 || b), dtype, Ka, Kb, B, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W)) return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const DepthGeom g{ph, pw, pad_h, pad_w, sw_h, sw_w, H, W};
+    if (dtype == CMAX_F32) launch_depth_to_dense<float, float>((const double *)a, (const double *)b, (const double *)s_, A, B, Ka, Kb, g, 1.0, nullptr, (float *)out, s);
+    else launch_depth_to_dense<double, double>((const double *)a, (const double *)b, (const double *)s_, A, B, Ka, Kb, g, 1.0, nullptr, (double *)out, s);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+int cmax_depth_to_dense_tan(const void *a, const void *s_, const void *da, const void *db, const void *ds, const void *A, const void *B, int dtype, int Ka,
+                            int Kb, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, void *out, cmax_stream_t stream) {
+    if (int rc = depth_leaf_check("depth_to_dense_tan", a && s_ && da && ds && A && out && (Kb == 0 || db), dtype, Ka, Kb, B, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W))
+        return rc;
+    hipStream_t s = (hipStream_t)stream;
+    const DepthGeom g{ph, pw, pad_h, pad_w, sw_h, sw_w, H, W};
+    if (dtype == CMAX_F32)
+        launch_depth_to_dense_tan<float, float>((const double *)a, (const double *)s_, (const double *)da, (const double *)db, (const double *)ds, A, B, Ka, Kb, g, 1.0,
+                                                (float *)out, s);
+    else
+        launch_depth_to_dense_tan<double, double>((const double *)a, (const double *)s_, (const double *)da, (const double *)db, (const double *)ds, A, B, Ka, Kb, g,
+                                                  1.0, (double *)out, s);
+    CMAX_CHECK_LAUNCH();
+    return 0;
+}
+
+// both adjoints of the leaf: chunk sums, the folded [a | b] block and the plane q in ONE stream-ordered temporary
+static int depth_leaf_adjoint(bool second, const void *a, const void *s_, const void *da, const void *ds, const void *g, const void *dg, const void *A,
+                              const void *B, int dtype, int Ka, int Kb, const DepthGeom &geo, double *out_a, double *out_b, double *out_s, hipStream_t s) {
+    const int64_t hw = (int64_t)geo.H * geo.W;
+    const int K = Ka + Kb;
+    const size_t n_partial = (size_t)depth_adj_chunks(hw) * K;
+    double *tmp = nullptr;
+    CMAX_CHECK_HIP(hipMallocAsync((void **)&tmp, (n_partial + K + (size_t)hw) * sizeof(double), s));
+    double *ab = tmp + n_partial, *q = ab + K;
+    const double *a_ = (const double *)a, *sg = (const double *)s_, *da_ = (const double *)da, *ds_ = (const double *)ds;
+    if (dtype == CMAX_F32) {
+        if (second) launch_depth_adj<float, float, true>((const float *)g, (const float *)dg, a_, sg, da_, ds_, A, B, Ka, Kb, geo, tmp, q, ab, out_s, s);
+        else launch_depth_adj<float, float, false>((const float *)g, (const float *)nullptr, a_, sg, da_, ds_, A, B, Ka, Kb, geo, tmp, q, ab, out_s, s);
+    } else {
+        if (second) launch_depth_adj<double, double, true>((const double *)g, (const double *)dg, a_, sg, da_, ds_, A, B, Ka, Kb, geo, tmp, q, ab, out_s, s);
+        else launch_depth_adj<double, double, false>((const double *)g, (const double *)nullptr, a_, sg, da_, ds_, A, B, Ka, Kb, geo, tmp, q, ab, out_s, s);
+    }
+    hipError_t e = hipGetLastError();
+    if (e == hipSuccess) e = hipMemcpyAsync(out_a, ab, (size_t)Ka * sizeof(double), hipMemcpyDeviceToDevice, s);
+    if (e == hipSuccess && Kb > 0) e = hipMemcpyAsync(out_b, ab + Ka, (size_t)Kb * sizeof(double), hipMemcpyDeviceToDevice, s);
+    CMAX_CHECK_HIP(hipFreeAsync(tmp, s));
+    CMAX_CHECK_HIP(e);
+    return 0;
+}
+
+int cmax_depth_to_dense_adj(const void *a, const void *s_, const void *g, const void *A, const void *B, int dtype, int Ka, int Kb, int ph, int pw, int pad_h,
+                            int pad_w, int sw_h, int sw_w, int H, int W, double *g_a, double *g_b, double *g_s, cmax_stream_t stream) {
+    if (int rc = depth_leaf_check("depth_to_dense_adj", a && s_ && g && A && g_a && g_s && (Kb == 0 || g_b), dtype, Ka, Kb, B, ph, pw, pad_h, pad_w, sw_h, sw_w, H, W))
+        return rc;
+    return depth_leaf_adjoint(false, a, s_, nullptr, nullptr, g, nullptr, A, B, dtype, Ka, Kb, DepthGeom{ph, pw, pad_h, pad_w, sw_h, sw_w, H, W}, g_a, g_b, g_s,
+                              (hipStream_t)stream);
+}
+
+int cmax_depth_to_dense_adj2(const void *a, const void *s_, const void *da, const void *ds, const void *g, const void *dg, const void *A, const void *B, int dtype,
+                             int Ka, int Kb, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, double *out_a, double *out_b, double *out_s,
+                             cmax_stream_t stream) {
+    if (int rc = depth_leaf_check("depth_to_dense_adj2", a && s_ && da && ds && g && dg && A && out_a && out_s && (Kb == 0 || out_b), dtype, Ka, Kb, B, ph, pw, pad_h,
+                                  pad_w, sw_h, sw_w, H, W))
+        return rc;
+    return depth_leaf_adjoint(true, a, s_, da, ds, g, dg, A, B, dtype, Ka, Kb, DepthGeom{ph, pw, pad_h, pad_w, sw_h, sw_w, H, W}, out_a, out_b, out_s,
+                              (hipStream_t)stream);
+}
+
 int cmax_patch_plan_set_t_scale(cmax_patch_plan_t p, double t_scale) {
     CMAX_REQUIRE(p != nullptr, "patch_plan_set_t_scale");
     if (p->d.t_scale != t_scale) {
@@ -1828,6 +2137,13 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
         int rc = p->dflow64.reserve(nullptr, p->nflow, (hipStream_t)stream);
         if (rc) return rc;
     }
+    if (p->map_kind == kMapDepth && !d.time_aware) {  // the fp64 tangent field, the second seed and the device-side maximum, on first use
+        hipStream_t s = (hipStream_t)stream;
+        int rc = p->dflow64.reserve(nullptr, p->nflow, s);
+        if (!rc) rc = p->dgacc64.reserve(nullptr, p->nmotion, s);
+        if (!rc) rc = p->scal.reserve(nullptr, 4, s);
+        if (rc) return rc;
+    }
     if (d.time_aware) {  // second-order buffers of the voxel chain, on first use
         hipStream_t s = (hipStream_t)stream;
         int rc = p->dflow64.reserve(nullptr, p->nflow, s);
@@ -1837,7 +2153,8 @@ int cmax_patch_plan_hvp(cmax_patch_plan_t p, const double *x_host, const double 
         if (!rc) rc = p->scal.reserve(nullptr, 4, s);
         if (rc) return rc;
     }
-    // |v|_inf bounds |P v|_inf (a negated convex combination); a basis can amplify: sum_k |v_k| max|B_k| bounds |B v|_inf
+    // |v|_inf bounds |P v|_inf (a negated convex combination); a basis can amplify: sum_k |v_k| max|B_k| bounds |B v|_inf.  A depth plan
+    // takes its scale on the device (enqueue_hvp_depth): here |v|_inf only tells a zero tangent from any other
     double vmax = 0.0;
     if (p->map_kind == kMapBasis)
         for (int j = 0; j < p->nx; ++j) vmax += fabs(v_host[j]) * p->bmax[j];

@@ -424,6 +424,80 @@ def basis_to_dense(theta, basis):
     return _BasisToDenseFn.apply(theta, basis)
 
 
+def _depth_geometry(geometry):
+    """(ph, pw, pad_h, pad_w, sw_h, sw_w) from a sequence of six integers or a mapping with the keys patch_image_size, pad, sliding_window."""
+    if isinstance(geometry, dict):
+        geometry = tuple(geometry["patch_image_size"]) + tuple(geometry["pad"]) + tuple(geometry["sliding_window"])
+    g = tuple(int(v) for v in geometry)
+    if len(g) != 6 or min(g[0], g[1], g[4], g[5]) < 1 or min(g[2], g[3]) < 0:
+        raise ValueError(f"geometry must be (ph, pw, pad_h, pad_w, sw_h, sw_w) with positive sizes, got {geometry!r}")
+    return g
+
+
+class _DepthToDenseFn(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b, s, A, B, geo):
+        Ka, _, H, W = A.shape
+        Kb = 0 if B is None else B.shape[0]
+        a64, s64 = a.detach().to(torch.float64).contiguous(), s.detach().to(torch.float64).contiguous()
+        b64 = None if Kb == 0 else b.detach().to(torch.float64).contiguous()
+        flow = torch.empty((2, H, W), dtype=A.dtype, device=A.device)
+        check(_lib.load().cmax_depth_to_dense(_ptr(a64), None if Kb == 0 else _ptr(b64), _ptr(s64), _ptr(A), None if Kb == 0 else _ptr(B), _code(A), Ka, Kb,
+                                              *geo, H, W, _ptr(flow), _stream()))
+        ctx.save_for_backward(a64, s64, A, *(() if Kb == 0 else (B,)))
+        ctx.meta = (geo, a.dtype, None if b is None else b.dtype, s.dtype, s.shape, None if b is None else b.shape)
+        return flow
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, gflow):
+        a64, s64, A, *rest = ctx.saved_tensors
+        B = rest[0] if rest else None
+        geo, a_dtype, b_dtype, s_dtype, s_shape, b_shape = ctx.meta
+        Ka, _, H, W = A.shape
+        Kb = 0 if B is None else B.shape[0]
+        gflow = gflow.to(A.dtype).contiguous()
+        ga = torch.empty(Ka, dtype=torch.float64, device=A.device)
+        gb = torch.empty(max(Kb, 1), dtype=torch.float64, device=A.device)
+        gs = torch.empty(geo[0] * geo[1], dtype=torch.float64, device=A.device)
+        check(_lib.load().cmax_depth_to_dense_adj(_ptr(a64), _ptr(s64), _ptr(gflow), _ptr(A), None if Kb == 0 else _ptr(B), _code(A), Ka, Kb, *geo, H, W,
+                                                  _ptr(ga), _ptr(gb), _ptr(gs), _stream()))
+        g_b = None if b_dtype is None else (gb[:Kb].to(b_dtype).reshape(b_shape) if Kb else torch.zeros(b_shape, dtype=b_dtype, device=A.device))
+        return ga.to(a_dtype), g_b, gs.to(s_dtype).reshape(s_shape), None, None, None
+
+
+def depth_to_dense(a, b, s, A, B, geometry):
+    """Dense flow of the motion field over a grid of inverse depth (include/cmax_hip.h, "Depth and ego-motion"):
+        D = (Q s) * sum_k a_k A_k + sum_j b_j B_j
+    a [Ka], b [Kb] (None or empty with B None / [0,2,H,W]), s [ph,pw] (or flat), A [Ka,2,H,W], B [Kb,2,H,W] (float32 or float64, both the
+    same; Ka >= 1, Ka + Kb <= 64), geometry = (ph, pw, pad_h, pad_w, sw_h, sw_w) or {"patch_image_size", "pad", "sliding_window"}: Q is the
+    bilinear interpolation of `patch_to_dense` on one plane WITHOUT its negation.  -> [2,H,W] in the bases' dtype, accumulated in float64 and
+    rounded once.  The backward is the adjoint in float64 without atomics (bit-repeatable); it is once differentiable (the exact product
+    lives in solver.DepthEgoMotionObjective).  The bases are constants and receive no gradient."""
+    _lib.require_gpu()
+    geo = _depth_geometry(geometry)
+    A = _cuda(A, "A")
+    if A.dim() != 4 or A.shape[1] != 2:
+        raise ValueError(f"A must be [Ka, 2, H, W], got {tuple(A.shape)}")
+    if B is not None and B.shape[0] == 0:
+        B = None
+    if B is not None:
+        B = _cuda(B, "B")
+        if B.dim() != 4 or tuple(B.shape[1:]) != tuple(A.shape[1:]) or B.dtype != A.dtype:
+            raise ValueError(f"B must be [Kb, 2, H, W] like A ({tuple(A.shape[1:])}, {A.dtype}), got {tuple(B.shape)} {B.dtype}")
+    Ka, Kb = A.shape[0], 0 if B is None else B.shape[0]
+    if not (1 <= Ka and Ka + Kb <= _lib.BASIS_MAX_K):
+        raise ValueError(f"the bases have 1 <= Ka and Ka + Kb <= {_lib.BASIS_MAX_K} fields, got Ka = {Ka}, Kb = {Kb}")
+    a = _cuda(a, "a").reshape(-1)
+    s = _cuda(s, "s")
+    if b is not None:
+        b = _cuda(b, "b").reshape(-1)
+    if a.numel() != Ka or (0 if b is None else b.numel()) != Kb or s.numel() != geo[0] * geo[1]:
+        raise ValueError(f"a, b, s have {a.numel()}, {0 if b is None else b.numel()}, {s.numel()} elements; the bases have {Ka}, {Kb} fields and the grid "
+                         f"{geo[0]} x {geo[1]} cells")
+    return _DepthToDenseFn.apply(a, b, s, A.contiguous(), None if B is None else B.contiguous(), geo)
+
+
 class _FieldMaxFn(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x):

@@ -69,6 +69,26 @@ def flow_basis(model: str, image_size: tuple, calib=None) -> np.ndarray:
     return np.ascontiguousarray(0.0 - np.stack([np.stack(f) for f in u]))  # (0.0 - x: no negative zeros)
 
 
+def motion_field_basis(image_size: tuple, calib) -> tuple:
+    """(A [3,2,H,W], B [3,2,H,W]) float64: the motion field of a static scene seen by a calibrated camera that moves, split into the part
+    that scales with inverse depth and the part that does not (functional.depth_to_dense, solver.DepthEgoMotionObjective):
+        u(x) = rho(x) * sum_k v_k a_k(x) + sum_j w_j b_j(x),   v = (v_x, v_y, v_z) the linear, w the angular velocity.
+    calib = (fx, fy, cx, cy) and every convention of `flow_basis("rotation")`: rows first, x = (j - cx) / fx, y = (i - cy) / fy, the
+    fields stored as -u (the dense-flow rule is x' = x - dt D[src]).  B IS flow_basis("rotation", image_size, calib); A is the
+    translational field per unit inverse depth,
+        u_col = fx (-v_x + x v_z),   u_row = fy (-v_y + y v_z)."""
+    if calib is None or len(calib) != 4:
+        raise ValueError("motion_field_basis needs calib = (fx, fy, cx, cy)")
+    H, W = int(image_size[0]), int(image_size[1])
+    fx, fy, cx, cy = (float(v) for v in calib)
+    i, j = np.meshgrid(np.arange(H, dtype=np.float64), np.arange(W, dtype=np.float64), indexing="ij")
+    x, y = (j - cx) / fx, (i - cy) / fy
+    zero = np.zeros((H, W))
+    u = [(zero, zero - fx), (zero - fy, zero), (fy * y, fx * x)]  # (u_row, u_col) per v_x, v_y, v_z
+    A = np.ascontiguousarray(0.0 - np.stack([np.stack(f) for f in u]))
+    return A, flow_basis("rotation", image_size, calib)
+
+
 def construct_dense_flow_voxel_torch(dense_flow: torch.Tensor, time_bin: int, scheme: str = "upwind",
                                      t0_location: str = "middle", clamp: Optional[int] = None) -> torch.Tensor:
     """[(b,) 2,H,W] flow at t0 -> [(b,) time_bin, 2, H, W] voxel, differentiable.

@@ -941,6 +941,75 @@ int cmax_sizeof_basis_objective(void);
 int cmax_basis_plan_create(cmax_handle_t h, const cmax_basis_objective_t *desc_host, const void *basis_dev, cmax_stream_t stream,
                            cmax_patch_plan_t *out);
 
+/* =============================================================================================
+ * Depth and ego-motion: the motion field of a static scene over a grid of inverse depth.
+ *   x = [a_0 .. a_{Ka-1} | b_0 .. b_{Kb-1} | s]   s: a scalar patch grid [ph][pw], row-major;  nx = Ka + Kb + ph pw
+ *   rho = Q s          Q: the bilinear interpolation of cmax_patch_to_dense (replicate pad, align_corners = False, centre crop) on ONE
+ *                      plane and WITHOUT the negation the patch map carries
+ *   U = sum_k a_k A_k,  R = sum_j b_j B_j,   D[c][e] = rho[e] U[c][e] + R[c][e]
+ * A [Ka][2][H][W]: the translational field per unit inverse depth; B [Kb][2][H][W]: what does not depend on depth (the rotational
+ * field of a calibrated camera).  1 <= Ka, 0 <= Kb, Ka + Kb <= CMAX_BASIS_MAX_K.  D is a PRODUCT of unknowns: neither the patch
+ * plan nor the basis plan expresses it.  Gallego, Rebecq, Scaramuzza (CVPR 2018) name depth among the applications of contrast
+ * maximisation; Shiba, Klose, Aoki, Gallego (TPAMI 2024) put inverse depth on a patch grid.  The reference has no counterpart; D is
+ * warped by its dense-flow rule x' = x - dt * D[src] (src/warp.py:263-313).
+ * GAUGE: (a, s) -> (lambda a, s / lambda) leaves D unchanged, so the Hessian is singular along that line.  That is a property of the
+ * model; nothing here works around it.
+ * Leaf operators (a, b, s, da, db, ds: device fp64; A, B, g, dg, out of the forward and the tangent: `dtype`; every adjoint output:
+ * device fp64).  fp64 arithmetic, one rounding at the store, no atomics (fixed trees: two runs agree bit for bit).  b, B, db, g_b
+ * may be NULL when Kb = 0.  The adjoints cut the image into chunks of CMAX_DEPTH_ADJ_CHUNK consecutive pixels and use a
+ * stream-ordered temporary (hipMallocAsync) of ceil(H W / CMAX_DEPTH_ADJ_CHUNK) (Ka + Kb) + Ka + Kb + H W doubles.
+ *   cmax_depth_to_dense        out = D
+ *   cmax_depth_to_dense_tan    out = dD = (Q ds) U + rho (A da) + B db
+ *   cmax_depth_to_dense_adj    g_a[k] = sum rho A_k . g,  g_b[j] = sum B_j . g,  g_s = Q^T q with q[e] = sum_c U[c][e] g[c][e]
+ *   cmax_depth_to_dense_adj2   J(x)^T dg + (dJ[u])^T g for u = (da, db, ds):  out_a[k] = sum rho A_k . dg + sum (Q ds) A_k . g,
+ *                              out_b[j] = sum B_j . dg,  out_s = Q^T [U . dg + (A da) . g]     (db does not enter)
+ * Only the bilinear filter is built.                                                                                          */
+#define CMAX_DEPTH_ADJ_CHUNK 1024
+int cmax_depth_to_dense(const void *a, const void *b, const void *s, const void *A, const void *B, int dtype, int Ka, int Kb, int ph,
+                        int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, void *out, cmax_stream_t stream);
+int cmax_depth_to_dense_tan(const void *a, const void *s, const void *da, const void *db, const void *ds, const void *A, const void *B,
+                            int dtype, int Ka, int Kb, int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W,
+                            void *out, cmax_stream_t stream);
+int cmax_depth_to_dense_adj(const void *a, const void *s, const void *g, const void *A, const void *B, int dtype, int Ka, int Kb,
+                            int ph, int pw, int pad_h, int pad_w, int sw_h, int sw_w, int H, int W, double *g_a, double *g_b,
+                            double *g_s, cmax_stream_t stream);
+int cmax_depth_to_dense_adj2(const void *a, const void *s, const void *da, const void *ds, const void *g, const void *dg,
+                             const void *A, const void *B, int dtype, int Ka, int Kb, int ph, int pw, int pad_h, int pad_w, int sw_h,
+                             int sw_w, int H, int W, double *out_a, double *out_b, double *out_s, cmax_stream_t stream);
+
+/* Depth plan: the optimiser's objective for that model in one call.
+ *   x (host fp64) -> D * t_scale [-> voxel (cmax_voxel_construct)] -> fp32 -> loss = sum_i weight_i * cmax_objective(term_i)
+ * and back: the gradient t J^T dL/dF, the exact product (the map is not linear: t [J^T (H_FF t dD) + (dJ[v])^T g_F], with the tangent of
+ * the flow scaled to unit max-norm by a maximum taken ON THE DEVICE -- a host bound does not hold for a product of unknowns), the
+ * device-resident descent and L-BFGS.  cmax_depth_plan_create returns a cmax_patch_plan_t with nx = Ka + Kb + ph pw on which
+ * cmax_patch_plan_evaluate / _hvp / _descend / _lbfgs / _set_t_scale / _set_flow_regularizer / _info / _destroy work unchanged
+ * (with_tv is ignored).  cmax_depth_objective_t is a new struct: the ABI version is unchanged.                                   */
+typedef struct {
+    int32_t n_terms;          /* 1..4 fused contrast terms */
+    int32_t time_aware;       /* 0: terms use CMAX_MODEL_DENSE; 1: CMAX_MODEL_VOXEL on the propagated flow */
+    int32_t T, scheme, t0;    /* as cmax_patch_objective_t */
+    int32_t H, W;             /* sensor size of the handle */
+    int32_t Ka, Kb;           /* fields of A (>= 1) and of B (>= 0); Ka + Kb <= CMAX_BASIS_MAX_K */
+    int32_t ph, pw;           /* the grid of inverse depth */
+    int32_t pad_h, pad_w;     /* as cmax_patch_objective_t */
+    int32_t sw_h, sw_w;
+    int32_t basis_dtype;      /* CMAX_F32 or CMAX_F64: what A_dev and B_dev point to, and what the plan keeps */
+    int32_t scale_later;      /* must be 0 (CMAX_EINVAL) */
+    int32_t filter_type;      /* must be CMAX_FILTER_BILINEAR: the nearest filter is not built for this map (CMAX_EINVAL) */
+    double t_scale;           /* pixel per time unit -> pixel per normalised batch period */
+    double weight[4];
+    double tv_weight;         /* must be 0: total variation of the depth grid is not built (CMAX_EINVAL) */
+    cmax_objective_t term[4]; /* motion_dtype == CMAX_F64 on all of them or on none (an exact plan, as for the patch plan) */
+} cmax_depth_objective_t;
+int cmax_sizeof_depth_objective(void);
+/* A_dev [Ka][2][H][W], B_dev [Kb][2][H][W] (NULL when Kb = 0) in desc->basis_dtype; the plan keeps ITS OWN COPY (copied on `stream`,
+ * which the call synchronises).  Refused: Ka < 1, Kb < 0, Ka + Kb > CMAX_BASIS_MAX_K, an unknown basis_dtype, scale_later != 0,
+ * filter_type != CMAX_FILTER_BILINEAR, tv_weight != 0 and everything cmax_patch_plan_create checks about sizes and terms
+ * (CMAX_EINVAL); a handle that holds a communicator and a handle that holds per-event weights (CMAX_EUNSUPPORTED).  A plan on a
+ * deterministic handle is bit-repeatable: the depth kernels use no atomics.                                                     */
+int cmax_depth_plan_create(cmax_handle_t h, const cmax_depth_objective_t *desc_host, const void *A_dev, const void *B_dev,
+                           cmax_stream_t stream, cmax_patch_plan_t *out);
+
 /* The reduction of the scale_later map as a leaf operator (the autograd-chained path chains it with cmax_patch_to_dense and
  * cmax_voxel_construct).  x: device fp32 / fp64 [n].  out: device double[4] -- out[0] = max x (signed), out[1] = number of
  * elements EQUAL to it (exact comparison of the values the device holds), out[2..3] scratch.  Asynchronous.                 */
