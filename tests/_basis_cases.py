@@ -67,6 +67,7 @@ PLAN_CASES = [
     _model_case("similarity-27x40-exact-one", "similarity", (27, 40), terms=ONE_TERM, exact=True),
     _model_case("similarity-27x40-burgers", "similarity", (27, 40), terms=TWO_TERMS, **BURGERS),
     _model_case("affine-27x40-upwind-first-T5", "affine", (27, 40), terms=ONE_TERM, **UPWIND),
+    _model_case("similarity-27x40-exact-burgers", "similarity", (27, 40), terms=TWO_TERMS, exact=True, **BURGERS),  # both planes from the fp64 voxel
 ]
 PLAN = {c["id"]: c for c in PLAN_CASES}
 GRAPH_CASE = "affine-27x40-two"
@@ -81,6 +82,9 @@ HVP_CASES = [
     # With both sides even the coordinates are half-integers and neither component of the similarity field vanishes at a pixel
     # (tests/test_basis_reference.py checks that no time-aware product case sits on such a zero).
     _model_case("hvp-similarity-68x90-burgers", "similarity", (68, 90), terms=TWO_TERMS, **BURGERS),
+    # an exact plan (the fused terms take both planes of the fp64 motion), without and with the voxel chain; both sides even, as above
+    _model_case("hvp-similarity-20x32-exact-f32basis", "similarity", (20, 32), terms=TWO_TERMS, exact=True, basis_dtype="float32"),
+    _model_case("hvp-similarity-20x32-exact-burgers", "similarity", (20, 32), terms=TWO_TERMS, exact=True, **BURGERS),
 ]
 HVP = {c["id"]: c for c in HVP_CASES}
 

@@ -80,6 +80,7 @@ PLAN_CASES = [
     case("cam-27x40-f32basis", "3x4-odd", (27, 40), terms=ONE_TERM, basis_dtype="float32"),
     case("cam-27x40-burgers", "3x4-odd", (27, 40), terms=TWO_TERMS, **BURGERS),
     case("cam-27x40-upwind-first-T5", "3x4-odd", (27, 40), terms=ONE_TERM, **UPWIND),
+    case("cam-27x40-exact-burgers", "3x4-odd", (27, 40), terms=TWO_TERMS, exact=True, **BURGERS),  # both planes from the fp64 voxel
 ]
 PLAN = {c["id"]: c for c in PLAN_CASES}
 GRAPH_CASE = "cam-27x40-two"
@@ -90,6 +91,9 @@ FLOW_REG = {"kind": "divergence", "weight": 0.05, "eps": 1e-3, "s": 1.0}
 HVP_CASES = [
     case("hvp-cam-68x90-two", "overlap", (68, 90), terms=TWO_TERMS),
     case("hvp-cam-20x32-burgers", "3x4-odd", (20, 32), terms=TWO_TERMS, **BURGERS),
+    # an exact plan (the fused terms take both planes of the fp64 motion) on an fp32 basis, without and with the voxel chain
+    case("hvp-cam-20x32-exact-f32basis", "3x4-odd", (20, 32), terms=TWO_TERMS, exact=True, basis_dtype="float32"),
+    case("hvp-cam-20x32-exact-burgers-f32basis", "3x4-odd", (20, 32), terms=TWO_TERMS, exact=True, basis_dtype="float32", **BURGERS),
 ]
 HVP = {c["id"]: c for c in HVP_CASES}
 

@@ -82,12 +82,19 @@ PATCH_PLANS = [
     ("burgers-area", "burgers", "bilinear", "area"),           # the 68 x 90 sensor
     ("upwind-div", "upwind", "bilinear", "divergence"),
     ("exact-area", "plain-exact", "bilinear", "area"),         # exact_flow
+    # exact_flow behind the voxel chain, and the nearest filter with the chain, with exact_flow, with both
+    ("burgers-exact-area", "burgers-exact", "bilinear", "area"),
+    ("nearest-burgers-area", "burgers", "nearest", "area-half"),
+    ("nearest-exact-area", "plain-exact", "nearest", "area-half"),
+    ("nearest-burgers-exact-area", "burgers-exact", "nearest", "area-half"),
 ]
 # (id, B.HVP row, regulariser)
 BASIS_PLANS = [
     ("affine-area", "hvp-affine-27x40-two", "area"),                   # K = 6
     ("similarity-div", "hvp-similarity-68x90-one", "divergence"),      # K = 4, one term: the accumulate path only because of the term
     ("similarity-burgers-area", "hvp-similarity-68x90-burgers", "area-half"),
+    ("similarity-exact-div", "hvp-similarity-20x32-exact-f32basis", "divergence"),            # exact_flow, an fp32 basis
+    ("similarity-exact-burgers-area", "hvp-similarity-20x32-exact-burgers", "area-half"),     # exact_flow behind the voxel chain
 ]
 GRAPH_PLAN = "affine-area"
 _BUILT = {}
