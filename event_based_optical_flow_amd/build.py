@@ -16,7 +16,7 @@ CSRC = os.path.join(PKG_DIR, "csrc")
 LIB_PATH = os.environ.get("CMAX_LIB", os.path.join(PKG_DIR, "libcmax_hip.so"))
 OBJ_DIR = os.path.join(PKG_DIR, "_obj")  # objects and their dependency files (git-ignored)
 # every *.hip of csrc/ (tests/test_host_logic.py checks it); all are compiled at once, cmax_event_launch.hip is the long pole
-SOURCES = ["cmax_leaf.hip", "cmax_flow.hip", "cmax_event_launch.hip", "cmax_fused.hip", "cmax_solver.hip", "cmax_comm.hip"]
+SOURCES = ["cmax_leaf.hip", "cmax_flow.hip", "cmax_event_launch.hip", "cmax_fused.hip", "cmax_batch.hip", "cmax_solver.hip", "cmax_comm.hip"]
 PUBLIC_HEADER = os.path.join(PKG_DIR, "..", "include", "cmax_hip.h")
 # -munsafe-fp-atomics: fp32/fp64 atomicAdd lower to global_atomic_add_f32/_f64 and ds_add_f32
 # (hardware atomics) instead of compare-and-swap loops.

@@ -634,7 +634,7 @@ void launch_vote_tan2(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, 
     }
 }
 
-// the compact copy of the sorted events, one region per segment of the current work list (build_segments, cmax_fused.hip)
+// the compact copy of the sorted events, one region per segment of the current work list (build_segments, cmax_batch.hip)
 int pack_compact_events(cmax_handle_s *h, hipStream_t s) {
     int rc = h->cev.reserve(&h->bytes, (int64_t)h->nseg * b512::kCompactStride, s);
     if (rc) return rc;

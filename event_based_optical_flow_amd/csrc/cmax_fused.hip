@@ -30,9 +30,10 @@
 //                   accumulators in block-scaled fixed point)
 //   k_finish / k_finish_deferred   sum the per-segment partials (2-DoF), write loss + gradient
 // Every launch covers all reference times of the objective (blockIdx.y).  The event kernels (K1, K3, the tangent and per-event
-// gathers: cmax_event_kernels.inc) and their launch layer are a translation unit of their own, cmax_event_launch.hip; this unit
-// holds the handle, the per-batch preparation, the image-side kernels and the orchestration of an evaluation, and reaches the
-// event kernels through the launchers declared in cmax_fused_internal.h (launch_vote, launch_grad, ...) alone.
+// gathers: cmax_event_kernels.inc) and their launch layer are a translation unit of their own, cmax_event_launch.hip; so are the
+// handle's lifetime and everything done once per batch (set_events above), cmax_batch.hip.  This unit holds what is done PER
+// EVALUATION -- the image-side kernels and the orchestration -- and reaches the event kernels through the launchers declared in
+// cmax_fused_internal.h (launch_vote, launch_grad, ...) alone.
 //
 // fp32 per event with the integer source pixel split from the fp32 displacement (keeps the
 // bilinear fractions accurate to ulp(displacement) instead of ulp(coordinate)); fp64 reductions.
@@ -44,13 +45,9 @@
 #include "cmax_fused_device.h"
 #include "cmax_image_kernels.h"
 #include "cmax_search_kernels.h"
-#include "cmax_sort_kernels.h"
-#include "cmax_radix_sort.h"
 
-// Environment knobs (tuning experiments and A/B tests only; none changes results beyond rounding):
-//   CMAX_NO_OWNED=1      never build the group-aligned "owned groups" work list (cmax_set_events)
-//   CMAX_NO_RUN_SORT=1   leave the events of a source pixel in the order the tile sort produced (no ordering by time)
-//   CMAX_SEG_CAP=n        free-cut work lists: events per segment (<= the layout's cap; profiles/r04_ablation.txt 18)
+// Environment knobs this unit reads (tuning experiments and A/B tests only; none changes results beyond rounding; the per-batch ones
+// are listed in cmax_batch.hip):
 //   CMAX_NO_STATS_INSIDE=1   plain variance on owned groups: k_stats as a launch of its own instead of inside K3's
 //   CMAX_STAT_SWEEPS=n       statistics inside K3's launch: 4-pixel sweeps per statistics workgroup (fewer, longer workgroups)
 //   CMAX_NO_FUSED_BLURVAR=1  blurred variance: k_blur_stats_var + k_gimage_blur_adj_var instead of k_blur_stats_adj_var
@@ -58,131 +55,7 @@
 //   CMAX_NSUB=n          statistics sub-accumulators (cache lines) per image
 //   CMAX_TAN2=0 | 1      2-DoF tangent-image path: never / also without a communicator
 //   CMAX_PLAN_GRAPHS=1   replay the patch plan from captured hipGraphs (cmax_solver.hip)
-//   CMAX_COMPACT=0       big segments read the plain 8-byte events instead of the 4.5-byte compact copy (fp32 time instead of 24-bit fixed point)
-//   CMAX_DEBUG_COMPACT=1 cmax_set_events synchronises behind k_pack_compact and fails if an event did not fit its region's coordinates (tests read the flag
-//                         with cmax_debug_compact_events instead)
-//   CMAX_SORT=radix | bucket   per-batch order by the stable radix sort (cmax_radix_sort.h) / the two-level counting sort, whatever the size
 namespace cmax {
-
-// ---------------------------------------------------------------------------------------------
-// set_events: pack + two-level sort (cmax_sort_kernels.h); the scan of the tile counts lives here
-// ---------------------------------------------------------------------------------------------
-__global__ void k_tmm_set(double *tmm, double lo, double hi) {
-    tmm[0] = lo;
-    tmm[1] = hi;
-}
-
-// Exclusive scan of counts[0..m) in place, counts[m] = total, in three small launches: sums of 2048-element
-// chunks, scan of the chunk sums by one workgroup, scan inside every chunk (a single-workgroup scan of the
-// 921k pixel keys of a 1280x720 sensor took 1.4 ms).
-constexpr int kScanChunk = 2048;  // elements per workgroup (256 threads x 8)
-
-// nonzero (optional): += number of keys with at least one event (one atomic per workgroup)
-__global__ void __launch_bounds__(256) k_scan_sums(const int *__restrict__ counts, int m, int *__restrict__ chunk_sum, int *__restrict__ nonzero) {
-    __shared__ int s_w[4], s_n[4];
-    const int base = blockIdx.x * kScanChunk + threadIdx.x * 8;
-    int s = 0, nz = 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        const int c = base + u < m ? counts[base + u] : 0;
-        s += c;
-        nz += c != 0;
-    }
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) {
-        s += __shfl_xor(s, o, kWave);
-        nz += __shfl_xor(nz, o, kWave);
-    }
-    if ((threadIdx.x & (kWave - 1)) == 0) {
-        s_w[threadIdx.x / kWave] = s;
-        s_n[threadIdx.x / kWave] = nz;
-    }
-    __syncthreads();
-    if (threadIdx.x == 0) {
-        chunk_sum[blockIdx.x] = s_w[0] + s_w[1] + s_w[2] + s_w[3];
-        if (nonzero) atomicAdd(nonzero, s_n[0] + s_n[1] + s_n[2] + s_n[3]);
-    }
-}
-
-// one workgroup: exclusive scan of the chunk sums in place (nchunk <= 1024 * per-thread loop), total -> *total_out
-__global__ void __launch_bounds__(1024) k_scan_chunks(int *__restrict__ chunk_sum, int nchunk, int *__restrict__ total_out) {
-    __shared__ int part[1024];
-    const int t = threadIdx.x;
-    const int per = (nchunk + 1023) / 1024;
-    const int b = t * per, e = min(b + per, nchunk);
-    int s = 0;
-    for (int i = b; i < e; ++i) s += chunk_sum[i];
-    part[t] = s;
-    __syncthreads();
-    for (int o = 1; o < 1024; o <<= 1) {  // Hillis-Steele inclusive scan of the per-thread totals
-        int v = t >= o ? part[t - o] : 0;
-        __syncthreads();
-        part[t] += v;
-        __syncthreads();
-    }
-    int run = part[t] - s;
-    for (int i = b; i < e; ++i) {
-        const int c = chunk_sum[i];
-        chunk_sum[i] = run;
-        run += c;
-    }
-    if (t == 1023) *total_out = part[1023];
-}
-
-__global__ void __launch_bounds__(256) k_scan_apply(int *__restrict__ counts, int m, const int *__restrict__ chunk_off) {
-    __shared__ int s_w[4];
-    const int lane = threadIdx.x & (kWave - 1), wave = threadIdx.x / kWave;
-    const int base = blockIdx.x * kScanChunk + threadIdx.x * 8;
-    int c[8], s = 0;
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        c[u] = base + u < m ? counts[base + u] : 0;
-        s += c[u];
-    }
-    int incl = s;  // inclusive scan of the per-thread sums over the wave
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int v = __shfl_up(incl, o, kWave);
-        if (lane >= o) incl += v;
-    }
-    if (lane == kWave - 1) s_w[wave] = incl;
-    __syncthreads();
-    int run = chunk_off[blockIdx.x] + incl - s;
-    for (int w = 0; w < wave; ++w) run += s_w[w];
-#pragma unroll
-    for (int u = 0; u < 8; ++u) {
-        if (base + u < m) counts[base + u] = run;
-        run += c[u];
-    }
-}
-
-// m <= 4096: the whole scan in one workgroup (thread q owns counts[4q .. 4q+3]) instead of three launches
-__global__ void __launch_bounds__(1024) k_scan_small(int *__restrict__ counts, int m) {
-    __shared__ int s_w[1024 / kWave];
-    const int t = threadIdx.x, lane = t & (kWave - 1), wave = t / kWave;
-    int c[4], sum = 0;
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        c[j] = 4 * t + j < m ? counts[4 * t + j] : 0;
-        sum += c[j];
-    }
-    int incl = sum;
-#pragma unroll
-    for (int o = 1; o < kWave; o <<= 1) {
-        const int v = __shfl_up(incl, o, kWave);
-        if (lane >= o) incl += v;
-    }
-    if (lane == kWave - 1) s_w[wave] = incl;
-    __syncthreads();
-    int run = incl - sum;
-    for (int w = 0; w < wave; ++w) run += s_w[w];
-#pragma unroll
-    for (int j = 0; j < 4; ++j) {
-        if (4 * t + j < m) counts[4 * t + j] = run;
-        run += c[j];
-    }
-    if (t == 1023) counts[m] = run;
-}
 
 // An fp64 flow / voxel at the boundary: out[i] = hi = (float)v[i] -- the value an fp32 caller passes, read by every kernel -- and
 // out[count + i] = lo = (float)(v[i] - hi), read only where K1 decides a cell in fp64 (hi + lo = v to 2^-48 relative, what the source
@@ -1266,22 +1139,6 @@ k_finish_raw_step_batch(const double *__restrict__ raw, int n_ref, ObjParams op,
 // ---------------------------------------------------------------------------------------------
 // host-side orchestration
 // ---------------------------------------------------------------------------------------------
-// exclusive scan of h->counts[0..m) in place, counts[m] = total
-// exclusive scan of counts[0 .. m) in place, counts[m] = total (tmp: ceil(m / 2048) + 1 ints)
-static void launch_scan_buf(int *counts, int m, int *tmp, hipStream_t s, int *nonzero = nullptr, int *total_out = nullptr) {
-    const int nchunk = div_up(m, kScanChunk);
-    hipLaunchKernelGGL(k_scan_sums, dim3(nchunk), dim3(256), 0, s, counts, m, tmp, nonzero);
-    hipLaunchKernelGGL(k_scan_chunks, dim3(1), dim3(1024), 0, s, tmp, nchunk, total_out ? total_out : counts + m);
-    hipLaunchKernelGGL(k_scan_apply, dim3(nchunk), dim3(256), 0, s, counts, m, tmp);
-}
-static void launch_scan(cmax_handle_s *h, int m, hipStream_t s, int *nonzero = nullptr) {
-    if (m <= 4096 && !nonzero) {
-        hipLaunchKernelGGL(k_scan_small, dim3(1), dim3(1024), 0, s, h->counts, m);
-        return;
-    }
-    launch_scan_buf(h->counts, m, h->scan_tmp, s, nonzero);
-}
-
 static float ref_fraction(int ref_mode, double frac) {
     if (ref_mode == CMAX_REF_FIRST) return 0.f;
     if (ref_mode == CMAX_REF_LAST) return 1.f;
@@ -1492,468 +1349,7 @@ static int launch_stats(cmax_handle_s *h, int cost, const float *img, int omit, 
     return 0;
 }
 
-// The event kernels read the sorted events in 16-byte pairs, so the pair that holds the last event of the last
-// segment can reach one element past the batch.  That slot is not voted, but its pixel still indexes the flow
-// field (dense / voxel warp): the two padding elements must decode to pixel (0, 0), bin 0 -- not to whatever the
-// allocation held before.
-static int pad_event_tail(cmax_handle_s *h, hipStream_t s) {
-    CMAX_CHECK_HIP(hipMemsetAsync(h->evp + h->n, 0, 2 * sizeof(uint2), s));
-    return 0;
-}
-
-// host copy of what one batch left on the device: [0] any fractional source coordinate, [1] dropped events,
-// [2] events kept from off the sensor (cmax_set_keep_outside); batch time extremes
-struct BatchReadback {
-    int flags[4] = {0, 0, 0, 0};
-    double tmm[2] = {0.0, 0.0};
-    int64_t n_in = 0;
-};
-
-// Work list of the event kernels from the sorted events.  counts[] = exclusive scan of the sort-key histogram;
-// a GROUP = `stride` consecutive keys = one source tile (pixel keys) or one (tile, time bin).
-// Segments: <= kSegMax consecutive sorted events (fixed-point range) inside one tile row, spanning <= 12 groups
-// (the flow-gradient accumulator of the voxel K3 holds kAccCells = 12 * 256 cells).  Two regimes, measured on MI355X:
-//   * batches that fill the chip several times over (> 1024 full segments): cut every kSegMax events, group
-//     boundaries ignored -- every workgroup full (dense K3 of cfg3 30 -> 25 us);
-//   * smaller batches are latency-bound: small groups are merged while they fit, a group with more than
-//     kSegMax events is split into EQUAL parts -- group-aligned windows are tighter and no workgroup is left
-//     with a small remainder (cfg2: 2040 + 806 per tile -> 2 x 1423).
-
-// overlap: launched (by the caller's functor) BEHIND the read-back copies and an event, i.e. work the GPU does while the host
-// waits for that event only, cuts the segments and uploads them -- the ordering of the pixel runs by time (k_run_time_sort),
-// which moves events inside their groups and leaves the group starts alone (round 3: 0.16 -> see profiles, per 1M events)
-template <typename Overlap>
-static int build_segments(cmax_handle_s *h, int stride, hipStream_t s, BatchReadback *rb, Overlap overlap) {
-    // slab-major handles (cmax_set_time_slabs): the groups are (tile row, slab, tile column) -- ntr * S rows of ntc groups, one group per
-    // "tile" of that virtual grid; cut like an un-binned list, never owned (a source pixel belongs to S groups)
-    const bool slab = stride == 1 && h->slab_major && h->n_time_bin > 0;
-    const int T = (stride == 1 && !slab) ? h->n_time_bin : 1;  // groups per tile
-    const int ngroups = h->ntr * h->ntc * (slab ? h->n_time_bin : T);
-    const int ntiles = h->ntr * h->ntc;
-    const bool want_active = rb && h->n_time_bin == 0;
-    // the pinned read-back mirrors the device allocation: [2 doubles] extremes | [4] flags | [ntiles] active pixels | [ngroups + 1] group starts
-    const int64_t off_tmm = 0, off_flags = 4, off_active = 8, off_start = 8 + ntiles;
-    (void)want_active;
-    int rc = h->hp_read.reserve(off_start + ngroups + 1);
-    if (rc) return rc;
-    const int *group_start = h->hp_read + off_start;
-    CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_read, h->d_batch, (size_t)(off_start + ngroups + 1) * sizeof(int), hipMemcpyDeviceToHost, s));
-    if (!h->read_done) CMAX_CHECK_HIP(hipEventCreateWithFlags(&h->read_done, hipEventDisableTiming));
-    CMAX_CHECK_HIP(hipEventRecord(h->read_done, s));
-    rc = overlap();
-    if (rc) return rc;
-    {  // busy-wait: hipEventSynchronize sleeps and wakes up tens of microseconds late
-        hipError_t e;
-        while ((e = hipEventQuery(h->read_done)) == hipErrorNotReady) {
-        }
-        CMAX_CHECK_HIP(e);
-    }
-    if (rb) {
-        for (int k = 0; k < 4; ++k) rb->flags[k] = h->hp_read[off_flags + k];
-        std::memcpy(rb->tmm, h->hp_read + off_tmm, 2 * sizeof(double));
-        h->has_frac = rb->flags[0] != 0;
-        h->n = rb->n_in - rb->flags[1];
-        if (h->generation_counted != h->generation) {  // a new batch (re-binning keeps the count of cmax_set_events)
-            h->n_dropped = rb->flags[1];
-            h->n_outside = rb->flags[2];
-            h->generation_counted = h->generation;
-        }
-        int64_t active = 0;  // source pixels that hold events (un-binned order)
-        if (want_active)
-            for (int k = 0; k < ntiles; ++k) active += h->hp_read[off_active + k];
-        h->long_runs = active > 0 && h->n >= 8 * active;
-        h->tmin_host = rb->tmm[0];
-        h->tmax_host = rb->tmm[1];
-        rc = pad_event_tail(h, s);
-        if (rc) return rc;
-    }
-    // un-binned handles: a segment spans <= 3 source tiles.  Sparse tiles used to be merged up to 12 wide; the LDS
-    // window of such a segment (16 * span + displacement range wide) overflowed its 4096 words as soon as the motion
-    // was a few pixels, and the clipped path (bounds tests, global atomics for the overflow) made those few workgroups
-    // the tail of the launch: 1M events whose lower tile rows are sparse, K1 7.5 -> 6.9 us, K3 10.4 -> 7.3 us.
-    // binned handles: 12 (tile, bin) groups, what the LDS accumulators of the voxel K3 hold -- unless every segment is
-    // below kSparseSegment events anyway (then that kernel adds straight to memory): up to 3 tiles' worth of groups,
-    // instead of ~100-event segments cut by the span (30k events, T = 10: 312 -> 125 segments)
-    // BIG segments for batches that fill the chip many times over (CMAX_BIG_SEG=0 / 1 overrides for A/B runs): the per-workgroup
-    // fixed costs of the event kernels are paid once per 4088 events instead of once per 2040.  Pays from ~2000 big segments on
-    // (256 CUs x 3 resident workgroups, several rounds): measured (profiles/r03_ablation.txt 8) 20M events 104.3 -> 95.0 us per
-    // evaluation, 64M events 323.6 -> 292.6; 5M events (1223 segments) 38.5 -> 38.2; below that fewer, longer workgroups LOSE
-    // (2.5M events @720p 30.6 -> 33.1, 2M-event voxel batch 31.4 -> 33.5).
-    // Between 522k and 8M events the choice follows the work list itself (tools/probe_rounds.py, profiles/r03_ablation.txt 17): both
-    // group-aligned cuts are counted, and big segments are taken when they need <= 4/11 of the standard cut's workgroups (720p: 4M
-    // events = 3600 one-tile segments of 1100 events vs 1200 three-tile ones, 41.5 -> 38.7 us; voxel T = 10: 4M events 47.1 -> 41.0)
-    // -- at a ratio of 2 .. 2.5 the standard cut wins (cfg5's shard 30.6 vs 33.1, cfg4 31.4 vs 33.5) -- or, from 4M events on, when
-    // the standard cut is not group-aligned at all (groups above 2040 events: 720p 7M 56.4 -> 47.9 us; cfg3 37.9 -> 36.9 us).
-    static const int big_env = getenv("CMAX_BIG_SEG") ? atoi(getenv("CMAX_BIG_SEG")) : -1;
-    auto owned_count = [&](int cut, int span_max) -> int {  // segments of the group-aligned cut; -1: a group exceeds `cut`
-        for (int g = 0; g < ngroups; ++g)
-            if (group_start[g + 1] - group_start[g] > cut) return -1;
-        const int row_groups = h->ntc * T;
-        int cnt = 0;
-        for (int r0 = 0; r0 < ngroups; r0 += row_groups) {
-            int g = r0;
-            while (g < r0 + row_groups) {
-                const int gs = g;
-                int c = 0;
-                while (g < r0 + row_groups && g - gs < span_max && c + (group_start[g + 1] - group_start[g]) <= cut) {
-                    c += group_start[g + 1] - group_start[g];
-                    ++g;
-                }
-                ++cnt;
-            }
-        }
-        return cnt;
-    };
-    // MID segments (round 4; CMAX_MID_SEG=0 / 1 overrides for A/B runs): 3064 events, four source tiles or five well-filled (tile, bin)
-    // groups wide.  A launch of more workgroups than the chip holds at once (256 CUs x 4 workgroups of 512 threads) runs in rounds, and
-    // every round pays the ~2.5 us a workgroup waits for its first loads again (tools/timeline.py): the standard cut of cfg5's shard is
-    // 1693 workgroups -- two rounds, the second two thirds full -- this one 900 in ONE round; cfg4: 1258 -> 748.  Taken when it fits one
-    // round where the standard cut does not.
-    static const int mid_env = getenv("CMAX_MID_SEG") ? atoi(getenv("CMAX_MID_SEG")) : -1;
-    constexpr int kResidentGroups = 1024;  // workgroups of 512 threads the chip holds at once
-    h->mid = false;
-    if (slab) {
-        h->big = false;
-    } else if (big_env >= 0) {
-        h->big = big_env != 0;
-    } else if (h->n >= (int64_t)8000000) {
-        h->big = true;
-    } else if (h->n < (int64_t)256 * kSegMax) {
-        h->big = false;
-    } else {
-        const bool small_std = T > 1 && h->n >= (int64_t)480 * ngroups;  // (see small_acc below)
-        const int std_n = owned_count(kSegMax, T == 1 ? 3 : (small_std ? kAccCellsDense / 256 : kAccCells / 256));
-        const int big_n = std_n >= 0 ? owned_count(4088, T == 1 ? 6 : kAccCells / 256) : -1;
-        h->big = std_n >= 0 ? (int64_t)std_n * 4 >= (int64_t)big_n * 11 : h->n >= (int64_t)4000000;
-        if (!h->big && mid_env != 0 && !getenv("CMAX_NO_OWNED")) {
-            const int mid_n = owned_count(3064, T == 1 ? 4 : (small_std ? 5 : kAccCells / 256));
-            h->mid = mid_env > 0 ? mid_n > 0 : (mid_n > 0 && mid_n <= kResidentGroups && std_n > kResidentGroups);
-        }
-    }
-    h->seg_max = h->big ? 4088 : (h->mid ? 3064 : kSegMax);
-    const int kSegCut = h->seg_max;
-    int max_groups = T == 1 ? 3 : kAccCells / 256;
-    static const int free_env = getenv("CMAX_FREE_CUT") ? atoi(getenv("CMAX_FREE_CUT")) : -1;  // tuning only
-    const bool free_cut = free_env >= 0 ? free_env != 0 : h->n > (int64_t)1024 * kSegMax;
-    // batches far below one full segment per CU (the solver's 30k-event slices): a workgroup walks its events
-    // 8 (4) per thread, so 2040-event segments leave 15 workgroups with long serial work on a 256-CU chip.
-    // Cap the segment at n / 512 (>= 256 events): cfg1-shaped K3 13 -> 5 us.
-    int seg_cap = kSegCut;
-    if (h->n < (int64_t)256 * kSegMax) seg_cap = (int)std::min<int64_t>(kSegCut, std::max<int64_t>(256, (h->n + 511) / 512));
-    static const int cap_env = getenv("CMAX_SEG_CAP") ? atoi(getenv("CMAX_SEG_CAP")) : 0;  // tuning only
-    if (cap_env > 0 && free_cut) seg_cap = std::min(kSegCut, cap_env & ~1);
-    if (T > 1 && seg_cap < kSparseSegment) max_groups = std::max(max_groups, 3 * T);
-    std::vector<int4> segs;
-    // Owned groups (batches of at least one full segment per CU whose groups all fit a segment): every group -- empty
-    // ones included -- belongs to exactly ONE segment made of whole consecutive groups of one tile row, at most 3 tiles
-    // (LDS window) / kAccCells / 256 groups (LDS accumulators).  The flow-gradient kernel of a single-reference objective
-    // then stores its groups' pixels instead of adding to them (k_grad, kGradOwned), and the buffer needs no clearing.
-    h->owned = false;
-    if (h->n >= (int64_t)256 * kSegMax && !getenv("CMAX_NO_OWNED") && !slab) {
-        bool fits = true;
-        for (int g = 0; g < ngroups && fits; ++g) fits = group_start[g + 1] - group_start[g] <= kSegCut;
-        h->owned = fits;
-    }
-    h->row_seg_start.clear();
-    // Binned handles whose groups are dense (>= 480 events per (tile, bin) group on average: four groups would not fit a segment
-    // anyway): segments of <= 3 groups, so that the voxel K3 needs 768 accumulator cells per channel instead of 3072 -- 40 KB of LDS
-    // per workgroup instead of 58, i.e. FOUR 512-thread workgroups per CU with 4 events per thread instead of two 1024-thread ones
-    // with 2 (the per-thread fixed costs of K3 are spread over twice the events).  CMAX_SMALL_ACC=0 / 1 overrides (A/B runs).
-    static const int small_env = getenv("CMAX_SMALL_ACC") ? atoi(getenv("CMAX_SMALL_ACC")) : -1;
-    h->small_acc = T > 1 && h->owned && !h->big && (small_env >= 0 ? small_env != 0 : h->n >= (int64_t)480 * ngroups);
-    if (h->mid && !h->owned) {  // (the mid layout exists for group-aligned work lists only: fall back to the standard cut)
-        h->mid = false;
-        h->seg_max = kSegMax;
-        set_error("build_segments: mid layout chosen for a work list that is not group-aligned");
-        return CMAX_ESTATE;
-    }
-    if (h->owned) {
-        const int span_max = T == 1 ? (h->big ? 6 : (h->mid ? 4 : 3)) : (h->small_acc ? (h->mid ? 5 : kAccCellsDense / 256) : kAccCells / 256), row_groups = h->ntc * T;  // dense: kAccCellsDense (x 2 for big segments)
-        for (int r0 = 0; r0 < ngroups; r0 += row_groups) {
-            h->row_seg_start.push_back((int)segs.size());
-            int g = r0;
-            while (g < r0 + row_groups) {
-                const int gs = g;
-                int cnt = 0;
-                while (g < r0 + row_groups && g - gs < span_max && cnt + (group_start[g + 1] - group_start[g]) <= kSegCut) {
-                    cnt += group_start[g + 1] - group_start[g];
-                    ++g;
-                }
-                segs.push_back(make_int4(group_start[gs], cnt, gs, g - gs));
-            }
-        }
-        h->row_seg_start.push_back((int)segs.size());
-    }
-    int begin = 0, count = 0, row_of_begin = -1, g0 = 0, g_last = 0;
-    auto close = [&]() {
-        if (count > 0) segs.push_back(make_int4(begin, count, g0, g_last - g0 + 1));
-        count = 0;
-    };
-    for (int g = 0; g < ngroups && !h->owned; ++g) {
-        int b = group_start[g], c = group_start[g + 1] - group_start[g];
-        const int trow = (g / T) / h->ntc;
-        if (c == 0) continue;
-        if (count > 0 && (trow != row_of_begin || g - g0 + 1 > max_groups || (!free_cut && count + c > seg_cap))) close();
-        int limit = seg_cap;
-        if (!free_cut && c > seg_cap) {
-            const int parts = (c + seg_cap - 1) / seg_cap;
-            limit = (c + parts - 1) / parts;
-        }
-        while (c > 0) {
-            if (count == 0) {
-                begin = b;
-                row_of_begin = trow;
-                g0 = g;
-            }
-            g_last = g;
-            const int take = c < limit - count ? c : limit - count;
-            count += take;
-            b += take;
-            c -= take;
-            if (count >= limit) close();
-        }
-    }
-    close();
-    h->nseg = (int)segs.size();
-    static const bool debug_segs = getenv("CMAX_DEBUG_SEGS") != nullptr;  // tools/probe_rounds.py
-    if (debug_segs)
-        fprintf(stderr, "[cmax] work list: n=%lld groups=%d segments=%d owned=%d big=%d small_acc=%d\n", (long long)h->n, ngroups, h->nseg, (int)h->owned,
-                (int)h->big, (int)h->small_acc);
-    if (h->nseg > h->d_segs.capacity()) {
-        // the workspace of cmax_objective_batch is sized by the work list too (its layout: batch_seg_cap): allocated again on its next call
-        rc = release_all(s, h->d_segs, h->d_gpart, h->d_win, h->d_shifts, h->bimg, h->braw, h->bwin, h->bshifts);
-        if (rc) return rc;
-        h->batch_cap = h->batch_seg_cap = 0;
-    }
-    bool fresh = false;
-    rc = h->d_segs.reserve(&h->bytes, h->nseg, s);
-    if (!rc) rc = h->d_win.reserve(&h->bytes, (int64_t)4 * h->nseg, s);
-    if (!rc) rc = h->d_shifts.reserve(&h->bytes, (int64_t)4 * h->nseg * kShiftWordsMax, s, &fresh);
-    if (!rc) rc = h->d_gpart.reserve(&h->bytes, (int64_t)4 * h->nseg * 2, s);
-    if (rc) return rc;
-    // (K3 reads an offset word only where K1 flagged its block; cleared once so that no word ever holds allocator garbage)
-    if (fresh) CMAX_CHECK_HIP(hipMemsetAsync(h->d_shifts, 0, (size_t)h->d_shifts.capacity() * sizeof(unsigned), s));
-    if (h->nseg > 0) {
-        // upload from pinned memory, no wait: the buffer is only rewritten after the event below has passed
-        if (h->segs_copied) CMAX_CHECK_HIP(hipEventSynchronize(h->segs_copied));
-        else CMAX_CHECK_HIP(hipEventCreateWithFlags(&h->segs_copied, hipEventDisableTiming));
-        rc = h->hp_segs.reserve(h->nseg);
-        if (rc) return rc;
-        std::memcpy(h->hp_segs, segs.data(), segs.size() * sizeof(int4));
-        CMAX_CHECK_HIP(hipMemcpyAsync(h->d_segs, h->hp_segs, segs.size() * sizeof(int4), hipMemcpyHostToDevice, s));
-        CMAX_CHECK_HIP(hipEventRecord(h->segs_copied, s));
-    }
-    // Big segments of an un-binned handle: the compact copy the hot kernels read (4.5 B/event, one aligned region per segment).
-    // CMAX_COMPACT=0 switches it off (A/B runs).
-    static const int compact_env = getenv("CMAX_COMPACT") ? atoi(getenv("CMAX_COMPACT")) : 1;
-    h->compact = false;
-    // ... and long runs only: the dense K3 of a short-run batch that is not `owned` is kGradStrided, whose slot layout reads the 8-byte
-    // events -- K1 must then warp with the same fp32 time (K3 follows K1's cells and windows without tests), so such a handle gets no compact
-    // copy at all (big segments + short runs = a sparse batch on a very large sensor, or CMAX_BIG_SEG=1).
-    if (h->big && T == 1 && !slab && h->n_time_bin == 0 && h->nseg > 0 && compact_env != 0 && h->long_runs) {
-        rc = pack_compact_events(h, s);  // (cmax_event_launch.hip: the kernel is a template over the event layouts)
-        if (rc) return rc;
-        static const bool debug_compact = getenv("CMAX_DEBUG_COMPACT") != nullptr;
-        if (debug_compact) {  // (k_pack_compact raises d_flags[3] when an event lies outside its segment's tile row / 8-tile span: never)
-            int bad = 0;
-            CMAX_CHECK_HIP(hipMemcpyAsync(&bad, h->d_flags + 3, sizeof(int), hipMemcpyDeviceToHost, s));
-            CMAX_CHECK_HIP(hipStreamSynchronize(s));
-            if (bad) {
-                set_error("k_pack_compact: an event does not fit the compact coordinates of its segment");
-                return CMAX_ESTATE;
-            }
-        }
-        h->compact = true;
-    }
-    return 0;
-}
-
-// Order `n_in` events from `src` for h->n_time_bin (cmax_sort_kernels.h) into the handle's SoA, then build the work
-// list.  first_flag: d_flags[first_flag .. 3] are cleared (0 for a new batch; 1 keeps "fractional sources" when re-binning).
-// the handle's own event arrays and their staging copies change roles
-static void swap_event_arrays(cmax_handle_s *h) {
-    swap(h->evp, h->evp_alt);
-    swap(h->rx, h->rx_alt);
-    swap(h->ry, h->ry_alt);
-    swap(h->rl, h->rl_alt);
-    swap(h->tau64, h->tau64_alt);
-    swap(h->src, h->src_alt);
-}
-
-template <typename SRC>
-static int sort_events(cmax_handle_s *h, const SRC &src, int64_t n_in, bool reduce_time, int first_flag, hipStream_t s) {
-    const int ntiles = h->ntr * h->ntc, T = h->n_time_bin;
-    {  // staging SoA of the bucket pass: as large as the handle's own arrays (cmax_set_events releases it when those grow)
-        int rc = h->evp_alt.reserve(&h->bytes, h->evp.capacity(), s);
-        if (!rc) rc = h->rx_alt.reserve(&h->bytes, h->rx.capacity(), s);
-        if (!rc) rc = h->ry_alt.reserve(&h->bytes, h->ry.capacity(), s);
-        if (!rc) rc = h->rl_alt.reserve(&h->bytes, h->rl.capacity(), s);
-        if (!rc) rc = h->tau64_alt.reserve(&h->bytes, h->tau64.capacity(), s);
-        if (!rc) rc = h->src_alt.reserve(&h->bytes, h->src.capacity(), s);
-        if (rc) return rc;
-    }
-
-    SortOut stage = {h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt, h->src_alt};
-    SortOut fin = {h->evp, h->rx, h->ry, h->rl, h->tau64, h->src};
-    unsigned long long *keys = reduce_time ? reinterpret_cast<unsigned long long *>(h->d_tmm) : nullptr;
-    // Large batches: the STABLE radix sort (cmax_radix_sort.h) -- every pass streams, the events of a pixel come out by time without
-    // k_run_time_sort, and the packed order is a function of the batch alone.  Small ones (a few launches fewer) keep the counting sort.
-    static const char *sort_env = getenv("CMAX_SORT");
-    const bool radix = sort_env ? strcmp(sort_env, "radix") == 0 : n_in >= kRadixMinEvents;
-    if (radix) {
-        const RsKey key = {h->ntc, T, (T == 0 || T * 256 <= kTileKeysMax) ? 1 : 0};
-        const int ngroups_all = ntiles * (T > 0 ? T : 1);
-        int gb = 1;
-        while ((1 << gb) < ngroups_all) ++gb;
-        // Digits of <= kRsMaxDigitBits bits: a pass writes one stream per (workgroup, digit), and its time follows the number of streams
-        // (64M events: 1.41 ms per pass at 1024 digits, 0.53 at 32 -- cmax_radix_sort.h), so more, narrower passes win.
-        // Un-binned handles: the whole key (8 pixel bits + tile bits) in equal digits -- every digit of it follows from the source pixel
-        // alone.  Binned handles: the pixel byte first (the time bin, which needs the batch's extremes, sits above it), then the group bits.
-        // (worst case: 2-bit digits -- un-binned 8 + 16 bits = 12 passes; fine binned, pixel byte + 21 bits = 12; coarse 24 bits = 12)
-        constexpr int kRsMaxPasses = 16;
-        int nb[kRsMaxPasses], sh[kRsMaxPasses], P = 0, shift = 0;
-        static const int digit_bits = getenv("CMAX_RS_BITS") ? std::min(kRsMaxDigitBits, std::max(2, atoi(getenv("CMAX_RS_BITS")))) : kRsMaxDigitBits;  // tuning only
-        auto split = [&](int total_bits) {
-            const int parts = div_up(total_bits, digit_bits);
-            if (P + parts > kRsMaxPasses) return false;
-            for (int q = 0, done = 0; q < parts; ++q) {
-                const int bits = div_up(total_bits - done, parts - q);
-                nb[P] = bits;
-                sh[P++] = shift;
-                shift += bits;
-                done += bits;
-            }
-            return true;
-        };
-        bool planned;
-        if (T == 0) {
-            planned = split(8 + gb);
-        } else {
-            if (key.fine) {
-                nb[P] = 8;
-                sh[P++] = 0;
-                shift = 8;
-            }
-            planned = split(gb);
-        }
-        CMAX_REQUIRE(planned, "sort_events: the radix sort's pass plan exceeds kRsMaxPasses");
-        int maxbits = 0;
-        for (int q = 0; q < P; ++q) maxbits = std::max(maxbits, nb[q]);
-        const int nwg = (int)std::min<int64_t>(kRsMaxGroups, std::max<int64_t>(1, div_up(n_in, (int64_t)kRsChunk)));
-        const int64_t range = (int64_t)div_up(div_up(n_in, (int64_t)nwg), (int64_t)kRsThreads) * kRsThreads;
-        const int64_t need = ((int64_t)1 << maxbits) * nwg + 1;
-        int rc = need > h->rs_hist.capacity() ? release_all(s, h->rs_hist, h->rs_tmp) : 0;
-        if (!rc) rc = h->rs_hist.reserve(&h->bytes, need, s);
-        if (!rc) rc = h->rs_tmp.reserve(&h->bytes, div_up(need, (int64_t)kScanChunk) + 2, s);
-        if (rc) return rc;
-        hipLaunchKernelGGL(k_rs_clear, dim3(div_up(std::max(ntiles, 4), 256)), dim3(256), 0, s, h->d_active, ntiles, h->d_flags, first_flag, keys);
-        if (!key.fine && keys)  // (the first digit needs the time bin: the batch's extremes first)
-            hipLaunchKernelGGL((k_rs_time_extremes<SRC>), dim3(nwg), dim3(kRsThreads), 0, s, src, n_in, keys);
-        // pass q writes buffer (P - 1 - q) % 2 (0: the handle's own arrays, 1: the staging copy), so that the last pass lands in the own arrays.
-        // Re-binning reads the own arrays: when pass 0 would write them too, the two sets swap roles first (the source then IS the staging set).
-        if (!std::is_same<SRC, RawSource<float>>::value && !std::is_same<SRC, RawSource<double>>::value && (P - 1) % 2 == 0) {
-            swap_event_arrays(h);
-            std::swap(stage, fin);
-        }
-        // the number of packed events (every pass's scan writes it again): where the other pipeline keeps its total, outside the histogram
-        // buffer the next pass overwrites
-        int *total = h->counts + ntiles;
-        for (int q = 0; q < P; ++q) {
-            const int D = 1 << nb[q], m = D * nwg;
-            const SortOut &out = (P - 1 - q) % 2 == 0 ? fin : stage;
-            const SortOut &in = (P - 1 - q) % 2 == 0 ? stage : fin;
-            if (q == 0) hipLaunchKernelGGL((k_rs_hist_src<SRC>), dim3(nwg), dim3(kRsThreads), (size_t)D * sizeof(int), s, src, n_in, range, key, nb[q], h->rs_hist, h->d_flags, keys);
-            else hipLaunchKernelGGL(k_rs_hist, dim3(nwg), dim3(kRsThreads), (size_t)D * sizeof(int), s, (const uint2 *)in.evp, (const int *)total, range, key, sh[q], nb[q], h->rs_hist);
-            launch_scan_buf(h->rs_hist, m, h->rs_tmp, s, nullptr, total);
-            const size_t lds = (size_t)D * (sizeof(int) + sizeof(unsigned long long));
-            if (q == 0) hipLaunchKernelGGL((k_rs_scatter_src<SRC>), dim3(nwg), dim3(kRsThreads), lds, s, src, n_in, range, key, nb[q], (const int *)h->rs_hist, (const int *)h->d_flags, out);
-            else hipLaunchKernelGGL(k_rs_scatter, dim3(nwg), dim3(kRsThreads), lds, s, in, (const int *)total, range, key, sh[q], nb[q], (const int *)h->rs_hist, (const int *)h->d_flags, out);
-            CMAX_CHECK_LAUNCH();
-        }
-        hipLaunchKernelGGL(k_rs_meta, dim3(div_up(n_in, 256)), dim3(256), 0, s, (const uint2 *)fin.evp, (const int *)total, key, ngroups_all, h->d_tile_start,
-                           T == 0 ? h->d_active : (int *)nullptr, std::max(1, ntiles), keys);
-        CMAX_CHECK_LAUNCH();
-    } else {
-    const int grid = (int)div_up(n_in, (int64_t)kSortChunk);
-    hipLaunchKernelGGL(k_sort_clear, dim3(div_up(ntiles + 1, 256)), dim3(256), 0, s, h->counts, h->cursor, ntiles, h->d_flags, first_flag, keys);
-    hipLaunchKernelGGL((k_bucket_hist<SRC>), dim3(grid), dim3(kSortThreads), 0, s, src, n_in, h->ntc, ntiles, h->counts, h->d_flags, keys);
-    launch_scan(h, ntiles, s);
-    hipLaunchKernelGGL((k_bucket_scatter<SRC>), dim3(grid), dim3(kSortThreads), 0, s, src, n_in, h->ntc, ntiles, T, h->counts, h->cursor, h->d_flags, stage);
-    hipLaunchKernelGGL(k_tile_sort, dim3(ntiles), dim3(kTileSortThreads), 0, s, ntiles, T, h->counts, stage, fin, h->d_tile_start, h->d_active, h->d_flags, keys);
-    CMAX_CHECK_LAUNCH();
-    }
-    if (T > 0 && h->slab_major) {  // slab-major group order (cmax_sort_kernels.h, S4b): final SoA -> staging SoA, the two swap roles
-        const int ngroups = ntiles * T;
-        hipLaunchKernelGGL(k_slab_offsets, dim3(1), dim3(1024), 0, s, h->d_tile_start, ngroups, h->ntc, T, h->cursor);
-        hipLaunchKernelGGL(k_slab_regroup, dim3(ngroups), dim3(256), 0, s, h->d_tile_start, h->cursor, h->ntc, T, fin, stage, h->d_flags);
-        CMAX_CHECK_LAUNCH();
-        CMAX_CHECK_HIP(hipMemcpyAsync(h->d_tile_start, h->cursor, (size_t)(ngroups + 1) * sizeof(int), hipMemcpyDeviceToDevice, s));
-        swap_event_arrays(h);
-    }
-    static const bool run_sort = !getenv("CMAX_NO_RUN_SORT");
-    BatchReadback rb;
-    rb.n_in = n_in;
-    return build_segments(h, T > 0 ? 1 : 256, s, &rb, [&]() -> int {
-        if (T == 0 && run_sort && !radix) {
-            // pixel runs ordered by time: final SoA -> staging SoA, then the two swap roles (same capacities).  Runs on the GPU
-            // while the host cuts the segments: it needs nothing from the host and changes nothing the host reads back.
-            hipLaunchKernelGGL(k_run_time_sort, dim3(div_up(n_in, kRunSortChunk)), dim3(256), 0, s, fin, stage, h->counts + ntiles, h->d_flags);
-            CMAX_CHECK_LAUNCH();
-            swap_event_arrays(h);
-        }
-        return 0;
-    });
-}
-
 bool handle_is_deterministic(cmax_handle_t h) { return h && h->deterministic; }
-bool handle_is_weighted(cmax_handle_t h) { return h && h->weighted; }
-
-// ---- per-event weights (cmax_set_event_weights) -------------------------------------------------------------------------------
-// W1: the caller's weights as fp32 in the caller's order (kept: a re-ordering of the batch gathers from them again); flags[3] != 0 if
-// one of them is not finite.
-template <typename T>
-__global__ void __launch_bounds__(256) k_weights_keep(const T *__restrict__ w, int64_t n, float *__restrict__ w_user, unsigned *__restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    if (i >= n) return;
-    const float v = (float)w[i];
-    w_user[i] = v;
-    if (!(fabsf(v) <= 3.4028234e38f)) atomicOr(&flags[3], 1u);
-}
-// W2: packed order (slot l of a segment reads w_packed[first + l]) through the source index the sort carried, zeros in the padding behind
-// the last event, and max |w| over the PACKED events (a dropped event drops its weight) as the bits of a non-negative float in flags[2].
-__global__ void __launch_bounds__(256) k_weights_gather(const float *__restrict__ w_user, const int *__restrict__ src, int64_t n, int64_t n_pad,
-                                                        float *__restrict__ w_packed, unsigned *__restrict__ flags) {
-    const int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x;
-    float v = 0.f;
-    if (i < n) v = w_user[src[i]];
-    if (i < n_pad) w_packed[i] = v;
-    float m = fabsf(v);
-    if (!(m <= 3.4028234e38f)) m = 0.f;  // (non-finite values are reported by k_weights_keep)
-#pragma unroll
-    for (int o = kWave / 2; o > 0; o >>= 1) m = fmaxf(m, __shfl_xor(m, o, kWave));
-    if ((threadIdx.x & (kWave - 1)) == 0 && m > 0.f) atomicMax(&flags[2], __float_as_uint(m));
-}
-// W3: (1 / wmax, wmax) for the event kernels -- plain stores of one thread
-__global__ void k_weights_norm(float *__restrict__ wnorm) {
-    const float wmax = __uint_as_float(reinterpret_cast<const unsigned *>(wnorm)[2]);
-    wnorm[0] = wmax > 0.f ? 1.f / wmax : 0.f;
-    wnorm[1] = wmax;
-}
-
-// the packed-order copy of the kept weights for the CURRENT order of the batch (after cmax_set_event_weights and after every re-ordering)
-static int gather_weights(cmax_handle_s *h, hipStream_t s) {
-    const int64_t n_pad = h->n + kWeightPad;
-    int rc = h->w_packed.reserve(&h->bytes, n_pad, s);
-    if (rc) return rc;
-    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm.get());
-    CMAX_CHECK_HIP(hipMemsetAsync(flags + 2, 0, sizeof(unsigned), s));
-    hipLaunchKernelGGL(k_weights_gather, dim3(div_up(n_pad, 256)), dim3(256), 0, s, (const float *)h->w_user, (const int *)h->src, h->n, n_pad, h->w_packed, flags);
-    hipLaunchKernelGGL(k_weights_norm, dim3(1), dim3(1), 0, s, h->d_wnorm);
-    CMAX_CHECK_LAUNCH();
-    h->orig_valid = false;  // the un-warped image is weighted too
-    h->win_generation = ~(uint64_t)0;
-    return 0;
-}
 
 void handle_get_eval_state(cmax_handle_t h, HandleEvalState *out) {
     out->cur_buf = h->cur_buf;
@@ -2003,235 +1399,6 @@ void handle_set_eval_state(cmax_handle_t h, const HandleEvalState *in) {
 using namespace cmax;
 
 extern "C" {
-
-int cmax_create(int H, int W, int ph, int pw, cmax_handle_t *out) {
-    CMAX_REQUIRE(out != nullptr, "create: out");
-    CMAX_REQUIRE(H > 0 && W > 0 && H <= 4096 && W <= 4096 && ph >= 0 && pw >= 0, "create: image size must be in 1..4096");
-    int ndev = 0;
-    if (hipGetDeviceCount(&ndev) != hipSuccess || ndev == 0) {
-        set_error("no HIP device visible");
-        return CMAX_ENODEV;
-    }
-    cmax_handle_s *h = new cmax_handle_s();
-    h->H = H;
-    h->W = W;
-    h->ph = ph;
-    h->pw = pw;
-    h->Hp = H + 2 * ph;
-    h->Wp = W + 2 * pw;
-    CMAX_CHECK_HIP(hipGetDevice(&h->device));
-    h->ntr = div_up(H, kTile);
-    h->ntc = div_up(W, kTile);
-    h->nkeys = h->ntr * h->ntc * kTile * kTile;
-    const int64_t npix = (int64_t)h->Hp * h->Wp;
-    int rc = h->imgs.reserve(&h->bytes, 2 * 5 * npix, nullptr);
-    for (int k = 0; k < 5 && !rc; ++k) rc = h->iweb[k].reserve(&h->bytes, npix, nullptr);
-    if (!rc) rc = h->G.reserve(&h->bytes, 4 * npix, nullptr);  // dL/dIWE of up to 4 reference times
-    if (!rc) rc = h->Gt.reserve(&h->bytes, npix, nullptr);
-    {
-        const int ntiles = h->ntr * h->ntc;
-        const int64_t nints = 4 /* tmm */ + 4 /* flags */ + ntiles + ((int64_t)ntiles * 256 + 1);  // tile starts: up to 255 time bins per tile
-        if (!rc) rc = h->d_batch.reserve(&h->bytes, nints, nullptr);
-        if (!rc) {
-            h->d_tmm = reinterpret_cast<double *>(h->d_batch.get());
-            h->d_flags = h->d_batch + 4;
-            h->d_active = h->d_batch + 8;
-            h->d_tile_start = h->d_batch + 8 + ntiles;
-        }
-    }
-    if (!rc) rc = h->d_stat.reserve(&h->bytes, kStatSlots * kStatStride, nullptr);
-    if (!rc) rc = h->counts.reserve(&h->bytes, h->nkeys + 1, nullptr);
-    if (!rc) rc = h->cursor.reserve(&h->bytes, h->nkeys, nullptr);
-    if (!rc) rc = h->scan_tmp.reserve(&h->bytes, div_up(h->nkeys, kScanChunk) + 1, nullptr);
-    if (!rc) rc = h->d_raw.reserve(&h->bytes, 4 * kRawStride, nullptr);
-    if (!rc) rc = h->d_host_result.reserve(&h->bytes, 8, nullptr);
-    if (!rc) rc = h->d_musum.reserve(&h->bytes, 2 * 4 * kMuStride, nullptr);
-    if (!rc) rc = h->d_ticket.reserve(&h->bytes, kTicketLines * kTicketLineInts, nullptr);
-    if (!rc && hipMemset(h->d_ticket, 0, kTicketLines * kTicketLineInts * sizeof(int)) != hipSuccess) {
-        set_error("cmax_create: clearing the arrival counters failed");
-        rc = CMAX_ENOMEM;
-    }
-    if (!rc && hipMemset(h->d_musum, 0, 2 * 4 * kMuStride * sizeof(double)) != hipSuccess) {
-        set_error("cmax_create: clearing the accumulators failed");
-        rc = CMAX_ENOMEM;
-    }
-    if (rc) {
-        cmax_destroy(h);
-        return rc;
-    }
-    *out = h;
-    return 0;
-}
-
-int cmax_destroy(cmax_handle_t h) {
-    if (!h) return 0;
-    comm_destroy(h->comm);
-    h->comm = nullptr;
-    if (h->comm_stream) (void)hipStreamDestroy(h->comm_stream);
-    for (hipEvent_t e : h->band_ev) (void)hipEventDestroy(e);
-    if (h->segs_copied) (void)hipEventDestroy(h->segs_copied);
-    if (h->read_done) (void)hipEventDestroy(h->read_done);
-    for (int c = 0; c < CMAX_PROF_CLASSES; ++c)
-        for (hipEvent_t e : h->prof_ev[c]) (void)hipEventDestroy(e);
-    delete h;  // (the buffers free themselves)
-    return 0;
-}
-
-int cmax_set_events(cmax_handle_t h, const void *events, int dtype, int64_t n, int have_tminmax, double tmin, double tmax,
-                    int n_time_bin, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr, "set_events: handle");
-    CMAX_REQUIRE(n >= 0 && n < (int64_t)2147483647 && (n == 0 || events), "set_events: n / events");
-    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "set_events: dtype");
-    CMAX_REQUIRE(n_time_bin >= 0 && n_time_bin <= 255, "set_events: n_time_bin must be in 0..255");
-    hipStream_t s = (hipStream_t)stream;
-    h->orig_valid = false;
-    h->n = 0;
-    h->n_dropped = 0;
-    h->n_outside = 0;
-    h->weighted = false;  // weights belong to a batch (like time slabs)
-    h->wmax_host = 0.0;
-    h->n_in = n;
-    ++h->generation;
-    h->generation_counted = ~(uint64_t)0;
-    {
-        // All six arrays are freed before the first is allocated again.  Each one then answers for itself: an array that a failed
-        // growth left empty is allocated by the next call, whatever that call's n.
-        const bool grow = n > h->src.capacity();
-        int rc = grow ? release_all(s, h->evp, h->rx, h->ry, h->rl, h->tau64, h->src) : 0;
-        if (!rc) rc = h->evp.reserve(&h->bytes, n ? n + 2 : 0, s);  // +2: the vector loads may touch one event past the end
-        if (!rc) rc = h->rx.reserve(&h->bytes, n, s);
-        if (!rc) rc = h->ry.reserve(&h->bytes, n, s);
-        if (!rc) rc = h->rl.reserve(&h->bytes, n, s);
-        if (!rc) rc = h->tau64.reserve(&h->bytes, n, s);
-        if (!rc) rc = h->src.reserve(&h->bytes, n, s);
-        if (!rc && grow) rc = release_all(s, h->evp_alt, h->rx_alt, h->ry_alt, h->rl_alt, h->tau64_alt, h->src_alt);  // the staging SoA follows (sort_events)
-        if (rc) return rc;
-    }
-    // global time extremes: given (a time slice of a larger batch), or reduced by the first sort kernel
-    if (have_tminmax) {
-        CMAX_REQUIRE(tmax >= tmin, "set_events: tmax < tmin");
-        hipLaunchKernelGGL(k_tmm_set, dim3(1), dim3(1), 0, s, h->d_tmm, tmin, tmax);
-        CMAX_CHECK_LAUNCH();
-    } else if (n == 0) {
-        hipLaunchKernelGGL(k_tmm_set, dim3(1), dim3(1), 0, s, h->d_tmm, (double)INFINITY, -(double)INFINITY);
-        CMAX_CHECK_LAUNCH();
-    }
-    h->n_time_bin = n_time_bin;
-    h->slab_major = false;  // the slab order is a property of the batch cmax_set_time_slabs re-ordered, not of the handle
-    if (n == 0) {
-        CMAX_CHECK_HIP(hipMemsetAsync(h->d_flags, 0, 4 * sizeof(int), s));
-        h->has_frac = false;
-        h->nseg = 0;
-        return 0;
-    }
-    // pack + order (tile-major; by pixel or by time bin inside a tile) + work list; one host synchronisation
-    const int keyed = have_tminmax ? 0 : 1;
-    const int keep = h->keep_outside ? 1 : 0;
-    if (dtype == CMAX_F32) return sort_events(h, RawSource<float>{(const float *)events, h->d_tmm, h->H, h->W, keyed, keep}, n, keyed != 0, 0, s);
-    return sort_events(h, RawSource<double>{(const double *)events, h->d_tmm, h->H, h->W, keyed, keep}, n, keyed != 0, 0, s);
-}
-
-// Re-ordering the packed events (time bins, time slabs) makes a new work list but NOT a new batch: the events the batch dropped /
-// kept from off the sensor were counted by cmax_set_events from the raw input; the re-sort reads the packed SoA with those flags
-// cleared and must not overwrite the counts (the guards of the dense / voxel objectives read n_outside)
-static void bump_generation_keep_counts(cmax_handle_s *h) {
-    const bool counted = h->generation_counted == h->generation;
-    ++h->generation;
-    if (counted) h->generation_counted = h->generation;
-}
-
-int cmax_set_time_bins(cmax_handle_t h, int n_time_bin, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr, "set_time_bins: handle");
-    CMAX_REQUIRE(n_time_bin >= 0 && n_time_bin <= 255, "set_time_bins: n_time_bin must be in 0..255");
-    if (n_time_bin == h->n_time_bin && !h->slab_major) return 0;
-    h->n_time_bin = n_time_bin;
-    h->slab_major = false;
-    bump_generation_keep_counts(h);
-    if (h->n == 0) return 0;
-    hipStream_t s = (hipStream_t)stream;
-    // re-order the packed events in place (through the staging SoA); [0] "fractional sources" stays what it was
-    int rc = sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0, h->src}, h->n, false, 1, s);
-    if (!rc && h->weighted) rc = gather_weights(h, s);  // the weights follow the new order
-    return rc;
-}
-
-int cmax_set_time_slabs(cmax_handle_t h, int n_slab, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr, "set_time_slabs: handle");
-    CMAX_REQUIRE(n_slab >= 0 && n_slab <= 64, "set_time_slabs: n_slab must be in 0..64");
-    if (n_slab <= 1) n_slab = 0;  // one slab is the un-binned order
-    if (n_slab == 0 && !h->slab_major) return h->n_time_bin == 0 ? 0 : cmax_set_time_bins(h, 0, stream);
-    if (n_slab == h->n_time_bin && h->slab_major) return 0;
-    h->n_time_bin = n_slab;
-    h->slab_major = n_slab > 0;
-    bump_generation_keep_counts(h);
-    if (h->n == 0) return 0;
-    int rc = sort_events(h, PackedSource{h->evp, h->rx, h->ry, h->rl, h->tau64, h->has_frac ? 1 : 0, h->src}, h->n, false, 1, (hipStream_t)stream);
-    if (!rc && h->weighted) rc = gather_weights(h, (hipStream_t)stream);
-    return rc;
-}
-
-int cmax_set_event_weights(cmax_handle_t h, const void *weights, int dtype, int64_t n, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr, "set_event_weights: handle");
-    hipStream_t s = (hipStream_t)stream;
-    if (weights == nullptr) {  // back to the unweighted state: the kernels, instantiations and numbers of a handle that never had weights
-        if (h->weighted) {
-            h->weighted = false;
-            h->wmax_host = 0.0;
-            h->orig_valid = false;
-            h->win_generation = ~(uint64_t)0;
-            bump_generation_keep_counts(h);  // launch sequences captured in the other state (patch plans) are dropped
-        }
-        return 0;
-    }
-    CMAX_REQUIRE(dtype == CMAX_F32 || dtype == CMAX_F64, "set_event_weights: dtype");
-    CMAX_REQUIRE(n == h->n_in, "set_event_weights: n must equal the n of the last cmax_set_events (one weight per event, in the caller's order)");
-    if (h->deterministic) {
-        set_error("set_event_weights: not built for deterministic mode (cmax_set_deterministic)");
-        return CMAX_EUNSUPPORTED;
-    }
-    if (h->comm) {
-        set_error("set_event_weights: not built for a handle with a communicator (cmax_comm_init)");
-        return CMAX_EUNSUPPORTED;
-    }
-    if (n == 0) {
-        h->weighted = true;
-        h->wmax_host = 0.0;
-        return 0;
-    }
-    int rc = h->d_wnorm.reserve(&h->bytes, 4, s);
-    if (!rc) rc = h->w_user.reserve(&h->bytes, n, s);
-    if (rc) return rc;
-    unsigned *flags = reinterpret_cast<unsigned *>(h->d_wnorm.get());
-    CMAX_CHECK_HIP(hipMemsetAsync(h->d_wnorm, 0, 4 * sizeof(float), s));
-    if (dtype == CMAX_F32) hipLaunchKernelGGL((k_weights_keep<float>), dim3(div_up(n, 256)), dim3(256), 0, s, (const float *)weights, n, h->w_user, flags);
-    else hipLaunchKernelGGL((k_weights_keep<double>), dim3(div_up(n, 256)), dim3(256), 0, s, (const double *)weights, n, h->w_user, flags);
-    CMAX_CHECK_LAUNCH();
-    rc = gather_weights(h, s);
-    if (rc) return rc;
-    // blocks once, like cmax_set_events: the non-finite flag and wmax for cmax_batch_weighted
-    float host[4];
-    CMAX_CHECK_HIP(hipMemcpyAsync(host, h->d_wnorm, sizeof(host), hipMemcpyDeviceToHost, s));
-    CMAX_CHECK_HIP(hipStreamSynchronize(s));
-    unsigned bad;
-    std::memcpy(&bad, &host[3], sizeof(bad));
-    if (bad) {
-        h->weighted = false;
-        h->wmax_host = 0.0;
-        set_error("set_event_weights: weights must be finite in fp32, the format they are kept in (|w| <= 3.4e38; the handle is unweighted now)");
-        return CMAX_EINVAL;
-    }
-    h->weighted = true;
-    h->wmax_host = (double)host[1];
-    bump_generation_keep_counts(h);
-    return 0;
-}
-
-int cmax_batch_weighted(cmax_handle_t h, int *weighted, double *wmax_host) {
-    CMAX_REQUIRE(h != nullptr, "batch_weighted: handle");
-    if (weighted) *weighted = h->weighted ? 1 : 0;
-    if (wmax_host) *wmax_host = h->weighted ? h->wmax_host : 0.0;
-    return 0;
-}
 
 int cmax_iwe(cmax_handle_t h, int model, const float *motion, int T, int ref_mode, double ref_frac, int normalize_t,
              double sigma, float *iwe_out, cmax_stream_t stream) {
@@ -4387,83 +3554,6 @@ int cmax_patch_search(cmax_handle_t h, int n_patch, const int *boxes, int img_h,
     hipLaunchKernelGGL(k_patch_search, dim3(n_patch, n_cand + 1), dim3(kSearchThreads), lds, s, a, h->search_range, n_cand,
                        (const float2 *)cand, (float)(h->tmax_host - h->tmin_host), (float)sigma, radius, gm_out);
     CMAX_CHECK_LAUNCH();
-    return 0;
-}
-
-int cmax_batch_info(cmax_handle_t h, int64_t *n_packed, int64_t *n_dropped, int *has_fractional, int *owned_groups) {
-    CMAX_REQUIRE(h != nullptr, "batch_info");
-    if (n_packed) *n_packed = h->n;
-    if (n_dropped) *n_dropped = h->n_dropped;
-    if (has_fractional) *has_fractional = h->has_frac ? 1 : 0;
-    if (owned_groups) *owned_groups = h->owned ? 1 : 0;
-    return 0;
-}
-
-int cmax_set_keep_outside(cmax_handle_t h, int on) {
-    CMAX_REQUIRE(h != nullptr, "set_keep_outside");
-    h->keep_outside = on != 0;  // takes effect with the next cmax_set_events
-    return 0;
-}
-
-int cmax_batch_outside(cmax_handle_t h, int64_t *n_outside) {
-    CMAX_REQUIRE(h != nullptr && n_outside != nullptr, "batch_outside");
-    *n_outside = h->n_outside;
-    return 0;
-}
-
-int cmax_work_list_info(cmax_handle_t h, int *n_segments, int *segment_events, int *small_accumulators) {
-    CMAX_REQUIRE(h != nullptr, "work_list_info");
-    if (n_segments) *n_segments = h->nseg;
-    if (segment_events) *segment_events = h->seg_max;
-    if (small_accumulators) *small_accumulators = h->small_acc ? 1 : 0;
-    return 0;
-}
-
-int cmax_handle_info(cmax_handle_t h, int64_t *n_events, int64_t *workspace_bytes) {
-    CMAX_REQUIRE(h != nullptr, "handle_info");
-    if (n_events) *n_events = h->n;
-    if (workspace_bytes) *workspace_bytes = h->bytes;
-    return 0;
-}
-
-int cmax_debug_packed_events(cmax_handle_t h, void *events_out, int *group_start_out, int *n_groups_host, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr && events_out != nullptr, "debug_packed_events");
-    const int ngroups = h->ntr * h->ntc * (h->n_time_bin > 0 ? h->n_time_bin : 1);
-    if (n_groups_host) *n_groups_host = ngroups;
-    if (h->n > 0) CMAX_CHECK_HIP(hipMemcpyAsync(events_out, h->evp, (size_t)h->n * sizeof(uint2), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    if (group_start_out && h->n == 0)  // (an empty batch is not sorted: d_tile_start holds whatever the allocation or the last batch left)
-        CMAX_CHECK_HIP(hipMemsetAsync(group_start_out, 0, (size_t)(ngroups + 1) * sizeof(int), (hipStream_t)stream));
-    else if (group_start_out)
-        CMAX_CHECK_HIP(hipMemcpyAsync(group_start_out, h->d_tile_start, (size_t)(ngroups + 1) * sizeof(int), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
-}
-
-int cmax_debug_work_list(cmax_handle_t h, void *segments_out, int *n_segments_host, unsigned *flags_host, int *seg_max_host, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr, "debug_work_list");
-    if (n_segments_host) *n_segments_host = h->nseg;
-    if (flags_host)
-        *flags_host = (h->big ? CMAX_WL_BIG : 0u) | (h->mid ? CMAX_WL_MID : 0u) | (h->owned ? CMAX_WL_OWNED : 0u) | (h->small_acc ? CMAX_WL_SMALL_ACC : 0u) |
-                      ((h->slab_major && h->n_time_bin > 0) ? CMAX_WL_SLAB_MAJOR : 0u) | (h->compact ? CMAX_WL_COMPACT : 0u) | (h->long_runs ? CMAX_WL_LONG_RUNS : 0u);
-    if (seg_max_host) *seg_max_host = h->seg_max;
-    if (segments_out && h->nseg > 0)  // the list the kernels read, not the host's staging copy
-        CMAX_CHECK_HIP(hipMemcpyAsync(segments_out, h->d_segs, (size_t)h->nseg * sizeof(int4), hipMemcpyDeviceToDevice, (hipStream_t)stream));
-    return 0;
-}
-
-int cmax_debug_compact_events(cmax_handle_t h, void *regions_out, int *flag_host, cmax_stream_t stream) {
-    CMAX_REQUIRE(h != nullptr && regions_out != nullptr, "debug_compact_events");
-    if (!h->compact || h->nseg <= 0) {
-        set_error("debug_compact_events: the current work list has no compact copy");
-        return CMAX_ESTATE;
-    }
-    hipStream_t s = (hipStream_t)stream;
-    CMAX_CHECK_HIP(hipMemcpyAsync(regions_out, h->cev, (size_t)h->nseg * (size_t)compact_region_bytes(), hipMemcpyDeviceToDevice, s));
-    if (flag_host) {  // what k_pack_compact raised: an event that does not fit its segment's strip
-        // (into the flag's own slot of the pinned read-back, which every cut has sized: build_segments)
-        CMAX_CHECK_HIP(hipMemcpyAsync(h->hp_read + 7, h->d_flags + 3, sizeof(int), hipMemcpyDeviceToHost, s));
-        CMAX_CHECK_HIP(hipStreamSynchronize(s));
-        *flag_host = h->hp_read[7];
-    }
     return 0;
 }
 

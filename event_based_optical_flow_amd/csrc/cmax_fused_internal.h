@@ -1,9 +1,11 @@
-// Private header of the fused contrast-maximization objective: what its two translation units share on the HOST side.
+// Private header of the fused contrast-maximization objective: what its three translation units share on the HOST side.
 //   cmax_event_launch.hip  the per-event kernels (cmax_event_kernels.inc) and their launch layer, one launcher per kernel family
-//   cmax_fused.hip         the handle, the per-batch preparation, the image-side kernels and the orchestration of an evaluation
+//   cmax_batch.hip         the handle's lifetime and everything done once per batch: pack, sort, scan, read-back, work list, compact
+//                          copy, per-event weights (the host's decisions on the way: cmax_batch_plan.h, plain C++)
+//   cmax_fused.hip         everything done per evaluation: the image-side kernels and the orchestration
 // Kernel arguments, the handle, the constants the host sizes buffers with, and the declarations of the host functions that cross a
 // unit (hidden: none of them is exported).  Device helpers shared by the event kernels and the image-side kernels live in
-// cmax_fused_device.h.  Every kernel is compiled in exactly one unit (-fno-gpu-rdc).  The environment knobs are listed in cmax_fused.hip.
+// cmax_fused_device.h.  Every kernel is compiled in exactly one unit (-fno-gpu-rdc).  Each unit lists the environment knobs it reads.
 #pragma once
 
 #include <cstdlib>
@@ -11,21 +13,15 @@
 #include <type_traits>
 #include <vector>
 
+#include "cmax_batch_plan.h"
 #include "cmax_buffers.h"
 #include "cmax_comm.h"
 #include "cmax_common.h"
 
 namespace cmax {
 
-constexpr int kSparseSegment = 512;  // voxel K3: segments below this many events add straight to memory (no LDS accumulators)
-constexpr int kTile = 16;  // source-pixel tile edge of the counting sort
-constexpr int kSegMax = 2040;                 // events per segment (+1 for the even-aligned start still fits 2048);
-                                              // |sum of votes| <= 2040 * 2^20 < 2^31
-constexpr int kAccCells = 3072;               // flow-gradient accumulator cells per channel in LDS (voxel K3): 12 (tile, bin) groups
-constexpr int kAccCellsDense = 768;           // the same for the dense K3 with owned tiles: 3 source tiles
+// (kTile, kSegMax, kSparseSegment, kAccCells, kAccCellsDense and the other constants the host's per-batch decisions need: cmax_batch_plan.h)
 constexpr int kWinMaxW = 128;                 // widest window when the bounding box has to be clipped
-constexpr int64_t kRadixMinEvents = 8000000;  // batches from here on are ordered by the stable radix sort (cmax_radix_sort.h): 8M events 550 vs 556 us,
-                                              // 12M 765 vs 875, 20M 1177 vs 1419, 64M 3483 vs 4754 (profiles/r05_set_events.txt); below, the counting sort's fewer launches win
 constexpr int kShiftWordsMax = 512;           // words of cell offsets per (reference time, segment): 4 bits per slot of a big segment
 // (votes are accumulated as signed fixed point in the LDS windows: 12.20, big segments 13.19 -- kFixNS of cmax_event_kernels.inc)
 
@@ -167,20 +163,20 @@ struct cmax_handle_s {
     int *d_flags = nullptr;  // [0] any fractional source coordinate, [1] dropped events, [2] events kept from off the sensor (cmax_set_keep_outside)
     bool long_runs = false;  // >= 8 events per active source pixel on average: the dense K3 reduces runs serially per thread
     bool mid = false;        // MID segments: up to 3064 events, four source tiles (five (tile, bin) groups) wide, event kernels of the m512 namespace -- when the
-                             // standard cut would need more workgroups than the chip holds at once and this one does not (build_segments)
+                             // standard cut would need more workgroups than the chip holds at once and this one does not (cut_work_list)
     bool big = false;        // BIG segments: up to 4088 events each, event kernels of the b512 / b1024 namespaces (batches of >= 8M events)
-    int seg_max = 2040;      // events per segment of the current work list (kSegMax, or 4088 for big segments)
+    int seg_max = cmax::kSegMax;  // events per segment of the current work list (kSegMax, kSegMid or kSegBig)
     bool small_acc = false;  // binned handle, owned groups of <= 3 groups per segment: the voxel K3 with kAccCellsDense accumulator cells (kGradOwnedSmall)
     bool owned = false;      // the work list gives every group (empty ones included) to exactly one segment, <= kAccCells / 256 groups each
     int *d_tile_start = nullptr;  // [ngroups + 1] first sorted event of every group (source tile, or (tile, time bin))
     // What the host reads back once per batch lives in ONE allocation, in this order: d_tmm (2 doubles) | d_flags (4 ints) |
-    // d_active (ntiles ints) | d_tile_start (...): one device-to-host copy instead of four (each ~4 us of copy latency)
+    // d_active (ntiles ints) | d_tile_start (...) -- ReadbackLayout, cmax_batch.hip: one device-to-host copy instead of four (each ~4 us of copy latency)
     cmax::DevBuf<int> d_batch;   // base of that allocation (as ints)
     int *d_active = nullptr;  // [ntiles] source pixels that hold events, per tile (un-binned order; written by k_tile_sort)
     cmax::DevBuf<int4> d_segs;       // [nseg] (begin, count, first source tile, tiles spanned): work items of the event kernels
     cmax::DevBuf<int4> d_win;        // [4][nseg] LDS windows of the last objective vote (K1 -> K3 of the same evaluation)
     // compact copy of the sorted events, one region per segment of the work list (EventLoads in cmax_event_kernels.inc): big segments of
-    // un-binned handles; valid for the current work list only (build_segments)
+    // un-binned handles; valid for the current work list only (build_segments, cmax_batch.hip)
     cmax::DevBuf<char> cev;
     bool compact = false;
     // cmax_objective_batch: K candidate motions per launch (allocated on first use, sized for batch_cap candidates)
@@ -416,7 +412,7 @@ CMAX_HIDDEN void launch_grad_hvp(cmax_handle_s *h, const EvView &ev, const WarpP
 CMAX_HIDDEN void launch_vote_tan2(cmax_handle_s *h, const EvView &ev, const WarpParams &wp, const RefArgs &ra, int n_ref, hipStream_t s);
 CMAX_HIDDEN Layout grad_layout(const cmax_handle_s *h, int model, bool owned);
 CMAX_HIDDEN int layout_threads(Layout id);
-// ... and k_pack_compact behind build_segments (cmax_fused.hip): the compact copy of the current work list's events, grown on demand
+// ... and k_pack_compact behind build_segments (cmax_batch.hip): the compact copy of the current work list's events, grown on demand
 CMAX_HIDDEN int pack_compact_events(cmax_handle_s *h, hipStream_t s);
 CMAX_HIDDEN int64_t compact_region_bytes();  // bytes per region of that copy (the big layout's kCompactStride)
 #ifdef CMAX_TIMELINE

@@ -27,17 +27,13 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cmax_batch_plan.h"  // kRsThreads, kRsSlots, kRsChunk, kRsMaxGroups, kRsMaxDigitBits
 #include "cmax_common.h"
 #include "cmax_sort_kernels.h"
 
 namespace cmax {
 
-constexpr int kRsThreads = 512;          // R1 / R3
 constexpr int kRsWaves = kRsThreads / kWave;
-constexpr int kRsSlots = 4;              // events per thread and iteration of R3 (their loads are in flight together)
-constexpr int kRsChunk = kRsThreads * kRsSlots;
-constexpr int kRsMaxGroups = 1024;       // workgroups per pass (four per CU: all resident)
-constexpr int kRsMaxDigitBits = 6;   // (see sort_events: a pass is as fast as its output streams are few)
 static_assert(kRsWaves == 8, "one byte per wave in a 64-bit LDS word");
 
 struct RsKey {

@@ -20,6 +20,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 
+#include "cmax_batch_plan.h"  // kTile, kTileKeysMax
 #include "cmax_common.h"
 
 namespace cmax {
@@ -391,7 +392,7 @@ k_bucket_scatter(SRC src, int64_t n, int ntc, int ntiles, int T, const int *__re
 // group_start: [ntiles + 1] (T == 0) or [ntiles * T + 1]; active[tile] (T == 0): source pixels of this tile that hold
 // events; tmm_keys (optional): the keyed batch extremes S1 reduced, converted to the two doubles by the first workgroup
 // (nothing in this launch reads them).
-constexpr int kTileKeysMax = 8192;  // 32 KB of counters: (bin, pixel) keys up to T = 32
+// (kTileKeysMax, cmax_batch_plan.h: 32 KB of counters, (bin, pixel) keys up to T = 32)
 __global__ void __launch_bounds__(kTileSortThreads)
 k_tile_sort(int ntiles, int T, const int *__restrict__ tile_off, SortOut in, SortOut out, int *__restrict__ group_start, int *__restrict__ active,
             const int *__restrict__ flags, unsigned long long *__restrict__ tmm_keys) {

@@ -112,7 +112,7 @@ def slab_regroup(row, col, tau64, S, ntc):
 
 
 def pass_plan(size, T, n_in, digit_bits=RS_MAX_DIGIT_BITS):
-    """The passes `sort_events` runs: dict(P, nb [P] digit widths lowest first, fine, nwg, range)."""
+    """The passes `sort_events` runs (`radix_pass_plan`, csrc/cmax_batch_plan.h): dict(P, nb [P] digit widths lowest first, fine, nwg, range)."""
     digit_bits = min(RS_MAX_DIGIT_BITS, max(2, digit_bits))
     gb = 1
     while (1 << gb) < n_groups(size, T):

@@ -1,4 +1,4 @@
-"""The work list `build_segments` (csrc/cmax_fused.hip) cuts from the group starts and the compact copy `k_pack_compact`
+"""The work list `cut_work_list` (csrc/cmax_batch_plan.h, called by `build_segments` of csrc/cmax_batch.hip) cuts from the group starts and the compact copy `k_pack_compact`
 (csrc/cmax_event_kernels.inc) writes for big segments, restated in numpy (no GPU, no import of the package).
 
 `cut` restates the RULES of the host's cut, constants named.  `check_invariants` is written from what the event kernels REQUIRE of any

@@ -1,4 +1,4 @@
-"""The stable LSD radix sort (csrc/cmax_radix_sort.h, the radix branch of sort_events) at SMALL sizes, on every branch: the packed
+"""The stable LSD radix sort (csrc/cmax_radix_sort.h, the radix branch of sort_events in csrc/cmax_batch.hip) at SMALL sizes, on every branch: the packed
 order bit for bit against the numpy restatement of tests/_sort_ref.py.  A stable sort has one right answer per input, so nothing here
 has a tolerance except the evaluations, which are held to the oracle at the project's plain gate (1e-4 of the largest entry).
 

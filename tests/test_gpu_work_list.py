@@ -1,4 +1,4 @@
-"""The host's cut into segments (`build_segments`, csrc/cmax_fused.hip) and the compact copy of big segments (`k_pack_compact`,
+"""The host's cut into segments (`build_segments`, csrc/cmax_batch.hip; its rules: `cut_work_list`, csrc/cmax_batch_plan.h) and the compact copy of big segments (`k_pack_compact`,
 csrc/cmax_event_kernels.inc), EXACTLY, in every regime: the read-backs cmax_debug_work_list / cmax_debug_compact_events against the
 numpy restatement of tests/_worklist_ref.py.
 

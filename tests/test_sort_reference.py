@@ -114,7 +114,7 @@ def test_dropped_and_kept_events():
 
 
 def test_case_table_reaches_every_branch():
-    """The pass plans of the case table (the formula of sort_events): both parities of P on both sizes in both children, the 8-bit
+    """The pass plans of the case table (the formula of radix_pass_plan): both parities of P on both sizes in both children, the 8-bit
     first pass (D = 256) of fine binned keys up to T = 32, coarse keys from T = 33 on, ranges that end inside a step, one group."""
     for k, bits in enumerate(C.CHILD_DIGIT_BITS):
         P = {size: R.pass_plan(size, 0, 50_000, bits)["P"] for size in (C.SIZE_A, C.SIZE_B)}

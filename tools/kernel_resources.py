@@ -2,7 +2,7 @@
 """SGPR / VGPR / occupancy / LDS per kernel from hipcc's -Rpass-analysis=kernel-resource-usage remarks:
    hipcc --offload-arch=gfx950 -O3 -std=c++17 -munsafe-fp-atomics -fno-gpu-rdc --cuda-device-only -c csrc/cmax_event_launch.hip \
          -o /tmp/x.o -Rpass-analysis=kernel-resource-usage 2> /tmp/res.txt
-   (the event kernels; csrc/cmax_fused.hip holds the image-side and the per-batch kernels -- tools/resources.sh runs both)
+   (the event kernels; csrc/cmax_batch.hip holds the per-batch kernels and csrc/cmax_fused.hip the image-side ones -- tools/resources.sh runs all three)
    python tools/kernel_resources.py /tmp/res.txt [regex on the demangled name]
 (The rule of profiles/r02_ablation.txt: <= 80 SGPRs keeps 8 waves per SIMD; check k_grad<cmax::t512, ...> and k_grad<cmax::t1024, ...> after every change.)"""
 import re
